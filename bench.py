@@ -75,6 +75,7 @@ PEAK_FP32_MFMA_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_16x16x4_f32, 25
 PEAK_HBM_GBS = 8000.0
 DTYPE_OUT = {"fp32": "f32"}
 PRECISION_CHUNKS = 8192  # chunks of the headline data evaluated on the CPU (fp64 + fp32) for the `parity` / `precision` objects
+DUMP_LIMIT = 64 << 20  # bytes: what --dump-outputs writes in all
 LINE_LIMIT = 4096  # bytes: the ONE stdout line stays below this (the driver keeps a bounded tail); the rest -> bench_details.json
 BLOCK = 1_000_000  # the synthetic data set is defined in blocks of 1 M chunks (seed = base + block index)
 
@@ -815,6 +816,30 @@ def write_details(out, path):
 _T0 = time.time()
 
 
+def dump_outputs(path, job, rank):
+    """--dump-outputs DIR: what the timed path handed its caller after the last timed step, as DIR/<name>.npy -
+    logits.npy (float32 [chunks, classes]: the last step's logits, every rank's chunks in rank order) and label_counts.npy
+    (float64 [classes]: the per-label counts accumulated over the timed steps, all-reduced over the ranks).  Logits over
+    DUMP_LIMIT are cut to a fixed, seeded sample of rows; logits_rows.npy (float64) then holds their row indices.  A collective
+    (every rank calls it); rank 0 writes.  Returns {name: shape} on rank 0."""
+    from remora_amd import dist as rdist
+
+    logits = rdist.gather_arrays(job.logits.float().cpu().numpy())
+    if rank != 0:
+        return None
+    arrays = {"label_counts": job.counts.cpu().numpy().astype(np.float64)}
+    if logits.nbytes + arrays["label_counts"].nbytes > DUMP_LIMIT:
+        keep = (DUMP_LIMIT - (1 << 20)) // (logits[0].nbytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(logits.shape[0], keep, replace=False))
+        arrays["logits_rows"] = rows.astype(np.float64)
+        logits = logits[rows]
+    arrays["logits"] = np.ascontiguousarray(logits, np.float32)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def note(msg):
     """progress breadcrumb on stderr (stdout carries exactly one line: the result)"""
     print(f"[bench {time.time() - _T0:6.1f}s] {msg}", file=sys.stderr, flush=True)
@@ -847,9 +872,13 @@ def main():
                          "sha256 of their concatenation in rank order in the details file")
     ap.add_argument("--force-device", type=int, default=None, help="testing: put every rank on this GPU")
     ap.add_argument("--shard-base", type=int, default=0, help="testing: rank r of a weak run takes the data of rank shard_base + r")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(sys.argv[1:], args.gpus))
 
@@ -923,6 +952,7 @@ def main():
 
         allg = rdist.gather_arrays(job.logits.cpu().numpy())
         logits_sha = hashlib.sha256(np.ascontiguousarray(allg).tobytes()).hexdigest()
+    dumped = dump_outputs(args.dump_outputs, job, rank) if args.dump_outputs else None
     coll = None
     if world > 1:
         backend = rdist.transport()
@@ -998,7 +1028,7 @@ def main():
         "label_counts": rep["label_counts"], "label_counts_match_logits_argmax": counts_exact,
         "label_counts_per_rank": [[int(x) for x in r] for r in per_rank] if per_rank is not None else None,
         "allreduce_counts_c_abi": cabi if world == 1 else "run after the result line; result on stderr (see bench.py)",
-        "collective": coll, "logits_sha256": logits_sha,
+        "collective": coll, "logits_sha256": logits_sha, "outputs_dumped": dumped,
     }
     if world == 1:
         legs = side_legs(job, args, job.logits)
