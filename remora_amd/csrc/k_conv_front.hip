@@ -681,8 +681,9 @@ __global__ __launch_bounds__(256) void seq2_front_kernel(ConvFrontArgs a) {
 // filters of 5, 4 and 4 taps, all three taken as F(4, 5) at 0, +-1, +-2, +-1/2, inf (the 4-tap ones with a zero fifth tap): 8 points x
 // K = 48, 168 MFMAs per chunk at C100 instead of 364.  V is TWICE the rows here; it fits a half CU at four chunks per iteration only
 // because it takes the place of the producer's gather tables and scratch, which are dead once the rows are staged - the 14 KB
-// seq_conv1 table is therefore re-read from L2 every iteration (into registers under the matrix phase, into LDS behind the barrier that
-// frees V).
+// seq_conv1 table is therefore re-read from L2 every iteration, straight into LDS by DMA (global_load_lds) behind the barrier that frees
+// V, waited for before the producer starts.  No VGPR carries it: it used to travel through 15 registers under the matrix phase (33 VGPRs
+// spilled, now none).  Staging the first chunk under the DMA measured slower (1.69 against 1.66 ms a launch).
 // ---------------------------------------------------------------------------------------
 template <int K>
 __global__ __launch_bounds__(256, 2) void seq2_front_wino_kernel(ConvFrontArgs a) {
@@ -700,10 +701,18 @@ __global__ __launch_bounds__(256, 2) void seq2_front_wino_kernel(ConvFrontArgs a
     const f32x4 b4 = *reinterpret_cast<const f32x4 *>(a.bias + 16 * w + 4 * q);
     constexpr int wt_words = KW1 * K * 80;
     float *s_wt = smem + a.o_front;  // [KW1][K][5][16]
-    constexpr int WT_PER = (wt_words + 255) / 256;
-    float wt_pre[WT_PER];  // this thread's share of the table, fetched under the matrix phase for the next iteration
+    // the table goes L2 -> LDS by DMA (global_load_lds, 16 B a lane, no VGPR): slot u * 256 + tid of 16 B, a wave's 64 slots
+    // contiguous from its wave-uniform base as the instruction writes them
+    constexpr int WT_SLOTS = wt_words / 4, WT_PER = (WT_SLOTS + 255) / 256;
+    static_assert(wt_words % 4 == 0, "the gather table moves in 16-byte slots");
+    auto load_table = [&]() {
 #pragma unroll
-    for (int u = 0; u < WT_PER; ++u) wt_pre[u] = tid + 256 * u < wt_words ? a.wt5[tid + 256 * u] : 0.0f;
+        for (int u = 0; u < WT_PER; ++u)
+            if (tid + 256 * u < WT_SLOTS)
+                __builtin_amdgcn_global_load_lds(reinterpret_cast<const void *>(a.wt5 + (size_t)(tid + 256 * u) * 4),
+                                                 (__attribute__((address_space(3))) void *)(s_wt + (256 * u + 64 * w) * 4),
+                                                 16, 0, 0);
+    };
     float *const V = smem + a.o_v;
     const int XIV = 12 * a.vplane;
     const f32x2 bq_lo = f32x2{a.b_seq1[4 * quad], a.b_seq1[4 * quad + 1]}, bq_hi = f32x2{a.b_seq1[4 * quad + 2], a.b_seq1[4 * quad + 3]};
@@ -727,9 +736,8 @@ __global__ __launch_bounds__(256, 2) void seq2_front_wino_kernel(ConvFrontArgs a
         const int64_t chunk0 = it * a.cb;
         const int nch = (int)((a.n - chunk0) < a.cb ? (a.n - chunk0) : a.cb);
         RMR_SYNC();  // the matrix phase of the previous iteration has read V: its place is the table's and the scratch's again
-#pragma unroll
-        for (int u = 0; u < WT_PER; ++u)
-            if (tid + 256 * u < wt_words) s_wt[tid + 256 * u] = wt_pre[u];
+        load_table();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's share of the table has landed
         RMR_SYNC();  // gather table visible
         for (int c = w; c < nch; c += 4) {
             const int64_t chunk = chunk0 + c;
@@ -747,18 +755,24 @@ __global__ __launch_bounds__(256, 2) void seq2_front_wino_kernel(ConvFrontArgs a
             } else {
                 len = a.lens[chunk];
                 const int16_t *mp = a.maps + (size_t)chunk * a.map_w;
+                // the copy and run loops stay scalar: vectorised, their loop-invariant index vectors take VGPRs the kernel has not
+                // got (spills)
+#pragma clang loop vectorize(disable) interleave(disable)
                 for (int j = lane; j < a.map_w; j += 64) s_map[j] = mp[j];
                 const int8_t *sq = a.seqs + (size_t)chunk * a.seq_w;
+#pragma clang loop vectorize(disable) interleave(disable)
                 for (int j = lane; j < a.seq_w; j += 64) s_seq[j] = sq[j];
             }
             len = len < 0 ? 0 : (len > a.maxlen ? a.maxlen : len);
             for (int i = lane; i < KW1 * 16; i += 64) s_u[(size_t)a.maxlen * KW1 * 16 + i] = 0.0f;
+#pragma clang loop vectorize(disable) interleave(disable)
             for (int s = lane; s < a.L; s += 64) s_pidx[s] = (int16_t)a.maxlen;
             wave_sync();
             // base covering every signal position, written as runs (base p owns [map[p], map[p+1])); positions no base
             // owns keep the zero row `maxlen` (the gather form of the reference's scatter loops, encoded_kmers.pyx:33-44)
             for (int p = lane; p < len; p += 64) {
                 const int s0 = max((int)s_map[p], 0), s1 = min((int)s_map[p + 1], a.L);
+#pragma clang loop vectorize(disable) interleave(disable)
                 for (int s = s0; s < s1; ++s) s_pidx[s] = (int16_t)p;
                 unsigned long long wv = 0;
 #pragma unroll
@@ -868,9 +882,6 @@ __global__ __launch_bounds__(256, 2) void seq2_front_wino_kernel(ConvFrontArgs a
                 for (int x = 0; x < 8; ++x) *reinterpret_cast<f32x4 *>(dst + (size_t)x * XIV) = v[x];
             }
         }
-        // the table for the next iteration leaves L2 now and lands under the matrix phase
-#pragma unroll
-        for (int u = 0; u < WT_PER; ++u) wt_pre[u] = tid + 256 * u < wt_words ? a.wt5[tid + 256 * u] : 0.0f;
         RMR_SYNC();
         // ---- eight GEMMs of K = 48 per column tile; steps = (phase, half of the points); AT m, bias, swish, four stores per column
         const int ntl = (ncols + 15) >> 4;
