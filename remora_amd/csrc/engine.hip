@@ -430,6 +430,15 @@ int rmr_engine::allow_big_lds(const void *kernel, size_t bytes) {
     return 0;
 }
 
+int rmr_engine::kernel_regs(const void *kernel) {
+    for (const auto &kr : regs_seen)
+        if (kr.first == kernel) return kr.second;
+    hipFuncAttributes attr;
+    const int regs = hipFuncGetAttributes(&attr, kernel) == hipSuccess && attr.numRegs > 0 ? attr.numRegs : 256;
+    regs_seen.emplace_back(kernel, regs);
+    return regs;
+}
+
 int rmr_engine::prof_begin(int id, hipEvent_t *t1, hipStream_t s) {
     hipEvent_t ev[2];
     for (int k = 0; k < 2; ++k) {
@@ -1432,6 +1441,9 @@ int run_pipeline(rmr_model *m, const float *signal, const float *enc, const int8
                  float *logits) {
     rmr_engine *e = m->eng;
     if (n <= 0) return 0;
+    // the switches of every kernel choice below, read once per call
+    const FwdSwitches sw{tune_int("RMR_FUSED", 1) != 0, tune_int("RMR_CONV_FRONT", 1) != 0, tune_int("RMR_WINOGRAD", 1) != 0,
+                         tune_int("RMR_SIG3_MFMA", 1) != 0};
     if (m->nparts == 1 && m->desc.size > 64) {
         // bf16 / f16 above 64 channels (k_stream16.hip): fp32 front kernels (sig_conv1/2, seq_conv1: 16 channels), then the three
         // size-wide convolutions and the LSTM on the 16-bit matrix cores with streamed weights; cat and x are 16-bit in HBM
@@ -1465,7 +1477,7 @@ int run_pipeline(rmr_model *m, const float *signal, const float *enc, const int8
     if (m->f16 && (enc || !fused_front_supported(m, seq_w, map_w)))
         RMR_FAIL(RMR_ERR_INVALID, "dtype f16 runs on the fused kernels only: chunk arrays (not a dense one-hot tensor), sequence rows of at "
                                   "most 256 columns, a chunk length that is a multiple of 4");
-    if (!enc && fused_front_supported(m, seq_w, map_w) && (m->f16 || tune_int("RMR_FUSED", 1))) {
+    if (!enc && fused_front_supported(m, seq_w, map_w) && (m->f16 || sw.fused)) {
         // plain-bf16 ConvLSTM: two launches per sub-batch, x (bf16, 3 KB/chunk @C100) is the only intermediate in
         // HBM; sub-batches are sized so that x stays in the 256 MiB Infinity Cache between producer and consumer
         int64_t sb = e->subbatch > 0 ? e->subbatch : 65536;
@@ -1502,10 +1514,10 @@ int run_pipeline(rmr_model *m, const float *signal, const float *enc, const int8
     // fp32 ConvLSTM size 64 straight from the chunk arrays: sig_conv1/2 and seq_conv1 are produced inside the staging of
     // sig_conv3 / seq_conv2 (k_conv_front.hip); sig2 / seq1 never exist in HBM.  (RMR_CONV_FRONT=0: the separate front
     // kernels - the comparand of tests/test_gpu_conv_front.py)
-    const bool fold = !enc && tune_int("RMR_CONV_FRONT", 1) && conv_front_supported(m, kb, ka, seq_w, map_w);
+    const bool fold = !enc && sw.conv_front && conv_front_supported(m, kb, ka, seq_w, map_w);
     // every other fp32 path (Conv_w_ref; ConvLSTM shapes the two-branch fold does not cover): the signal branch alone is
     // folded - sig_conv1 / sig_conv2 (matrix cores) produced inside the staging of sig_conv3, sig2 never in HBM
-    const bool sigfold = !fold && m->nparts == 0 && sig3_front_mfma_supported(m);
+    const bool sigfold = !fold && m->nparts == 0 && sw.sig3_mfma && sig3_front_mfma_supported(m);
     // (Running the front kernels of sub-batch i + 1 on a second stream under the matrix kernels of sub-batch i was measured in
     //  rounds 1-2 in two forms and gained nothing - they share the CUs with conv_sig3, or half a register file under the LSTM -
     //  and is gone; profiles/NOTES_r03.md.)
@@ -1529,10 +1541,10 @@ int run_pipeline(rmr_model *m, const float *signal, const float *enc, const int8
         }
         float *base = rest;
         float *cat = base; base += (size_t)nb * m->P3 * 2 * sz;
-        if (fold) RMR_TRY(launch_conv_front(m, sig_b, seqs + (size_t)c0 * seq_w, seq_w, maps + (size_t)c0 * map_w, map_w, lens + c0, nb, cat));
+        if (fold) RMR_TRY(launch_conv_front(m, sig_b, seqs + (size_t)c0 * seq_w, seq_w, maps + (size_t)c0 * map_w, map_w, lens + c0, nb, cat, sw));
         else if (split_conv) RMR_TRY(launch_conv_split(e, m->sig3, m->nparts, sig2, 16, m->P2, cat, 2 * sz, 0, m->P3, nb));
-        else if (sigfold) RMR_TRY(launch_sig3_front_mfma(m, sig_b, nb, cat));
-        else RMR_TRY(launch_conv(e, m->sig3, sig2, 16, m->P2, cat, 2 * sz, 0, m->P3, nb));
+        else if (sigfold) RMR_TRY(launch_sig3_front_mfma(m, sig_b, nb, cat, sw.winograd));
+        else RMR_TRY(launch_conv(e, m->sig3, sig2, 16, m->P2, cat, 2 * sz, 0, m->P3, nb, sw.winograd));
 #ifdef RMR_TIMING_ABLATIONS  // experiment build only (tools/stress_determinism.py): cat [nb][P3][2 sz] of the last sub-batch
         if (const char *dump = fold ? getenv("RMR_DUMP_CAT") : nullptr) {
             std::vector<float> h((size_t)nb * m->P3 * 2 * sz);
@@ -1547,13 +1559,13 @@ int run_pipeline(rmr_model *m, const float *signal, const float *enc, const int8
         if (m->desc.arch == RMR_ARCH_CONV_LSTM) {
             float *x = base; base += (size_t)nb * m->T * sz;
             if (fold) {
-                RMR_TRY(launch_conv(e, m->merge1, cat, 2 * sz, m->P3, x, sz, 0, m->T, nb));
+                RMR_TRY(launch_conv(e, m->merge1, cat, 2 * sz, m->P3, x, sz, 0, m->T, nb, sw.winograd));
             } else if (split_conv) {
                 RMR_TRY(launch_conv_split(e, m->seq2, m->nparts, seq1, 16, m->P1, cat, 2 * sz, sz, m->P3, nb));
                 RMR_TRY(launch_conv_split(e, m->merge1, m->nparts, cat, 2 * sz, m->P3, x, sz, 0, m->T, nb));
             } else {
-                RMR_TRY(launch_conv(e, m->seq2, seq1, 16, m->P1, cat, 2 * sz, sz, m->P3, nb));
-                RMR_TRY(launch_conv(e, m->merge1, cat, 2 * sz, m->P3, x, sz, 0, m->T, nb));
+                RMR_TRY(launch_conv(e, m->seq2, seq1, 16, m->P1, cat, 2 * sz, sz, m->P3, nb, sw.winograd));
+                RMR_TRY(launch_conv(e, m->merge1, cat, 2 * sz, m->P3, x, sz, 0, m->T, nb, sw.winograd));
             }
             if (m->nparts > 0 && lstm_x16s_supported(m)) RMR_TRY(launch_lstm_head_x16s(m, x, nb, logits + (size_t)c0 * m->desc.num_out));
             else if (m->nparts > 0) RMR_TRY(launch_lstm_head_split(m, x, nb, logits + (size_t)c0 * m->desc.num_out));
@@ -1564,12 +1576,12 @@ int run_pipeline(rmr_model *m, const float *signal, const float *enc, const int8
             float *m2 = base; base += (size_t)nb * m->T2 * sz;
             float *m3 = base; base += (size_t)nb * m->T3 * sz;
             float *m4 = base; base += (size_t)nb * m->T4 * sz;
-            RMR_TRY(launch_conv(e, m->seq2, seq1, 16, m->P1, seq2, 32, 0, m->PQ2, nb));
-            RMR_TRY(launch_conv(e, m->seq3, seq2, 32, m->PQ2, cat, 2 * sz, sz, m->P3, nb));
-            RMR_TRY(launch_conv(e, m->merge1, cat, 2 * sz, m->P3, m1, sz, 0, m->T, nb));
-            RMR_TRY(launch_conv(e, m->merge2, m1, sz, m->T, m2, sz, 0, m->T2, nb));
-            RMR_TRY(launch_conv(e, m->merge3, m2, sz, m->T2, m3, sz, 0, m->T3, nb));
-            RMR_TRY(launch_conv(e, m->merge4, m3, sz, m->T3, m4, sz, 0, m->T4, nb));
+            RMR_TRY(launch_conv(e, m->seq2, seq1, 16, m->P1, seq2, 32, 0, m->PQ2, nb, sw.winograd));
+            RMR_TRY(launch_conv(e, m->seq3, seq2, 32, m->PQ2, cat, 2 * sz, sz, m->P3, nb, sw.winograd));
+            RMR_TRY(launch_conv(e, m->merge1, cat, 2 * sz, m->P3, m1, sz, 0, m->T, nb, sw.winograd));
+            RMR_TRY(launch_conv(e, m->merge2, m1, sz, m->T, m2, sz, 0, m->T2, nb, sw.winograd));
+            RMR_TRY(launch_conv(e, m->merge3, m2, sz, m->T2, m3, sz, 0, m->T3, nb, sw.winograd));
+            RMR_TRY(launch_conv(e, m->merge4, m3, sz, m->T3, m4, sz, 0, m->T4, nb, sw.winograd));
             RMR_TRY(launch_fc_head(m, m4, nb, logits + (size_t)c0 * m->desc.num_out));
         }
     }

@@ -22,6 +22,7 @@
 // [row][IC+4] image measured 54 % of LDS cycles lost to 2-way conflicts, profiles/r01).
 #include "rmr_internal.h"
 #include "rmr_math.h"
+#include "rmr_plan.h"
 
 namespace rmr {
 
@@ -189,72 +190,20 @@ __global__ __launch_bounds__(256, conv_min_waves(IC, KW)) void conv_mfma_kernel(
 template <int IC, int KW, int STRIDE>
 static int launch_conv_t(rmr_engine *e, const ConvLayer &c, const float *in, int in_row, int pin,
                          float *out, int out_row, int out_coff, int pout, int64_t n) {
-    constexpr int G = IC / 16;
-    constexpr int RS = (G % 2 == 0) ? IC / 4 + 4 : IC / 4;
-    // chunks per iteration.  How many blocks a CU holds is set by the instantiation's registers (512 per SIMD lane, granule
-    // 8: the 16-channel layers reach 3-4 waves per SIMD, merge_conv1's 160-register weight slice 2), so the LDS budget of a
-    // block is its share of the 160 KB at that occupancy, capped at 72 KB (two blocks per CU).  Among the
-    // chunk counts that fit, the one whose columns fill their 16-column tiles best wins (Conv_w_ref's merge_conv1: 4 x 20
-    // columns = 5 tiles exactly, where 5 chunks would pad the 7th tile to 25 %); ties go to the larger count.
-    const int threads_pb = 64 * (c.oc / 16);
-    static int regs = 0;  // per instantiation; the same binary on every device
-    if (regs == 0) {
-        hipFuncAttributes attr;
-        regs = hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(conv_mfma_kernel<IC, KW, STRIDE>)) == hipSuccess ? attr.numRegs : 256;
-        if (regs < 1) regs = 256;
-    }
-    int wps = 512 / ((regs + 7) & ~7);
-    wps = wps < 1 ? 1 : (wps > 8 ? 8 : wps);
-    int resident = wps * 4 / (threads_pb / 64);
-    resident = resident < 1 ? 1 : (resident > 8 ? 8 : resident);
-    const size_t row_bytes = (size_t)pin * RS * 4 * sizeof(float);  // all four planes
-    size_t budget = (size_t)73728;
-    const size_t share = (size_t)160 * 1024 / resident - 512;
-    if (share < budget) budget = share;
-    int cb_max = (int)(budget / row_bytes);
-    if (cb_max < 1) cb_max = 1;
-    if (cb_max > 8) cb_max = 8;
-    int cb = cb_max;
-    double best = -1.0;
-    for (int k = cb_max; k >= (cb_max + 1) / 2; --k) {
-        const int cols = k * pout;
-        const double eff = (double)cols / (16.0 * ((cols + 15) / 16));
-        if (eff > best + 1e-9) { best = eff; cb = k; }
-    }
-    // a small batch (one read per call: a few hundred chunks) spread over the CUs: fewer chunks per iteration until there is a block
-    // for every CU - a chunk's columns are computed the same way whatever its neighbours in the iteration (same bits), and a
-    // half-filled tile on an otherwise idle CU costs nothing
-    while (cb > 1 && (n + cb - 1) / cb < e->num_cus) cb = (cb + 1) / 2;
-    // a chunk whose rows do not fit a block's share goes through position windows: the most output positions whose input rows
-    // ((win - 1) * STRIDE + KW of them) fit the share, one window of one chunk per iteration
-    int nwin = 1, pin_w = pin, pout_w = pout;
-    if (row_bytes > budget) {
-        const int rows_fit = (int)(budget / ((size_t)RS * 4 * sizeof(float)));
-        pout_w = (rows_fit - KW) / STRIDE + 1;
-        if (pout_w < 16) RMR_FAIL(RMR_ERR_INVALID, "conv layer: not even a 16-column window fits %zu B of LDS", budget);
-        pout_w &= ~15;  // whole column tiles
-        nwin = (pout + pout_w - 1) / pout_w;
-        pin_w = (pout_w - 1) * STRIDE + KW;
-        cb = 1;
-    }
-    const int plane = ((cb * pin_w * RS) + 63) & ~63;
-    const size_t lds = (size_t)plane * 4 * sizeof(float) + 64;  // + trash slot for masked staging writes
-    if (lds > 160 * 1024) RMR_FAIL(RMR_ERR_INVALID, "conv layer needs %zu B of LDS", lds);
+    auto kern = conv_mfma_kernel<IC, KW, STRIDE>;
+    // chunks per iteration, position windows for long chunks, LDS layout and grid (rmr_plan.h): the LDS budget of a block is its
+    // share of the CU at the occupancy the instantiation's registers allow
+    const ConvPlan p = plan_conv_mfma(IC, KW, STRIDE, c.oc, pin, pout, n, e->num_cus, e->kernel_regs(reinterpret_cast<const void *>(kern)));
+    if (!p.ok) RMR_FAIL(RMR_ERR_INVALID, "conv layer %d->%d x%d: a chunk of %d positions does not fit %zu B of LDS", IC, c.oc, KW, pin, p.budget);
+    if (p.grid < 1) return 0;
     ConvArgs a;
     a.in = in; a.out = out; a.apack = c.apack; a.bias = c.bias; a.n = n;
-    a.in_row = in_row; a.pin = pin_w; a.pout = pout_w; a.out_row = out_row; a.out_coff = out_coff;
-    a.cb = cb; a.plane = plane; a.div_pout = make_fastdiv(pout_w);
-    a.nwin = nwin; a.pin_total = pin; a.pout_total = pout;
-    const int64_t iters = nwin > 1 ? n * nwin : (n + cb - 1) / cb;
-    const int threads = threads_pb;
-    // persistent blocks: a grid of several times the resident count evens out the tail
-    int64_t grid = (int64_t)e->num_cus * 8 * (c.oc >= 64 ? 1 : 64 / c.oc);
-    if (grid > iters) grid = iters;
-    if (grid < 1) return 0;
-    auto kern = conv_mfma_kernel<IC, KW, STRIDE>;
+    a.in_row = in_row; a.pin = p.pin; a.pout = p.pout; a.out_row = out_row; a.out_coff = out_coff;
+    a.cb = p.cb; a.plane = p.plane; a.div_pout = make_fastdiv(p.pout);
+    a.nwin = p.nwin; a.pin_total = pin; a.pout_total = pout;
     RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(kern)));
     ProfScope ps(e, c.kid);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(threads), lds, e->stream, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(64 * (c.oc / 16)), p.lds, e->stream, a);
     RMR_HIP(hipGetLastError());
     return 0;
 }
@@ -265,13 +214,14 @@ static int launch_conv_t(rmr_engine *e, const ConvLayer &c, const float *in, int
 //  only 5 column tiles of work between its four barriers; removed.)
 
 int launch_conv(rmr_engine *e, const ConvLayer &c, const float *in, int in_row, int pin,
-                float *out, int out_row, int out_coff, int pout, int64_t n) {
+                float *out, int out_row, int out_coff, int pout, int64_t n, bool winograd) {
     if (in_row != c.ic) RMR_FAIL(RMR_ERR_INVALID, "conv input row %d != ic %d", in_row, c.ic);
     if (c.apack4) return launch_conv_stream(e, c, in, in_row, pin, out, out_row, out_coff, pout, n);  // > 64 channels: k_stream.hip
-    // 5 taps, stride 1, 64 output channels: Winograd F(4, 5), 0.4 of the MFMAs (k_wino.hip).  RMR_WINOGRAD=0: the direct form below
-    // (its comparand, tests/test_gpu_wino.py).  Every batch size takes it: the bits of a chunk do not depend on the batch it arrives in
-    if (conv_wino_supported(c, pin, pout) && tune_int("RMR_WINOGRAD", 1)) return launch_conv_wino(e, c, in, in_row, pin, out, out_row, out_coff, pout, n);
-    if (conv_wino_s3_supported(c, pin, pout) && tune_int("RMR_WINOGRAD", 1)) return launch_conv_wino_s3(e, c, in, in_row, pin, out, out_row, out_coff, pout, n);
+    // 5 taps, stride 1, 64 output channels: Winograd F(4, 5), 0.4 of the MFMAs (k_wino.hip).  !winograd (RMR_WINOGRAD=0): the direct
+    // form below (its comparand, tests/test_gpu_wino.py).  Every batch size takes it: the bits of a chunk do not depend on the batch
+    // it arrives in
+    if (winograd && conv_wino_supported(c, pin, pout)) return launch_conv_wino(e, c, in, in_row, pin, out, out_row, out_coff, pout, n);
+    if (winograd && conv_wino_s3_supported(c, pin, pout)) return launch_conv_wino_s3(e, c, in, in_row, pin, out, out_row, out_coff, pout, n);
 #define RMR_CONV_CASE(IC_, KW_, ST_)                                  \
     if (c.ic == IC_ && c.kw == KW_ && c.stride == ST_)                \
         return launch_conv_t<IC_, KW_, ST_>(e, c, in, in_row, pin, out, out_row, out_coff, pout, n);

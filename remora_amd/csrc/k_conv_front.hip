@@ -23,10 +23,9 @@
 // producer phase running under the other block's matrix phase is slowed by what it saves (shared fp32 datapath).
 // What did pay inside the producers: the K gathers of an item batched before the first add (1.22 -> 1.12), exact tile
 // groups + the next iteration's rows requested under the matrix phase (-> 1.00; sig -3 %).
-#include <algorithm>
-
 #include "rmr_internal.h"
 #include "rmr_math.h"
+#include "rmr_plan.h"
 
 namespace rmr {
 
@@ -946,223 +945,110 @@ __global__ __launch_bounds__(256, 2) void seq2_front_wino_kernel(ConvFrontArgs a
 
 }  // namespace
 
-static constexpr size_t CONV_FRONT_MAX_LDS = 156 * 1024;  // of the CU's 160 KB
+// the matrix-core producer's kernel of sig_conv1 width kw1 (5 or 11), Winograd or direct sig_conv3
+static void (*sig3_mfma_kernel(int kw1, bool wino))(ConvFrontArgs) {
+    return wino ? (kw1 == 5 ? sig3_front_wino_kernel<5, 6> : sig3_front_wino_kernel<11, 5>)
+                : (kw1 == 5 ? sig3_front_mfma_kernel<5, 6> : sig3_front_mfma_kernel<11, 5>);
+}
 
+static FrontPlan sig3_mfma_plan(const rmr_model *m, int64_t n, bool wino) {
+    rmr_engine *e = m->eng;
+    const int kw1 = m->front.kw1;
+    return plan_sig3_front_mfma(m->L, m->P1, m->P2, m->P3, n, e->num_cus, wino,
+                                e->kernel_regs(reinterpret_cast<const void *>(sig3_mfma_kernel(kw1, true))),
+                                e->kernel_regs(reinterpret_cast<const void *>(sig3_mfma_kernel(kw1, false))));
+}
+
+// one chunk per block iteration must fit a CU's LDS in both kernels (long chunk contexts / sequences otherwise go through the
+// separate front + conv_mfma kernels).  Whether a plan exists does not depend on the batch size, and the Winograd plans fall
+// back to the direct ones.
 bool conv_front_supported(const rmr_model *m, int kb, int ka, int seq_w, int map_w) {
     if (m->desc.arch != RMR_ARCH_CONV_LSTM || m->desc.size != 64 || m->nparts != 0 || m->front.kw1 != 5) return false;
     if (m->sig3.ic != 16 || m->sig3.kw != 9 || m->sig3.stride != 3 || m->sig3.oc != 64) return false;
     if (m->seq2.ic != 16 || m->seq2.kw != 13 || m->seq2.stride != 3 || m->seq2.oc != 64) return false;
     if (kb + ka + 1 != m->desc.kmer_len || m->desc.kmer_len != 9) return false;  // the instantiated k-mer length
     if (map_w < 2 || seq_w < map_w - 1 + m->desc.kmer_len - 1) return false;
-    // one chunk per block iteration must fit a CU's LDS in both kernels (long chunk contexts / sequences otherwise go
-    // through the separate front + conv_mfma kernels): the same sizes launch_conv_front computes
-    auto up4 = [](int words) { return (words + 3) & ~3; };
-    const size_t sig1 = ((size_t)(4 * (((m->P2 * 4) + 63) & ~63) + 16) + up4(((m->L + 3) & ~3) + m->P1 * 4)) * sizeof(float);
-    const int maxlen = map_w - 1;
-    const int per_seq = up4(up4((map_w * 2 + 3) / 4) + up4((seq_w + 3) / 4) + up4(maxlen * 2) + up4((m->L * 2 + 3) / 4) + (maxlen + 1) * 5 * 16);
-    const size_t seq1 = ((size_t)(4 * (((m->P1 * 4) + 63) & ~63) + 16) + 5 * m->desc.kmer_len * 80 + per_seq) * sizeof(float);
-    return sig1 <= CONV_FRONT_MAX_LDS && seq1 <= CONV_FRONT_MAX_LDS;
+    return plan_sig3_front_valu(m->L, m->P1, m->P2, 1, m->eng->num_cus).ok &&
+           plan_seq2_front(m->L, m->P1, m->P3, m->desc.kmer_len, seq_w, map_w, 1, m->eng->num_cus, false).ok;
 }
 
 bool sig3_front_mfma_supported(const rmr_model *m) {
     if (m->desc.size != 64 || m->nparts != 0 || (m->front.kw1 != 5 && m->front.kw1 != 11)) return false;
     if (m->sig3.ic != 16 || m->sig3.kw != 9 || m->sig3.stride != 3 || m->sig3.oc != 64) return false;
-    const int Lp = (m->L + 3) & ~3, Pst = (m->P1 + 16 + 3) & ~3;
-    const size_t one = ((size_t)(4 * (((m->P2 * 4) + 63) & ~63) + 16) + 4 * (size_t)(Lp + 4 * Pst)) * sizeof(float);
-    return one <= CONV_FRONT_MAX_LDS && tune_int("RMR_SIG3_MFMA", 1) != 0;
+    return sig3_mfma_plan(m, 1, false).ok;
 }
 
-// sig_conv1 -> sig_conv2 (matrix cores) -> sig_conv3 of `n` chunks into channels [0, 64) of cat [n][P3][out_row]
-int launch_sig3_front_mfma(rmr_model *m, const float *signal, int64_t n, float *cat) {
+// sig_conv1 -> sig_conv2 (matrix cores) -> sig_conv3 of `n` chunks into channels [0, 64) of cat [n][P3][out_row]; sig_conv3 in
+// polyphase Winograd form (sig3_front_wino_kernel) where its x-domain image fits beside the rows (rmr_plan.h), the direct form
+// for !winograd (RMR_WINOGRAD=0) and long chunk contexts
+int launch_sig3_front_mfma(rmr_model *m, const float *signal, int64_t n, float *cat, bool winograd) {
     rmr_engine *e = m->eng;
     if (n <= 0) return 0;
-    const int sz = m->desc.size, kw1 = m->front.kw1;
+    const FrontPlan p = sig3_mfma_plan(m, n, m->sig3.wpack && winograd);
+    if (!p.ok) RMR_FAIL(RMR_ERR_INVALID, "sig3_front: one chunk of %d samples does not fit the LDS", m->L);
     ConvFrontArgs a{};
     a.signal = signal; a.w_sig1 = m->front.w_sig1; a.b_sig1 = m->front.b_sig1; a.w_sig2 = m->front.w_sig2; a.b_sig2 = m->front.b_sig2;
     a.L = m->L; a.P1 = m->P1;
     a.out = cat; a.apack = m->sig3.apack; a.bias = m->sig3.bias; a.n = n;
-    a.pin = m->P2; a.pout = m->P3; a.out_row = 2 * sz; a.out_coff = 0; a.div_pout = make_fastdiv(m->P3);
-    const int Lp = (m->L + 3) & ~3, Pst = (m->P1 + 16 + 3) & ~3;
-    a.per_chunk = Lp + 4 * Pst;  // scratch per WAVE
-    // sig_conv3 in polyphase Winograd form (sig3_front_wino_kernel) where its x-domain image fits beside the rows; RMR_WINOGRAD=0 and
-    // long chunk contexts: the direct form
-    bool wino = m->sig3.wpack && tune_int("RMR_WINOGRAD", 1);
-    a.wpack = m->sig3.wpack; a.ngrp = (m->P3 + 3) / 4; a.div_ngrp = make_fastdiv(a.ngrp);
-    for (int attempt = 0; attempt < 2; ++attempt, wino = false) {
-        void (*kern)(ConvFrontArgs) = wino ? (kw1 == 5 ? sig3_front_wino_kernel<5, 6> : sig3_front_wino_kernel<11, 5>)
-                                           : (kw1 == 5 ? sig3_front_mfma_kernel<5, 6> : sig3_front_mfma_kernel<11, 5>);
-        // blocks per CU by registers, LDS share accordingly; among the chunk counts that fit, the one that fills its tiles best
-        static int regs_tab[2][2] = {{0, 0}, {0, 0}};
-        int &regs = regs_tab[wino ? 1 : 0][kw1 == 5 ? 0 : 1];
-        if (regs == 0) {
-            hipFuncAttributes attr;
-            regs = hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(kern)) == hipSuccess && attr.numRegs > 0 ? attr.numRegs : 256;
-        }
-        int resident = 512 / ((regs + 7) & ~7);
-        resident = resident < 1 ? 1 : (resident > 4 ? 4 : resident);
-        if (wino && resident > 2) resident = 2;  // V is 1.5 x the rows: four chunks per iteration need a half CU's LDS
-        size_t budget = (size_t)73728;
-        const size_t share = (size_t)160 * 1024 / resident - 512;
-        if (share < budget) budget = share;
-        // LDS of k chunks per iteration: the four row planes, (Winograd) V = 6 points x 12 (phase, plane) planes of the padded columns, the waves' scratch
-        auto plan = [&](int k, int *plane, int *vplane, size_t *need) {
-            *plane = ((k * a.pin * 4) + 63) & ~63;
-            *vplane = wino ? ((k * a.ngrp + 15) & ~15) * 4 : 0;
-            *need = ((size_t)4 * *plane + 16 + (size_t)72 * *vplane + 4 * (size_t)a.per_chunk) * sizeof(float);
-        };
-        // score of a chunk count = tile fill of the matrix phase x balance of the producer phase (4 waves, one chunk at a time)
-        int cb = 0;
-        size_t lds = 0;
-        double best = -1.0;
-        for (int k = 8; k >= 1; --k) {
-            int plane, vplane;
-            size_t need;
-            plan(k, &plane, &vplane, &need);
-            if (need > budget && !(k == 1 && !wino && need <= CONV_FRONT_MAX_LDS)) continue;
-            if (cb == 0) cb = k;            // the largest count that fits
-            if (2 * k < cb) break;          // never below half of it
-            const int cols = wino ? k * a.ngrp : k * a.pout;
-            const double score = (double)cols / (16.0 * ((cols + 15) / 16)) * (double)k / (4.0 * ((k + 3) / 4));
-            if (score > best + 1e-9) { best = score; a.cb = k; lds = need; }
-        }
-        if (cb == 0 || (wino && a.cb < 3)) {
-            // Winograd with fewer than three chunks per iteration (C200: rows + V of ONE chunk fill a half CU) leaves three of the four
-            // producing waves idle - 4.5 against the direct form's 3.1 ms per 250 k chunks; the direct form has its own plan for long chunks
-            if (wino) continue;
-            RMR_FAIL(RMR_ERR_INVALID, "sig3_front: one chunk of %d samples does not fit the LDS", m->L);
-        }
-        while (a.cb > 1 && (n + a.cb - 1) / a.cb < e->num_cus) a.cb = (a.cb + 1) / 2;  // a small batch spread over the CUs (same bits for any count)
-        plan(a.cb, &a.plane, &a.vplane, &lds);
-        a.o_v = 4 * a.plane + 16;
-        a.o_front = a.o_v + 72 * a.vplane;
-        a.abl = abl_int("RMR_CONV_FRONT_ABLATE", 0);  // ignored unless built with -DRMR_TIMING_ABLATIONS
-        const int64_t iters = (n + a.cb - 1) / a.cb;
-        int64_t grid = (int64_t)e->num_cus * 8;
-        if (grid > iters) grid = iters;
-        RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(kern)));
-        ProfScope ps(e, K_SIG3_FRONT);
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, e->stream, a);
-        RMR_HIP(hipGetLastError());
-        return 0;
-    }
-    RMR_FAIL(RMR_ERR_INVALID, "sig3_front: no launch plan");
+    a.pin = m->P2; a.pout = m->P3; a.out_row = 2 * m->desc.size; a.out_coff = 0; a.div_pout = make_fastdiv(m->P3);
+    a.per_chunk = p.per_chunk;  // scratch per WAVE
+    a.wpack = m->sig3.wpack; a.ngrp = p.ngrp; a.div_ngrp = make_fastdiv(p.ngrp);
+    a.cb = p.cb; a.plane = p.plane; a.vplane = p.vplane; a.o_v = p.o_v; a.o_front = p.o_front;
+    a.abl = abl_int("RMR_CONV_FRONT_ABLATE", 0);  // ignored unless built with -DRMR_TIMING_ABLATIONS
+    void (*kern)(ConvFrontArgs) = sig3_mfma_kernel(m->front.kw1, p.wino);
+    RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(kern)));
+    ProfScope ps(e, K_SIG3_FRONT);
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(256), p.lds, e->stream, a);
+    RMR_HIP(hipGetLastError());
+    return 0;
 }
 
 // sig_conv3 (+ sig_conv1/2) and seq_conv2 (+ seq_conv1) of `n` chunks into the two halves of cat [n][P3][128]
 int launch_conv_front(rmr_model *m, const float *signal, const int8_t *seqs, int seq_w, const int16_t *maps, int map_w,
-                      const int16_t *lens, int64_t n, float *cat) {
+                      const int16_t *lens, int64_t n, float *cat, const FwdSwitches &sw) {
     rmr_engine *e = m->eng;
     if (n <= 0) return 0;
     const int sz = m->desc.size, K = m->desc.kmer_len;
-    const int budget = 73728;
-    auto up4 = [](int words) { return (words + 3) & ~3; };
     // The matrix-core producer is the default since round 4: bit-identical to the VALU one, 5.39 against 5.47 ns per chunk at
     // C100 (12.57 against 12.03 at C200), and it is the one that stayed exact next to foreign processes on the same GPU in
-    // every run (rmr_math.h, pk_fma).  RMR_SIG3_MFMA=0 selects the VALU producers (the comparand of tests/test_gpu_conv_front.py).
-    if (sig3_front_mfma_supported(m)) {
-        RMR_TRY(launch_sig3_front_mfma(m, signal, n, cat));
+    // every run (rmr_math.h, pk_fma).  !sig3_mfma (RMR_SIG3_MFMA=0) selects the VALU producers (the comparand of
+    // tests/test_gpu_conv_front.py).
+    if (sw.sig3_mfma && sig3_front_mfma_supported(m)) {
+        RMR_TRY(launch_sig3_front_mfma(m, signal, n, cat, sw.winograd));
     } else {   // ---- signal branch, VALU producer ----
+        const FrontPlan p = plan_sig3_front_valu(m->L, m->P1, m->P2, n, e->num_cus);
+        if (!p.ok) RMR_FAIL(RMR_ERR_INVALID, "sig3_front: one chunk of %d samples needs %zu B of LDS", m->L, p.lds);
         ConvFrontArgs a{};
         a.signal = signal; a.w_sig1 = m->front.w_sig1; a.b_sig1 = m->front.b_sig1; a.w_sig2 = m->front.w_sig2; a.b_sig2 = m->front.b_sig2;
         a.L = m->L; a.P1 = m->P1;
         a.out = cat; a.apack = m->sig3.apack; a.bias = m->sig3.bias; a.n = n;
         a.pin = m->P2; a.pout = m->P3; a.out_row = 2 * sz; a.out_coff = 0; a.div_pout = make_fastdiv(m->P3);
-        a.per_chunk = up4(((m->L + 3) & ~3) + m->P1 * 4);
-        int cb = 8;
-        size_t lds = 0;
-        for (; cb >= 1; --cb) {
-            a.plane = ((cb * a.pin * 4) + 63) & ~63;
-            a.o_front = 4 * a.plane + 16;
-            lds = ((size_t)a.o_front + (size_t)cb * a.per_chunk) * sizeof(float);
-            if (lds <= (size_t)budget) break;
-        }
-        if (cb < 1) {  // a long chunk context: one chunk per iteration, one block per CU
-            cb = 1;
-            if (lds > CONV_FRONT_MAX_LDS) RMR_FAIL(RMR_ERR_INVALID, "sig3_front: one chunk of %d samples needs %zu B of LDS", m->L, lds);
-        }
-        a.cb = cb;
+        a.per_chunk = p.per_chunk; a.cb = p.cb; a.plane = p.plane; a.o_front = p.o_front;
         a.abl = abl_int("RMR_CONV_FRONT_ABLATE", 0);  // ignored unless built with -DRMR_TIMING_ABLATIONS
-        const int64_t iters = (n + cb - 1) / cb;
-        int64_t grid = (int64_t)e->num_cus * 8;
-        if (grid > iters) grid = iters;
         RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(sig3_front_kernel)));
         ProfScope ps(e, K_SIG3_FRONT);
-        hipLaunchKernelGGL(sig3_front_kernel, dim3((unsigned)grid), dim3(256), lds, e->stream, a);
+        hipLaunchKernelGGL(sig3_front_kernel, dim3((unsigned)p.grid), dim3(256), p.lds, e->stream, a);
         RMR_HIP(hipGetLastError());
     }
-    {   // ---- sequence branch ----
-        ConvFrontArgs a{};
-        a.seqs = seqs; a.maps = maps; a.lens = lens; a.wt5 = m->front.wt5_seq1; a.b_seq1 = m->front.b_seq1;
-        a.L = m->L; a.P1 = m->P1; a.seq_w = seq_w; a.map_w = map_w; a.K = K; a.maxlen = map_w - 1;
-        a.out = cat; a.apack = m->seq2.apack; a.bias = m->seq2.bias; a.n = n;
-        a.pin = m->P1; a.pout = m->P3; a.out_row = 2 * sz; a.out_coff = sz; a.div_pout = make_fastdiv(m->P3);
-        int off = 0;
-        a.o_map = off; off += up4((map_w * 2 + 3) / 4);
-        a.o_seq = off; off += up4((seq_w + 3) / 4);
-        a.o_code = off; off += up4(a.maxlen * 2);
-        a.o_pidx = off; off += up4((m->L * 2 + 3) / 4);
-        a.o_u = off; off += (a.maxlen + 1) * 5 * 16;
-        a.per_chunk = up4(off);
-        const int wt_words = 5 * K * 80;
-        int cb = 8;
-        size_t lds = 0;
-        // seq_conv2 in polyphase Winograd form (seq2_front_wino_kernel) where at least three chunks per iteration fit a half CU with V in
-        // the place of the gather table and the scratch; RMR_WINOGRAD=0, long chunks and small batches: the direct form
-        bool wino = false;
-        if (m->seq2.wpack && tune_int("RMR_WINOGRAD", 1)) {
-            a.wpack = m->seq2.wpack; a.ngrp = (m->P3 + 3) / 4; a.div_ngrp = make_fastdiv(a.ngrp);
-            auto plan = [&](int k) {
-                a.plane = ((k * a.pin * 4) + 63) & ~63;
-                a.vplane = ((k * a.ngrp + 15) & ~15) * 4;
-                a.o_front = 4 * a.plane + 16;
-                a.o_v = a.o_front;
-                return ((size_t)a.o_front + std::max((size_t)wt_words + (size_t)k * a.per_chunk, (size_t)96 * a.vplane)) * sizeof(float);
-            };
-            for (int k = 8; k >= 3 && !wino; --k)
-                if (plan(k) <= (size_t)80 * 1024 - 512) { wino = true; cb = k; }
-            if (wino) {
-                while (cb > 1 && (n + cb - 1) / cb < e->num_cus) cb = (cb + 1) / 2;  // a small batch spread over the CUs (same bits for any count)
-                lds = plan(cb);
-            }
-        }
-        if (wino) {
-            a.cb = cb;
-            a.abl = 0;
-            const int64_t iters = (n + cb - 1) / cb;
-            int64_t grid = (int64_t)e->num_cus * 8;
-            if (grid > iters) grid = iters;
-            RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(seq2_front_wino_kernel<9>)));
-            ProfScope ps(e, K_SEQ2_FRONT);
-            hipLaunchKernelGGL(seq2_front_wino_kernel<9>, dim3((unsigned)grid), dim3(256), lds, e->stream, a);
-            RMR_HIP(hipGetLastError());
-            return 0;
-        }
-        for (; cb >= 1; --cb) {
-            a.plane = ((cb * a.pin * 4) + 63) & ~63;
-            a.o_front = 4 * a.plane + 16;
-            lds = ((size_t)a.o_front + wt_words + (size_t)cb * a.per_chunk) * sizeof(float);
-            if (lds <= (size_t)budget) break;
-        }
-        if (cb < 1) {
-            cb = 1;
-            if (lds > CONV_FRONT_MAX_LDS) RMR_FAIL(RMR_ERR_INVALID, "seq2_front: max_seq_len %d needs %zu B of LDS", a.maxlen, lds);
-        }
-        while (cb > 1 && (n + cb - 1) / cb < e->num_cus) {  // a small batch spread over the CUs (same bits for any count)
-            cb = (cb + 1) / 2;
-            a.plane = ((cb * a.pin * 4) + 63) & ~63;
-            a.o_front = 4 * a.plane + 16;
-            lds = ((size_t)a.o_front + wt_words + (size_t)cb * a.per_chunk) * sizeof(float);
-        }
-        a.cb = cb;
-        a.abl = abl_int("RMR_CONV_FRONT_ABLATE", 0);  // ignored unless built with -DRMR_TIMING_ABLATIONS
-        const int64_t iters = (n + cb - 1) / cb;
-        int64_t grid = (int64_t)e->num_cus * 8;
-        if (grid > iters) grid = iters;
-        RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(seq2_front_kernel<9>)));
-        ProfScope ps(e, K_SEQ2_FRONT);
-        hipLaunchKernelGGL(seq2_front_kernel<9>, dim3((unsigned)grid), dim3(256), lds, e->stream, a);
-        RMR_HIP(hipGetLastError());
-    }
+    // ---- sequence branch: seq_conv2 in polyphase Winograd form (seq2_front_wino_kernel) where at least three chunks per
+    // iteration fit; !winograd, long chunks and small batches: the direct form ----
+    const bool wino = m->seq2.wpack && sw.winograd;
+    const FrontPlan p = plan_seq2_front(m->L, m->P1, m->P3, K, seq_w, map_w, n, e->num_cus, wino);
+    if (!p.ok) RMR_FAIL(RMR_ERR_INVALID, "seq2_front: max_seq_len %d needs %zu B of LDS", map_w - 1, p.lds);
+    ConvFrontArgs a{};
+    a.seqs = seqs; a.maps = maps; a.lens = lens; a.wt5 = m->front.wt5_seq1; a.b_seq1 = m->front.b_seq1;
+    a.L = m->L; a.P1 = m->P1; a.seq_w = seq_w; a.map_w = map_w; a.K = K; a.maxlen = map_w - 1;
+    a.out = cat; a.apack = m->seq2.apack; a.bias = m->seq2.bias; a.n = n;
+    a.pin = m->P1; a.pout = m->P3; a.out_row = 2 * sz; a.out_coff = sz; a.div_pout = make_fastdiv(m->P3);
+    a.o_map = p.o_map; a.o_seq = p.o_seq; a.o_code = p.o_code; a.o_pidx = p.o_pidx; a.o_u = p.o_u; a.per_chunk = p.per_chunk;
+    if (wino) { a.wpack = m->seq2.wpack; a.ngrp = p.ngrp; a.div_ngrp = make_fastdiv(p.ngrp); }
+    a.cb = p.cb; a.plane = p.plane; a.vplane = p.vplane; a.o_v = p.o_v; a.o_front = p.o_front;
+    a.abl = p.wino ? 0 : abl_int("RMR_CONV_FRONT_ABLATE", 0);  // ignored unless built with -DRMR_TIMING_ABLATIONS
+    void (*kern)(ConvFrontArgs) = p.wino ? seq2_front_wino_kernel<9> : seq2_front_kernel<9>;
+    RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(kern)));
+    ProfScope ps(e, K_SEQ2_FRONT);
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(256), p.lds, e->stream, a);
+    RMR_HIP(hipGetLastError());
     return 0;
 }
 

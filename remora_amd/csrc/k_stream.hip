@@ -423,9 +423,7 @@ int launch_lstm_stream(rmr_model *m, const float *x, int64_t n, float *logits) {
     a.a_ih1 = m->lstm.t_ih1; a.a_hh1 = m->lstm.t_hh1; a.b1 = m->lstm.b1;
     a.a_ih2 = m->lstm.t_ih2; a.b2 = m->lstm.b2; a.w_fc = m->lstm.w_fc; a.b_fc = m->lstm.b_fc;
     // column tiles per wave: four halve the weight traffic of two, and fit (registers: 512 threads; LDS) up to 128 units
-    const int nt = (H <= 128 ? 4 : 2);
-    if (H <= 128 && nt == 4) return launch_lstm_stream_t<4, 512>(m, a, n);
-    if (H <= 128) return launch_lstm_stream_t<2, 512>(m, a, n);
+    if (H <= 128) return launch_lstm_stream_t<4, 512>(m, a, n);
     return launch_lstm_stream_t<2, 1024>(m, a, n);
 }
 

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/remora_hip.h"
@@ -113,6 +114,9 @@ struct rmr_engine {
     // process would skip the second engine of a multi-GPU process); guarded by `mu` like every launch
     std::vector<const void *> lds_attr_set;
     int allow_big_lds(const void *kernel, size_t bytes = 160 * 1024);  // `bytes`: the dynamic share (a kernel with static LDS asks for less)
+    // numRegs of a kernel (256 where it cannot be read), the input of its launch plan (rmr_plan.h); guarded by `mu` as well
+    std::vector<std::pair<const void *, int>> regs_seen;
+    int kernel_regs(const void *kernel);
 
     // profiling
     bool profiling = false;
@@ -272,15 +276,23 @@ int launch_front(rmr_model *m, hipStream_t st, const float *signal, const int8_t
                  const int16_t *maps, int map_w, const int16_t *lens, int kb, int ka, int64_t n,
                  float *sig2, float *seq1 /* nullptr: skip seq path */);
 int launch_seq1_dense(rmr_model *m, const float *enc, int64_t n, float *seq1);
+// the kernel switches of the fp32 path: read from the environment once per forward call (run_pipeline) and passed
+// down, so that a change between two calls on the same model takes effect
+struct FwdSwitches {
+    bool fused;       // RMR_FUSED
+    bool conv_front;  // RMR_CONV_FRONT
+    bool winograd;    // RMR_WINOGRAD
+    bool sig3_mfma;   // RMR_SIG3_MFMA
+};
 // k_conv_front.hip: fp32 sig_conv3 / seq_conv2 with their producers (sig_conv1/2, seq_conv1) folded into the staging
 bool conv_front_supported(const rmr_model *m, int kb, int ka, int seq_w, int map_w);
 // the signal half alone with sig_conv2 on the matrix cores (both architectures, 5 or 11 taps): signal -> cat channels [0, 64)
 bool sig3_front_mfma_supported(const rmr_model *m);
-int launch_sig3_front_mfma(rmr_model *m, const float *signal, int64_t n, float *cat);
+int launch_sig3_front_mfma(rmr_model *m, const float *signal, int64_t n, float *cat, bool winograd);
 int launch_conv_front(rmr_model *m, const float *signal, const int8_t *seqs, int seq_w, const int16_t *maps, int map_w,
-                      const int16_t *lens, int64_t n, float *cat);
+                      const int16_t *lens, int64_t n, float *cat, const FwdSwitches &sw);
 int launch_conv(rmr_engine *e, const ConvLayer &c, const float *in, int in_row, int pin,
-                float *out, int out_row, int out_coff, int pout, int64_t n);
+                float *out, int out_row, int out_coff, int pout, int64_t n, bool winograd);
 int launch_lstm_head(rmr_model *m, const float *x, int64_t n, float *logits);
 // k_wino.hip: the 5-tap stride-1 layers of 64 output channels as a Winograd F(4, 5) convolution (0.4 of the direct form's MFMAs)
 bool conv_wino_supported(const ConvLayer &c, int pin, int pout);

@@ -1,0 +1,234 @@
+// Launch plans of the fp32 convolutions: conv_mfma_kernel (k_conv.hip) and the folded fronts sig3_front_* / seq2_front_*
+// (k_conv_front.hip) - chunks per block iteration, LDS layout, dynamic LDS bytes and grid, from the model geometry, the batch
+// size, the CU count and the kernel's registers.  Plain integers in, a plain struct out, no HIP: the support checks and the
+// launchers call the same function (tests/c/front_plans.cpp calls it on the CPU).
+//
+// The common recipe: blocks per CU from the kernel's registers (512 per SIMD lane, granule 8), the LDS budget of a block =
+// its share of the CU's 160 KB at that occupancy, capped at 72 KB (two blocks per CU); the chunk count per iteration that
+// fits the budget (and fills its 16-column tiles best); fewer chunks for a small batch; persistent blocks, 8 per CU.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+namespace rmr {
+
+constexpr size_t PLAN_LDS_CU = 160 * 1024;
+constexpr size_t PLAN_LDS_BUDGET = 73728;           // 72 KB: two blocks per CU
+constexpr size_t CONV_FRONT_MAX_LDS = 156 * 1024;   // what one front block may take of the CU's 160 KB (a long chunk context)
+
+// blocks of `waves` waves each that a CU (4 SIMDs) holds at `regs` registers per lane, clamped to [1, max_blocks]
+inline int plan_resident(int regs, int waves, int max_blocks) {
+    int wps = 512 / ((regs + 7) & ~7);
+    wps = wps < 1 ? 1 : (wps > 8 ? 8 : wps);
+    const int r = wps * 4 / waves;
+    return r < 1 ? 1 : (r > max_blocks ? max_blocks : r);
+}
+inline size_t plan_budget(int resident) {
+    const size_t share = PLAN_LDS_CU / resident - 512;
+    return share < PLAN_LDS_BUDGET ? share : PLAN_LDS_BUDGET;
+}
+inline double plan_tile_fill(int cols) { return (double)cols / (16.0 * ((cols + 15) / 16)); }
+// a small batch (one read per call: a few hundred chunks) spread over the CUs: fewer chunks per iteration until there is a
+// block for every CU - a chunk's columns are computed the same way whatever its neighbours in the iteration (same bits), and
+// a half-filled tile on an otherwise idle CU costs nothing
+inline int plan_spread(int cb, int64_t n, int num_cus) {
+    while (cb > 1 && (n + cb - 1) / cb < num_cus) cb = (cb + 1) / 2;
+    return cb;
+}
+// persistent blocks: a grid of several times the resident count evens out the tail
+inline int64_t plan_grid(int64_t iters, int num_cus, int per_cu) {
+    const int64_t g = (int64_t)num_cus * per_cu;
+    return g < iters ? g : iters;
+}
+// floats per LDS row plane of k chunks of `pin` rows (4 channels a row), and per Winograd V plane of k chunks of `ngrp` groups
+inline int plan_plane(int k, int pin) { return ((k * pin * 4) + 63) & ~63; }
+inline int plan_vplane(int k, int ngrp) { return ((k * ngrp + 15) & ~15) * 4; }
+inline int up4(int words) { return (words + 3) & ~3; }
+
+// ---- conv_mfma_kernel<IC, KW, STRIDE> of `oc` output channels (k_conv.hip) ----
+struct ConvPlan {
+    bool ok = false;
+    int cb = 0;                  // chunks per iteration (1 with windows)
+    int nwin = 1, pin = 0, pout = 0;  // position windows: rows staged / columns computed per window (the chunk's when nwin == 1)
+    int plane = 0;               // LDS plane stride in floats
+    size_t budget = 0, lds = 0;  // the block's LDS share; dynamic LDS bytes
+    int64_t grid = 0;
+};
+
+inline ConvPlan plan_conv_mfma(int ic, int kw, int stride, int oc, int pin, int pout, int64_t n, int num_cus, int regs) {
+    ConvPlan p;
+    const int RS = (ic / 16) % 2 == 0 ? ic / 4 + 4 : ic / 4;  // floats per row per plane (conv_mfma_kernel)
+    p.budget = plan_budget(plan_resident(regs, oc / 16, 8));
+    // among the chunk counts that fit, the one whose columns fill their 16-column tiles best wins (Conv_w_ref's merge_conv1:
+    // 4 x 20 columns = 5 tiles exactly, where 5 chunks would pad the 7th tile to 25 %); ties go to the larger count
+    const size_t row_bytes = (size_t)pin * RS * 4 * sizeof(float);  // all four planes
+    int cb_max = (int)(p.budget / row_bytes);
+    cb_max = cb_max < 1 ? 1 : (cb_max > 8 ? 8 : cb_max);
+    int cb = cb_max;
+    double best = -1.0;
+    for (int k = cb_max; k >= (cb_max + 1) / 2; --k) {
+        const double eff = plan_tile_fill(k * pout);
+        if (eff > best + 1e-9) { best = eff; cb = k; }
+    }
+    cb = plan_spread(cb, n, num_cus);
+    // a chunk whose rows do not fit the share goes through position windows: the most output positions whose input rows
+    // ((win - 1) * stride + kw of them) fit, whole column tiles, one window of one chunk per iteration
+    p.pin = pin;
+    p.pout = pout;
+    if (row_bytes > p.budget) {
+        const int rows_fit = (int)(p.budget / ((size_t)RS * 4 * sizeof(float)));
+        p.pout = (rows_fit - kw) / stride + 1;
+        if (p.pout < 16) return p;
+        p.pout &= ~15;
+        p.nwin = (pout + p.pout - 1) / p.pout;
+        p.pin = (p.pout - 1) * stride + kw;
+        cb = 1;
+    }
+    p.cb = cb;
+    p.plane = ((cb * p.pin * RS) + 63) & ~63;
+    p.lds = (size_t)p.plane * 4 * sizeof(float) + 64;  // + trash slot for masked staging writes
+    if (p.lds > PLAN_LDS_CU) return p;
+    const int64_t iters = p.nwin > 1 ? n * p.nwin : (n + cb - 1) / cb;
+    p.grid = plan_grid(iters, num_cus, 8 * (oc >= 64 ? 1 : 64 / oc));
+    p.ok = true;
+    return p;
+}
+
+// ---- the folded fronts (k_conv_front.hip): 4 waves, 64 output channels, 16 input channels (4 floats per row and plane) ----
+struct FrontPlan {
+    bool ok = false;
+    bool wino = false;       // the Winograd kernel (sig3_front_wino_kernel / seq2_front_wino_kernel)
+    int cb = 0;              // chunks per iteration
+    int plane = 0;           // floats per row plane
+    int vplane = 0, o_v = 0; // Winograd: floats per V plane, LDS offset of V
+    int o_front = 0;         // LDS offset of the producer scratch
+    int per_chunk = 0;       // producer scratch per chunk (sig3 matrix-core producer: per wave)
+    int o_map = 0, o_seq = 0, o_code = 0, o_pidx = 0, o_u = 0;  // seq2: offsets inside a chunk's scratch
+    int ngrp = 0;            // groups of four output positions per chunk (the Winograd forms)
+    size_t budget = 0;       // the LDS budget the chunk count was chosen against (one chunk may exceed it: CONV_FRONT_MAX_LDS)
+    size_t lds = 0;          // dynamic LDS bytes
+    int64_t grid = 0;
+};
+
+inline void plan_finish(FrontPlan &p, int64_t n, int num_cus) {
+    p.grid = plan_grid((n + p.cb - 1) / p.cb, num_cus, 8);
+    p.ok = true;
+}
+
+// sig_conv1 -> sig_conv2 (matrix cores) -> sig_conv3 (sig3_front_mfma_kernel / sig3_front_wino_kernel).  `wino`: the
+// Winograd form is allowed; it is taken where at least three chunks per iteration fit (with fewer, three of the four producing
+// waves idle: C200, 4.5 against the direct form's 3.1 ms per 250 k chunks).  The direct form takes one chunk past the 72 KB
+// budget (long chunk contexts), up to CONV_FRONT_MAX_LDS.
+inline void plan_sig3_mfma_layout(FrontPlan &p, int k, int P2) {
+    p.plane = plan_plane(k, P2);
+    p.vplane = p.wino ? plan_vplane(k, p.ngrp) : 0;
+    p.o_v = 4 * p.plane + 16;
+    p.o_front = p.o_v + 72 * p.vplane;  // V = 6 points x 12 (phase, plane) planes
+    p.lds = ((size_t)p.o_front + 4 * (size_t)p.per_chunk) * sizeof(float);
+}
+
+inline FrontPlan plan_sig3_front_mfma(int L, int P1, int P2, int P3, int64_t n, int num_cus, bool wino, int regs_wino,
+                                      int regs_direct) {
+    FrontPlan p;
+    p.per_chunk = ((L + 3) & ~3) + 4 * ((P1 + 16 + 3) & ~3);
+    p.ngrp = (P3 + 3) / 4;
+    for (p.wino = wino;; p.wino = false) {
+        int resident = plan_resident(p.wino ? regs_wino : regs_direct, 4, 4);
+        if (p.wino && resident > 2) resident = 2;  // V is 1.5 x the rows: four chunks per iteration need a half CU's LDS
+        const size_t budget = p.budget = plan_budget(resident);
+        // score of a chunk count = tile fill of the matrix phase x balance of the producer phase (4 waves, one chunk at a time),
+        // never below half of the largest count that fits
+        int cb_max = 0, cb = 0;
+        double best = -1.0;
+        for (int k = 8; k >= 1; --k) {
+            plan_sig3_mfma_layout(p, k, P2);
+            if (p.lds > budget && !(k == 1 && !p.wino && p.lds <= CONV_FRONT_MAX_LDS)) continue;
+            if (cb_max == 0) cb_max = k;
+            if (2 * k < cb_max) break;
+            const double score = plan_tile_fill(p.wino ? k * p.ngrp : k * P3) * (double)k / (4.0 * ((k + 3) / 4));
+            if (score > best + 1e-9) { best = score; cb = k; }
+        }
+        if (cb_max == 0 || (p.wino && cb < 3)) {
+            if (p.wino) continue;
+            return p;  // one chunk does not fit
+        }
+        p.cb = plan_spread(cb, n, num_cus);
+        plan_sig3_mfma_layout(p, p.cb, P2);
+        plan_finish(p, n, num_cus);
+        return p;
+    }
+}
+
+// the same with the VALU producers (sig3_front_kernel): the largest chunk count within 72 KB, else one chunk per iteration up
+// to CONV_FRONT_MAX_LDS; no spreading of small batches
+inline FrontPlan plan_sig3_front_valu(int L, int P1, int P2, int64_t n, int num_cus) {
+    FrontPlan p;
+    p.per_chunk = up4(((L + 3) & ~3) + P1 * 4);
+    p.budget = PLAN_LDS_BUDGET;
+    for (p.cb = 8; p.cb >= 1; --p.cb) {
+        p.plane = plan_plane(p.cb, P2);
+        p.o_front = 4 * p.plane + 16;
+        p.lds = ((size_t)p.o_front + (size_t)p.cb * p.per_chunk) * sizeof(float);
+        if (p.lds <= p.budget || p.cb == 1) break;
+    }
+    if (p.lds > CONV_FRONT_MAX_LDS) return p;
+    plan_finish(p, n, num_cus);
+    return p;
+}
+
+// seq_conv1 (the gather-sum) -> seq_conv2 (seq2_front_kernel / seq2_front_wino_kernel).  `wino`: the polyphase Winograd form
+// is allowed; it is taken where at least three chunks per iteration fit a half CU with V in the place of the gather table and
+// the scratch.  The direct form: the largest chunk count within 72 KB, else one chunk up to CONV_FRONT_MAX_LDS.
+inline FrontPlan plan_seq2_front(int L, int P1, int P3, int K, int seq_w, int map_w, int64_t n, int num_cus, bool wino) {
+    FrontPlan p;
+    const int maxlen = map_w - 1, wt_words = 5 * K * 80;  // wt_words: the gather table
+    int off = 0;
+    p.o_map = off; off += up4((map_w * 2 + 3) / 4);
+    p.o_seq = off; off += up4((seq_w + 3) / 4);
+    p.o_code = off; off += up4(maxlen * 2);
+    p.o_pidx = off; off += up4((L * 2 + 3) / 4);
+    p.o_u = off; off += (maxlen + 1) * 5 * 16;
+    p.per_chunk = up4(off);
+    if (wino) {
+        p.ngrp = (P3 + 3) / 4;
+        auto layout = [&](int k) {
+            p.plane = plan_plane(k, P1);
+            p.vplane = plan_vplane(k, p.ngrp);
+            p.o_front = p.o_v = 4 * p.plane + 16;
+            const size_t front = (size_t)wt_words + (size_t)k * p.per_chunk, v = (size_t)96 * p.vplane;
+            p.lds = ((size_t)p.o_front + (front > v ? front : v)) * sizeof(float);
+        };
+        int k = 8;
+        for (; k >= 3; --k) {
+            layout(k);
+            if (p.lds <= (size_t)80 * 1024 - 512) break;
+        }
+        if (k >= 3) {
+            p.wino = true;
+            p.budget = (size_t)80 * 1024 - 512;
+            p.cb = plan_spread(k, n, num_cus);
+            layout(p.cb);
+            plan_finish(p, n, num_cus);
+            return p;
+        }
+        // (the direct kernel reads neither vplane nor o_v: they keep what the three-chunk trial left)
+    }
+    auto layout = [&](int k) {
+        p.plane = plan_plane(k, P1);
+        p.o_front = 4 * p.plane + 16;
+        p.lds = ((size_t)p.o_front + wt_words + (size_t)k * p.per_chunk) * sizeof(float);
+    };
+    p.budget = PLAN_LDS_BUDGET;
+    int k = 8;
+    for (; k > 1; --k) {
+        layout(k);
+        if (p.lds <= p.budget) break;
+    }
+    p.cb = plan_spread(k, n, num_cus);
+    layout(p.cb);
+    if (p.lds > CONV_FRONT_MAX_LDS) return p;
+    plan_finish(p, n, num_cus);
+    return p;
+}
+
+}  // namespace rmr

@@ -2802,6 +2802,53 @@ def test_chunk_geometry_searches_from_a_hint_equal_bisection(tmp_path):
     assert run.returncode == 0 and run.stdout.strip().endswith("0 mismatches"), run.stdout + run.stderr
 
 
+def test_front_plans_fit_their_budgets_and_pin_the_benchmark_shapes(tmp_path):
+    """rmr_plan.h is the ONE place where the launch plans of the fp32 conv and front kernels are made (the support checks and the
+    launchers of k_conv.hip / k_conv_front.hip call it).  tests/c/front_plans.cpp: over a sweep of chunk lengths, sequence
+    widths, batch sizes, CU counts and register counts every plan stays within the LDS budget it was planned against and within
+    160 KB; the plans of ConvLSTM_w_ref size 64 at C100 / C200 (256 CUs, the kernels' gfx950 register counts) are pinned."""
+    import shutil
+
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is part of the image"
+    (tmp_path / "hip").mkdir()
+    (tmp_path / "hip" / "hip_runtime.h").write_text("#pragma once\n#define __host__\n#define __device__\n")
+    exe = str(tmp_path / "plans")
+    cc = subprocess.run([gxx, "-O2", "-std=c++17", "-Wall", "-I", str(tmp_path), "-I", os.path.join(ROOT, "remora_amd", "csrc"),
+                         os.path.join(ROOT, "tests", "c", "front_plans.cpp"), "-o", exe], capture_output=True, text=True)
+    assert cc.returncode == 0, cc.stderr
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, run.stdout + run.stderr
+    out = run.stdout.strip().splitlines()
+    assert out[0].endswith(" 0 violations") and int(out[0].split()[0]) > 1_000_000, out[0]
+    assert out[1:] == [
+        "C100/262144 sig3_mfma ok=1 wino=1 cb=4 plane=1472 vplane=128 o_v=5904 o_front=15120 per_chunk=548 o_map=0 o_seq=0 o_code=0 o_pidx=0 o_u=0 lds=69248 grid=2048",
+        "C100/262144 sig3_valu ok=1 wino=0 cb=8 plane=2944 vplane=0 o_v=0 o_front=11792 per_chunk=484 o_map=0 o_seq=0 o_code=0 o_pidx=0 o_u=0 lds=62656 grid=2048",
+        "C100/262144 seq2 ok=1 wino=1 cb=4 plane=1536 vplane=128 o_v=6160 o_front=6160 per_chunk=1792 o_map=0 o_seq=12 o_code=20 o_pidx=60 o_u=112 lds=73792 grid=2048",
+        "C100/262144 seq2_direct ok=1 wino=0 cb=4 plane=1536 vplane=0 o_v=0 o_front=6160 per_chunk=1792 o_map=0 o_seq=12 o_code=20 o_pidx=60 o_u=112 lds=67712 grid=2048",
+        "C100/262144 sig_conv3 ok=1 cb=4 nwin=1 pin=92 pout=28 plane=1472 lds=23616 grid=2048",
+        "C100/262144 seq_conv2 ok=1 cb=4 nwin=1 pin=96 pout=28 plane=1536 lds=24640 grid=2048",
+        "C100/300 sig3_mfma ok=1 wino=1 cb=1 plane=384 vplane=64 o_v=1552 o_front=6160 per_chunk=548 o_map=0 o_seq=0 o_code=0 o_pidx=0 o_u=0 lds=33408 grid=300",
+        "C100/300 sig3_valu ok=1 wino=0 cb=8 plane=2944 vplane=0 o_v=0 o_front=11792 per_chunk=484 o_map=0 o_seq=0 o_code=0 o_pidx=0 o_u=0 lds=62656 grid=38",
+        "C100/300 seq2 ok=1 wino=1 cb=1 plane=384 vplane=64 o_v=1552 o_front=1552 per_chunk=1792 o_map=0 o_seq=12 o_code=20 o_pidx=60 o_u=112 lds=30784 grid=300",
+        "C100/300 seq2_direct ok=1 wino=0 cb=1 plane=384 vplane=0 o_v=0 o_front=1552 per_chunk=1792 o_map=0 o_seq=12 o_code=20 o_pidx=60 o_u=112 lds=27776 grid=300",
+        "C100/300 sig_conv3 ok=1 cb=1 nwin=1 pin=92 pout=28 plane=384 lds=6208 grid=300",
+        "C100/300 seq_conv2 ok=1 cb=1 nwin=1 pin=96 pout=28 plane=384 lds=6208 grid=300",
+        "C200/262144 sig3_mfma ok=1 wino=0 cb=3 plane=2304 vplane=0 o_v=9232 o_front=9232 per_chunk=1048 o_map=0 o_seq=0 o_code=0 o_pidx=0 o_u=0 lds=53696 grid=2048",
+        "C200/262144 sig3_valu ok=1 wino=0 cb=4 plane=3072 vplane=0 o_v=0 o_front=12304 per_chunk=984 o_map=0 o_seq=0 o_code=0 o_pidx=0 o_u=0 lds=64960 grid=2048",
+        "C200/262144 seq2 ok=1 wino=0 cb=2 plane=1600 vplane=192 o_v=9488 o_front=6416 per_chunk=3496 o_map=0 o_seq=24 o_code=36 o_pidx=116 o_u=216 lds=68032 grid=2048",
+        "C200/262144 seq2_direct ok=1 wino=0 cb=2 plane=1600 vplane=0 o_v=0 o_front=6416 per_chunk=3496 o_map=0 o_seq=24 o_code=36 o_pidx=116 o_u=216 lds=68032 grid=2048",
+        "C200/262144 sig_conv3 ok=1 cb=3 nwin=1 pin=192 pout=62 plane=2304 lds=36928 grid=2048",
+        "C200/262144 seq_conv2 ok=1 cb=3 nwin=1 pin=196 pout=62 plane=2368 lds=37952 grid=2048",
+        "C200/300 sig3_mfma ok=1 wino=0 cb=1 plane=768 vplane=0 o_v=3088 o_front=3088 per_chunk=1048 o_map=0 o_seq=0 o_code=0 o_pidx=0 o_u=0 lds=29120 grid=300",
+        "C200/300 sig3_valu ok=1 wino=0 cb=4 plane=3072 vplane=0 o_v=0 o_front=12304 per_chunk=984 o_map=0 o_seq=0 o_code=0 o_pidx=0 o_u=0 lds=64960 grid=75",
+        "C200/300 seq2 ok=1 wino=0 cb=1 plane=832 vplane=192 o_v=9488 o_front=3344 per_chunk=3496 o_map=0 o_seq=24 o_code=36 o_pidx=116 o_u=216 lds=41760 grid=300",
+        "C200/300 seq2_direct ok=1 wino=0 cb=1 plane=832 vplane=0 o_v=0 o_front=3344 per_chunk=3496 o_map=0 o_seq=24 o_code=36 o_pidx=116 o_u=216 lds=41760 grid=300",
+        "C200/300 sig_conv3 ok=1 cb=1 nwin=1 pin=192 pout=62 plane=768 lds=12352 grid=300",
+        "C200/300 seq_conv2 ok=1 cb=1 nwin=1 pin=196 pout=62 plane=832 lds=13376 grid=300",
+    ]
+
+
 def test_subbatch_cuts_partition_a_batch_of_reads():
     """inference._subbatch_cuts: contiguous, complete, non-empty pieces for any batch size; a short start (the GPU gets work
     after a quarter sub-batch has been staged) and a short end (what remains to be done when the stager is finished)."""
