@@ -1,5 +1,5 @@
 """Toom-Cook / Winograd minimal filtering F(m, r) in exact rational arithmetic - the derivation of the three matrices that
-remora_amd/csrc/k_wino.hip (BT, AT) and engine.hip pack_conv (G) hold as constants for the fp32 5-tap stride-1 convolutions
+remora_amd/csrc/k_wino.hip (BT, AT) and rmr_pack.cpp wino_filter (G) hold as constants for the fp32 5-tap stride-1 convolutions
 (merge_conv1 / merge_conv2: models/ConvLSTM_w_ref.py:36-37,50, models/Conv_w_ref.py:35-38,54-55).
 
 TEST INFRASTRUCTURE ONLY (see oracle/oracle.py header for who may import this).  Nothing here is the reference's algorithm: the

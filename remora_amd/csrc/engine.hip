@@ -598,576 +598,12 @@ int rmr_profile_get(rmr_engine *e, int id, double *total_ms, int64_t *launches) 
 }  // extern "C"
 
 // =========================================================================================
-// model: parse the canonical blob, fold BN, pack
+// model: fold and pack on the host (rmr_pack.h), upload
 // =========================================================================================
-namespace {
-
-struct ConvSpec { int ic, oc, kw, stride; };
-
-struct Folded {
-    ConvSpec s;
-    std::vector<float> w;  // [oc][ic][kw] folded
-    std::vector<float> b;  // [oc]
-};
-
-size_t conv_count(const ConvSpec &s) { return (size_t)s.oc * s.ic * s.kw + 5 * (size_t)s.oc; }
-
-std::vector<ConvSpec> conv_specs(const rmr_model_desc &d) {
-    const int sz = d.size, ec = 4 * d.kmer_len;
-    if (d.arch == RMR_ARCH_CONV_LSTM)
-        return {{1, 4, 5, 1}, {4, 16, 5, 1}, {16, sz, 9, 3}, {ec, 16, 5, 1}, {16, sz, 13, 3}, {2 * sz, sz, 5, 1}};
-    return {{1, 4, 11, 1}, {4, 16, 11, 1}, {16, sz, 9, 3}, {ec, 16, 11, 1}, {16, 32, 11, 1},
-            {32, sz, 9, 3}, {2 * sz, sz, 5, 1}, {sz, sz, 5, 1}, {sz, sz, 3, 2}, {sz, sz, 3, 2}};
-}
-
-// ---- split-bf16 helpers (host twins of split_parts/pack2 in k_lstm_bf16s.hip) -------------
-static inline uint32_t f2u(float x) { uint32_t u; memcpy(&u, &x, 4); return u; }
-static inline float u2f(uint32_t u) { float x; memcpy(&x, &u, 4); return x; }
-static inline uint32_t rne_bf16(uint32_t b) { return (b + 0x7fffu + ((b >> 16) & 1u)) & 0xffff0000u; }
-// one fp32 value as the 16-bit operand of the fused kernels, in the HIGH half of the returned word (as rne_bf16 returns
-// it): bf16, or IEEE half (round to nearest even; the compiler's conversion)
-static inline uint32_t to_op16(float v, bool f16) {
-    if (!f16) {
-        uint32_t b;
-        memcpy(&b, &v, 4);
-        return rne_bf16(b);
-    }
-    const _Float16 h = (_Float16)v;
-    uint16_t hb;
-    memcpy(&hb, &h, 2);
-    return (uint32_t)hb << 16;
-}
-static void split_parts_host(float x, int np, uint32_t *p, bool f16 = false) {
-    if (f16) {  // dtype f16x3: hi = half(x), lo = half(x - hi) (split_parts<2, true> in k_lstm_bf16s.hip)
-        const _Float16 hi = (_Float16)x;
-        const _Float16 lo = (_Float16)(x - (float)hi);
-        uint16_t hb, lb;
-        memcpy(&hb, &hi, 2);
-        memcpy(&lb, &lo, 2);
-        p[0] = (uint32_t)hb << 16;
-        p[1] = (uint32_t)lb << 16;
-        return;
-    }
-    if (np == 1) { p[0] = rne_bf16(f2u(x)); return; }
-    float r = x;
-    for (int i = 0; i < np; ++i) {
-        const uint32_t b = f2u(r);
-        p[i] = (i + 1 < np || np == 3) ? (b & 0xffff0000u) : rne_bf16(b);
-        r -= u2f(p[i]);
-    }
-}
-
-// [rows][K] row-major fp32 (row = gates[gi]*H + 16*wv + m) -> bf16x8 A fragments
-// [H/16 waves][ngates][K/32][np][64 lanes][4 dwords]; lane (q, m) holds k = 32ks + 8q + j
-std::vector<float> pack_split_a(const std::vector<float> &w, int K, int nw, const int *rowbase, int ngates, int np, bool f16 = false) {
-    const int KS32 = K / 32;
-    std::vector<uint32_t> out((size_t)nw * ngates * KS32 * np * 64 * 4);
-    for (int wv = 0; wv < nw; ++wv)
-        for (int gi = 0; gi < ngates; ++gi)
-            for (int ks = 0; ks < KS32; ++ks)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int q = lane >> 4, mm = lane & 15;
-                    const int row = rowbase[gi] + 16 * wv + mm;
-                    uint32_t parts[8][3];
-                    for (int j = 0; j < 8; ++j) split_parts_host(w[(size_t)row * K + 32 * ks + 8 * q + j], np, parts[j], f16);
-                    for (int p = 0; p < np; ++p)
-                        for (int i = 0; i < 4; ++i)
-                            out[(((((size_t)wv * ngates + gi) * KS32 + ks) * np + p) * 64 + lane) * 4 + i] =
-                                (parts[2 * i][p] >> 16) | parts[2 * i + 1][p];
-                }
-    std::vector<float> f(out.size());
-    memcpy(f.data(), out.data(), out.size() * 4);
-    return f;
-}
-
-// The channel count the kernels run a network of `size` channels at (models/ConvLSTM_w_ref.py:11-37 and Conv_w_ref.py:11-42
-// are parametric in `size`, the CLI takes any int: src/remora/parsers.py:858-862).  Up to 64 the kernels with register-resident
-// weight slices exist for 16 / 32 / 64; above, the streamed-weight kernels (k_stream.hip) take any multiple of 16 up to 256.
-// Channels between `size` and the padded count carry zero weights and zero bias: swish(0) = 0 and an LSTM unit with zero
-// weights stays at c = h = 0 exactly, and a zero product added to an fp32 sum leaves it unchanged - the logits are those of
-// the unpadded network (pad_model_blob below; rmr_model_pad_weights exposes the transform).
-int padded_size(int size, int dtype = 0) {
-    if (size <= 16) return 16;
-    if (size <= 32) return 32;
-    if (size <= 64) return 64;
-    return dtype == 0 ? (size + 15) & ~15 : (size + 31) & ~31;  // the 16-bit MFMA takes K in steps of 32 (k_stream16.hip)
-}
-constexpr int kMaxPaddedSize = 256;
-
-bool desc_ok(const rmr_model_desc &d) {
-    if (d.arch != RMR_ARCH_CONV_LSTM && d.arch != RMR_ARCH_CONV_ONLY) return false;
-    if (d.size < 1 || d.dtype < 0 || d.dtype > 5 || padded_size(d.size, d.dtype) > kMaxPaddedSize) return false;
-    const int sp = padded_size(d.size, d.dtype);
-    if (d.kmer_len < 1 || d.kmer_len > 64) return false;
-    if (d.num_out < 1 || d.num_out > 16) return false;
-    if (d.dtype < 0 || d.dtype > 5) return false;  // 5 = f16x3: two-part IEEE half split on the unfused kernels
-    if (d.dtype == 4 && sp <= 64 && (sp != 64 || (d.kmer_len != 9 && d.kmer_len != 6))) return false;  // half up to 64 channels: the fused kernels only
-    if (d.dtype != 0 && (d.arch != RMR_ARCH_CONV_LSTM || sp % 32)) return false;
-    if (d.dtype != 0 && sp > 64 && d.dtype != 1 && d.dtype != 4) return false;  // above 64 channels: fp32, bf16 or f16 (the split dtypes stop at 64)
-    return true;
-}
-
-// The canonical blob (include/remora_hip.h, rmr_model_create) of the same network with `sp` channels where `d` has d.size:
-// zero weights / bias for the added output channels (BatchNorm of an added channel: gamma 1, beta 0, mean 0, var 1 - it folds
-// to weight 0, bias 0), zero columns for the added input channels; merge_conv1 reads cat = [signal branch | sequence branch],
-// so its input channel sz + c moves to sp + c.
-std::vector<float> pad_model_blob(const rmr_model_desc &d, const float *w, int sp) {
-    const int sz = d.size;
-    rmr_model_desc pd = d;
-    pd.size = sp;
-    const std::vector<ConvSpec> ts = conv_specs(d), ps = conv_specs(pd);
-    size_t total = 0;
-    for (auto &s : ps) total += conv_count(s);
-    const size_t H = sz, HP = sp;
-    if (d.arch == RMR_ARCH_CONV_LSTM) total += 2 * (2 * 4 * HP * HP + 2 * 4 * HP) + (size_t)d.num_out * HP + d.num_out;
-    else total += (size_t)d.num_out * HP * 3 + d.num_out;
-    std::vector<float> o(total, 0.0f);
-    const float *p = w;
-    float *q = o.data();
-    const size_t merge1 = d.arch == RMR_ARCH_CONV_LSTM ? 5 : 6;
-    for (size_t li = 0; li < ts.size(); ++li) {
-        const ConvSpec &t = ts[li], &u = ps[li];
-        for (int oc = 0; oc < t.oc; ++oc)
-            for (int ic = 0; ic < t.ic; ++ic) {
-                const int icp = (li == merge1 && ic >= sz) ? sp + (ic - sz) : ic;
-                memcpy(q + ((size_t)oc * u.ic + icp) * u.kw, p + ((size_t)oc * t.ic + ic) * t.kw, (size_t)t.kw * sizeof(float));
-            }
-        p += (size_t)t.oc * t.ic * t.kw;
-        q += (size_t)u.oc * u.ic * u.kw;
-        for (int part = 0; part < 5; ++part) {  // bias, gamma, beta, mean, var
-            memcpy(q, p, (size_t)t.oc * sizeof(float));
-            if (part == 1 || part == 4)
-                for (int oc = t.oc; oc < u.oc; ++oc) q[oc] = 1.0f;
-            p += t.oc;
-            q += u.oc;
-        }
-    }
-    if (d.arch == RMR_ARCH_CONV_LSTM) {
-        for (int l = 0; l < 2; ++l) {
-            for (int m = 0; m < 2; ++m) {  // weight_ih, weight_hh: [4H][H], row = gate * H + unit
-                for (int g = 0; g < 4; ++g)
-                    for (size_t r = 0; r < H; ++r) memcpy(q + ((size_t)g * HP + r) * HP, p + ((size_t)g * H + r) * H, H * sizeof(float));
-                p += 4 * H * H;
-                q += 4 * HP * HP;
-            }
-            for (int m = 0; m < 2; ++m) {  // bias_ih, bias_hh: [4H]
-                for (int g = 0; g < 4; ++g) memcpy(q + (size_t)g * HP, p + (size_t)g * H, H * sizeof(float));
-                p += 4 * H;
-                q += 4 * HP;
-            }
-        }
-        for (int oo = 0; oo < d.num_out; ++oo) memcpy(q + (size_t)oo * HP, p + (size_t)oo * H, H * sizeof(float));
-        p += (size_t)d.num_out * H;
-        q += (size_t)d.num_out * HP;
-    } else {  // fc over flatten([size][3]): index c * 3 + t, channels first - the added channels sit behind the real ones
-        for (int oo = 0; oo < d.num_out; ++oo) memcpy(q + (size_t)oo * HP * 3, p + (size_t)oo * H * 3, H * 3 * sizeof(float));
-        p += (size_t)d.num_out * H * 3;
-        q += (size_t)d.num_out * HP * 3;
-    }
-    memcpy(q, p, (size_t)d.num_out * sizeof(float));
-    return o;
-}
-
-Folded fold(const ConvSpec &s, const float *&p) {
-    Folded f;
-    f.s = s;
-    const size_t nw = (size_t)s.oc * s.ic * s.kw;
-    const float *w = p; p += nw;
-    const float *b = p; p += s.oc;
-    const float *g = p; p += s.oc;
-    const float *beta = p; p += s.oc;
-    const float *mean = p; p += s.oc;
-    const float *var = p; p += s.oc;
-    f.w.resize(nw);
-    f.b.resize(s.oc);
-    for (int o = 0; o < s.oc; ++o) {
-        // eval-mode BatchNorm1d, eps = 1e-5 (torch default; the reference folds the same
-        // way for its Dorado export, src/remora/model_util.py:199-221)
-        const double sc = (double)g[o] / std::sqrt((double)var[o] + 1e-5);
-        for (size_t i = 0; i < (size_t)s.ic * s.kw; ++i)
-            f.w[(size_t)o * s.ic * s.kw + i] = (float)((double)w[(size_t)o * s.ic * s.kw + i] * sc);
-        f.b[o] = (float)(((double)b[o] - (double)mean[o]) * sc + (double)beta[o]);
-    }
-    return f;
-}
-
-int upload(rmr_model *m, const std::vector<float> &h, float **dev) {
-    void *p = nullptr;
-    RMR_HIP(hipMalloc(&p, h.size() * sizeof(float) + 16));
-    m->dev_allocs.push_back(p);
-    RMR_HIP(hipMemcpy(p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    *dev = reinterpret_cast<float *>(p);
-    return 0;
-}
-
-int pack_conv(rmr_model *m, const Folded &f, int kid, ConvLayer *out) {
-    const ConvSpec &s = f.s;
-    if (s.ic % 16 || s.oc % 16) RMR_FAIL(RMR_ERR_INVALID, "conv %dx%d not MFMA-tileable", s.ic, s.oc);
-    const int G = s.ic / 16, S = s.kw * s.ic / 4, W = s.oc / 16;
-    if (s.oc > 64 || s.ic > 128) {  // a layer of a network with more than 64 channels: the streamed kernel's order (k_stream.hip)
-        std::vector<float> ap((size_t)W * s.kw * G * 64 * 4);
-        for (int w = 0; w < W; ++w)
-            for (int tap = 0; tap < s.kw; ++tap)
-                for (int g = 0; g < G; ++g)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 4; ++j) {
-                            const int q = lane >> 4, mm = lane & 15;
-                            const int oc = 16 * w + mm, ic = 16 * g + 4 * q + j;
-                            ap[((((size_t)w * s.kw + tap) * G + g) * 64 + lane) * 4 + j] = f.w[((size_t)oc * s.ic + ic) * s.kw + tap];
-                        }
-        out->ic = s.ic; out->oc = s.oc; out->kw = s.kw; out->stride = s.stride; out->kid = kid;
-        RMR_TRY(upload(m, ap, &out->apack4));
-        RMR_TRY(upload(m, f.b, &out->bias));
-        return 0;
-    }
-    std::vector<float> ap((size_t)W * S * 64);
-    for (int w = 0; w < W; ++w)
-        for (int tap = 0; tap < s.kw; ++tap)
-            for (int g = 0; g < G; ++g)
-                for (int j = 0; j < 4; ++j) {
-                    const int st = (tap * G + g) * 4 + j;
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int q = lane >> 4, mm = lane & 15;
-                        const int oc = 16 * w + mm, ic = 16 * g + 4 * q + j;
-                        ap[((size_t)w * S + st) * 64 + lane] = f.w[((size_t)oc * s.ic + ic) * s.kw + tap];
-                    }
-                }
-    out->ic = s.ic; out->oc = s.oc; out->kw = s.kw; out->stride = s.stride; out->kid = kid;
-    RMR_TRY(upload(m, ap, &out->apack));
-    RMR_TRY(upload(m, f.b, &out->bias));
-    if (s.kw == 5 && s.stride == 1 && s.oc == 64 && (s.ic == 128 || s.ic == 64)) {
-        // Winograd F(4, 5) filter transform U = G W at the Toom-Cook points 0, 1, -1, 2, -2, 1/2, -1/2, inf (k_wino.hip has BT and AT;
-        // oracle/winograd.py derives all three), in float64 from the folded fp32 weights, ONE rounding to fp32.  Rows in the kernel's
-        // x order - the points 1, -1, 2, -2 (wave half 0), then 0, 1/2, -1/2, inf (half 1); fragment order
-        // [oc/16][(x * G + g) * 4 + j][64 lanes].
-        static const double GM[8][5] = {{1.0 / 18, 1.0 / 18, 1.0 / 18, 1.0 / 18, 1.0 / 18},
-                                        {1.0 / 18, -1.0 / 18, 1.0 / 18, -1.0 / 18, 1.0 / 18},
-                                        {1.0 / 360, 1.0 / 180, 1.0 / 90, 1.0 / 45, 2.0 / 45},
-                                        {1.0 / 360, -1.0 / 180, 1.0 / 90, -1.0 / 45, 2.0 / 45},
-                                        {1.0 / 4, 0, 0, 0, 0},
-                                        {16.0 / 45, 8.0 / 45, 4.0 / 45, 2.0 / 45, 1.0 / 45},
-                                        {16.0 / 45, -8.0 / 45, 4.0 / 45, -2.0 / 45, 1.0 / 45},
-                                        {0, 0, 0, 0, 1.0 / 4}};
-        const int SW = 8 * s.ic / 4;
-        std::vector<float> wp((size_t)W * SW * 64);
-        for (int w = 0; w < W; ++w)
-            for (int x = 0; x < 8; ++x)
-                for (int g = 0; g < G; ++g)
-                    for (int j = 0; j < 4; ++j)
-                        for (int lane = 0; lane < 64; ++lane) {
-                            const int q = lane >> 4, mm = lane & 15;
-                            const int oc = 16 * w + mm, ic = 16 * g + 4 * q + j;
-                            double u = 0.0;
-                            for (int tap = 0; tap < 5; ++tap) u += GM[x][tap] * (double)f.w[((size_t)oc * s.ic + ic) * 5 + tap];
-                            wp[((size_t)w * SW + (x * G + g) * 4 + j) * 64 + lane] = (float)u;
-                        }
-        RMR_TRY(upload(m, wp, &out->wpack));
-    }
-    if (s.stride == 3 && s.ic == 16 && s.oc == 64 && s.kw == 9) {
-        // sig_conv3 (models/ConvLSTM_w_ref.py:22-23,43; models/Conv_w_ref.py:22-23,47) for k_conv_front.hip's sig3_front_wino_kernel: the three
-        // phase filters w_p[m] = w[3 m + p] in F(4, 3) form, natural point order (0, 1, -1, 2, -2, inf); [oc/16][(x * 3 + p) * 4 + j][64 lanes]
-        static const double G3n[6][3] = {{1.0 / 4, 0, 0}, {1.0 / 6, 1.0 / 6, 1.0 / 6}, {1.0 / 6, -1.0 / 6, 1.0 / 6},
-                                         {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1.0}};
-        const int SW = 6 * 12;
-        std::vector<float> wp((size_t)W * SW * 64);
-        for (int w = 0; w < W; ++w)
-            for (int x = 0; x < 6; ++x)
-                for (int ph = 0; ph < 3; ++ph)
-                    for (int j = 0; j < 4; ++j)
-                        for (int lane = 0; lane < 64; ++lane) {
-                            const int q = lane >> 4, mm = lane & 15;
-                            const int oc = 16 * w + mm, ic = 4 * q + j;
-                            double u = 0.0;
-                            for (int t = 0; t < 3; ++t) u += G3n[x][t] * (double)f.w[((size_t)oc * s.ic + ic) * s.kw + 3 * t + ph];
-                            wp[((size_t)w * SW + (x * 3 + ph) * 4 + j) * 64 + lane] = (float)u;
-                        }
-        RMR_TRY(upload(m, wp, &out->wpack));
-    }
-    if (s.stride == 3 && s.ic == 16 && s.oc == 64 && s.kw == 13) {
-        // seq_conv2 (models/ConvLSTM_w_ref.py:30-31,46) for k_conv_front.hip's seq2_front_wino_kernel: phase filters w_p[m] = w[3 m + p] of 5, 4 and
-        // 4 taps, all as F(4, 5) (a zero fifth tap where 3 m + p > 12), natural point order (0, 1, -1, 2, -2, 1/2, -1/2, inf);
-        // [oc/16][(x * 3 + p) * 4 + j][64 lanes]
-        static const double G5n[8][5] = {{1.0 / 4, 0, 0, 0, 0},
-                                         {1.0 / 18, 1.0 / 18, 1.0 / 18, 1.0 / 18, 1.0 / 18},
-                                         {1.0 / 18, -1.0 / 18, 1.0 / 18, -1.0 / 18, 1.0 / 18},
-                                         {1.0 / 360, 1.0 / 180, 1.0 / 90, 1.0 / 45, 2.0 / 45},
-                                         {1.0 / 360, -1.0 / 180, 1.0 / 90, -1.0 / 45, 2.0 / 45},
-                                         {16.0 / 45, 8.0 / 45, 4.0 / 45, 2.0 / 45, 1.0 / 45},
-                                         {16.0 / 45, -8.0 / 45, 4.0 / 45, -2.0 / 45, 1.0 / 45},
-                                         {0, 0, 0, 0, 1.0 / 4}};
-        const int SW = 8 * 12;
-        std::vector<float> wp((size_t)W * SW * 64);
-        for (int w = 0; w < W; ++w)
-            for (int x = 0; x < 8; ++x)
-                for (int ph = 0; ph < 3; ++ph)
-                    for (int j = 0; j < 4; ++j)
-                        for (int lane = 0; lane < 64; ++lane) {
-                            const int q = lane >> 4, mm = lane & 15;
-                            const int oc = 16 * w + mm, ic = 4 * q + j;
-                            double u = 0.0;
-                            for (int t = 0; t < 5; ++t)
-                                if (3 * t + ph < s.kw) u += G5n[x][t] * (double)f.w[((size_t)oc * s.ic + ic) * s.kw + 3 * t + ph];
-                            wp[((size_t)w * SW + (x * 3 + ph) * 4 + j) * 64 + lane] = (float)u;
-                        }
-        RMR_TRY(upload(m, wp, &out->wpack));
-    }
-    if (s.stride == 3 && s.ic == 32 && s.oc == 64 && s.kw == 9) {
-        // Conv_w_ref's seq_conv3 (models/Conv_w_ref.py:31-32,51): stride 3 as three phase filters w_p[m] = w[3 m + p] of three taps
-        // each, F(4, 3) at 0, +-1, +-2, inf (k_wino.hip wino_s3_kernel; oracle/winograd.py); natural point order; fragment order
-        // [oc/16][((x * 3 + p) * G + g) * 4 + j][64 lanes], K of a point's GEMM = (phase, channel)
-        static const double G3[6][3] = {{1.0 / 4, 0, 0}, {1.0 / 6, 1.0 / 6, 1.0 / 6}, {1.0 / 6, -1.0 / 6, 1.0 / 6},
-                                        {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1.0}};
-        static const int XO[6] = {1, 2, 0, 3, 4, 5};  // the kernel's x order: wave half 0 (+1, -1, 0), half 1 (+2, -2, inf)
-        const int NX = 6, SW = NX * 3 * G * 4;
-        std::vector<float> wp((size_t)W * SW * 64);
-        for (int w = 0; w < W; ++w)
-            for (int x = 0; x < NX; ++x)
-                for (int ph = 0; ph < 3; ++ph)
-                    for (int g = 0; g < G; ++g)
-                        for (int j = 0; j < 4; ++j)
-                            for (int lane = 0; lane < 64; ++lane) {
-                                const int q = lane >> 4, mm = lane & 15;
-                                const int oc = 16 * w + mm, ic = 16 * g + 4 * q + j;
-                                double u = 0.0;
-                                for (int t = 0; t < 3; ++t) u += G3[XO[x]][t] * (double)f.w[((size_t)oc * s.ic + ic) * s.kw + 3 * t + ph];
-                                wp[((size_t)w * SW + ((x * 3 + ph) * G + g) * 4 + j) * 64 + lane] = (float)u;
-                            }
-        RMR_TRY(upload(m, wp, &out->wpack));
-    }
-    return 0;
-}
-
-// gate pre-scale used by lstm_step (k_lstm.hip): sigmoid(x) = 1/(1+2^(-x log2 e)) for i,f,o;
-// tanh(x) = 1 - 2/(1+2^(2x log2 e)) for g.  torch gate order i,f,g,o.
-static inline double lstm1_gate_scale(int gate) {
-    const double log2e = 1.4426950408889634;
-    return gate == 2 ? 2.0 * log2e : -log2e;
-}
-
-// conv weights -> split-bf16 A fragments [oc/16][steps][np][64 lanes][4 dwords]
-// (k-slot mapping documented at the top of k_conv_bf16s.hip)
-int pack_conv_split(rmr_model *m, const Folded &f, int np, ConvLayer *out) {
-    out->split_f16 = m->split_f16;
-    const ConvSpec &s = f.s;
-    const bool pair = (s.ic == 16);
-    if (!pair && s.ic % 32) RMR_FAIL(RMR_ERR_INVALID, "split conv needs ic 16 or a multiple of 32 (got %d)", s.ic);
-    const int KS = pair ? 1 : s.ic / 32;
-    const int steps = pair ? (s.kw + 1) / 2 : s.kw * KS;
-    const int W = s.oc / 16;
-    std::vector<uint32_t> o((size_t)W * steps * np * 64 * 4);
-    for (int w = 0; w < W; ++w)
-        for (int st = 0; st < steps; ++st)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int q = lane >> 4, oc = 16 * w + (lane & 15);
-                uint32_t parts[8][3];
-                for (int j = 0; j < 8; ++j) {
-                    int tap, ch;
-                    if (pair) { tap = 2 * st + (q >> 1); ch = 8 * (q & 1) + j; }
-                    else { tap = st / KS; ch = 32 * (st % KS) + 8 * q + j; }
-                    const float v = tap < s.kw ? f.w[((size_t)oc * s.ic + ch) * s.kw + tap] : 0.0f;
-                    split_parts_host(v, np, parts[j], m->split_f16);
-                }
-                for (int p = 0; p < np; ++p)
-                    for (int i = 0; i < 4; ++i)
-                        o[((((size_t)w * steps + st) * np + p) * 64 + lane) * 4 + i] = (parts[2 * i][p] >> 16) | parts[2 * i + 1][p];
-            }
-    std::vector<float> fl(o.size());
-    memcpy(fl.data(), o.data(), o.size() * 4);
-    return upload(m, fl, &out->spack);
-}
-
-// conv weights -> bf16 A fragments of the fused front kernel: [oc/16][ksteps][64 lanes][4 dwords]; lane (q, m) of
-// k-step s holds k = 32 s + 8 q + j, k = tap * C + channel (C = row width of the operand in LDS, k_fused.hip);
-// taps >= kw and channels >= ic are zero
-int pack_flat_a(rmr_model *m, const Folded &f, int C, int ksteps, double scale, float **dev, bool f16 = false) {
-    const ConvSpec &s = f.s;
-    const int W = s.oc / 16;
-    std::vector<uint32_t> o((size_t)W * ksteps * 64 * 4);
-    for (int w = 0; w < W; ++w)
-        for (int st = 0; st < ksteps; ++st)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int q = lane >> 4, oc = 16 * w + (lane & 15);
-                uint32_t b[8];
-                for (int j = 0; j < 8; ++j) {
-                    const int k = 32 * st + 8 * q + j, tap = k / C, ch = k % C;
-                    const float v = (tap < s.kw && ch < s.ic) ? (float)(scale * (double)f.w[((size_t)oc * s.ic + ch) * s.kw + tap]) : 0.0f;
-                    b[j] = to_op16(v, f16);
-                }
-                for (int i = 0; i < 4; ++i) o[(((size_t)w * ksteps + st) * 64 + lane) * 4 + i] = (b[2 * i] >> 16) | b[2 * i + 1];
-            }
-    std::vector<float> fl(o.size());
-    memcpy(fl.data(), o.data(), o.size() * 4);
-    return upload(m, fl, dev);
-}
-
-// LSTM weights for k_lstm_x16.hip (H = 64): 16-row MFMA tiles with UNIT-MAJOR rows — row r of tile (wave wv, t) is
-// (unit 8 wv + 2 (r >> 2) + t, gate r & 3) — as bf16 A fragments [8][2][2 k-steps][64 lanes][4 dwords]; gate rows
-// pre-scaled (lstm1_gate_scale); `skip_f` zeroes the f rows (lstm2: c0 = 0)
-std::vector<float> pack_lstm_x16(const float *w, bool skip_f, bool f16 = false) {
-    const int H = 64;
-    std::vector<uint32_t> o((size_t)8 * 2 * 2 * 64 * 4);
-    for (int wv = 0; wv < 8; ++wv)
-        for (int t = 0; t < 2; ++t)
-            for (int ks = 0; ks < 2; ++ks)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int ql = lane >> 4, mm = lane & 15, gate = mm & 3, unit = 8 * wv + 2 * (mm >> 2) + t;
-                    uint32_t b[8];
-                    for (int j = 0; j < 8; ++j) {
-                        const int k = 32 * ks + 8 * ql + j;
-                        const double v = (skip_f && gate == 1) ? 0.0 : (double)w[(size_t)(gate * H + unit) * H + k] * lstm1_gate_scale(gate);
-                        b[j] = to_op16((float)v, f16);
-                    }
-                    for (int i = 0; i < 4; ++i)
-                        o[((((size_t)wv * 2 + t) * 2 + ks) * 64 + lane) * 4 + i] = (b[2 * i] >> 16) | b[2 * i + 1];
-                }
-    std::vector<float> f(o.size());
-    memcpy(f.data(), o.data(), o.size() * 4);
-    return f;
-}
-// the same fragments as NP split parts (k_lstm_x16s.hip): [8][2][2 k-steps][np][64 lanes][4 dwords]
-std::vector<float> pack_lstm_x16_split(const float *w, bool skip_f, int np, bool f16) {
-    const int H = 64;
-    std::vector<uint32_t> o((size_t)8 * 2 * 2 * np * 64 * 4);
-    for (int wv = 0; wv < 8; ++wv)
-        for (int t = 0; t < 2; ++t)
-            for (int ks = 0; ks < 2; ++ks)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int ql = lane >> 4, mm = lane & 15, gate = mm & 3, unit = 8 * wv + 2 * (mm >> 2) + t;
-                    uint32_t parts[8][3];
-                    for (int j = 0; j < 8; ++j) {
-                        const int k = 32 * ks + 8 * ql + j;
-                        const double v = (skip_f && gate == 1) ? 0.0 : (double)w[(size_t)(gate * H + unit) * H + k] * lstm1_gate_scale(gate);
-                        split_parts_host((float)v, np, parts[j], f16);
-                    }
-                    for (int p = 0; p < np; ++p)
-                        for (int i = 0; i < 4; ++i)
-                            o[(((((size_t)wv * 2 + t) * 2 + ks) * np + p) * 64 + lane) * 4 + i] = (parts[2 * i][p] >> 16) | parts[2 * i + 1][p];
-                }
-    std::vector<float> f(o.size());
-    memcpy(f.data(), o.data(), o.size() * 4);
-    return f;
-}
-// matching biases [8][2][4 q][4 gates]: (b_ih + b_hh) of unit 8 wv + 2 q + t, pre-scaled
-std::vector<float> pack_bias_x16(const float *bih, const float *bhh, bool skip_f) {
-    const int H = 64;
-    std::vector<float> o((size_t)8 * 2 * 4 * 4);
-    for (int wv = 0; wv < 8; ++wv)
-        for (int t = 0; t < 2; ++t)
-            for (int q = 0; q < 4; ++q)
-                for (int gate = 0; gate < 4; ++gate) {
-                    const int unit = 8 * wv + 2 * q + t;
-                    o[(((size_t)wv * 2 + t) * 4 + q) * 4 + gate] =
-                        (skip_f && gate == 1) ? 0.0f : (float)(((double)bih[gate * H + unit] + (double)bhh[gate * H + unit]) * lstm1_gate_scale(gate));
-                }
-    return o;
-}
-
-// [4H][H] row-major -> [H/16 waves][H/16 k groups][ngates][64 lanes][4] (k_stream.hip: one 16-byte fragment per gate and group)
-std::vector<float> pack_lstm_stream(const float *w, int H, const int *gates, int ngates, bool prescale) {
-    const int G = H / 16, W = H / 16;
-    std::vector<float> ap((size_t)W * G * ngates * 64 * 4);
-    for (int wv = 0; wv < W; ++wv)
-        for (int g = 0; g < G; ++g)
-            for (int gi = 0; gi < ngates; ++gi)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 4; ++j) {
-                        const int q = lane >> 4, mm = lane & 15;
-                        const int row = gates[gi] * H + 16 * wv + mm, k = 16 * g + 4 * q + j;
-                        const double sc = prescale ? lstm1_gate_scale(gates[gi]) : 1.0;
-                        ap[((((size_t)wv * G + g) * ngates + gi) * 64 + lane) * 4 + j] = (float)((double)w[(size_t)row * H + k] * sc);
-                    }
-    return ap;
-}
-
-// LSTM weights for k_stream16.hip (H a multiple of 32 above 64): [H/16 waves][4 tiles][H/32 k-steps][64 lanes][4 dwords]; row m of tile t of
-// wave wv = (unit 16 wv + 4 (m >> 2) + t, gate m & 3); gate rows pre-scaled (lstm1_gate_scale); `skip_f` zeroes the f rows (lstm2: c0 = 0)
-std::vector<float> pack_lstm_s16(const float *w, int H, bool skip_f, bool f16) {
-    const int W = H / 16, KSH = H / 32;
-    std::vector<uint32_t> o((size_t)W * 4 * KSH * 64 * 4);
-    for (int wv = 0; wv < W; ++wv)
-        for (int t = 0; t < 4; ++t)
-            for (int ks = 0; ks < KSH; ++ks)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int ql = lane >> 4, mm = lane & 15, gate = mm & 3, unit = 16 * wv + 4 * (mm >> 2) + t;
-                    uint32_t b[8];
-                    for (int j = 0; j < 8; ++j) {
-                        const int k = 32 * ks + 8 * ql + j;
-                        const double v = (skip_f && gate == 1) ? 0.0 : (double)w[(size_t)(gate * H + unit) * H + k] * lstm1_gate_scale(gate);
-                        b[j] = to_op16((float)v, f16);
-                    }
-                    for (int i = 0; i < 4; ++i) o[((((size_t)wv * 4 + t) * KSH + ks) * 64 + lane) * 4 + i] = (b[2 * i] >> 16) | b[2 * i + 1];
-                }
-    std::vector<float> f(o.size());
-    memcpy(f.data(), o.data(), o.size() * 4);
-    return f;
-}
-// matching biases [H/16][4 tiles][4 q][4 gates]: (b_ih + b_hh) of unit 16 wv + 4 q + t, pre-scaled
-std::vector<float> pack_bias_s16(const float *bih, const float *bhh, int H, bool skip_f) {
-    const int W = H / 16;
-    std::vector<float> o((size_t)W * 4 * 4 * 4);
-    for (int wv = 0; wv < W; ++wv)
-        for (int t = 0; t < 4; ++t)
-            for (int q = 0; q < 4; ++q)
-                for (int gate = 0; gate < 4; ++gate) {
-                    const int unit = 16 * wv + 4 * q + t;
-                    o[(((size_t)wv * 4 + t) * 4 + q) * 4 + gate] =
-                        (skip_f && gate == 1) ? 0.0f : (float)(((double)bih[gate * H + unit] + (double)bhh[gate * H + unit]) * lstm1_gate_scale(gate));
-                }
-    return o;
-}
-
-// [4H][H] row-major (H = 64) -> [4 waves][64 k in lstm_head_kernel's order: position (g * 4 + j) * 4 + q = k 16 g + 4 q + j][64 lanes],
-// lane l = gate gates[l & 3] (a negative entry: zeros) of unit 16 w + (l >> 2)   (lstm_small_kernel, k_lstm.hip)
-std::vector<float> pack_lstm_small(const float *w, const int *gates, bool prescale) {
-    const int H = 64;
-    std::vector<float> ap((size_t)4 * H * 64);
-    for (int wv = 0; wv < 4; ++wv)
-        for (int g = 0; g < 4; ++g)
-            for (int j = 0; j < 4; ++j)
-                for (int q = 0; q < 4; ++q)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int gate = gates[lane & 3], unit = 16 * wv + (lane >> 2), k = 16 * g + 4 * q + j;
-                        const double sc = prescale && gate >= 0 ? lstm1_gate_scale(gate) : 1.0;
-                        ap[((size_t)wv * H + (g * 4 + j) * 4 + q) * 64 + lane] =
-                            gate < 0 ? 0.0f : (float)((double)w[(size_t)(gate * H + unit) * H + k] * sc);
-                    }
-    return ap;
-}
-
-// [4H][H] row-major -> [H/16 waves][ngates][H/4][64]
-std::vector<float> pack_lstm(const float *w, int H, const int *gates, int ngates, bool prescale = false) {
-    const int KS = H / 4, G = H / 16, W = H / 16;
-    std::vector<float> ap((size_t)W * ngates * KS * 64);
-    for (int wv = 0; wv < W; ++wv)
-        for (int gi = 0; gi < ngates; ++gi)
-            for (int g = 0; g < G; ++g)
-                for (int j = 0; j < 4; ++j)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int q = lane >> 4, mm = lane & 15;
-                        const int row = gates[gi] * H + 16 * wv + mm, k = 16 * g + 4 * q + j;
-                        const double sc = prescale ? lstm1_gate_scale(gates[gi]) : 1.0;
-                        ap[(((size_t)wv * ngates + gi) * KS + g * 4 + j) * 64 + lane] = (float)((double)w[(size_t)row * H + k] * sc);
-                    }
-    return ap;
-}
-
-}  // namespace
 
 extern "C" {
 
-size_t rmr_model_weight_count(const rmr_model_desc *d) {
-    if (!d || !desc_ok(*d)) return 0;
-    size_t n = 0;
-    for (auto &s : conv_specs(*d)) n += conv_count(s);
-    const size_t H = d->size;
-    if (d->arch == RMR_ARCH_CONV_LSTM) {
-        n += 2 * (2 * 4 * H * H + 2 * 4 * H);
-        n += (size_t)d->num_out * H + d->num_out;
-    } else {
-        n += (size_t)d->num_out * H * 3 + d->num_out;
-    }
-    return n;
-}
+size_t rmr_model_weight_count(const rmr_model_desc *d) { return (d && desc_ok(*d)) ? weight_count(*d) : 0; }
 
 void rmr_model_destroy(rmr_model *m) {
     if (!m) return;
@@ -1228,191 +664,26 @@ int rmr_model_create(rmr_engine *e, const rmr_model_desc *desc, const float *wei
 
 // `desc->size` is a size the kernels run at (padded_size is the identity on it)
 static int model_create_at_kernel_size(rmr_engine *e, const rmr_model_desc *desc, const float *weights, size_t n_floats, rmr_model **out) {
-    const size_t want = rmr_model_weight_count(desc);
-    if (want != n_floats) RMR_FAIL(RMR_ERR_INVALID, "internal: padded weight blob has %zu floats, expected %zu", n_floats, want);
     std::lock_guard<std::mutex> lk(e->mu);
     RMR_HIP(hipSetDevice(e->device));
     std::unique_ptr<rmr_model, void (*)(rmr_model *)> m(new rmr_model(), rmr_model_destroy);
     m->eng = e;
-    m->desc = *desc;
     m->true_size = desc->size;
-    m->nparts = desc->dtype == 4 ? 1 : (desc->dtype == 5 ? 2 : desc->dtype);  // 0 fp32 MFMA; 1 bf16; 2 bf16x3 (2-part split); 3 bf16x6 (3-part split)
-    m->split_f16 = desc->dtype == 5;  // f16x3: the two parts are IEEE half
-    m->f16 = desc->dtype == 4;                       // 4: one-part operands as IEEE half (fused kernels)
-    const int sz = desc->size, K = desc->kmer_len, L = desc->chunk_len;
-
-    const float *p = weights;
-    std::vector<Folded> convs;
-    for (auto &s : conv_specs(*desc)) convs.push_back(fold(s, p));
-
-    // ---- geometry ----
-    const int kw1 = convs[0].s.kw;
-    m->L = L;
-    m->P1 = L - kw1 + 1;
-    m->P2 = m->P1 - kw1 + 1;
-    if (m->P2 < 9) RMR_FAIL(RMR_ERR_INVALID, "chunk_len %d too short for this architecture", L);
-    m->P3 = (m->P2 - 9) / 3 + 1;
-    if (desc->arch == RMR_ARCH_CONV_LSTM) {
-        if ((m->P1 - 13) / 3 + 1 != m->P3) RMR_FAIL(RMR_ERR_INVALID, "branch lengths differ");
-        m->T = m->P3 - 4;
-        if (m->T < 1) RMR_FAIL(RMR_ERR_INVALID, "chunk_len %d too short", L);
-    } else {
-        m->PQ2 = m->P1 - 10;
-        if (m->PQ2 < 9 || (m->PQ2 - 9) / 3 + 1 != m->P3) RMR_FAIL(RMR_ERR_INVALID, "branch lengths differ");
-        m->T = m->P3 - 4;
-        m->T2 = m->T - 4;
-        m->T3 = (m->T2 - 3) / 2 + 1;
-        m->T4 = (m->T3 - 3) / 2 + 1;
-        if (m->T2 < 3 || m->T3 < 3 || m->T4 != 3)
-            RMR_FAIL(RMR_ERR_INVALID, "Conv_w_ref needs 3 final positions (fc in = size*3), chunk_len %d gives %d", L, m->T4);
-    }
-
-    // ---- front weights ----
-    {
-        const Folded &s1 = convs[0], &s2 = convs[1], &q1 = convs[3];
-        std::vector<float> w1((size_t)kw1 * 4), w2((size_t)kw1 * 64), wt((size_t)kw1 * K * 64);
-        for (int t = 0; t < kw1; ++t)
-            for (int o = 0; o < 4; ++o) w1[t * 4 + o] = s1.w[(size_t)o * kw1 + t];
-        for (int t = 0; t < kw1; ++t)
-            for (int ic = 0; ic < 4; ++ic)
-                for (int o = 0; o < 16; ++o) w2[(t * 4 + ic) * 16 + o] = s2.w[((size_t)o * 4 + ic) * kw1 + t];
-        const int ec = 4 * K;
-        for (int t = 0; t < kw1; ++t)
-            for (int c = 0; c < ec; ++c)
-                for (int o = 0; o < 16; ++o) wt[((size_t)t * ec + c) * 16 + o] = q1.w[((size_t)o * ec + c) * kw1 + t];
-        m->front.kw1 = kw1;
-        RMR_TRY(upload(m.get(), w1, &m->front.w_sig1));
-        RMR_TRY(upload(m.get(), s1.b, &m->front.b_sig1));
-        RMR_TRY(upload(m.get(), w2, &m->front.w_sig2));
-        RMR_TRY(upload(m.get(), s2.b, &m->front.b_sig2));
-        RMR_TRY(upload(m.get(), wt, &m->front.wt_seq1));
-        std::vector<float> wt5((size_t)kw1 * K * 80, 0.0f);
-        for (int t = 0; t < kw1; ++t)
-            for (int kp = 0; kp < K; ++kp)
-                for (int b = 0; b < 4; ++b)
-                    for (int o = 0; o < 16; ++o)
-                        wt5[(((size_t)t * K + kp) * 5 + b) * 16 + o] = q1.w[((size_t)o * ec + 4 * kp + b) * kw1 + t];
-        RMR_TRY(upload(m.get(), wt5, &m->front.wt5_seq1));
-        RMR_TRY(upload(m.get(), q1.b, &m->front.b_seq1));
-    }
-    RMR_TRY(pack_conv(m.get(), convs[2], K_CONV_SIG3, &m->sig3));
-    RMR_TRY(pack_conv(m.get(), convs[4], K_CONV_SEQ2, &m->seq2));
-    if (desc->arch == RMR_ARCH_CONV_LSTM) {
-        RMR_TRY(pack_conv(m.get(), convs[5], K_CONV_MERGE1, &m->merge1));
-        if (m->nparts > 0) {
-            RMR_TRY(pack_conv_split(m.get(), convs[2], m->nparts, &m->sig3));
-            RMR_TRY(pack_conv_split(m.get(), convs[4], m->nparts, &m->seq2));
-            RMR_TRY(pack_conv_split(m.get(), convs[5], m->nparts, &m->merge1));
-        }
-        if (m->nparts == 1 && sz > 64) {  // k_stream16.hip: 16-bit A fragments of the three size-wide layers, k = tap * ic + channel
-            RMR_TRY(pack_flat_a(m.get(), convs[2], convs[2].s.ic, (convs[2].s.kw * convs[2].s.ic + 31) / 32, 1.0, &m->sig3.apack16, m->f16));
-            RMR_TRY(pack_flat_a(m.get(), convs[4], convs[4].s.ic, (convs[4].s.kw * convs[4].s.ic + 31) / 32, 1.0, &m->seq2.apack16, m->f16));
-            RMR_TRY(pack_flat_a(m.get(), convs[5], convs[5].s.ic, (convs[5].s.kw * convs[5].s.ic + 31) / 32, 1.0, &m->merge1.apack16, m->f16));
-        }
-        if (m->nparts == 1 && sz == 64 && (K == 9 || K == 6) && kw1 == 5) {  // operands of the fused front kernel
-            const int cg = (4 * K + 7) / 8;
-            const double log2e = 1.4426950408889634;
-            RMR_TRY(pack_flat_a(m.get(), convs[1], 4, 1, 1.0, &m->fused.a_sig2, m->f16));
-            RMR_TRY(pack_flat_a(m.get(), convs[3], 8 * cg, (5 * cg * 8 + 31) / 32, log2e, &m->fused.a_seq1, m->f16));
-            RMR_TRY(pack_flat_a(m.get(), convs[2], 16, 5, 1.0, &m->fused.a_sig3, m->f16));
-            RMR_TRY(pack_flat_a(m.get(), convs[4], 16, 7, 1.0, &m->fused.a_seq2, m->f16));
-            RMR_TRY(pack_flat_a(m.get(), convs[5], 2 * sz, 20, 1.0, &m->fused.a_merge1, m->f16));
-            auto scaled = [&](const std::vector<float> &v) {
-                std::vector<float> o(v.size());
-                for (size_t i = 0; i < v.size(); ++i) o[i] = (float)((double)v[i] * log2e);
-                return o;
-            };
-            std::vector<float> w1s((size_t)kw1 * 4);
-            for (int t = 0; t < kw1; ++t)
-                for (int o = 0; o < 4; ++o) w1s[t * 4 + o] = (float)((double)convs[0].w[(size_t)o * kw1 + t] * log2e);
-            RMR_TRY(upload(m.get(), w1s, &m->fused.w_sig1));
-            RMR_TRY(upload(m.get(), scaled(convs[0].b), &m->fused.b_sig1));
-            RMR_TRY(upload(m.get(), scaled(convs[1].b), &m->fused.b_sig2));
-            RMR_TRY(upload(m.get(), scaled(convs[3].b), &m->fused.b_seq1));
-            RMR_TRY(upload(m.get(), scaled(convs[2].b), &m->fused.b_sig3));
-            RMR_TRY(upload(m.get(), scaled(convs[4].b), &m->fused.b_seq2));
-            RMR_TRY(upload(m.get(), scaled(convs[5].b), &m->fused.b_merge1));
-        }
-        const int H = sz;
-        const float *wih1 = p; p += (size_t)4 * H * H;
-        const float *whh1 = p; p += (size_t)4 * H * H;
-        const float *bih1 = p; p += 4 * H;
-        const float *bhh1 = p; p += 4 * H;
-        const float *wih2 = p; p += (size_t)4 * H * H;
-        p += (size_t)4 * H * H;  // lstm2.weight_hh_l0 multiplies h0 == 0: never reaches the output
-        const float *bih2 = p; p += 4 * H;
-        const float *bhh2 = p; p += 4 * H;
-        const float *wfc = p; p += (size_t)desc->num_out * H;
-        const float *bfc = p; p += desc->num_out;
-        const int g4[4] = {0, 1, 2, 3}, g3[3] = {0, 2, 3};
-        if (H > 64) {  // k_stream.hip
-            RMR_TRY(upload(m.get(), pack_lstm_stream(wih1, H, g4, 4, true), &m->lstm.t_ih1));
-            RMR_TRY(upload(m.get(), pack_lstm_stream(whh1, H, g4, 4, true), &m->lstm.t_hh1));
-            RMR_TRY(upload(m.get(), pack_lstm_stream(wih2, H, g3, 3, false), &m->lstm.t_ih2));
-        } else {
-            RMR_TRY(upload(m.get(), pack_lstm(wih1, H, g4, 4, true), &m->lstm.a_ih1));
-            RMR_TRY(upload(m.get(), pack_lstm(whh1, H, g4, 4, true), &m->lstm.a_hh1));
-            RMR_TRY(upload(m.get(), pack_lstm(wih2, H, g3, 3), &m->lstm.a_ih2));
-            if (H == 64 && m->nparts == 0) {  // the four-chunk kernel of small batches (one read per call)
-                const int g3z[4] = {0, 2, 3, -1};
-                RMR_TRY(upload(m.get(), pack_lstm_small(wih1, g4, true), &m->lstm.q_ih1));
-                RMR_TRY(upload(m.get(), pack_lstm_small(whh1, g4, true), &m->lstm.q_hh1));
-                RMR_TRY(upload(m.get(), pack_lstm_small(wih2, g3z, false), &m->lstm.q_ih2));
-            }
-        }
-        if (m->nparts > 0) {
-            std::vector<float> si((size_t)4 * H * H), sh((size_t)4 * H * H);
-            for (int r = 0; r < 4 * H; ++r)
-                for (int k = 0; k < H; ++k) {
-                    si[(size_t)r * H + k] = (float)((double)wih1[(size_t)r * H + k] * lstm1_gate_scale(r / H));
-                    sh[(size_t)r * H + k] = (float)((double)whh1[(size_t)r * H + k] * lstm1_gate_scale(r / H));
-                }
-            const int rb[4] = {0, H, 2 * H, 3 * H};
-            RMR_TRY(upload(m.get(), pack_split_a(si, H, H / 16, rb, 4, m->nparts, m->split_f16), &m->lstm.s_ih1));
-            RMR_TRY(upload(m.get(), pack_split_a(sh, H, H / 16, rb, 4, m->nparts, m->split_f16), &m->lstm.s_hh1));
-        }
-        if (m->nparts >= 2 && H == 64) {  // split operands in the x16 layout (k_lstm_x16s.hip)
-            RMR_TRY(upload(m.get(), pack_lstm_x16_split(wih1, false, m->nparts, m->split_f16), &m->lstm.xs_ih));
-            RMR_TRY(upload(m.get(), pack_lstm_x16_split(whh1, false, m->nparts, m->split_f16), &m->lstm.xs_hh));
-            RMR_TRY(upload(m.get(), pack_lstm_x16_split(wih2, true, m->nparts, m->split_f16), &m->lstm.xs_ih2));
-            RMR_TRY(upload(m.get(), pack_bias_x16(bih1, bhh1, false), &m->lstm.x_b1));
-            RMR_TRY(upload(m.get(), pack_bias_x16(bih2, bhh2, true), &m->lstm.x_b2));
-        }
-        if (m->nparts == 1 && H > 64) {  // k_stream16.hip
-            RMR_TRY(upload(m.get(), pack_lstm_s16(wih1, H, false, m->f16), &m->lstm.s16_ih));
-            RMR_TRY(upload(m.get(), pack_lstm_s16(whh1, H, false, m->f16), &m->lstm.s16_hh));
-            RMR_TRY(upload(m.get(), pack_lstm_s16(wih2, H, true, m->f16), &m->lstm.s16_ih2));
-            RMR_TRY(upload(m.get(), pack_bias_s16(bih1, bhh1, H, false), &m->lstm.s16_b1));
-            RMR_TRY(upload(m.get(), pack_bias_s16(bih2, bhh2, H, true), &m->lstm.s16_b2));
-        }
-        if (m->nparts == 1 && H == 64) {
-            RMR_TRY(upload(m.get(), pack_lstm_x16(wih1, false, m->f16), &m->lstm.x_ih));
-            RMR_TRY(upload(m.get(), pack_lstm_x16(whh1, false, m->f16), &m->lstm.x_hh));
-            RMR_TRY(upload(m.get(), pack_lstm_x16(wih2, true, m->f16), &m->lstm.x_ih2));
-            RMR_TRY(upload(m.get(), pack_bias_x16(bih1, bhh1, false), &m->lstm.x_b1));
-            RMR_TRY(upload(m.get(), pack_bias_x16(bih2, bhh2, true), &m->lstm.x_b2));
-        }
-        std::vector<float> b1(4 * H), b2(3 * H);
-        for (int i = 0; i < 4 * H; ++i)
-            b1[i] = (float)(((double)bih1[i] + (double)bhh1[i]) * lstm1_gate_scale(i / H));
-        for (int gi = 0; gi < 3; ++gi)
-            for (int u = 0; u < H; ++u) b2[gi * H + u] = bih2[g3[gi] * H + u] + bhh2[g3[gi] * H + u];
-        RMR_TRY(upload(m.get(), b1, &m->lstm.b1));
-        RMR_TRY(upload(m.get(), b2, &m->lstm.b2));
-        RMR_TRY(upload(m.get(), std::vector<float>(wfc, wfc + (size_t)desc->num_out * H), &m->lstm.w_fc));
-        RMR_TRY(upload(m.get(), std::vector<float>(bfc, bfc + desc->num_out), &m->lstm.b_fc));
-    } else {
-        RMR_TRY(pack_conv(m.get(), convs[5], K_CONV_SEQ3, &m->seq3));
-        RMR_TRY(pack_conv(m.get(), convs[6], K_CONV_MERGE1, &m->merge1));
-        RMR_TRY(pack_conv(m.get(), convs[7], K_CONV_MERGE2, &m->merge2));
-        RMR_TRY(pack_conv(m.get(), convs[8], K_CONV_MERGE3, &m->merge3));
-        RMR_TRY(pack_conv(m.get(), convs[9], K_CONV_MERGE4, &m->merge4));
-        const float *wfc = p; p += (size_t)desc->num_out * sz * 3;
-        const float *bfc = p; p += desc->num_out;
-        RMR_TRY(upload(m.get(), std::vector<float>(wfc, wfc + (size_t)desc->num_out * sz * 3), &m->w_fc));
-        RMR_TRY(upload(m.get(), std::vector<float>(bfc, bfc + desc->num_out), &m->b_fc));
-    }
-    if ((size_t)(p - weights) != n_floats) RMR_FAIL(RMR_ERR_INVALID, "internal: blob walk mismatch");
+    RMR_TRY(pack_model(*desc, weights, n_floats, m.get(), [&](const std::string &, const std::vector<float> &h, float **dev) -> int {
+        void *p = nullptr;
+        RMR_HIP(hipMalloc(&p, h.size() * sizeof(float) + 16));
+        m->dev_allocs.push_back(p);
+        RMR_HIP(hipMemcpy(p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+        *dev = reinterpret_cast<float *>(p);
+        return 0;
+    }));
+    m->sig3.kid = K_CONV_SIG3;  // profiling ids
+    m->seq2.kid = K_CONV_SEQ2;
+    m->seq3.kid = K_CONV_SEQ3;
+    m->merge1.kid = K_CONV_MERGE1;
+    m->merge2.kid = K_CONV_MERGE2;
+    m->merge3.kid = K_CONV_MERGE3;
+    m->merge4.kid = K_CONV_MERGE4;
     *out = m.release();
     return 0;
 }

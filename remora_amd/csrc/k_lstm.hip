@@ -71,7 +71,7 @@ __device__ __forceinline__ void gates(const f32x4 (&acc)[4], f32x4 &c, f32x4 &h)
 // The fp32 MFMA shares the SIMD's fp32 datapath with ordinary VALU work (ablation: removing
 // the gate transcendentals raised the kernel from 114 to 134 TFLOP/s), so the gate math is
 // kept minimal: the i/f/o rows of W and b are pre-scaled by -log2(e) and the g rows by
-// 2 log2(e) on the host (engine.hip), making sigmoid = rcp(1 + exp2(a)) and
+// 2 log2(e) on the host (rmr_pack.cpp), making sigmoid = rcp(1 + exp2(a)) and
 // tanh = 1 - 2 rcp(1 + exp2(a)) three/four instructions each.  The projection MFMAs of step
 // t+1 are sliced between the gate slices so that MFMA issue never waits for a long
 // dependent VALU chain.

@@ -7,11 +7,11 @@
 // 256: here a wave fetches the A fragment of one k-step group (16 bytes per lane = the four MFMAs of one ds_read_b128 B
 // fragment) two groups ahead of its use and amortises it over NT column tiles whose accumulators it holds (NT x 4 VGPRs), so
 // the L2 -> CU weight traffic is 1 / NT of a fetch per MFMA.  Channel counts are runtime values (any multiple of 16 up to 256;
-// engine.hip pads other sizes with zero-weight channels), LDS images are the four-plane layout of k_conv.hip with the row
+// rmr_pack.cpp pads other sizes with zero-weight channels), LDS images are the four-plane layout of k_conv.hip with the row
 // stride computed at launch (rowstride / 4 odd: every 16-lane ds_read_b128 group on 16 distinct bank slots).
 //
 // Arithmetic: identical operations in identical order to the resident kernels (bias first, k ascending over (tap, channel),
-// the x projection before the recurrent one; gates on exp2 / rcp with the pre-scaled rows of engine.hip) - fp32 MFMA is a
+// the x projection before the recurrent one; gates on exp2 / rcp with the pre-scaled rows of rmr_pack.cpp) - fp32 MFMA is a
 // k-ordered fmaf chain, so a network padded from 64 to 80 channels returns the 64-channel kernels' bits.
 #include "rmr_internal.h"
 #include "rmr_math.h"
@@ -238,7 +238,7 @@ int launch_conv_stream(rmr_engine *e, const ConvLayer &c, const float *in, int i
 struct LstmSArgs {
     const float *x;  // [n][T][H] channel-last merge_conv1 output
     float *logits;   // [n][num_out]
-    // a_ih1 / a_hh1: [H/16 waves][H/16 k groups][4 gates][64 lanes][4] (rows pre-scaled, engine.hip lstm1_gate_scale);
+    // a_ih1 / a_hh1: [H/16 waves][H/16 k groups][4 gates][64 lanes][4] (rows pre-scaled, rmr_pack.cpp gate_scale);
     // a_ih2: [H/16][H/16][3 gates i, g, o][64][4]; b1 [4H] (b_ih + b_hh, pre-scaled), b2 [3H]
     const float *a_ih1, *a_hh1, *b1, *a_ih2, *b2, *w_fc, *b_fc;
     int64_t n;

@@ -241,7 +241,7 @@ struct LstmS16Args {
     const uint16_t *x;  // 16-bit [n][T][H]
     float *logits;
     // a_ih / a_hh / a_ih2: [H/16 waves][4 tiles][ksh][64 lanes] x 16 B; row m of tile t of wave w = (unit 16 w + 4 (m >> 2) + t, gate m & 3),
-    // rows pre-scaled (engine.hip lstm1_gate_scale), lstm2 with a zero f row; b1 / b2: [H/16][4 tiles][4 q][4 gates]
+    // rows pre-scaled (rmr_pack.cpp gate_scale), lstm2 with a zero f row; b1 / b2: [H/16][4 tiles][4 q][4 gates]
     const uint4 *a_ih, *a_hh, *a_ih2;
     const float *b1, *b2, *w_fc, *b_fc;
     int64_t n;

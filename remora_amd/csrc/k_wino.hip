@@ -12,7 +12,7 @@
 // three matrices from the points in exact rational arithmetic and a CPU test holds the constants below to them):
 //
 //     y[4t + i][oc] = sum_x AT[i][x] * ( sum_ic U[x][oc][ic] * V[x][t][ic] ),     i = 0..3,   x = 0..7
-//     U[x][oc][ic]  = sum_tap G[x][tap] * W[oc][ic][tap]          (host, float64, one rounding: engine.hip pack_conv)
+//     U[x][oc][ic]  = sum_tap G[x][tap] * W[oc][ic][tap]          (host, float64, one rounding: rmr_pack.cpp wino_filter)
 //     V[x][t][ic]   = sum_j  BT[x][j]  * in[4t + j][ic]           (this kernel; small-integer coefficients)
 //
 //     BT =  4   0 -21   0  21   0  -4   0        G = 1/4    0      0     0     0        AT = 1  1  1  1  1   1    1   0

@@ -2849,6 +2849,42 @@ def test_front_plans_fit_their_budgets_and_pin_the_benchmark_shapes(tmp_path):
     ]
 
 
+_MODEL_PACKS_RUN = {}
+
+
+def _model_packs_output():
+    """stdout of tests/c/model_packs.cpp, built with remora_amd/csrc/rmr_pack.cpp by ROCm's clang++ (the compiler hipcc wraps; the
+    library's host flags) and run once per session."""
+    if "out" not in _MODEL_PACKS_RUN:
+        import tempfile
+
+        clang = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
+        assert os.path.exists(clang), clang
+        csrc = os.path.join(ROOT, "remora_amd", "csrc")
+        exe = os.path.join(tempfile.mkdtemp(), "model_packs")
+        cc = subprocess.run([clang, "-O3", "-std=c++17", "-Wall", "-I", csrc, os.path.join(ROOT, "tests", "c", "model_packs.cpp"),
+                             os.path.join(csrc, "rmr_pack.cpp"), "-o", exe], capture_output=True, text=True)
+        assert cc.returncode == 0, cc.stderr
+        run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+        assert run.returncode == 0, run.stdout[-2000:] + run.stderr
+        _MODEL_PACKS_RUN["out"] = run.stdout.splitlines()
+    return _MODEL_PACKS_RUN["out"]
+
+
+def test_model_packs_are_pinned_buffer_by_buffer():
+    """rmr_pack.h pack_model is what rmr_model_create runs on the host: it folds BatchNorm, packs every layer into its kernels'
+    fragment layouts and decides which buffers a model gets.  tests/c/model_packs.cpp runs it on seeded blobs of ConvLSTM_w_ref at
+    16 / 32 / 64 / 96 / 128 / 256 channels (k-mer 9; 6 and 5 at 64, 5 at 128; 40 channels padded to 64) in every dtype desc_ok
+    takes, and of Conv_w_ref at 64 / 96, and prints the geometry and an FNV-1a digest of every uploaded buffer.  The pinned lines
+    (_MODEL_PACKS, end of file) were produced by the packers as they stood before rmr_pack.h (engine.hip, with the upload
+    stubbed): every buffer of every listed model, byte for byte."""
+    got = [line for line in _model_packs_output() if not line.startswith(("wino ", "G5 ", "G3 "))]
+    want = _MODEL_PACKS.strip().splitlines()
+    missing, extra = sorted(set(want) - set(got)), sorted(set(got) - set(want))
+    assert not missing and not extra, f"missing: {missing[:20]}\nextra: {extra[:20]}"
+    assert got == want
+
+
 def test_subbatch_cuts_partition_a_batch_of_reads():
     """inference._subbatch_cuts: contiguous, complete, non-empty pieces for any batch size; a short start (the GPU gets work
     after a quarter sub-batch has been staged) and a short end (what remains to be done when the stager is finished)."""
@@ -3234,11 +3270,14 @@ def test_padded_network_is_the_same_function(O, name, padded):
     assert np.abs(got - O.forward(state, g["sigs"], enc)).max() < 1e-6  # zero channels change nothing but the summation tree
 
 
-def test_winograd_constants_match_the_exact_derivation():
-    """k_wino.hip / engine.hip hold the F(4, 5) matrices as constants: the filter transform G (engine.hip `GM`, rows in the kernel's x
-    order) and the BT / G / AT table of k_wino.hip's header are the ones oracle/winograd.py derives from the eight points in exact
-    rational arithmetic; the derivation itself reproduces the plain sums y[i] = sum_k g[k] d[i + k] exactly; and the even / odd
-    evaluation the kernel uses for BT d (restated here line by line from wino_in_transform) equals BT d."""
+def test_winograd_filter_transforms_match_the_exact_derivation():
+    """k_wino.hip / rmr_pack.cpp hold the F(4, 5) and F(4, 3) matrices as constants: the filter transforms G (rmr_pack.cpp `G5`,
+    `G3`, natural point order) and the BT / G / AT table of k_wino.hip's header are the ones oracle/winograd.py derives from the
+    points in exact rational arithmetic; the packed U = G W of a one-hot filter (tests/c/model_packs.cpp runs rmr_pack.cpp's
+    wino_filter) is G in each point order a kernel reads - F(4, 5) in wino_kernel's order and in natural order for seq_conv2's
+    phases, F(4, 3) in natural order and in wino_s3_kernel's; the derivation itself reproduces the plain sums y[i] =
+    sum_k g[k] d[i + k] exactly; and the even / odd evaluation the kernel uses for BT d (restated here line by line from
+    wino_in_transform) equals BT d."""
     import random
     from fractions import Fraction as Fr
 
@@ -3250,18 +3289,27 @@ def test_winograd_constants_match_the_exact_derivation():
         g = [Fr(rnd.randint(-9, 9), rnd.randint(1, 7)) for _ in range(5)]
         d = [Fr(rnd.randint(-9, 9), rnd.randint(1, 7)) for _ in range(8)]
         assert W.apply(AT, G, BT, g, d) == W.correlate(g, d, 4)
-    # engine.hip: static const double GM[8][5] = {{...}, ...}; entries are C expressions like 1.0 / 18 or -8.0 / 45
-    eng = open(os.path.join(ROOT, "remora_amd", "csrc", "engine.hip")).read()
-    blk = eng[eng.index("static const double GM[8][5]") :]
-    blk = blk[blk.index("{") : blk.index("};") + 1]
-    rows = re.findall(r"\{([^{}]+)\}", blk)
-    assert len(rows) == 8
-    for k, row in enumerate(rows):
-        vals = []
-        for e in row.split(","):
-            num, _, den = e.strip().partition("/")
-            vals.append(Fr(num.strip()) / (Fr(den.strip()) if den else 1))
-        assert vals == G[W.F45_KERNEL_ORDER[k]], (k, row)
+    # the tables of rmr_pack.cpp (float64, natural order), and U = G W as pack_model uploads it: every phase p of a stride-3 layer,
+    # every tap t, every point x in the kernel's order, and no weight anywhere else in the buffer
+    AT3, G3, BT3 = W.matrices(4, 3, (0, 1, -1, 2, -2, None))
+    out = _model_packs_output()
+    tables = {"G5": G, "G3": G3}
+    seen = {"G5": 0, "G3": 0}
+    for line in out:
+        name, x, t, v = (line.split() + [None] * 4)[:4]
+        if name in tables:
+            assert float(v) == float(tables[name][int(x)][int(t)]), line
+            seen[name] += 1
+    assert seen == {"G5": 40, "G3": 18}
+    forms = {"f45_kernel": (G, W.F45_KERNEL_ORDER, 1, 5), "f45_natural_s3": (G, tuple(range(8)), 3, 13),
+             "f43_natural_s3": (G3, tuple(range(6)), 3, 9), "f43_kernel_s3": (G3, (1, 2, 0, 3, 4, 5), 3, 9)}
+    for form, (Gm, order, P, kw) in forms.items():
+        rows = [line.split()[2:] for line in out if line.startswith(f"wino {form} ")]
+        assert rows[-1] == ["misplaced", "0"], rows[-1]
+        vals = {(int(p), int(x), int(t)): float(v) for p, x, t, v in rows[:-1]}
+        assert set(vals) == {(p, x, t) for p in range(P) for t in range(len(Gm[0])) if P * t + p < kw for x in range(len(order))}, form
+        for (p, x, t), v in vals.items():
+            assert np.float32(v) == np.float32(float(Gm[order[x]][t])), (form, p, x, t, v)
     # k_wino.hip's header table (BT | G | AT side by side)
     src = open(os.path.join(ROOT, "remora_amd", "csrc", "k_wino.hip")).read()
     tab = src[src.index("//     BT = ") :].split("\n")[:8]
@@ -3284,18 +3332,7 @@ def test_winograd_constants_match_the_exact_derivation():
              21 * (d[3] - d[5]) + 4 * (d[7] - d[1])]
         want = [sum(BT[x][j] * d[j] for j in range(8)) for x in W.F45_KERNEL_ORDER]
         assert v == want
-    # F(4, 3) of the stride-3 kernel: engine.hip `G3` (natural order) and wino_in_transform6 (kernel order 1, 2, 0, 3, 4, 5)
-    AT3, G3, BT3 = W.matrices(4, 3, (0, 1, -1, 2, -2, None))
-    blk = eng[eng.index("static const double G3[6][3]") :]
-    blk = blk[blk.index("{") : blk.index("};") + 1]
-    rows = re.findall(r"\{([^{}]+)\}", blk)
-    assert len(rows) == 6
-    for k, row in enumerate(rows):
-        vals = []
-        for e in row.split(","):
-            num, _, den = e.strip().partition("/")
-            vals.append(Fr(num.strip()) / (Fr(den.strip()) if den else 1))
-        assert vals == G3[k], (k, row)
+    # F(4, 3) of the stride-3 kernel: wino_in_transform6 (kernel order 1, 2, 0, 3, 4, 5) and its output stage
     for _ in range(10):
         d = [Fr(rnd.randint(-50, 50), rnd.randint(1, 9)) for _ in range(6)]
         a_, b_ = 4 * d[2] - d[4], 4 * d[1] - d[3]
@@ -3311,3 +3348,1389 @@ def test_winograd_constants_match_the_exact_derivation():
         s12, d12, s34, d34, s56, d56 = m[1] + m[2], m[1] - m[2], m[3] + m[4], m[3] - m[4], m[5] + m[6], m[5] - m[6]
         y = [(s12 + s34) + (m[0] + s56), (2 * d34 + d12) + d56 / 2, (4 * s34 + s12) + s56 / 4, (8 * d34 + d12) + (d56 / 8 + m[7])]
         assert y == [sum(AT[i][x] * m[x] for x in range(8)) for i in range(4)]
+
+
+# tests/c/model_packs.cpp on the packers before rmr_pack.h (test_model_packs_are_pinned_buffer_by_buffer): per model its geometry,
+# then "<model> <buffer> <floats> <FNV-1a 64 of the bytes>" for every buffer it uploads
+_MODEL_PACKS = """
+lstm_s16_k9_fp32 geometry nparts=0 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s16_k9_fp32 front.b_seq1 16 dc144c309972e556
+lstm_s16_k9_fp32 front.b_sig1 4 66752726d6894f90
+lstm_s16_k9_fp32 front.b_sig2 16 f12cc0a532286361
+lstm_s16_k9_fp32 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s16_k9_fp32 front.w_sig2 320 092b55db23ba607a
+lstm_s16_k9_fp32 front.wt5_seq1 3600 a2ccb86cf6330650
+lstm_s16_k9_fp32 front.wt_seq1 2880 7506009ef743fd50
+lstm_s16_k9_fp32 lstm.a_hh1 1024 1fdc9e7bbeb43f7b
+lstm_s16_k9_fp32 lstm.a_ih1 1024 5fae513c29bf94a6
+lstm_s16_k9_fp32 lstm.a_ih2 768 68a6caff384dc1c7
+lstm_s16_k9_fp32 lstm.b1 64 7d2964a375d3d3ab
+lstm_s16_k9_fp32 lstm.b2 48 f412c702b3f886e5
+lstm_s16_k9_fp32 lstm.b_fc 2 f6b04e0dc7fdb3a5
+lstm_s16_k9_fp32 lstm.w_fc 32 f4e04ba439af5a83
+lstm_s16_k9_fp32 merge1.apack 2560 bd2ae15aa6cfde93
+lstm_s16_k9_fp32 merge1.bias 16 b0ba80debdd5ad72
+lstm_s16_k9_fp32 seq2.apack 3328 ae806876fdd7e683
+lstm_s16_k9_fp32 seq2.bias 16 9684e19df066a1b8
+lstm_s16_k9_fp32 sig3.apack 2304 1c802ffb32aa018c
+lstm_s16_k9_fp32 sig3.bias 16 615f1b0a0d67c637
+lstm_s32_k9_fp32 geometry nparts=0 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s32_k9_fp32 front.b_seq1 16 a6b06416914529c6
+lstm_s32_k9_fp32 front.b_sig1 4 66752726d6894f90
+lstm_s32_k9_fp32 front.b_sig2 16 f12cc0a532286361
+lstm_s32_k9_fp32 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s32_k9_fp32 front.w_sig2 320 092b55db23ba607a
+lstm_s32_k9_fp32 front.wt5_seq1 3600 794c590463e88f23
+lstm_s32_k9_fp32 front.wt_seq1 2880 d9a87d01fe1e8823
+lstm_s32_k9_fp32 lstm.a_hh1 4096 435ec2870ad0b9a7
+lstm_s32_k9_fp32 lstm.a_ih1 4096 ca0712943294f5c3
+lstm_s32_k9_fp32 lstm.a_ih2 3072 6404118fd0f3b335
+lstm_s32_k9_fp32 lstm.b1 128 03a00788de88c312
+lstm_s32_k9_fp32 lstm.b2 96 a30698f56bcd2e0e
+lstm_s32_k9_fp32 lstm.b_fc 2 9f61a5cd54a8a91d
+lstm_s32_k9_fp32 lstm.w_fc 64 21fec20db83a6457
+lstm_s32_k9_fp32 merge1.apack 10240 4e4097e4a66c44ae
+lstm_s32_k9_fp32 merge1.bias 32 677dc7a967364e72
+lstm_s32_k9_fp32 seq2.apack 6656 c7548e5d417db9fc
+lstm_s32_k9_fp32 seq2.bias 32 6e91d254a6f5e23e
+lstm_s32_k9_fp32 sig3.apack 4608 cca6f265071c6218
+lstm_s32_k9_fp32 sig3.bias 32 fc4d4ff2b120094d
+lstm_s32_k9_bf16 geometry nparts=1 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s32_k9_bf16 front.b_seq1 16 a6b06416914529c6
+lstm_s32_k9_bf16 front.b_sig1 4 66752726d6894f90
+lstm_s32_k9_bf16 front.b_sig2 16 f12cc0a532286361
+lstm_s32_k9_bf16 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s32_k9_bf16 front.w_sig2 320 092b55db23ba607a
+lstm_s32_k9_bf16 front.wt5_seq1 3600 794c590463e88f23
+lstm_s32_k9_bf16 front.wt_seq1 2880 d9a87d01fe1e8823
+lstm_s32_k9_bf16 lstm.a_hh1 4096 435ec2870ad0b9a7
+lstm_s32_k9_bf16 lstm.a_ih1 4096 ca0712943294f5c3
+lstm_s32_k9_bf16 lstm.a_ih2 3072 6404118fd0f3b335
+lstm_s32_k9_bf16 lstm.b1 128 03a00788de88c312
+lstm_s32_k9_bf16 lstm.b2 96 a30698f56bcd2e0e
+lstm_s32_k9_bf16 lstm.b_fc 2 9f61a5cd54a8a91d
+lstm_s32_k9_bf16 lstm.s_hh1 2048 c0056af0013343d7
+lstm_s32_k9_bf16 lstm.s_ih1 2048 16a0830e06a3073d
+lstm_s32_k9_bf16 lstm.w_fc 64 21fec20db83a6457
+lstm_s32_k9_bf16 merge1.apack 10240 4e4097e4a66c44ae
+lstm_s32_k9_bf16 merge1.bias 32 677dc7a967364e72
+lstm_s32_k9_bf16 merge1.spack 5120 1465373a3b82aa42
+lstm_s32_k9_bf16 seq2.apack 6656 c7548e5d417db9fc
+lstm_s32_k9_bf16 seq2.bias 32 6e91d254a6f5e23e
+lstm_s32_k9_bf16 seq2.spack 3584 02605de5c91de61d
+lstm_s32_k9_bf16 sig3.apack 4608 cca6f265071c6218
+lstm_s32_k9_bf16 sig3.bias 32 fc4d4ff2b120094d
+lstm_s32_k9_bf16 sig3.spack 2560 7833d0b4881fb2cd
+lstm_s32_k9_bf16x3 geometry nparts=2 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s32_k9_bf16x3 front.b_seq1 16 a6b06416914529c6
+lstm_s32_k9_bf16x3 front.b_sig1 4 66752726d6894f90
+lstm_s32_k9_bf16x3 front.b_sig2 16 f12cc0a532286361
+lstm_s32_k9_bf16x3 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s32_k9_bf16x3 front.w_sig2 320 092b55db23ba607a
+lstm_s32_k9_bf16x3 front.wt5_seq1 3600 794c590463e88f23
+lstm_s32_k9_bf16x3 front.wt_seq1 2880 d9a87d01fe1e8823
+lstm_s32_k9_bf16x3 lstm.a_hh1 4096 435ec2870ad0b9a7
+lstm_s32_k9_bf16x3 lstm.a_ih1 4096 ca0712943294f5c3
+lstm_s32_k9_bf16x3 lstm.a_ih2 3072 6404118fd0f3b335
+lstm_s32_k9_bf16x3 lstm.b1 128 03a00788de88c312
+lstm_s32_k9_bf16x3 lstm.b2 96 a30698f56bcd2e0e
+lstm_s32_k9_bf16x3 lstm.b_fc 2 9f61a5cd54a8a91d
+lstm_s32_k9_bf16x3 lstm.s_hh1 4096 68062a0001224d29
+lstm_s32_k9_bf16x3 lstm.s_ih1 4096 c9813bad85c4997b
+lstm_s32_k9_bf16x3 lstm.w_fc 64 21fec20db83a6457
+lstm_s32_k9_bf16x3 merge1.apack 10240 4e4097e4a66c44ae
+lstm_s32_k9_bf16x3 merge1.bias 32 677dc7a967364e72
+lstm_s32_k9_bf16x3 merge1.spack 10240 377adeaa49a891fa
+lstm_s32_k9_bf16x3 seq2.apack 6656 c7548e5d417db9fc
+lstm_s32_k9_bf16x3 seq2.bias 32 6e91d254a6f5e23e
+lstm_s32_k9_bf16x3 seq2.spack 7168 2978d76d34ee6fb4
+lstm_s32_k9_bf16x3 sig3.apack 4608 cca6f265071c6218
+lstm_s32_k9_bf16x3 sig3.bias 32 fc4d4ff2b120094d
+lstm_s32_k9_bf16x3 sig3.spack 5120 7e71514aacc0d3a0
+lstm_s32_k9_bf16x6 geometry nparts=3 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s32_k9_bf16x6 front.b_seq1 16 a6b06416914529c6
+lstm_s32_k9_bf16x6 front.b_sig1 4 66752726d6894f90
+lstm_s32_k9_bf16x6 front.b_sig2 16 f12cc0a532286361
+lstm_s32_k9_bf16x6 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s32_k9_bf16x6 front.w_sig2 320 092b55db23ba607a
+lstm_s32_k9_bf16x6 front.wt5_seq1 3600 794c590463e88f23
+lstm_s32_k9_bf16x6 front.wt_seq1 2880 d9a87d01fe1e8823
+lstm_s32_k9_bf16x6 lstm.a_hh1 4096 435ec2870ad0b9a7
+lstm_s32_k9_bf16x6 lstm.a_ih1 4096 ca0712943294f5c3
+lstm_s32_k9_bf16x6 lstm.a_ih2 3072 6404118fd0f3b335
+lstm_s32_k9_bf16x6 lstm.b1 128 03a00788de88c312
+lstm_s32_k9_bf16x6 lstm.b2 96 a30698f56bcd2e0e
+lstm_s32_k9_bf16x6 lstm.b_fc 2 9f61a5cd54a8a91d
+lstm_s32_k9_bf16x6 lstm.s_hh1 6144 b53012c0e86c10e4
+lstm_s32_k9_bf16x6 lstm.s_ih1 6144 73215061bde77230
+lstm_s32_k9_bf16x6 lstm.w_fc 64 21fec20db83a6457
+lstm_s32_k9_bf16x6 merge1.apack 10240 4e4097e4a66c44ae
+lstm_s32_k9_bf16x6 merge1.bias 32 677dc7a967364e72
+lstm_s32_k9_bf16x6 merge1.spack 15360 b5782dcd3928bfda
+lstm_s32_k9_bf16x6 seq2.apack 6656 c7548e5d417db9fc
+lstm_s32_k9_bf16x6 seq2.bias 32 6e91d254a6f5e23e
+lstm_s32_k9_bf16x6 seq2.spack 10752 ed2c6ccafa0b45cc
+lstm_s32_k9_bf16x6 sig3.apack 4608 cca6f265071c6218
+lstm_s32_k9_bf16x6 sig3.bias 32 fc4d4ff2b120094d
+lstm_s32_k9_bf16x6 sig3.spack 7680 a464f8f4aa995ce3
+lstm_s32_k9_f16x3 geometry nparts=2 split_f16=1 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s32_k9_f16x3 front.b_seq1 16 a6b06416914529c6
+lstm_s32_k9_f16x3 front.b_sig1 4 66752726d6894f90
+lstm_s32_k9_f16x3 front.b_sig2 16 f12cc0a532286361
+lstm_s32_k9_f16x3 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s32_k9_f16x3 front.w_sig2 320 092b55db23ba607a
+lstm_s32_k9_f16x3 front.wt5_seq1 3600 794c590463e88f23
+lstm_s32_k9_f16x3 front.wt_seq1 2880 d9a87d01fe1e8823
+lstm_s32_k9_f16x3 lstm.a_hh1 4096 435ec2870ad0b9a7
+lstm_s32_k9_f16x3 lstm.a_ih1 4096 ca0712943294f5c3
+lstm_s32_k9_f16x3 lstm.a_ih2 3072 6404118fd0f3b335
+lstm_s32_k9_f16x3 lstm.b1 128 03a00788de88c312
+lstm_s32_k9_f16x3 lstm.b2 96 a30698f56bcd2e0e
+lstm_s32_k9_f16x3 lstm.b_fc 2 9f61a5cd54a8a91d
+lstm_s32_k9_f16x3 lstm.s_hh1 4096 10d4fa3c84292458
+lstm_s32_k9_f16x3 lstm.s_ih1 4096 01aa3d864ab027cc
+lstm_s32_k9_f16x3 lstm.w_fc 64 21fec20db83a6457
+lstm_s32_k9_f16x3 merge1.apack 10240 4e4097e4a66c44ae
+lstm_s32_k9_f16x3 merge1.bias 32 677dc7a967364e72
+lstm_s32_k9_f16x3 merge1.spack 10240 612efe24215662d3
+lstm_s32_k9_f16x3 seq2.apack 6656 c7548e5d417db9fc
+lstm_s32_k9_f16x3 seq2.bias 32 6e91d254a6f5e23e
+lstm_s32_k9_f16x3 seq2.spack 7168 bee76f4a84bce346
+lstm_s32_k9_f16x3 sig3.apack 4608 cca6f265071c6218
+lstm_s32_k9_f16x3 sig3.bias 32 fc4d4ff2b120094d
+lstm_s32_k9_f16x3 sig3.spack 5120 b91bb90e04328671
+lstm_s64_k9_fp32 geometry nparts=0 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s64_k9_fp32 front.b_seq1 16 fe070bd9d668418d
+lstm_s64_k9_fp32 front.b_sig1 4 66752726d6894f90
+lstm_s64_k9_fp32 front.b_sig2 16 f12cc0a532286361
+lstm_s64_k9_fp32 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s64_k9_fp32 front.w_sig2 320 092b55db23ba607a
+lstm_s64_k9_fp32 front.wt5_seq1 3600 486622208a995a05
+lstm_s64_k9_fp32 front.wt_seq1 2880 a58c853b1d285105
+lstm_s64_k9_fp32 lstm.a_hh1 16384 fe4da9e9f7621fda
+lstm_s64_k9_fp32 lstm.a_ih1 16384 7e304295ebb02c7b
+lstm_s64_k9_fp32 lstm.a_ih2 12288 5ec2e5f8c35a87fd
+lstm_s64_k9_fp32 lstm.b1 256 f3f4c127c31fbdc9
+lstm_s64_k9_fp32 lstm.b2 192 b4bb20a230fe77a6
+lstm_s64_k9_fp32 lstm.b_fc 2 99050d189fa0aad7
+lstm_s64_k9_fp32 lstm.q_hh1 16384 8ec8fe046c43f8de
+lstm_s64_k9_fp32 lstm.q_ih1 16384 2f015cd894355c6b
+lstm_s64_k9_fp32 lstm.q_ih2 16384 c039b022fc9cb2d5
+lstm_s64_k9_fp32 lstm.w_fc 128 d20c879f909febc1
+lstm_s64_k9_fp32 merge1.apack 40960 802e9acb57d8c6ca
+lstm_s64_k9_fp32 merge1.bias 64 eaa48886fdddd804
+lstm_s64_k9_fp32 merge1.wpack 65536 95b0657a8026dbb8
+lstm_s64_k9_fp32 seq2.apack 13312 50ce784aa0c559fb
+lstm_s64_k9_fp32 seq2.bias 64 bed08e6a4dde5113
+lstm_s64_k9_fp32 seq2.wpack 24576 33a78157e976705f
+lstm_s64_k9_fp32 sig3.apack 9216 4e7afb98c552717a
+lstm_s64_k9_fp32 sig3.bias 64 88fdcc576756f7d7
+lstm_s64_k9_fp32 sig3.wpack 18432 7ed5e4ff1e0824d1
+lstm_s64_k9_bf16 geometry nparts=1 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s64_k9_bf16 front.b_seq1 16 fe070bd9d668418d
+lstm_s64_k9_bf16 front.b_sig1 4 66752726d6894f90
+lstm_s64_k9_bf16 front.b_sig2 16 f12cc0a532286361
+lstm_s64_k9_bf16 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s64_k9_bf16 front.w_sig2 320 092b55db23ba607a
+lstm_s64_k9_bf16 front.wt5_seq1 3600 486622208a995a05
+lstm_s64_k9_bf16 front.wt_seq1 2880 a58c853b1d285105
+lstm_s64_k9_bf16 fused.a_merge1 20480 2734f67d7f891cd4
+lstm_s64_k9_bf16 fused.a_seq1 1792 8ecd205f2a9df37c
+lstm_s64_k9_bf16 fused.a_seq2 7168 5bda34a4419838ff
+lstm_s64_k9_bf16 fused.a_sig2 256 b26b67a0e345ba42
+lstm_s64_k9_bf16 fused.a_sig3 5120 1759cf7d42c8102e
+lstm_s64_k9_bf16 fused.b_merge1 64 271d233674cf9b42
+lstm_s64_k9_bf16 fused.b_seq1 16 06378e18b7b4cefd
+lstm_s64_k9_bf16 fused.b_seq2 64 61991f5ceba16a69
+lstm_s64_k9_bf16 fused.b_sig1 4 edd80ab0d74827ef
+lstm_s64_k9_bf16 fused.b_sig2 16 7d6d04bbd93bd362
+lstm_s64_k9_bf16 fused.b_sig3 64 06b3912f36981abe
+lstm_s64_k9_bf16 fused.w_sig1 20 6817e404ab323544
+lstm_s64_k9_bf16 lstm.a_hh1 16384 fe4da9e9f7621fda
+lstm_s64_k9_bf16 lstm.a_ih1 16384 7e304295ebb02c7b
+lstm_s64_k9_bf16 lstm.a_ih2 12288 5ec2e5f8c35a87fd
+lstm_s64_k9_bf16 lstm.b1 256 f3f4c127c31fbdc9
+lstm_s64_k9_bf16 lstm.b2 192 b4bb20a230fe77a6
+lstm_s64_k9_bf16 lstm.b_fc 2 99050d189fa0aad7
+lstm_s64_k9_bf16 lstm.s_hh1 8192 5a0cf8fc8e909e66
+lstm_s64_k9_bf16 lstm.s_ih1 8192 e933f171bb12d23b
+lstm_s64_k9_bf16 lstm.w_fc 128 d20c879f909febc1
+lstm_s64_k9_bf16 lstm.x_b1 256 b11f7364b432a079
+lstm_s64_k9_bf16 lstm.x_b2 256 14f2db26041645b9
+lstm_s64_k9_bf16 lstm.x_hh 8192 7a2a8ff6f11391fa
+lstm_s64_k9_bf16 lstm.x_ih 8192 48d7182af7ef260f
+lstm_s64_k9_bf16 lstm.x_ih2 8192 a83289a532d5acd7
+lstm_s64_k9_bf16 merge1.apack 40960 802e9acb57d8c6ca
+lstm_s64_k9_bf16 merge1.bias 64 eaa48886fdddd804
+lstm_s64_k9_bf16 merge1.spack 20480 2734f67d7f891cd4
+lstm_s64_k9_bf16 merge1.wpack 65536 95b0657a8026dbb8
+lstm_s64_k9_bf16 seq2.apack 13312 50ce784aa0c559fb
+lstm_s64_k9_bf16 seq2.bias 64 bed08e6a4dde5113
+lstm_s64_k9_bf16 seq2.spack 7168 5bda34a4419838ff
+lstm_s64_k9_bf16 seq2.wpack 24576 33a78157e976705f
+lstm_s64_k9_bf16 sig3.apack 9216 4e7afb98c552717a
+lstm_s64_k9_bf16 sig3.bias 64 88fdcc576756f7d7
+lstm_s64_k9_bf16 sig3.spack 5120 1759cf7d42c8102e
+lstm_s64_k9_bf16 sig3.wpack 18432 7ed5e4ff1e0824d1
+lstm_s64_k9_bf16x3 geometry nparts=2 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s64_k9_bf16x3 front.b_seq1 16 fe070bd9d668418d
+lstm_s64_k9_bf16x3 front.b_sig1 4 66752726d6894f90
+lstm_s64_k9_bf16x3 front.b_sig2 16 f12cc0a532286361
+lstm_s64_k9_bf16x3 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s64_k9_bf16x3 front.w_sig2 320 092b55db23ba607a
+lstm_s64_k9_bf16x3 front.wt5_seq1 3600 486622208a995a05
+lstm_s64_k9_bf16x3 front.wt_seq1 2880 a58c853b1d285105
+lstm_s64_k9_bf16x3 lstm.a_hh1 16384 fe4da9e9f7621fda
+lstm_s64_k9_bf16x3 lstm.a_ih1 16384 7e304295ebb02c7b
+lstm_s64_k9_bf16x3 lstm.a_ih2 12288 5ec2e5f8c35a87fd
+lstm_s64_k9_bf16x3 lstm.b1 256 f3f4c127c31fbdc9
+lstm_s64_k9_bf16x3 lstm.b2 192 b4bb20a230fe77a6
+lstm_s64_k9_bf16x3 lstm.b_fc 2 99050d189fa0aad7
+lstm_s64_k9_bf16x3 lstm.s_hh1 16384 8e381003b8ce2e2f
+lstm_s64_k9_bf16x3 lstm.s_ih1 16384 e42566f92c6d5bd3
+lstm_s64_k9_bf16x3 lstm.w_fc 128 d20c879f909febc1
+lstm_s64_k9_bf16x3 lstm.x_b1 256 b11f7364b432a079
+lstm_s64_k9_bf16x3 lstm.x_b2 256 14f2db26041645b9
+lstm_s64_k9_bf16x3 lstm.xs_hh 16384 3917f25bc4566c8b
+lstm_s64_k9_bf16x3 lstm.xs_ih 16384 85769e9134fa62cb
+lstm_s64_k9_bf16x3 lstm.xs_ih2 16384 dffe25a7cc4b928c
+lstm_s64_k9_bf16x3 merge1.apack 40960 802e9acb57d8c6ca
+lstm_s64_k9_bf16x3 merge1.bias 64 eaa48886fdddd804
+lstm_s64_k9_bf16x3 merge1.spack 40960 2bfa37f447105344
+lstm_s64_k9_bf16x3 merge1.wpack 65536 95b0657a8026dbb8
+lstm_s64_k9_bf16x3 seq2.apack 13312 50ce784aa0c559fb
+lstm_s64_k9_bf16x3 seq2.bias 64 bed08e6a4dde5113
+lstm_s64_k9_bf16x3 seq2.spack 14336 172a8a28ca2e9635
+lstm_s64_k9_bf16x3 seq2.wpack 24576 33a78157e976705f
+lstm_s64_k9_bf16x3 sig3.apack 9216 4e7afb98c552717a
+lstm_s64_k9_bf16x3 sig3.bias 64 88fdcc576756f7d7
+lstm_s64_k9_bf16x3 sig3.spack 10240 d3ed508d3c2ec235
+lstm_s64_k9_bf16x3 sig3.wpack 18432 7ed5e4ff1e0824d1
+lstm_s64_k9_bf16x6 geometry nparts=3 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s64_k9_bf16x6 front.b_seq1 16 fe070bd9d668418d
+lstm_s64_k9_bf16x6 front.b_sig1 4 66752726d6894f90
+lstm_s64_k9_bf16x6 front.b_sig2 16 f12cc0a532286361
+lstm_s64_k9_bf16x6 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s64_k9_bf16x6 front.w_sig2 320 092b55db23ba607a
+lstm_s64_k9_bf16x6 front.wt5_seq1 3600 486622208a995a05
+lstm_s64_k9_bf16x6 front.wt_seq1 2880 a58c853b1d285105
+lstm_s64_k9_bf16x6 lstm.a_hh1 16384 fe4da9e9f7621fda
+lstm_s64_k9_bf16x6 lstm.a_ih1 16384 7e304295ebb02c7b
+lstm_s64_k9_bf16x6 lstm.a_ih2 12288 5ec2e5f8c35a87fd
+lstm_s64_k9_bf16x6 lstm.b1 256 f3f4c127c31fbdc9
+lstm_s64_k9_bf16x6 lstm.b2 192 b4bb20a230fe77a6
+lstm_s64_k9_bf16x6 lstm.b_fc 2 99050d189fa0aad7
+lstm_s64_k9_bf16x6 lstm.s_hh1 24576 aa995c915b30a143
+lstm_s64_k9_bf16x6 lstm.s_ih1 24576 70141cef9ebabea0
+lstm_s64_k9_bf16x6 lstm.w_fc 128 d20c879f909febc1
+lstm_s64_k9_bf16x6 lstm.x_b1 256 b11f7364b432a079
+lstm_s64_k9_bf16x6 lstm.x_b2 256 14f2db26041645b9
+lstm_s64_k9_bf16x6 lstm.xs_hh 24576 0dcd0dff44f06a93
+lstm_s64_k9_bf16x6 lstm.xs_ih 24576 8a2ad259f42784e0
+lstm_s64_k9_bf16x6 lstm.xs_ih2 24576 87b1d908fa810b8e
+lstm_s64_k9_bf16x6 merge1.apack 40960 802e9acb57d8c6ca
+lstm_s64_k9_bf16x6 merge1.bias 64 eaa48886fdddd804
+lstm_s64_k9_bf16x6 merge1.spack 61440 f0073d15ebdce733
+lstm_s64_k9_bf16x6 merge1.wpack 65536 95b0657a8026dbb8
+lstm_s64_k9_bf16x6 seq2.apack 13312 50ce784aa0c559fb
+lstm_s64_k9_bf16x6 seq2.bias 64 bed08e6a4dde5113
+lstm_s64_k9_bf16x6 seq2.spack 21504 7e41397f0f4e7241
+lstm_s64_k9_bf16x6 seq2.wpack 24576 33a78157e976705f
+lstm_s64_k9_bf16x6 sig3.apack 9216 4e7afb98c552717a
+lstm_s64_k9_bf16x6 sig3.bias 64 88fdcc576756f7d7
+lstm_s64_k9_bf16x6 sig3.spack 15360 bf76e3335d43c7c0
+lstm_s64_k9_bf16x6 sig3.wpack 18432 7ed5e4ff1e0824d1
+lstm_s64_k9_f16 geometry nparts=1 split_f16=0 f16=1 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s64_k9_f16 front.b_seq1 16 fe070bd9d668418d
+lstm_s64_k9_f16 front.b_sig1 4 66752726d6894f90
+lstm_s64_k9_f16 front.b_sig2 16 f12cc0a532286361
+lstm_s64_k9_f16 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s64_k9_f16 front.w_sig2 320 092b55db23ba607a
+lstm_s64_k9_f16 front.wt5_seq1 3600 486622208a995a05
+lstm_s64_k9_f16 front.wt_seq1 2880 a58c853b1d285105
+lstm_s64_k9_f16 fused.a_merge1 20480 87372b512497ca89
+lstm_s64_k9_f16 fused.a_seq1 1792 b8d4a56143c5cb29
+lstm_s64_k9_f16 fused.a_seq2 7168 96e4020a31cc6b91
+lstm_s64_k9_f16 fused.a_sig2 256 7c6c1f881b1f5895
+lstm_s64_k9_f16 fused.a_sig3 5120 814c9bf1785f8408
+lstm_s64_k9_f16 fused.b_merge1 64 271d233674cf9b42
+lstm_s64_k9_f16 fused.b_seq1 16 06378e18b7b4cefd
+lstm_s64_k9_f16 fused.b_seq2 64 61991f5ceba16a69
+lstm_s64_k9_f16 fused.b_sig1 4 edd80ab0d74827ef
+lstm_s64_k9_f16 fused.b_sig2 16 7d6d04bbd93bd362
+lstm_s64_k9_f16 fused.b_sig3 64 06b3912f36981abe
+lstm_s64_k9_f16 fused.w_sig1 20 6817e404ab323544
+lstm_s64_k9_f16 lstm.a_hh1 16384 fe4da9e9f7621fda
+lstm_s64_k9_f16 lstm.a_ih1 16384 7e304295ebb02c7b
+lstm_s64_k9_f16 lstm.a_ih2 12288 5ec2e5f8c35a87fd
+lstm_s64_k9_f16 lstm.b1 256 f3f4c127c31fbdc9
+lstm_s64_k9_f16 lstm.b2 192 b4bb20a230fe77a6
+lstm_s64_k9_f16 lstm.b_fc 2 99050d189fa0aad7
+lstm_s64_k9_f16 lstm.s_hh1 8192 5a0cf8fc8e909e66
+lstm_s64_k9_f16 lstm.s_ih1 8192 e933f171bb12d23b
+lstm_s64_k9_f16 lstm.w_fc 128 d20c879f909febc1
+lstm_s64_k9_f16 lstm.x_b1 256 b11f7364b432a079
+lstm_s64_k9_f16 lstm.x_b2 256 14f2db26041645b9
+lstm_s64_k9_f16 lstm.x_hh 8192 0e1ef099c448ccfb
+lstm_s64_k9_f16 lstm.x_ih 8192 38dc2f628a4a1ee8
+lstm_s64_k9_f16 lstm.x_ih2 8192 92fa5cd5116c838a
+lstm_s64_k9_f16 merge1.apack 40960 802e9acb57d8c6ca
+lstm_s64_k9_f16 merge1.bias 64 eaa48886fdddd804
+lstm_s64_k9_f16 merge1.spack 20480 2734f67d7f891cd4
+lstm_s64_k9_f16 merge1.wpack 65536 95b0657a8026dbb8
+lstm_s64_k9_f16 seq2.apack 13312 50ce784aa0c559fb
+lstm_s64_k9_f16 seq2.bias 64 bed08e6a4dde5113
+lstm_s64_k9_f16 seq2.spack 7168 5bda34a4419838ff
+lstm_s64_k9_f16 seq2.wpack 24576 33a78157e976705f
+lstm_s64_k9_f16 sig3.apack 9216 4e7afb98c552717a
+lstm_s64_k9_f16 sig3.bias 64 88fdcc576756f7d7
+lstm_s64_k9_f16 sig3.spack 5120 1759cf7d42c8102e
+lstm_s64_k9_f16 sig3.wpack 18432 7ed5e4ff1e0824d1
+lstm_s64_k9_f16x3 geometry nparts=2 split_f16=1 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s64_k9_f16x3 front.b_seq1 16 fe070bd9d668418d
+lstm_s64_k9_f16x3 front.b_sig1 4 66752726d6894f90
+lstm_s64_k9_f16x3 front.b_sig2 16 f12cc0a532286361
+lstm_s64_k9_f16x3 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s64_k9_f16x3 front.w_sig2 320 092b55db23ba607a
+lstm_s64_k9_f16x3 front.wt5_seq1 3600 486622208a995a05
+lstm_s64_k9_f16x3 front.wt_seq1 2880 a58c853b1d285105
+lstm_s64_k9_f16x3 lstm.a_hh1 16384 fe4da9e9f7621fda
+lstm_s64_k9_f16x3 lstm.a_ih1 16384 7e304295ebb02c7b
+lstm_s64_k9_f16x3 lstm.a_ih2 12288 5ec2e5f8c35a87fd
+lstm_s64_k9_f16x3 lstm.b1 256 f3f4c127c31fbdc9
+lstm_s64_k9_f16x3 lstm.b2 192 b4bb20a230fe77a6
+lstm_s64_k9_f16x3 lstm.b_fc 2 99050d189fa0aad7
+lstm_s64_k9_f16x3 lstm.s_hh1 16384 ef8ebbe57503725a
+lstm_s64_k9_f16x3 lstm.s_ih1 16384 a6d74e36ebcf7613
+lstm_s64_k9_f16x3 lstm.w_fc 128 d20c879f909febc1
+lstm_s64_k9_f16x3 lstm.x_b1 256 b11f7364b432a079
+lstm_s64_k9_f16x3 lstm.x_b2 256 14f2db26041645b9
+lstm_s64_k9_f16x3 lstm.xs_hh 16384 37d018d7056ec2ba
+lstm_s64_k9_f16x3 lstm.xs_ih 16384 a5bad0b09367b703
+lstm_s64_k9_f16x3 lstm.xs_ih2 16384 8102d14ca4f5810f
+lstm_s64_k9_f16x3 merge1.apack 40960 802e9acb57d8c6ca
+lstm_s64_k9_f16x3 merge1.bias 64 eaa48886fdddd804
+lstm_s64_k9_f16x3 merge1.spack 40960 e8f3ba6e7939a65a
+lstm_s64_k9_f16x3 merge1.wpack 65536 95b0657a8026dbb8
+lstm_s64_k9_f16x3 seq2.apack 13312 50ce784aa0c559fb
+lstm_s64_k9_f16x3 seq2.bias 64 bed08e6a4dde5113
+lstm_s64_k9_f16x3 seq2.spack 14336 bae86406368c9676
+lstm_s64_k9_f16x3 seq2.wpack 24576 33a78157e976705f
+lstm_s64_k9_f16x3 sig3.apack 9216 4e7afb98c552717a
+lstm_s64_k9_f16x3 sig3.bias 64 88fdcc576756f7d7
+lstm_s64_k9_f16x3 sig3.spack 10240 97cd4c5e314406a6
+lstm_s64_k9_f16x3 sig3.wpack 18432 7ed5e4ff1e0824d1
+lstm_s96_k9_fp32 geometry nparts=0 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s96_k9_fp32 front.b_seq1 16 a7bf2d11fa0faec0
+lstm_s96_k9_fp32 front.b_sig1 4 66752726d6894f90
+lstm_s96_k9_fp32 front.b_sig2 16 f12cc0a532286361
+lstm_s96_k9_fp32 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s96_k9_fp32 front.w_sig2 320 092b55db23ba607a
+lstm_s96_k9_fp32 front.wt5_seq1 3600 58118f8db176e06f
+lstm_s96_k9_fp32 front.wt_seq1 2880 8aba7df057b2f16f
+lstm_s96_k9_fp32 lstm.b1 384 51b6a6bc7842a32a
+lstm_s96_k9_fp32 lstm.b2 288 a08dac5f19c05e5e
+lstm_s96_k9_fp32 lstm.b_fc 2 014254f3d938b9ce
+lstm_s96_k9_fp32 lstm.t_hh1 36864 312b8db0276d9d35
+lstm_s96_k9_fp32 lstm.t_ih1 36864 ab425ddfdf85b219
+lstm_s96_k9_fp32 lstm.t_ih2 27648 5c6e39d3a0f03827
+lstm_s96_k9_fp32 lstm.w_fc 192 0a9498648718d389
+lstm_s96_k9_fp32 merge1.apack4 92160 55752f6a651685be
+lstm_s96_k9_fp32 merge1.bias 96 65f922a1c707e9b9
+lstm_s96_k9_fp32 seq2.apack4 19968 64382d250ee61dec
+lstm_s96_k9_fp32 seq2.bias 96 efb37b3e161716d0
+lstm_s96_k9_fp32 sig3.apack4 13824 c1020613f4ee4230
+lstm_s96_k9_fp32 sig3.bias 96 0d60c396f076e3b3
+lstm_s96_k9_bf16 geometry nparts=1 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s96_k9_bf16 front.b_seq1 16 a7bf2d11fa0faec0
+lstm_s96_k9_bf16 front.b_sig1 4 66752726d6894f90
+lstm_s96_k9_bf16 front.b_sig2 16 f12cc0a532286361
+lstm_s96_k9_bf16 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s96_k9_bf16 front.w_sig2 320 092b55db23ba607a
+lstm_s96_k9_bf16 front.wt5_seq1 3600 58118f8db176e06f
+lstm_s96_k9_bf16 front.wt_seq1 2880 8aba7df057b2f16f
+lstm_s96_k9_bf16 lstm.b1 384 51b6a6bc7842a32a
+lstm_s96_k9_bf16 lstm.b2 288 a08dac5f19c05e5e
+lstm_s96_k9_bf16 lstm.b_fc 2 014254f3d938b9ce
+lstm_s96_k9_bf16 lstm.s16_b1 384 b06a5e7985a29c16
+lstm_s96_k9_bf16 lstm.s16_b2 384 9ab572dc9ec4eac9
+lstm_s96_k9_bf16 lstm.s16_hh 18432 3e0deadc680c62f0
+lstm_s96_k9_bf16 lstm.s16_ih 18432 c6b0aef4b5203c9c
+lstm_s96_k9_bf16 lstm.s16_ih2 18432 47557ee9eeff4aa6
+lstm_s96_k9_bf16 lstm.s_hh1 18432 d631211746b932c0
+lstm_s96_k9_bf16 lstm.s_ih1 18432 2174a0d068f920a8
+lstm_s96_k9_bf16 lstm.t_hh1 36864 312b8db0276d9d35
+lstm_s96_k9_bf16 lstm.t_ih1 36864 ab425ddfdf85b219
+lstm_s96_k9_bf16 lstm.t_ih2 27648 5c6e39d3a0f03827
+lstm_s96_k9_bf16 lstm.w_fc 192 0a9498648718d389
+lstm_s96_k9_bf16 merge1.apack16 46080 88c842576e901fdd
+lstm_s96_k9_bf16 merge1.apack4 92160 55752f6a651685be
+lstm_s96_k9_bf16 merge1.bias 96 65f922a1c707e9b9
+lstm_s96_k9_bf16 merge1.spack 46080 88c842576e901fdd
+lstm_s96_k9_bf16 seq2.apack16 10752 b9b8157ef5373c1e
+lstm_s96_k9_bf16 seq2.apack4 19968 64382d250ee61dec
+lstm_s96_k9_bf16 seq2.bias 96 efb37b3e161716d0
+lstm_s96_k9_bf16 seq2.spack 10752 b9b8157ef5373c1e
+lstm_s96_k9_bf16 sig3.apack16 7680 465f0408773166cf
+lstm_s96_k9_bf16 sig3.apack4 13824 c1020613f4ee4230
+lstm_s96_k9_bf16 sig3.bias 96 0d60c396f076e3b3
+lstm_s96_k9_bf16 sig3.spack 7680 465f0408773166cf
+lstm_s96_k9_f16 geometry nparts=1 split_f16=0 f16=1 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s96_k9_f16 front.b_seq1 16 a7bf2d11fa0faec0
+lstm_s96_k9_f16 front.b_sig1 4 66752726d6894f90
+lstm_s96_k9_f16 front.b_sig2 16 f12cc0a532286361
+lstm_s96_k9_f16 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s96_k9_f16 front.w_sig2 320 092b55db23ba607a
+lstm_s96_k9_f16 front.wt5_seq1 3600 58118f8db176e06f
+lstm_s96_k9_f16 front.wt_seq1 2880 8aba7df057b2f16f
+lstm_s96_k9_f16 lstm.b1 384 51b6a6bc7842a32a
+lstm_s96_k9_f16 lstm.b2 288 a08dac5f19c05e5e
+lstm_s96_k9_f16 lstm.b_fc 2 014254f3d938b9ce
+lstm_s96_k9_f16 lstm.s16_b1 384 b06a5e7985a29c16
+lstm_s96_k9_f16 lstm.s16_b2 384 9ab572dc9ec4eac9
+lstm_s96_k9_f16 lstm.s16_hh 18432 42909971521a4078
+lstm_s96_k9_f16 lstm.s16_ih 18432 e6248d0249a7346c
+lstm_s96_k9_f16 lstm.s16_ih2 18432 b0bf2c7b9fa34487
+lstm_s96_k9_f16 lstm.s_hh1 18432 d631211746b932c0
+lstm_s96_k9_f16 lstm.s_ih1 18432 2174a0d068f920a8
+lstm_s96_k9_f16 lstm.t_hh1 36864 312b8db0276d9d35
+lstm_s96_k9_f16 lstm.t_ih1 36864 ab425ddfdf85b219
+lstm_s96_k9_f16 lstm.t_ih2 27648 5c6e39d3a0f03827
+lstm_s96_k9_f16 lstm.w_fc 192 0a9498648718d389
+lstm_s96_k9_f16 merge1.apack16 46080 9a739e30cfa0fed0
+lstm_s96_k9_f16 merge1.apack4 92160 55752f6a651685be
+lstm_s96_k9_f16 merge1.bias 96 65f922a1c707e9b9
+lstm_s96_k9_f16 merge1.spack 46080 88c842576e901fdd
+lstm_s96_k9_f16 seq2.apack16 10752 a78fb9838296ce4f
+lstm_s96_k9_f16 seq2.apack4 19968 64382d250ee61dec
+lstm_s96_k9_f16 seq2.bias 96 efb37b3e161716d0
+lstm_s96_k9_f16 seq2.spack 10752 b9b8157ef5373c1e
+lstm_s96_k9_f16 sig3.apack16 7680 f264979ba73341ed
+lstm_s96_k9_f16 sig3.apack4 13824 c1020613f4ee4230
+lstm_s96_k9_f16 sig3.bias 96 0d60c396f076e3b3
+lstm_s96_k9_f16 sig3.spack 7680 465f0408773166cf
+lstm_s128_k9_fp32 geometry nparts=0 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s128_k9_fp32 front.b_seq1 16 29b7877e4dc626b1
+lstm_s128_k9_fp32 front.b_sig1 4 66752726d6894f90
+lstm_s128_k9_fp32 front.b_sig2 16 f12cc0a532286361
+lstm_s128_k9_fp32 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s128_k9_fp32 front.w_sig2 320 092b55db23ba607a
+lstm_s128_k9_fp32 front.wt5_seq1 3600 398ce40105f03d0c
+lstm_s128_k9_fp32 front.wt_seq1 2880 f5cf838290470f0c
+lstm_s128_k9_fp32 lstm.b1 512 b3ba4d082b1a135b
+lstm_s128_k9_fp32 lstm.b2 384 446a21ab327bb67f
+lstm_s128_k9_fp32 lstm.b_fc 2 519fcdc34dd53105
+lstm_s128_k9_fp32 lstm.t_hh1 65536 a14e0ef44cd36bfe
+lstm_s128_k9_fp32 lstm.t_ih1 65536 3b7303f6c1301d94
+lstm_s128_k9_fp32 lstm.t_ih2 49152 3daf21f858f2519e
+lstm_s128_k9_fp32 lstm.w_fc 256 1a84cab60796d9f0
+lstm_s128_k9_fp32 merge1.apack4 163840 26ac9ca56d710b51
+lstm_s128_k9_fp32 merge1.bias 128 c5038dffb42c80fa
+lstm_s128_k9_fp32 seq2.apack4 26624 e136ef76938504f4
+lstm_s128_k9_fp32 seq2.bias 128 e5f5dd7957f33241
+lstm_s128_k9_fp32 sig3.apack4 18432 09bc66b716947c66
+lstm_s128_k9_fp32 sig3.bias 128 732b9b9156e4d774
+lstm_s128_k9_bf16 geometry nparts=1 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s128_k9_bf16 front.b_seq1 16 29b7877e4dc626b1
+lstm_s128_k9_bf16 front.b_sig1 4 66752726d6894f90
+lstm_s128_k9_bf16 front.b_sig2 16 f12cc0a532286361
+lstm_s128_k9_bf16 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s128_k9_bf16 front.w_sig2 320 092b55db23ba607a
+lstm_s128_k9_bf16 front.wt5_seq1 3600 398ce40105f03d0c
+lstm_s128_k9_bf16 front.wt_seq1 2880 f5cf838290470f0c
+lstm_s128_k9_bf16 lstm.b1 512 b3ba4d082b1a135b
+lstm_s128_k9_bf16 lstm.b2 384 446a21ab327bb67f
+lstm_s128_k9_bf16 lstm.b_fc 2 519fcdc34dd53105
+lstm_s128_k9_bf16 lstm.s16_b1 512 41b89c445b3c926b
+lstm_s128_k9_bf16 lstm.s16_b2 512 7ddfbed2b3529e79
+lstm_s128_k9_bf16 lstm.s16_hh 32768 b10f5c75c322e3e3
+lstm_s128_k9_bf16 lstm.s16_ih 32768 b7c8d600246b1ba3
+lstm_s128_k9_bf16 lstm.s16_ih2 32768 e3b9e76a9f302980
+lstm_s128_k9_bf16 lstm.s_hh1 32768 b0ae899b991dc8a3
+lstm_s128_k9_bf16 lstm.s_ih1 32768 d3b4494e185af72b
+lstm_s128_k9_bf16 lstm.t_hh1 65536 a14e0ef44cd36bfe
+lstm_s128_k9_bf16 lstm.t_ih1 65536 3b7303f6c1301d94
+lstm_s128_k9_bf16 lstm.t_ih2 49152 3daf21f858f2519e
+lstm_s128_k9_bf16 lstm.w_fc 256 1a84cab60796d9f0
+lstm_s128_k9_bf16 merge1.apack16 81920 5443b926d06178a3
+lstm_s128_k9_bf16 merge1.apack4 163840 26ac9ca56d710b51
+lstm_s128_k9_bf16 merge1.bias 128 c5038dffb42c80fa
+lstm_s128_k9_bf16 merge1.spack 81920 5443b926d06178a3
+lstm_s128_k9_bf16 seq2.apack16 14336 061f7d30daeb9e2d
+lstm_s128_k9_bf16 seq2.apack4 26624 e136ef76938504f4
+lstm_s128_k9_bf16 seq2.bias 128 e5f5dd7957f33241
+lstm_s128_k9_bf16 seq2.spack 14336 061f7d30daeb9e2d
+lstm_s128_k9_bf16 sig3.apack16 10240 0c07f27ec574ff9e
+lstm_s128_k9_bf16 sig3.apack4 18432 09bc66b716947c66
+lstm_s128_k9_bf16 sig3.bias 128 732b9b9156e4d774
+lstm_s128_k9_bf16 sig3.spack 10240 0c07f27ec574ff9e
+lstm_s128_k9_f16 geometry nparts=1 split_f16=0 f16=1 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s128_k9_f16 front.b_seq1 16 29b7877e4dc626b1
+lstm_s128_k9_f16 front.b_sig1 4 66752726d6894f90
+lstm_s128_k9_f16 front.b_sig2 16 f12cc0a532286361
+lstm_s128_k9_f16 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s128_k9_f16 front.w_sig2 320 092b55db23ba607a
+lstm_s128_k9_f16 front.wt5_seq1 3600 398ce40105f03d0c
+lstm_s128_k9_f16 front.wt_seq1 2880 f5cf838290470f0c
+lstm_s128_k9_f16 lstm.b1 512 b3ba4d082b1a135b
+lstm_s128_k9_f16 lstm.b2 384 446a21ab327bb67f
+lstm_s128_k9_f16 lstm.b_fc 2 519fcdc34dd53105
+lstm_s128_k9_f16 lstm.s16_b1 512 41b89c445b3c926b
+lstm_s128_k9_f16 lstm.s16_b2 512 7ddfbed2b3529e79
+lstm_s128_k9_f16 lstm.s16_hh 32768 3e56a60195fcc4d7
+lstm_s128_k9_f16 lstm.s16_ih 32768 7229cfb8e9ab84fa
+lstm_s128_k9_f16 lstm.s16_ih2 32768 535fed9bd71c4592
+lstm_s128_k9_f16 lstm.s_hh1 32768 b0ae899b991dc8a3
+lstm_s128_k9_f16 lstm.s_ih1 32768 d3b4494e185af72b
+lstm_s128_k9_f16 lstm.t_hh1 65536 a14e0ef44cd36bfe
+lstm_s128_k9_f16 lstm.t_ih1 65536 3b7303f6c1301d94
+lstm_s128_k9_f16 lstm.t_ih2 49152 3daf21f858f2519e
+lstm_s128_k9_f16 lstm.w_fc 256 1a84cab60796d9f0
+lstm_s128_k9_f16 merge1.apack16 81920 ac84299dd3f95b72
+lstm_s128_k9_f16 merge1.apack4 163840 26ac9ca56d710b51
+lstm_s128_k9_f16 merge1.bias 128 c5038dffb42c80fa
+lstm_s128_k9_f16 merge1.spack 81920 5443b926d06178a3
+lstm_s128_k9_f16 seq2.apack16 14336 5c0d6f259cf7a458
+lstm_s128_k9_f16 seq2.apack4 26624 e136ef76938504f4
+lstm_s128_k9_f16 seq2.bias 128 e5f5dd7957f33241
+lstm_s128_k9_f16 seq2.spack 14336 061f7d30daeb9e2d
+lstm_s128_k9_f16 sig3.apack16 10240 3ecbc3dda0f9b434
+lstm_s128_k9_f16 sig3.apack4 18432 09bc66b716947c66
+lstm_s128_k9_f16 sig3.bias 128 732b9b9156e4d774
+lstm_s128_k9_f16 sig3.spack 10240 0c07f27ec574ff9e
+lstm_s256_k9_fp32 geometry nparts=0 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s256_k9_fp32 front.b_seq1 16 668d27e4a85ca6fb
+lstm_s256_k9_fp32 front.b_sig1 4 66752726d6894f90
+lstm_s256_k9_fp32 front.b_sig2 16 f12cc0a532286361
+lstm_s256_k9_fp32 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s256_k9_fp32 front.w_sig2 320 092b55db23ba607a
+lstm_s256_k9_fp32 front.wt5_seq1 3600 d619bf348de55364
+lstm_s256_k9_fp32 front.wt_seq1 2880 c0a6de2d09e2d264
+lstm_s256_k9_fp32 lstm.b1 1024 baf7bc8437cc6774
+lstm_s256_k9_fp32 lstm.b2 768 578122ed299b3e97
+lstm_s256_k9_fp32 lstm.b_fc 2 1e7b7556f0bdf381
+lstm_s256_k9_fp32 lstm.t_hh1 262144 938c1842215bd662
+lstm_s256_k9_fp32 lstm.t_ih1 262144 cdc77f2aa36786cb
+lstm_s256_k9_fp32 lstm.t_ih2 196608 3716c8af9e4b2254
+lstm_s256_k9_fp32 lstm.w_fc 512 e66f5eff3c50857f
+lstm_s256_k9_fp32 merge1.apack4 655360 d8095f67efc6f86f
+lstm_s256_k9_fp32 merge1.bias 256 27e7d410dc18d160
+lstm_s256_k9_fp32 seq2.apack4 53248 701d12a1f4241e4d
+lstm_s256_k9_fp32 seq2.bias 256 b27dc98a9c607bb8
+lstm_s256_k9_fp32 sig3.apack4 36864 26c7217b27cc4edb
+lstm_s256_k9_fp32 sig3.bias 256 6e1cd138e38e175d
+lstm_s256_k9_bf16 geometry nparts=1 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s256_k9_bf16 front.b_seq1 16 668d27e4a85ca6fb
+lstm_s256_k9_bf16 front.b_sig1 4 66752726d6894f90
+lstm_s256_k9_bf16 front.b_sig2 16 f12cc0a532286361
+lstm_s256_k9_bf16 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s256_k9_bf16 front.w_sig2 320 092b55db23ba607a
+lstm_s256_k9_bf16 front.wt5_seq1 3600 d619bf348de55364
+lstm_s256_k9_bf16 front.wt_seq1 2880 c0a6de2d09e2d264
+lstm_s256_k9_bf16 lstm.b1 1024 baf7bc8437cc6774
+lstm_s256_k9_bf16 lstm.b2 768 578122ed299b3e97
+lstm_s256_k9_bf16 lstm.b_fc 2 1e7b7556f0bdf381
+lstm_s256_k9_bf16 lstm.s16_b1 1024 59bed600f9fd42c0
+lstm_s256_k9_bf16 lstm.s16_b2 1024 471d0c99c5ae4fcd
+lstm_s256_k9_bf16 lstm.s16_hh 131072 74c0f6c4dbd794fc
+lstm_s256_k9_bf16 lstm.s16_ih 131072 fcfd25a2f45755b0
+lstm_s256_k9_bf16 lstm.s16_ih2 131072 bb6606267bcb5b2c
+lstm_s256_k9_bf16 lstm.s_hh1 131072 38e714cae8b55fb0
+lstm_s256_k9_bf16 lstm.s_ih1 131072 3acd1e3cd124eb18
+lstm_s256_k9_bf16 lstm.t_hh1 262144 938c1842215bd662
+lstm_s256_k9_bf16 lstm.t_ih1 262144 cdc77f2aa36786cb
+lstm_s256_k9_bf16 lstm.t_ih2 196608 3716c8af9e4b2254
+lstm_s256_k9_bf16 lstm.w_fc 512 e66f5eff3c50857f
+lstm_s256_k9_bf16 merge1.apack16 327680 c8fcd85b9ca240a3
+lstm_s256_k9_bf16 merge1.apack4 655360 d8095f67efc6f86f
+lstm_s256_k9_bf16 merge1.bias 256 27e7d410dc18d160
+lstm_s256_k9_bf16 merge1.spack 327680 c8fcd85b9ca240a3
+lstm_s256_k9_bf16 seq2.apack16 28672 dbf3a296f3c3320e
+lstm_s256_k9_bf16 seq2.apack4 53248 701d12a1f4241e4d
+lstm_s256_k9_bf16 seq2.bias 256 b27dc98a9c607bb8
+lstm_s256_k9_bf16 seq2.spack 28672 dbf3a296f3c3320e
+lstm_s256_k9_bf16 sig3.apack16 20480 84fbfcd2ee2b68ca
+lstm_s256_k9_bf16 sig3.apack4 36864 26c7217b27cc4edb
+lstm_s256_k9_bf16 sig3.bias 256 6e1cd138e38e175d
+lstm_s256_k9_bf16 sig3.spack 20480 84fbfcd2ee2b68ca
+lstm_s256_k9_f16 geometry nparts=1 split_f16=0 f16=1 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s256_k9_f16 front.b_seq1 16 668d27e4a85ca6fb
+lstm_s256_k9_f16 front.b_sig1 4 66752726d6894f90
+lstm_s256_k9_f16 front.b_sig2 16 f12cc0a532286361
+lstm_s256_k9_f16 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s256_k9_f16 front.w_sig2 320 092b55db23ba607a
+lstm_s256_k9_f16 front.wt5_seq1 3600 d619bf348de55364
+lstm_s256_k9_f16 front.wt_seq1 2880 c0a6de2d09e2d264
+lstm_s256_k9_f16 lstm.b1 1024 baf7bc8437cc6774
+lstm_s256_k9_f16 lstm.b2 768 578122ed299b3e97
+lstm_s256_k9_f16 lstm.b_fc 2 1e7b7556f0bdf381
+lstm_s256_k9_f16 lstm.s16_b1 1024 59bed600f9fd42c0
+lstm_s256_k9_f16 lstm.s16_b2 1024 471d0c99c5ae4fcd
+lstm_s256_k9_f16 lstm.s16_hh 131072 6625ddee9b7910a1
+lstm_s256_k9_f16 lstm.s16_ih 131072 21ca78c23b67daef
+lstm_s256_k9_f16 lstm.s16_ih2 131072 95d4cc8ea95eade6
+lstm_s256_k9_f16 lstm.s_hh1 131072 38e714cae8b55fb0
+lstm_s256_k9_f16 lstm.s_ih1 131072 3acd1e3cd124eb18
+lstm_s256_k9_f16 lstm.t_hh1 262144 938c1842215bd662
+lstm_s256_k9_f16 lstm.t_ih1 262144 cdc77f2aa36786cb
+lstm_s256_k9_f16 lstm.t_ih2 196608 3716c8af9e4b2254
+lstm_s256_k9_f16 lstm.w_fc 512 e66f5eff3c50857f
+lstm_s256_k9_f16 merge1.apack16 327680 3b58c9de720e37b5
+lstm_s256_k9_f16 merge1.apack4 655360 d8095f67efc6f86f
+lstm_s256_k9_f16 merge1.bias 256 27e7d410dc18d160
+lstm_s256_k9_f16 merge1.spack 327680 c8fcd85b9ca240a3
+lstm_s256_k9_f16 seq2.apack16 28672 90a636a0fef6a961
+lstm_s256_k9_f16 seq2.apack4 53248 701d12a1f4241e4d
+lstm_s256_k9_f16 seq2.bias 256 b27dc98a9c607bb8
+lstm_s256_k9_f16 seq2.spack 28672 dbf3a296f3c3320e
+lstm_s256_k9_f16 sig3.apack16 20480 c19c4dcf53f6d04c
+lstm_s256_k9_f16 sig3.apack4 36864 26c7217b27cc4edb
+lstm_s256_k9_f16 sig3.bias 256 6e1cd138e38e175d
+lstm_s256_k9_f16 sig3.spack 20480 84fbfcd2ee2b68ca
+lstm_s64_k6_fp32 geometry nparts=0 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s64_k6_fp32 front.b_seq1 16 9cacd75918b31b0e
+lstm_s64_k6_fp32 front.b_sig1 4 66752726d6894f90
+lstm_s64_k6_fp32 front.b_sig2 16 f12cc0a532286361
+lstm_s64_k6_fp32 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s64_k6_fp32 front.w_sig2 320 092b55db23ba607a
+lstm_s64_k6_fp32 front.wt5_seq1 2400 ecb7d58993b42e12
+lstm_s64_k6_fp32 front.wt_seq1 1920 530c8d08e5e85c12
+lstm_s64_k6_fp32 lstm.a_hh1 16384 45854887a2218508
+lstm_s64_k6_fp32 lstm.a_ih1 16384 dc8dab829d8c3e10
+lstm_s64_k6_fp32 lstm.a_ih2 12288 ac56b5ef5bae1aff
+lstm_s64_k6_fp32 lstm.b1 256 27e4e3f198f73ee7
+lstm_s64_k6_fp32 lstm.b2 192 3c5d384546d3bca5
+lstm_s64_k6_fp32 lstm.b_fc 2 957e52e28b28c670
+lstm_s64_k6_fp32 lstm.q_hh1 16384 a795595a905ba548
+lstm_s64_k6_fp32 lstm.q_ih1 16384 ddea090f2efe9a04
+lstm_s64_k6_fp32 lstm.q_ih2 16384 0209b729b730fb9f
+lstm_s64_k6_fp32 lstm.w_fc 128 c8b928f91905a7e9
+lstm_s64_k6_fp32 merge1.apack 40960 ca9a356e004d7bf7
+lstm_s64_k6_fp32 merge1.bias 64 917831b283adb2e2
+lstm_s64_k6_fp32 merge1.wpack 65536 31d0feba2383f751
+lstm_s64_k6_fp32 seq2.apack 13312 cdfff911c75566c6
+lstm_s64_k6_fp32 seq2.bias 64 650a95825081bc1d
+lstm_s64_k6_fp32 seq2.wpack 24576 5e97aabda192627b
+lstm_s64_k6_fp32 sig3.apack 9216 4e7afb98c552717a
+lstm_s64_k6_fp32 sig3.bias 64 88fdcc576756f7d7
+lstm_s64_k6_fp32 sig3.wpack 18432 7ed5e4ff1e0824d1
+lstm_s64_k6_bf16 geometry nparts=1 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s64_k6_bf16 front.b_seq1 16 9cacd75918b31b0e
+lstm_s64_k6_bf16 front.b_sig1 4 66752726d6894f90
+lstm_s64_k6_bf16 front.b_sig2 16 f12cc0a532286361
+lstm_s64_k6_bf16 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s64_k6_bf16 front.w_sig2 320 092b55db23ba607a
+lstm_s64_k6_bf16 front.wt5_seq1 2400 ecb7d58993b42e12
+lstm_s64_k6_bf16 front.wt_seq1 1920 530c8d08e5e85c12
+lstm_s64_k6_bf16 fused.a_merge1 20480 72341a1b8ba338c4
+lstm_s64_k6_bf16 fused.a_seq1 1024 ba819ae699104349
+lstm_s64_k6_bf16 fused.a_seq2 7168 cd893181407e0d41
+lstm_s64_k6_bf16 fused.a_sig2 256 b26b67a0e345ba42
+lstm_s64_k6_bf16 fused.a_sig3 5120 1759cf7d42c8102e
+lstm_s64_k6_bf16 fused.b_merge1 64 66fc789f31b0ce10
+lstm_s64_k6_bf16 fused.b_seq1 16 28a19fae414de1ba
+lstm_s64_k6_bf16 fused.b_seq2 64 d84d340ac060411a
+lstm_s64_k6_bf16 fused.b_sig1 4 edd80ab0d74827ef
+lstm_s64_k6_bf16 fused.b_sig2 16 7d6d04bbd93bd362
+lstm_s64_k6_bf16 fused.b_sig3 64 06b3912f36981abe
+lstm_s64_k6_bf16 fused.w_sig1 20 6817e404ab323544
+lstm_s64_k6_bf16 lstm.a_hh1 16384 45854887a2218508
+lstm_s64_k6_bf16 lstm.a_ih1 16384 dc8dab829d8c3e10
+lstm_s64_k6_bf16 lstm.a_ih2 12288 ac56b5ef5bae1aff
+lstm_s64_k6_bf16 lstm.b1 256 27e4e3f198f73ee7
+lstm_s64_k6_bf16 lstm.b2 192 3c5d384546d3bca5
+lstm_s64_k6_bf16 lstm.b_fc 2 957e52e28b28c670
+lstm_s64_k6_bf16 lstm.s_hh1 8192 b1c4780309768e6f
+lstm_s64_k6_bf16 lstm.s_ih1 8192 a98c3dc4448598d8
+lstm_s64_k6_bf16 lstm.w_fc 128 c8b928f91905a7e9
+lstm_s64_k6_bf16 lstm.x_b1 256 a9961009b9b42967
+lstm_s64_k6_bf16 lstm.x_b2 256 075f4e61a5ec7f3a
+lstm_s64_k6_bf16 lstm.x_hh 8192 fa109fe6860fe133
+lstm_s64_k6_bf16 lstm.x_ih 8192 feb1883d39757ac8
+lstm_s64_k6_bf16 lstm.x_ih2 8192 7ba51fd77fae57e1
+lstm_s64_k6_bf16 merge1.apack 40960 ca9a356e004d7bf7
+lstm_s64_k6_bf16 merge1.bias 64 917831b283adb2e2
+lstm_s64_k6_bf16 merge1.spack 20480 72341a1b8ba338c4
+lstm_s64_k6_bf16 merge1.wpack 65536 31d0feba2383f751
+lstm_s64_k6_bf16 seq2.apack 13312 cdfff911c75566c6
+lstm_s64_k6_bf16 seq2.bias 64 650a95825081bc1d
+lstm_s64_k6_bf16 seq2.spack 7168 cd893181407e0d41
+lstm_s64_k6_bf16 seq2.wpack 24576 5e97aabda192627b
+lstm_s64_k6_bf16 sig3.apack 9216 4e7afb98c552717a
+lstm_s64_k6_bf16 sig3.bias 64 88fdcc576756f7d7
+lstm_s64_k6_bf16 sig3.spack 5120 1759cf7d42c8102e
+lstm_s64_k6_bf16 sig3.wpack 18432 7ed5e4ff1e0824d1
+lstm_s64_k6_bf16x3 geometry nparts=2 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s64_k6_bf16x3 front.b_seq1 16 9cacd75918b31b0e
+lstm_s64_k6_bf16x3 front.b_sig1 4 66752726d6894f90
+lstm_s64_k6_bf16x3 front.b_sig2 16 f12cc0a532286361
+lstm_s64_k6_bf16x3 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s64_k6_bf16x3 front.w_sig2 320 092b55db23ba607a
+lstm_s64_k6_bf16x3 front.wt5_seq1 2400 ecb7d58993b42e12
+lstm_s64_k6_bf16x3 front.wt_seq1 1920 530c8d08e5e85c12
+lstm_s64_k6_bf16x3 lstm.a_hh1 16384 45854887a2218508
+lstm_s64_k6_bf16x3 lstm.a_ih1 16384 dc8dab829d8c3e10
+lstm_s64_k6_bf16x3 lstm.a_ih2 12288 ac56b5ef5bae1aff
+lstm_s64_k6_bf16x3 lstm.b1 256 27e4e3f198f73ee7
+lstm_s64_k6_bf16x3 lstm.b2 192 3c5d384546d3bca5
+lstm_s64_k6_bf16x3 lstm.b_fc 2 957e52e28b28c670
+lstm_s64_k6_bf16x3 lstm.s_hh1 16384 5e5eb9c28edfa5cb
+lstm_s64_k6_bf16x3 lstm.s_ih1 16384 eb94b51398b89906
+lstm_s64_k6_bf16x3 lstm.w_fc 128 c8b928f91905a7e9
+lstm_s64_k6_bf16x3 lstm.x_b1 256 a9961009b9b42967
+lstm_s64_k6_bf16x3 lstm.x_b2 256 075f4e61a5ec7f3a
+lstm_s64_k6_bf16x3 lstm.xs_hh 16384 94eb6c9111eb342f
+lstm_s64_k6_bf16x3 lstm.xs_ih 16384 2167210f52113b96
+lstm_s64_k6_bf16x3 lstm.xs_ih2 16384 176f76e6684637b6
+lstm_s64_k6_bf16x3 merge1.apack 40960 ca9a356e004d7bf7
+lstm_s64_k6_bf16x3 merge1.bias 64 917831b283adb2e2
+lstm_s64_k6_bf16x3 merge1.spack 40960 a22139514a412e51
+lstm_s64_k6_bf16x3 merge1.wpack 65536 31d0feba2383f751
+lstm_s64_k6_bf16x3 seq2.apack 13312 cdfff911c75566c6
+lstm_s64_k6_bf16x3 seq2.bias 64 650a95825081bc1d
+lstm_s64_k6_bf16x3 seq2.spack 14336 bb4f482564beeb90
+lstm_s64_k6_bf16x3 seq2.wpack 24576 5e97aabda192627b
+lstm_s64_k6_bf16x3 sig3.apack 9216 4e7afb98c552717a
+lstm_s64_k6_bf16x3 sig3.bias 64 88fdcc576756f7d7
+lstm_s64_k6_bf16x3 sig3.spack 10240 d3ed508d3c2ec235
+lstm_s64_k6_bf16x3 sig3.wpack 18432 7ed5e4ff1e0824d1
+lstm_s64_k6_bf16x6 geometry nparts=3 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s64_k6_bf16x6 front.b_seq1 16 9cacd75918b31b0e
+lstm_s64_k6_bf16x6 front.b_sig1 4 66752726d6894f90
+lstm_s64_k6_bf16x6 front.b_sig2 16 f12cc0a532286361
+lstm_s64_k6_bf16x6 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s64_k6_bf16x6 front.w_sig2 320 092b55db23ba607a
+lstm_s64_k6_bf16x6 front.wt5_seq1 2400 ecb7d58993b42e12
+lstm_s64_k6_bf16x6 front.wt_seq1 1920 530c8d08e5e85c12
+lstm_s64_k6_bf16x6 lstm.a_hh1 16384 45854887a2218508
+lstm_s64_k6_bf16x6 lstm.a_ih1 16384 dc8dab829d8c3e10
+lstm_s64_k6_bf16x6 lstm.a_ih2 12288 ac56b5ef5bae1aff
+lstm_s64_k6_bf16x6 lstm.b1 256 27e4e3f198f73ee7
+lstm_s64_k6_bf16x6 lstm.b2 192 3c5d384546d3bca5
+lstm_s64_k6_bf16x6 lstm.b_fc 2 957e52e28b28c670
+lstm_s64_k6_bf16x6 lstm.s_hh1 24576 23ca8d45ca4b8615
+lstm_s64_k6_bf16x6 lstm.s_ih1 24576 592006842fe484df
+lstm_s64_k6_bf16x6 lstm.w_fc 128 c8b928f91905a7e9
+lstm_s64_k6_bf16x6 lstm.x_b1 256 a9961009b9b42967
+lstm_s64_k6_bf16x6 lstm.x_b2 256 075f4e61a5ec7f3a
+lstm_s64_k6_bf16x6 lstm.xs_hh 24576 49756d6bc6c46535
+lstm_s64_k6_bf16x6 lstm.xs_ih 24576 1bbf1a7bdeb1c8f3
+lstm_s64_k6_bf16x6 lstm.xs_ih2 24576 36b22dbb6deb6679
+lstm_s64_k6_bf16x6 merge1.apack 40960 ca9a356e004d7bf7
+lstm_s64_k6_bf16x6 merge1.bias 64 917831b283adb2e2
+lstm_s64_k6_bf16x6 merge1.spack 61440 c49e88b8270f4973
+lstm_s64_k6_bf16x6 merge1.wpack 65536 31d0feba2383f751
+lstm_s64_k6_bf16x6 seq2.apack 13312 cdfff911c75566c6
+lstm_s64_k6_bf16x6 seq2.bias 64 650a95825081bc1d
+lstm_s64_k6_bf16x6 seq2.spack 21504 df0eba404255ee82
+lstm_s64_k6_bf16x6 seq2.wpack 24576 5e97aabda192627b
+lstm_s64_k6_bf16x6 sig3.apack 9216 4e7afb98c552717a
+lstm_s64_k6_bf16x6 sig3.bias 64 88fdcc576756f7d7
+lstm_s64_k6_bf16x6 sig3.spack 15360 bf76e3335d43c7c0
+lstm_s64_k6_bf16x6 sig3.wpack 18432 7ed5e4ff1e0824d1
+lstm_s64_k6_f16 geometry nparts=1 split_f16=0 f16=1 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s64_k6_f16 front.b_seq1 16 9cacd75918b31b0e
+lstm_s64_k6_f16 front.b_sig1 4 66752726d6894f90
+lstm_s64_k6_f16 front.b_sig2 16 f12cc0a532286361
+lstm_s64_k6_f16 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s64_k6_f16 front.w_sig2 320 092b55db23ba607a
+lstm_s64_k6_f16 front.wt5_seq1 2400 ecb7d58993b42e12
+lstm_s64_k6_f16 front.wt_seq1 1920 530c8d08e5e85c12
+lstm_s64_k6_f16 fused.a_merge1 20480 3beddc815ffffe20
+lstm_s64_k6_f16 fused.a_seq1 1024 aae6a3ede3714ae2
+lstm_s64_k6_f16 fused.a_seq2 7168 d9c8eecc95f09247
+lstm_s64_k6_f16 fused.a_sig2 256 7c6c1f881b1f5895
+lstm_s64_k6_f16 fused.a_sig3 5120 814c9bf1785f8408
+lstm_s64_k6_f16 fused.b_merge1 64 66fc789f31b0ce10
+lstm_s64_k6_f16 fused.b_seq1 16 28a19fae414de1ba
+lstm_s64_k6_f16 fused.b_seq2 64 d84d340ac060411a
+lstm_s64_k6_f16 fused.b_sig1 4 edd80ab0d74827ef
+lstm_s64_k6_f16 fused.b_sig2 16 7d6d04bbd93bd362
+lstm_s64_k6_f16 fused.b_sig3 64 06b3912f36981abe
+lstm_s64_k6_f16 fused.w_sig1 20 6817e404ab323544
+lstm_s64_k6_f16 lstm.a_hh1 16384 45854887a2218508
+lstm_s64_k6_f16 lstm.a_ih1 16384 dc8dab829d8c3e10
+lstm_s64_k6_f16 lstm.a_ih2 12288 ac56b5ef5bae1aff
+lstm_s64_k6_f16 lstm.b1 256 27e4e3f198f73ee7
+lstm_s64_k6_f16 lstm.b2 192 3c5d384546d3bca5
+lstm_s64_k6_f16 lstm.b_fc 2 957e52e28b28c670
+lstm_s64_k6_f16 lstm.s_hh1 8192 b1c4780309768e6f
+lstm_s64_k6_f16 lstm.s_ih1 8192 a98c3dc4448598d8
+lstm_s64_k6_f16 lstm.w_fc 128 c8b928f91905a7e9
+lstm_s64_k6_f16 lstm.x_b1 256 a9961009b9b42967
+lstm_s64_k6_f16 lstm.x_b2 256 075f4e61a5ec7f3a
+lstm_s64_k6_f16 lstm.x_hh 8192 2a71ce721bb7124f
+lstm_s64_k6_f16 lstm.x_ih 8192 bf1637e2e4daf90c
+lstm_s64_k6_f16 lstm.x_ih2 8192 1697e4aff28b93b7
+lstm_s64_k6_f16 merge1.apack 40960 ca9a356e004d7bf7
+lstm_s64_k6_f16 merge1.bias 64 917831b283adb2e2
+lstm_s64_k6_f16 merge1.spack 20480 72341a1b8ba338c4
+lstm_s64_k6_f16 merge1.wpack 65536 31d0feba2383f751
+lstm_s64_k6_f16 seq2.apack 13312 cdfff911c75566c6
+lstm_s64_k6_f16 seq2.bias 64 650a95825081bc1d
+lstm_s64_k6_f16 seq2.spack 7168 cd893181407e0d41
+lstm_s64_k6_f16 seq2.wpack 24576 5e97aabda192627b
+lstm_s64_k6_f16 sig3.apack 9216 4e7afb98c552717a
+lstm_s64_k6_f16 sig3.bias 64 88fdcc576756f7d7
+lstm_s64_k6_f16 sig3.spack 5120 1759cf7d42c8102e
+lstm_s64_k6_f16 sig3.wpack 18432 7ed5e4ff1e0824d1
+lstm_s64_k6_f16x3 geometry nparts=2 split_f16=1 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s64_k6_f16x3 front.b_seq1 16 9cacd75918b31b0e
+lstm_s64_k6_f16x3 front.b_sig1 4 66752726d6894f90
+lstm_s64_k6_f16x3 front.b_sig2 16 f12cc0a532286361
+lstm_s64_k6_f16x3 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s64_k6_f16x3 front.w_sig2 320 092b55db23ba607a
+lstm_s64_k6_f16x3 front.wt5_seq1 2400 ecb7d58993b42e12
+lstm_s64_k6_f16x3 front.wt_seq1 1920 530c8d08e5e85c12
+lstm_s64_k6_f16x3 lstm.a_hh1 16384 45854887a2218508
+lstm_s64_k6_f16x3 lstm.a_ih1 16384 dc8dab829d8c3e10
+lstm_s64_k6_f16x3 lstm.a_ih2 12288 ac56b5ef5bae1aff
+lstm_s64_k6_f16x3 lstm.b1 256 27e4e3f198f73ee7
+lstm_s64_k6_f16x3 lstm.b2 192 3c5d384546d3bca5
+lstm_s64_k6_f16x3 lstm.b_fc 2 957e52e28b28c670
+lstm_s64_k6_f16x3 lstm.s_hh1 16384 dd885727dc6f5c04
+lstm_s64_k6_f16x3 lstm.s_ih1 16384 a9066992b062e2b5
+lstm_s64_k6_f16x3 lstm.w_fc 128 c8b928f91905a7e9
+lstm_s64_k6_f16x3 lstm.x_b1 256 a9961009b9b42967
+lstm_s64_k6_f16x3 lstm.x_b2 256 075f4e61a5ec7f3a
+lstm_s64_k6_f16x3 lstm.xs_hh 16384 8932b1c1fc20c360
+lstm_s64_k6_f16x3 lstm.xs_ih 16384 54e7a667cb77f245
+lstm_s64_k6_f16x3 lstm.xs_ih2 16384 8ce9660345ab606e
+lstm_s64_k6_f16x3 merge1.apack 40960 ca9a356e004d7bf7
+lstm_s64_k6_f16x3 merge1.bias 64 917831b283adb2e2
+lstm_s64_k6_f16x3 merge1.spack 40960 11491cfb7fbb44c4
+lstm_s64_k6_f16x3 merge1.wpack 65536 31d0feba2383f751
+lstm_s64_k6_f16x3 seq2.apack 13312 cdfff911c75566c6
+lstm_s64_k6_f16x3 seq2.bias 64 650a95825081bc1d
+lstm_s64_k6_f16x3 seq2.spack 14336 979b0600ab8c267c
+lstm_s64_k6_f16x3 seq2.wpack 24576 5e97aabda192627b
+lstm_s64_k6_f16x3 sig3.apack 9216 4e7afb98c552717a
+lstm_s64_k6_f16x3 sig3.bias 64 88fdcc576756f7d7
+lstm_s64_k6_f16x3 sig3.spack 10240 97cd4c5e314406a6
+lstm_s64_k6_f16x3 sig3.wpack 18432 7ed5e4ff1e0824d1
+lstm_s64_k5_fp32 geometry nparts=0 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s64_k5_fp32 front.b_seq1 16 155683171e0b6c51
+lstm_s64_k5_fp32 front.b_sig1 4 66752726d6894f90
+lstm_s64_k5_fp32 front.b_sig2 16 f12cc0a532286361
+lstm_s64_k5_fp32 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s64_k5_fp32 front.w_sig2 320 092b55db23ba607a
+lstm_s64_k5_fp32 front.wt5_seq1 2000 691f10e882daa87c
+lstm_s64_k5_fp32 front.wt_seq1 1600 b31fe872ae2bf47c
+lstm_s64_k5_fp32 lstm.a_hh1 16384 13b43bb22da55e7c
+lstm_s64_k5_fp32 lstm.a_ih1 16384 10966697dc9fdbf1
+lstm_s64_k5_fp32 lstm.a_ih2 12288 157731d03c69e521
+lstm_s64_k5_fp32 lstm.b1 256 e3e8ea13e67f6438
+lstm_s64_k5_fp32 lstm.b2 192 7d28caa38d8a13eb
+lstm_s64_k5_fp32 lstm.b_fc 2 10434914d46e6034
+lstm_s64_k5_fp32 lstm.q_hh1 16384 6fc0886ef1e48db0
+lstm_s64_k5_fp32 lstm.q_ih1 16384 dafbe567be495071
+lstm_s64_k5_fp32 lstm.q_ih2 16384 3f12ccf24ebf9d2d
+lstm_s64_k5_fp32 lstm.w_fc 128 b3677a37302d42cb
+lstm_s64_k5_fp32 merge1.apack 40960 58e3b67ca426cb95
+lstm_s64_k5_fp32 merge1.bias 64 a50bdcc45cd3701c
+lstm_s64_k5_fp32 merge1.wpack 65536 0bcf40badb220c6a
+lstm_s64_k5_fp32 seq2.apack 13312 4cd842d6ffffd486
+lstm_s64_k5_fp32 seq2.bias 64 784dc031878ca3d2
+lstm_s64_k5_fp32 seq2.wpack 24576 ca41de0e57623fd6
+lstm_s64_k5_fp32 sig3.apack 9216 4e7afb98c552717a
+lstm_s64_k5_fp32 sig3.bias 64 88fdcc576756f7d7
+lstm_s64_k5_fp32 sig3.wpack 18432 7ed5e4ff1e0824d1
+lstm_s64_k5_bf16 geometry nparts=1 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s64_k5_bf16 front.b_seq1 16 155683171e0b6c51
+lstm_s64_k5_bf16 front.b_sig1 4 66752726d6894f90
+lstm_s64_k5_bf16 front.b_sig2 16 f12cc0a532286361
+lstm_s64_k5_bf16 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s64_k5_bf16 front.w_sig2 320 092b55db23ba607a
+lstm_s64_k5_bf16 front.wt5_seq1 2000 691f10e882daa87c
+lstm_s64_k5_bf16 front.wt_seq1 1600 b31fe872ae2bf47c
+lstm_s64_k5_bf16 lstm.a_hh1 16384 13b43bb22da55e7c
+lstm_s64_k5_bf16 lstm.a_ih1 16384 10966697dc9fdbf1
+lstm_s64_k5_bf16 lstm.a_ih2 12288 157731d03c69e521
+lstm_s64_k5_bf16 lstm.b1 256 e3e8ea13e67f6438
+lstm_s64_k5_bf16 lstm.b2 192 7d28caa38d8a13eb
+lstm_s64_k5_bf16 lstm.b_fc 2 10434914d46e6034
+lstm_s64_k5_bf16 lstm.s_hh1 8192 453034a7caab3a80
+lstm_s64_k5_bf16 lstm.s_ih1 8192 3b485317ba19d161
+lstm_s64_k5_bf16 lstm.w_fc 128 b3677a37302d42cb
+lstm_s64_k5_bf16 lstm.x_b1 256 60bbc4593b39f21c
+lstm_s64_k5_bf16 lstm.x_b2 256 7187a54c2f6d6376
+lstm_s64_k5_bf16 lstm.x_hh 8192 db0fce65afdc89e4
+lstm_s64_k5_bf16 lstm.x_ih 8192 19a483982bf54d61
+lstm_s64_k5_bf16 lstm.x_ih2 8192 0909d78c49fb3020
+lstm_s64_k5_bf16 merge1.apack 40960 58e3b67ca426cb95
+lstm_s64_k5_bf16 merge1.bias 64 a50bdcc45cd3701c
+lstm_s64_k5_bf16 merge1.spack 20480 3ff29ba2ce3a98a5
+lstm_s64_k5_bf16 merge1.wpack 65536 0bcf40badb220c6a
+lstm_s64_k5_bf16 seq2.apack 13312 4cd842d6ffffd486
+lstm_s64_k5_bf16 seq2.bias 64 784dc031878ca3d2
+lstm_s64_k5_bf16 seq2.spack 7168 1b34dc61c4d5034f
+lstm_s64_k5_bf16 seq2.wpack 24576 ca41de0e57623fd6
+lstm_s64_k5_bf16 sig3.apack 9216 4e7afb98c552717a
+lstm_s64_k5_bf16 sig3.bias 64 88fdcc576756f7d7
+lstm_s64_k5_bf16 sig3.spack 5120 1759cf7d42c8102e
+lstm_s64_k5_bf16 sig3.wpack 18432 7ed5e4ff1e0824d1
+lstm_s64_k5_bf16x3 geometry nparts=2 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s64_k5_bf16x3 front.b_seq1 16 155683171e0b6c51
+lstm_s64_k5_bf16x3 front.b_sig1 4 66752726d6894f90
+lstm_s64_k5_bf16x3 front.b_sig2 16 f12cc0a532286361
+lstm_s64_k5_bf16x3 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s64_k5_bf16x3 front.w_sig2 320 092b55db23ba607a
+lstm_s64_k5_bf16x3 front.wt5_seq1 2000 691f10e882daa87c
+lstm_s64_k5_bf16x3 front.wt_seq1 1600 b31fe872ae2bf47c
+lstm_s64_k5_bf16x3 lstm.a_hh1 16384 13b43bb22da55e7c
+lstm_s64_k5_bf16x3 lstm.a_ih1 16384 10966697dc9fdbf1
+lstm_s64_k5_bf16x3 lstm.a_ih2 12288 157731d03c69e521
+lstm_s64_k5_bf16x3 lstm.b1 256 e3e8ea13e67f6438
+lstm_s64_k5_bf16x3 lstm.b2 192 7d28caa38d8a13eb
+lstm_s64_k5_bf16x3 lstm.b_fc 2 10434914d46e6034
+lstm_s64_k5_bf16x3 lstm.s_hh1 16384 925fd82a25b26b6f
+lstm_s64_k5_bf16x3 lstm.s_ih1 16384 da739778b3d05d27
+lstm_s64_k5_bf16x3 lstm.w_fc 128 b3677a37302d42cb
+lstm_s64_k5_bf16x3 lstm.x_b1 256 60bbc4593b39f21c
+lstm_s64_k5_bf16x3 lstm.x_b2 256 7187a54c2f6d6376
+lstm_s64_k5_bf16x3 lstm.xs_hh 16384 b8a67bef3150701b
+lstm_s64_k5_bf16x3 lstm.xs_ih 16384 19a4246b582f83cb
+lstm_s64_k5_bf16x3 lstm.xs_ih2 16384 a8ce82e74fdd9d35
+lstm_s64_k5_bf16x3 merge1.apack 40960 58e3b67ca426cb95
+lstm_s64_k5_bf16x3 merge1.bias 64 a50bdcc45cd3701c
+lstm_s64_k5_bf16x3 merge1.spack 40960 d4293696a7c8615e
+lstm_s64_k5_bf16x3 merge1.wpack 65536 0bcf40badb220c6a
+lstm_s64_k5_bf16x3 seq2.apack 13312 4cd842d6ffffd486
+lstm_s64_k5_bf16x3 seq2.bias 64 784dc031878ca3d2
+lstm_s64_k5_bf16x3 seq2.spack 14336 b0e6c378ea8d402e
+lstm_s64_k5_bf16x3 seq2.wpack 24576 ca41de0e57623fd6
+lstm_s64_k5_bf16x3 sig3.apack 9216 4e7afb98c552717a
+lstm_s64_k5_bf16x3 sig3.bias 64 88fdcc576756f7d7
+lstm_s64_k5_bf16x3 sig3.spack 10240 d3ed508d3c2ec235
+lstm_s64_k5_bf16x3 sig3.wpack 18432 7ed5e4ff1e0824d1
+lstm_s64_k5_bf16x6 geometry nparts=3 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s64_k5_bf16x6 front.b_seq1 16 155683171e0b6c51
+lstm_s64_k5_bf16x6 front.b_sig1 4 66752726d6894f90
+lstm_s64_k5_bf16x6 front.b_sig2 16 f12cc0a532286361
+lstm_s64_k5_bf16x6 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s64_k5_bf16x6 front.w_sig2 320 092b55db23ba607a
+lstm_s64_k5_bf16x6 front.wt5_seq1 2000 691f10e882daa87c
+lstm_s64_k5_bf16x6 front.wt_seq1 1600 b31fe872ae2bf47c
+lstm_s64_k5_bf16x6 lstm.a_hh1 16384 13b43bb22da55e7c
+lstm_s64_k5_bf16x6 lstm.a_ih1 16384 10966697dc9fdbf1
+lstm_s64_k5_bf16x6 lstm.a_ih2 12288 157731d03c69e521
+lstm_s64_k5_bf16x6 lstm.b1 256 e3e8ea13e67f6438
+lstm_s64_k5_bf16x6 lstm.b2 192 7d28caa38d8a13eb
+lstm_s64_k5_bf16x6 lstm.b_fc 2 10434914d46e6034
+lstm_s64_k5_bf16x6 lstm.s_hh1 24576 e5ee10fb18e3b022
+lstm_s64_k5_bf16x6 lstm.s_ih1 24576 a08e59678884c985
+lstm_s64_k5_bf16x6 lstm.w_fc 128 b3677a37302d42cb
+lstm_s64_k5_bf16x6 lstm.x_b1 256 60bbc4593b39f21c
+lstm_s64_k5_bf16x6 lstm.x_b2 256 7187a54c2f6d6376
+lstm_s64_k5_bf16x6 lstm.xs_hh 24576 b75ad81e103b938e
+lstm_s64_k5_bf16x6 lstm.xs_ih 24576 4a985106d2ae0735
+lstm_s64_k5_bf16x6 lstm.xs_ih2 24576 e8d32656915bab8b
+lstm_s64_k5_bf16x6 merge1.apack 40960 58e3b67ca426cb95
+lstm_s64_k5_bf16x6 merge1.bias 64 a50bdcc45cd3701c
+lstm_s64_k5_bf16x6 merge1.spack 61440 f4f83daea8acb4e1
+lstm_s64_k5_bf16x6 merge1.wpack 65536 0bcf40badb220c6a
+lstm_s64_k5_bf16x6 seq2.apack 13312 4cd842d6ffffd486
+lstm_s64_k5_bf16x6 seq2.bias 64 784dc031878ca3d2
+lstm_s64_k5_bf16x6 seq2.spack 21504 12fb92817e488320
+lstm_s64_k5_bf16x6 seq2.wpack 24576 ca41de0e57623fd6
+lstm_s64_k5_bf16x6 sig3.apack 9216 4e7afb98c552717a
+lstm_s64_k5_bf16x6 sig3.bias 64 88fdcc576756f7d7
+lstm_s64_k5_bf16x6 sig3.spack 15360 bf76e3335d43c7c0
+lstm_s64_k5_bf16x6 sig3.wpack 18432 7ed5e4ff1e0824d1
+lstm_s64_k5_f16x3 geometry nparts=2 split_f16=1 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s64_k5_f16x3 front.b_seq1 16 155683171e0b6c51
+lstm_s64_k5_f16x3 front.b_sig1 4 66752726d6894f90
+lstm_s64_k5_f16x3 front.b_sig2 16 f12cc0a532286361
+lstm_s64_k5_f16x3 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s64_k5_f16x3 front.w_sig2 320 092b55db23ba607a
+lstm_s64_k5_f16x3 front.wt5_seq1 2000 691f10e882daa87c
+lstm_s64_k5_f16x3 front.wt_seq1 1600 b31fe872ae2bf47c
+lstm_s64_k5_f16x3 lstm.a_hh1 16384 13b43bb22da55e7c
+lstm_s64_k5_f16x3 lstm.a_ih1 16384 10966697dc9fdbf1
+lstm_s64_k5_f16x3 lstm.a_ih2 12288 157731d03c69e521
+lstm_s64_k5_f16x3 lstm.b1 256 e3e8ea13e67f6438
+lstm_s64_k5_f16x3 lstm.b2 192 7d28caa38d8a13eb
+lstm_s64_k5_f16x3 lstm.b_fc 2 10434914d46e6034
+lstm_s64_k5_f16x3 lstm.s_hh1 16384 e2b439fb51cfaa85
+lstm_s64_k5_f16x3 lstm.s_ih1 16384 f8ddb93aac49eb34
+lstm_s64_k5_f16x3 lstm.w_fc 128 b3677a37302d42cb
+lstm_s64_k5_f16x3 lstm.x_b1 256 60bbc4593b39f21c
+lstm_s64_k5_f16x3 lstm.x_b2 256 7187a54c2f6d6376
+lstm_s64_k5_f16x3 lstm.xs_hh 16384 9c427175f60dd0ed
+lstm_s64_k5_f16x3 lstm.xs_ih 16384 8215bfb96cb5a3f0
+lstm_s64_k5_f16x3 lstm.xs_ih2 16384 9a7d089999604fc2
+lstm_s64_k5_f16x3 merge1.apack 40960 58e3b67ca426cb95
+lstm_s64_k5_f16x3 merge1.bias 64 a50bdcc45cd3701c
+lstm_s64_k5_f16x3 merge1.spack 40960 4acef7540656afe4
+lstm_s64_k5_f16x3 merge1.wpack 65536 0bcf40badb220c6a
+lstm_s64_k5_f16x3 seq2.apack 13312 4cd842d6ffffd486
+lstm_s64_k5_f16x3 seq2.bias 64 784dc031878ca3d2
+lstm_s64_k5_f16x3 seq2.spack 14336 cc42711ff68967a8
+lstm_s64_k5_f16x3 seq2.wpack 24576 ca41de0e57623fd6
+lstm_s64_k5_f16x3 sig3.apack 9216 4e7afb98c552717a
+lstm_s64_k5_f16x3 sig3.bias 64 88fdcc576756f7d7
+lstm_s64_k5_f16x3 sig3.spack 10240 97cd4c5e314406a6
+lstm_s64_k5_f16x3 sig3.wpack 18432 7ed5e4ff1e0824d1
+lstm_s128_k5_fp32 geometry nparts=0 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s128_k5_fp32 front.b_seq1 16 68142a946e2b417a
+lstm_s128_k5_fp32 front.b_sig1 4 66752726d6894f90
+lstm_s128_k5_fp32 front.b_sig2 16 f12cc0a532286361
+lstm_s128_k5_fp32 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s128_k5_fp32 front.w_sig2 320 092b55db23ba607a
+lstm_s128_k5_fp32 front.wt5_seq1 2000 dd3850ea3967e258
+lstm_s128_k5_fp32 front.wt_seq1 1600 527b48d5f2833a58
+lstm_s128_k5_fp32 lstm.b1 512 b9e40e8f27e4fa9a
+lstm_s128_k5_fp32 lstm.b2 384 72652c7eecb64edf
+lstm_s128_k5_fp32 lstm.b_fc 2 1f588bbe759631a7
+lstm_s128_k5_fp32 lstm.t_hh1 65536 01df79eab617ed7e
+lstm_s128_k5_fp32 lstm.t_ih1 65536 7bac0b6442993ae9
+lstm_s128_k5_fp32 lstm.t_ih2 49152 b8eda1004efb2edc
+lstm_s128_k5_fp32 lstm.w_fc 256 23b7e2b15339b390
+lstm_s128_k5_fp32 merge1.apack4 163840 fbc31d3a7bda5578
+lstm_s128_k5_fp32 merge1.bias 128 ce66c6d1dd780bdf
+lstm_s128_k5_fp32 seq2.apack4 26624 e3e801d2058ba2c3
+lstm_s128_k5_fp32 seq2.bias 128 50acd6294800f7a2
+lstm_s128_k5_fp32 sig3.apack4 18432 09bc66b716947c66
+lstm_s128_k5_fp32 sig3.bias 128 732b9b9156e4d774
+lstm_s128_k5_bf16 geometry nparts=1 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s128_k5_bf16 front.b_seq1 16 68142a946e2b417a
+lstm_s128_k5_bf16 front.b_sig1 4 66752726d6894f90
+lstm_s128_k5_bf16 front.b_sig2 16 f12cc0a532286361
+lstm_s128_k5_bf16 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s128_k5_bf16 front.w_sig2 320 092b55db23ba607a
+lstm_s128_k5_bf16 front.wt5_seq1 2000 dd3850ea3967e258
+lstm_s128_k5_bf16 front.wt_seq1 1600 527b48d5f2833a58
+lstm_s128_k5_bf16 lstm.b1 512 b9e40e8f27e4fa9a
+lstm_s128_k5_bf16 lstm.b2 384 72652c7eecb64edf
+lstm_s128_k5_bf16 lstm.b_fc 2 1f588bbe759631a7
+lstm_s128_k5_bf16 lstm.s16_b1 512 8d25983bd258a7ea
+lstm_s128_k5_bf16 lstm.s16_b2 512 313528855e27840d
+lstm_s128_k5_bf16 lstm.s16_hh 32768 1e08d4d9248cf788
+lstm_s128_k5_bf16 lstm.s16_ih 32768 7efe3fc81095518b
+lstm_s128_k5_bf16 lstm.s16_ih2 32768 a9ec2aec6fa6d3c8
+lstm_s128_k5_bf16 lstm.s_hh1 32768 6df9a18159bacb48
+lstm_s128_k5_bf16 lstm.s_ih1 32768 2cfc195f6d6b477b
+lstm_s128_k5_bf16 lstm.t_hh1 65536 01df79eab617ed7e
+lstm_s128_k5_bf16 lstm.t_ih1 65536 7bac0b6442993ae9
+lstm_s128_k5_bf16 lstm.t_ih2 49152 b8eda1004efb2edc
+lstm_s128_k5_bf16 lstm.w_fc 256 23b7e2b15339b390
+lstm_s128_k5_bf16 merge1.apack16 81920 4655c87a552af13f
+lstm_s128_k5_bf16 merge1.apack4 163840 fbc31d3a7bda5578
+lstm_s128_k5_bf16 merge1.bias 128 ce66c6d1dd780bdf
+lstm_s128_k5_bf16 merge1.spack 81920 4655c87a552af13f
+lstm_s128_k5_bf16 seq2.apack16 14336 5b2c33467445bc59
+lstm_s128_k5_bf16 seq2.apack4 26624 e3e801d2058ba2c3
+lstm_s128_k5_bf16 seq2.bias 128 50acd6294800f7a2
+lstm_s128_k5_bf16 seq2.spack 14336 5b2c33467445bc59
+lstm_s128_k5_bf16 sig3.apack16 10240 0c07f27ec574ff9e
+lstm_s128_k5_bf16 sig3.apack4 18432 09bc66b716947c66
+lstm_s128_k5_bf16 sig3.bias 128 732b9b9156e4d774
+lstm_s128_k5_bf16 sig3.spack 10240 0c07f27ec574ff9e
+lstm_s128_k5_f16 geometry nparts=1 split_f16=0 f16=1 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s128_k5_f16 front.b_seq1 16 68142a946e2b417a
+lstm_s128_k5_f16 front.b_sig1 4 66752726d6894f90
+lstm_s128_k5_f16 front.b_sig2 16 f12cc0a532286361
+lstm_s128_k5_f16 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s128_k5_f16 front.w_sig2 320 092b55db23ba607a
+lstm_s128_k5_f16 front.wt5_seq1 2000 dd3850ea3967e258
+lstm_s128_k5_f16 front.wt_seq1 1600 527b48d5f2833a58
+lstm_s128_k5_f16 lstm.b1 512 b9e40e8f27e4fa9a
+lstm_s128_k5_f16 lstm.b2 384 72652c7eecb64edf
+lstm_s128_k5_f16 lstm.b_fc 2 1f588bbe759631a7
+lstm_s128_k5_f16 lstm.s16_b1 512 8d25983bd258a7ea
+lstm_s128_k5_f16 lstm.s16_b2 512 313528855e27840d
+lstm_s128_k5_f16 lstm.s16_hh 32768 7bac6f3964d08328
+lstm_s128_k5_f16 lstm.s16_ih 32768 34dea96891d9a410
+lstm_s128_k5_f16 lstm.s16_ih2 32768 0d0d9e699aaa7666
+lstm_s128_k5_f16 lstm.s_hh1 32768 6df9a18159bacb48
+lstm_s128_k5_f16 lstm.s_ih1 32768 2cfc195f6d6b477b
+lstm_s128_k5_f16 lstm.t_hh1 65536 01df79eab617ed7e
+lstm_s128_k5_f16 lstm.t_ih1 65536 7bac0b6442993ae9
+lstm_s128_k5_f16 lstm.t_ih2 49152 b8eda1004efb2edc
+lstm_s128_k5_f16 lstm.w_fc 256 23b7e2b15339b390
+lstm_s128_k5_f16 merge1.apack16 81920 6dd2bee7c46ec0c8
+lstm_s128_k5_f16 merge1.apack4 163840 fbc31d3a7bda5578
+lstm_s128_k5_f16 merge1.bias 128 ce66c6d1dd780bdf
+lstm_s128_k5_f16 merge1.spack 81920 4655c87a552af13f
+lstm_s128_k5_f16 seq2.apack16 14336 b090750c9fc975fd
+lstm_s128_k5_f16 seq2.apack4 26624 e3e801d2058ba2c3
+lstm_s128_k5_f16 seq2.bias 128 50acd6294800f7a2
+lstm_s128_k5_f16 seq2.spack 14336 5b2c33467445bc59
+lstm_s128_k5_f16 sig3.apack16 10240 3ecbc3dda0f9b434
+lstm_s128_k5_f16 sig3.apack4 18432 09bc66b716947c66
+lstm_s128_k5_f16 sig3.bias 128 732b9b9156e4d774
+lstm_s128_k5_f16 sig3.spack 10240 0c07f27ec574ff9e
+lstm_s40_k9_fp32 geometry nparts=0 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s40_k9_fp32 front.b_seq1 16 67d571200acd7b1f
+lstm_s40_k9_fp32 front.b_sig1 4 66752726d6894f90
+lstm_s40_k9_fp32 front.b_sig2 16 f12cc0a532286361
+lstm_s40_k9_fp32 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s40_k9_fp32 front.w_sig2 320 092b55db23ba607a
+lstm_s40_k9_fp32 front.wt5_seq1 3600 70f2df0a97ffd5c8
+lstm_s40_k9_fp32 front.wt_seq1 2880 a0348e4a9de2a4c8
+lstm_s40_k9_fp32 lstm.a_hh1 16384 4e6f077eef6446bf
+lstm_s40_k9_fp32 lstm.a_ih1 16384 ec2255c098b55541
+lstm_s40_k9_fp32 lstm.a_ih2 12288 783e48c6de1a28c6
+lstm_s40_k9_fp32 lstm.b1 256 b7bd430b8d0fc4de
+lstm_s40_k9_fp32 lstm.b2 192 3aa0a547649d6c86
+lstm_s40_k9_fp32 lstm.b_fc 2 c9d6332e9d62146c
+lstm_s40_k9_fp32 lstm.q_hh1 16384 71921a7dce362323
+lstm_s40_k9_fp32 lstm.q_ih1 16384 08b815ca657899e5
+lstm_s40_k9_fp32 lstm.q_ih2 16384 78b6cb6e5a67b7aa
+lstm_s40_k9_fp32 lstm.w_fc 128 69a2a7f65c36e761
+lstm_s40_k9_fp32 merge1.apack 40960 ee0b9878fa065fa9
+lstm_s40_k9_fp32 merge1.bias 64 575d2930cb9548be
+lstm_s40_k9_fp32 merge1.wpack 65536 f7da6ca99e362df6
+lstm_s40_k9_fp32 seq2.apack 13312 a838e2fb5974cca8
+lstm_s40_k9_fp32 seq2.bias 64 7d69fd09d2052ef6
+lstm_s40_k9_fp32 seq2.wpack 24576 b85f34004361b0bc
+lstm_s40_k9_fp32 sig3.apack 9216 dc9786dce240a138
+lstm_s40_k9_fp32 sig3.bias 64 21ea6557686ea974
+lstm_s40_k9_fp32 sig3.wpack 18432 da8d48bbd71d373a
+lstm_s40_k9_bf16 geometry nparts=1 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s40_k9_bf16 front.b_seq1 16 67d571200acd7b1f
+lstm_s40_k9_bf16 front.b_sig1 4 66752726d6894f90
+lstm_s40_k9_bf16 front.b_sig2 16 f12cc0a532286361
+lstm_s40_k9_bf16 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s40_k9_bf16 front.w_sig2 320 092b55db23ba607a
+lstm_s40_k9_bf16 front.wt5_seq1 3600 70f2df0a97ffd5c8
+lstm_s40_k9_bf16 front.wt_seq1 2880 a0348e4a9de2a4c8
+lstm_s40_k9_bf16 fused.a_merge1 20480 41965d4fb6da5ede
+lstm_s40_k9_bf16 fused.a_seq1 1792 4e5a6a7c924cd3d5
+lstm_s40_k9_bf16 fused.a_seq2 7168 10d5749b5e3376e8
+lstm_s40_k9_bf16 fused.a_sig2 256 b26b67a0e345ba42
+lstm_s40_k9_bf16 fused.a_sig3 5120 e7196b9e14941910
+lstm_s40_k9_bf16 fused.b_merge1 64 afd6582e039ba27e
+lstm_s40_k9_bf16 fused.b_seq1 16 beb4315908c93df9
+lstm_s40_k9_bf16 fused.b_seq2 64 1f3529bfe61f9945
+lstm_s40_k9_bf16 fused.b_sig1 4 edd80ab0d74827ef
+lstm_s40_k9_bf16 fused.b_sig2 16 7d6d04bbd93bd362
+lstm_s40_k9_bf16 fused.b_sig3 64 6c0c465b3b59d6d3
+lstm_s40_k9_bf16 fused.w_sig1 20 6817e404ab323544
+lstm_s40_k9_bf16 lstm.a_hh1 16384 4e6f077eef6446bf
+lstm_s40_k9_bf16 lstm.a_ih1 16384 ec2255c098b55541
+lstm_s40_k9_bf16 lstm.a_ih2 12288 783e48c6de1a28c6
+lstm_s40_k9_bf16 lstm.b1 256 b7bd430b8d0fc4de
+lstm_s40_k9_bf16 lstm.b2 192 3aa0a547649d6c86
+lstm_s40_k9_bf16 lstm.b_fc 2 c9d6332e9d62146c
+lstm_s40_k9_bf16 lstm.s_hh1 8192 82441f08595e6d5b
+lstm_s40_k9_bf16 lstm.s_ih1 8192 cf3e85cf29f44403
+lstm_s40_k9_bf16 lstm.w_fc 128 69a2a7f65c36e761
+lstm_s40_k9_bf16 lstm.x_b1 256 28a33cf48ff488b2
+lstm_s40_k9_bf16 lstm.x_b2 256 162f8b374ce72f59
+lstm_s40_k9_bf16 lstm.x_hh 8192 2a2de42cd1d5ee3f
+lstm_s40_k9_bf16 lstm.x_ih 8192 7478f39def30c7ef
+lstm_s40_k9_bf16 lstm.x_ih2 8192 cac640339ee16c14
+lstm_s40_k9_bf16 merge1.apack 40960 ee0b9878fa065fa9
+lstm_s40_k9_bf16 merge1.bias 64 575d2930cb9548be
+lstm_s40_k9_bf16 merge1.spack 20480 41965d4fb6da5ede
+lstm_s40_k9_bf16 merge1.wpack 65536 f7da6ca99e362df6
+lstm_s40_k9_bf16 seq2.apack 13312 a838e2fb5974cca8
+lstm_s40_k9_bf16 seq2.bias 64 7d69fd09d2052ef6
+lstm_s40_k9_bf16 seq2.spack 7168 10d5749b5e3376e8
+lstm_s40_k9_bf16 seq2.wpack 24576 b85f34004361b0bc
+lstm_s40_k9_bf16 sig3.apack 9216 dc9786dce240a138
+lstm_s40_k9_bf16 sig3.bias 64 21ea6557686ea974
+lstm_s40_k9_bf16 sig3.spack 5120 e7196b9e14941910
+lstm_s40_k9_bf16 sig3.wpack 18432 da8d48bbd71d373a
+lstm_s40_k9_bf16x3 geometry nparts=2 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s40_k9_bf16x3 front.b_seq1 16 67d571200acd7b1f
+lstm_s40_k9_bf16x3 front.b_sig1 4 66752726d6894f90
+lstm_s40_k9_bf16x3 front.b_sig2 16 f12cc0a532286361
+lstm_s40_k9_bf16x3 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s40_k9_bf16x3 front.w_sig2 320 092b55db23ba607a
+lstm_s40_k9_bf16x3 front.wt5_seq1 3600 70f2df0a97ffd5c8
+lstm_s40_k9_bf16x3 front.wt_seq1 2880 a0348e4a9de2a4c8
+lstm_s40_k9_bf16x3 lstm.a_hh1 16384 4e6f077eef6446bf
+lstm_s40_k9_bf16x3 lstm.a_ih1 16384 ec2255c098b55541
+lstm_s40_k9_bf16x3 lstm.a_ih2 12288 783e48c6de1a28c6
+lstm_s40_k9_bf16x3 lstm.b1 256 b7bd430b8d0fc4de
+lstm_s40_k9_bf16x3 lstm.b2 192 3aa0a547649d6c86
+lstm_s40_k9_bf16x3 lstm.b_fc 2 c9d6332e9d62146c
+lstm_s40_k9_bf16x3 lstm.s_hh1 16384 79c8d616660567d1
+lstm_s40_k9_bf16x3 lstm.s_ih1 16384 d99071f92a460ea9
+lstm_s40_k9_bf16x3 lstm.w_fc 128 69a2a7f65c36e761
+lstm_s40_k9_bf16x3 lstm.x_b1 256 28a33cf48ff488b2
+lstm_s40_k9_bf16x3 lstm.x_b2 256 162f8b374ce72f59
+lstm_s40_k9_bf16x3 lstm.xs_hh 16384 3db7c7fdeb3575e5
+lstm_s40_k9_bf16x3 lstm.xs_ih 16384 f566f9dfbbf0766d
+lstm_s40_k9_bf16x3 lstm.xs_ih2 16384 f41ad637cab97eeb
+lstm_s40_k9_bf16x3 merge1.apack 40960 ee0b9878fa065fa9
+lstm_s40_k9_bf16x3 merge1.bias 64 575d2930cb9548be
+lstm_s40_k9_bf16x3 merge1.spack 40960 210cc9670f7820b6
+lstm_s40_k9_bf16x3 merge1.wpack 65536 f7da6ca99e362df6
+lstm_s40_k9_bf16x3 seq2.apack 13312 a838e2fb5974cca8
+lstm_s40_k9_bf16x3 seq2.bias 64 7d69fd09d2052ef6
+lstm_s40_k9_bf16x3 seq2.spack 14336 40aa16cab18c9ef9
+lstm_s40_k9_bf16x3 seq2.wpack 24576 b85f34004361b0bc
+lstm_s40_k9_bf16x3 sig3.apack 9216 dc9786dce240a138
+lstm_s40_k9_bf16x3 sig3.bias 64 21ea6557686ea974
+lstm_s40_k9_bf16x3 sig3.spack 10240 e9918252dcbbd6c0
+lstm_s40_k9_bf16x3 sig3.wpack 18432 da8d48bbd71d373a
+lstm_s40_k9_bf16x6 geometry nparts=3 split_f16=0 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s40_k9_bf16x6 front.b_seq1 16 67d571200acd7b1f
+lstm_s40_k9_bf16x6 front.b_sig1 4 66752726d6894f90
+lstm_s40_k9_bf16x6 front.b_sig2 16 f12cc0a532286361
+lstm_s40_k9_bf16x6 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s40_k9_bf16x6 front.w_sig2 320 092b55db23ba607a
+lstm_s40_k9_bf16x6 front.wt5_seq1 3600 70f2df0a97ffd5c8
+lstm_s40_k9_bf16x6 front.wt_seq1 2880 a0348e4a9de2a4c8
+lstm_s40_k9_bf16x6 lstm.a_hh1 16384 4e6f077eef6446bf
+lstm_s40_k9_bf16x6 lstm.a_ih1 16384 ec2255c098b55541
+lstm_s40_k9_bf16x6 lstm.a_ih2 12288 783e48c6de1a28c6
+lstm_s40_k9_bf16x6 lstm.b1 256 b7bd430b8d0fc4de
+lstm_s40_k9_bf16x6 lstm.b2 192 3aa0a547649d6c86
+lstm_s40_k9_bf16x6 lstm.b_fc 2 c9d6332e9d62146c
+lstm_s40_k9_bf16x6 lstm.s_hh1 24576 fdb2316cf3664166
+lstm_s40_k9_bf16x6 lstm.s_ih1 24576 e34a107831ac0cf9
+lstm_s40_k9_bf16x6 lstm.w_fc 128 69a2a7f65c36e761
+lstm_s40_k9_bf16x6 lstm.x_b1 256 28a33cf48ff488b2
+lstm_s40_k9_bf16x6 lstm.x_b2 256 162f8b374ce72f59
+lstm_s40_k9_bf16x6 lstm.xs_hh 24576 ceecdd84f938dfe6
+lstm_s40_k9_bf16x6 lstm.xs_ih 24576 c3fb860fc7ac360d
+lstm_s40_k9_bf16x6 lstm.xs_ih2 24576 5edd95c8e159125a
+lstm_s40_k9_bf16x6 merge1.apack 40960 ee0b9878fa065fa9
+lstm_s40_k9_bf16x6 merge1.bias 64 575d2930cb9548be
+lstm_s40_k9_bf16x6 merge1.spack 61440 141cbd4f855008ff
+lstm_s40_k9_bf16x6 merge1.wpack 65536 f7da6ca99e362df6
+lstm_s40_k9_bf16x6 seq2.apack 13312 a838e2fb5974cca8
+lstm_s40_k9_bf16x6 seq2.bias 64 7d69fd09d2052ef6
+lstm_s40_k9_bf16x6 seq2.spack 21504 6fe0abc9be15f63d
+lstm_s40_k9_bf16x6 seq2.wpack 24576 b85f34004361b0bc
+lstm_s40_k9_bf16x6 sig3.apack 9216 dc9786dce240a138
+lstm_s40_k9_bf16x6 sig3.bias 64 21ea6557686ea974
+lstm_s40_k9_bf16x6 sig3.spack 15360 3aa6c275d3aaebfd
+lstm_s40_k9_bf16x6 sig3.wpack 18432 da8d48bbd71d373a
+lstm_s40_k9_f16 geometry nparts=1 split_f16=0 f16=1 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s40_k9_f16 front.b_seq1 16 67d571200acd7b1f
+lstm_s40_k9_f16 front.b_sig1 4 66752726d6894f90
+lstm_s40_k9_f16 front.b_sig2 16 f12cc0a532286361
+lstm_s40_k9_f16 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s40_k9_f16 front.w_sig2 320 092b55db23ba607a
+lstm_s40_k9_f16 front.wt5_seq1 3600 70f2df0a97ffd5c8
+lstm_s40_k9_f16 front.wt_seq1 2880 a0348e4a9de2a4c8
+lstm_s40_k9_f16 fused.a_merge1 20480 9d6b938e2db0ec07
+lstm_s40_k9_f16 fused.a_seq1 1792 296b9d17454b5557
+lstm_s40_k9_f16 fused.a_seq2 7168 a5025124e73cfdbb
+lstm_s40_k9_f16 fused.a_sig2 256 7c6c1f881b1f5895
+lstm_s40_k9_f16 fused.a_sig3 5120 82aeb3817fbccefd
+lstm_s40_k9_f16 fused.b_merge1 64 afd6582e039ba27e
+lstm_s40_k9_f16 fused.b_seq1 16 beb4315908c93df9
+lstm_s40_k9_f16 fused.b_seq2 64 1f3529bfe61f9945
+lstm_s40_k9_f16 fused.b_sig1 4 edd80ab0d74827ef
+lstm_s40_k9_f16 fused.b_sig2 16 7d6d04bbd93bd362
+lstm_s40_k9_f16 fused.b_sig3 64 6c0c465b3b59d6d3
+lstm_s40_k9_f16 fused.w_sig1 20 6817e404ab323544
+lstm_s40_k9_f16 lstm.a_hh1 16384 4e6f077eef6446bf
+lstm_s40_k9_f16 lstm.a_ih1 16384 ec2255c098b55541
+lstm_s40_k9_f16 lstm.a_ih2 12288 783e48c6de1a28c6
+lstm_s40_k9_f16 lstm.b1 256 b7bd430b8d0fc4de
+lstm_s40_k9_f16 lstm.b2 192 3aa0a547649d6c86
+lstm_s40_k9_f16 lstm.b_fc 2 c9d6332e9d62146c
+lstm_s40_k9_f16 lstm.s_hh1 8192 82441f08595e6d5b
+lstm_s40_k9_f16 lstm.s_ih1 8192 cf3e85cf29f44403
+lstm_s40_k9_f16 lstm.w_fc 128 69a2a7f65c36e761
+lstm_s40_k9_f16 lstm.x_b1 256 28a33cf48ff488b2
+lstm_s40_k9_f16 lstm.x_b2 256 162f8b374ce72f59
+lstm_s40_k9_f16 lstm.x_hh 8192 2cb784a33dc47ca3
+lstm_s40_k9_f16 lstm.x_ih 8192 155a8a7fdb0412cf
+lstm_s40_k9_f16 lstm.x_ih2 8192 f9efb35c499933e8
+lstm_s40_k9_f16 merge1.apack 40960 ee0b9878fa065fa9
+lstm_s40_k9_f16 merge1.bias 64 575d2930cb9548be
+lstm_s40_k9_f16 merge1.spack 20480 41965d4fb6da5ede
+lstm_s40_k9_f16 merge1.wpack 65536 f7da6ca99e362df6
+lstm_s40_k9_f16 seq2.apack 13312 a838e2fb5974cca8
+lstm_s40_k9_f16 seq2.bias 64 7d69fd09d2052ef6
+lstm_s40_k9_f16 seq2.spack 7168 10d5749b5e3376e8
+lstm_s40_k9_f16 seq2.wpack 24576 b85f34004361b0bc
+lstm_s40_k9_f16 sig3.apack 9216 dc9786dce240a138
+lstm_s40_k9_f16 sig3.bias 64 21ea6557686ea974
+lstm_s40_k9_f16 sig3.spack 5120 e7196b9e14941910
+lstm_s40_k9_f16 sig3.wpack 18432 da8d48bbd71d373a
+lstm_s40_k9_f16x3 geometry nparts=2 split_f16=1 f16=0 L=100 P1=96 P2=92 P3=28 PQ2=0 T=24 T2=0 T3=0 T4=0 kw1=5
+lstm_s40_k9_f16x3 front.b_seq1 16 67d571200acd7b1f
+lstm_s40_k9_f16x3 front.b_sig1 4 66752726d6894f90
+lstm_s40_k9_f16x3 front.b_sig2 16 f12cc0a532286361
+lstm_s40_k9_f16x3 front.w_sig1 20 4268a84dfd19d2fa
+lstm_s40_k9_f16x3 front.w_sig2 320 092b55db23ba607a
+lstm_s40_k9_f16x3 front.wt5_seq1 3600 70f2df0a97ffd5c8
+lstm_s40_k9_f16x3 front.wt_seq1 2880 a0348e4a9de2a4c8
+lstm_s40_k9_f16x3 lstm.a_hh1 16384 4e6f077eef6446bf
+lstm_s40_k9_f16x3 lstm.a_ih1 16384 ec2255c098b55541
+lstm_s40_k9_f16x3 lstm.a_ih2 12288 783e48c6de1a28c6
+lstm_s40_k9_f16x3 lstm.b1 256 b7bd430b8d0fc4de
+lstm_s40_k9_f16x3 lstm.b2 192 3aa0a547649d6c86
+lstm_s40_k9_f16x3 lstm.b_fc 2 c9d6332e9d62146c
+lstm_s40_k9_f16x3 lstm.s_hh1 16384 ad1c4f425e51abab
+lstm_s40_k9_f16x3 lstm.s_ih1 16384 22b49261df34f67b
+lstm_s40_k9_f16x3 lstm.w_fc 128 69a2a7f65c36e761
+lstm_s40_k9_f16x3 lstm.x_b1 256 28a33cf48ff488b2
+lstm_s40_k9_f16x3 lstm.x_b2 256 162f8b374ce72f59
+lstm_s40_k9_f16x3 lstm.xs_hh 16384 dda8b356bf0219ff
+lstm_s40_k9_f16x3 lstm.xs_ih 16384 8bfd92ec51591dfb
+lstm_s40_k9_f16x3 lstm.xs_ih2 16384 aedadc2f0f59d173
+lstm_s40_k9_f16x3 merge1.apack 40960 ee0b9878fa065fa9
+lstm_s40_k9_f16x3 merge1.bias 64 575d2930cb9548be
+lstm_s40_k9_f16x3 merge1.spack 40960 19bc4aecfb58fda3
+lstm_s40_k9_f16x3 merge1.wpack 65536 f7da6ca99e362df6
+lstm_s40_k9_f16x3 seq2.apack 13312 a838e2fb5974cca8
+lstm_s40_k9_f16x3 seq2.bias 64 7d69fd09d2052ef6
+lstm_s40_k9_f16x3 seq2.spack 14336 11c0b108b28caa50
+lstm_s40_k9_f16x3 seq2.wpack 24576 b85f34004361b0bc
+lstm_s40_k9_f16x3 sig3.apack 9216 dc9786dce240a138
+lstm_s40_k9_f16x3 sig3.bias 64 21ea6557686ea974
+lstm_s40_k9_f16x3 sig3.spack 10240 4a58eccf947bb5de
+lstm_s40_k9_f16x3 sig3.wpack 18432 da8d48bbd71d373a
+conv_s64_k9_fp32 geometry nparts=0 split_f16=0 f16=0 L=100 P1=90 P2=80 P3=24 PQ2=80 T=20 T2=16 T3=7 T4=3 kw1=11
+conv_s64_k9_fp32 b_fc 2 696ffe0c67862cf2
+conv_s64_k9_fp32 front.b_seq1 16 dcfe074a7e665725
+conv_s64_k9_fp32 front.b_sig1 4 4101c245e8c7332d
+conv_s64_k9_fp32 front.b_sig2 16 2304f079b5197d63
+conv_s64_k9_fp32 front.w_sig1 44 fc45f3fc5e7b7948
+conv_s64_k9_fp32 front.w_sig2 704 ea07f11967c892a3
+conv_s64_k9_fp32 front.wt5_seq1 7920 a0e3c5d1dfb9c62f
+conv_s64_k9_fp32 front.wt_seq1 6336 86a958284061862f
+conv_s64_k9_fp32 merge1.apack 40960 e8c2f0006d644bb1
+conv_s64_k9_fp32 merge1.bias 64 3333949f27c2632f
+conv_s64_k9_fp32 merge1.wpack 65536 85af7b2bc83b209a
+conv_s64_k9_fp32 merge2.apack 20480 180b03b8043872ad
+conv_s64_k9_fp32 merge2.bias 64 1c8af354bdcf6225
+conv_s64_k9_fp32 merge2.wpack 32768 8d909a7af7ad0dcb
+conv_s64_k9_fp32 merge3.apack 12288 75ed4b7e370259e0
+conv_s64_k9_fp32 merge3.bias 64 8da657bd9c0f8ddf
+conv_s64_k9_fp32 merge4.apack 12288 38cc1c765ae51ba4
+conv_s64_k9_fp32 merge4.bias 64 ff140099ea5f497c
+conv_s64_k9_fp32 seq2.apack 5632 5b32f59cd3a61b34
+conv_s64_k9_fp32 seq2.bias 32 3e06b497d7de2f63
+conv_s64_k9_fp32 seq3.apack 18432 c644aa18767278b6
+conv_s64_k9_fp32 seq3.bias 64 f149e4f05c117d11
+conv_s64_k9_fp32 seq3.wpack 36864 9a541ed0383743c4
+conv_s64_k9_fp32 sig3.apack 9216 b80f93c288437b53
+conv_s64_k9_fp32 sig3.bias 64 75c698485e324cb3
+conv_s64_k9_fp32 sig3.wpack 18432 e6868a98d0e9d4af
+conv_s64_k9_fp32 w_fc 384 578b0317cb484d13
+conv_s96_k9_fp32 geometry nparts=0 split_f16=0 f16=0 L=100 P1=90 P2=80 P3=24 PQ2=80 T=20 T2=16 T3=7 T4=3 kw1=11
+conv_s96_k9_fp32 b_fc 2 5e67bc6e2b7e2863
+conv_s96_k9_fp32 front.b_seq1 16 42d3114576e5eb44
+conv_s96_k9_fp32 front.b_sig1 4 4101c245e8c7332d
+conv_s96_k9_fp32 front.b_sig2 16 2304f079b5197d63
+conv_s96_k9_fp32 front.w_sig1 44 fc45f3fc5e7b7948
+conv_s96_k9_fp32 front.w_sig2 704 ea07f11967c892a3
+conv_s96_k9_fp32 front.wt5_seq1 7920 8fddf8e45d38d168
+conv_s96_k9_fp32 front.wt_seq1 6336 c1beaff034183668
+conv_s96_k9_fp32 merge1.apack4 92160 4173a8add005ab47
+conv_s96_k9_fp32 merge1.bias 96 91956a6e9b77abab
+conv_s96_k9_fp32 merge2.apack4 46080 fb49866a14aa23d2
+conv_s96_k9_fp32 merge2.bias 96 01dc1a04db57806d
+conv_s96_k9_fp32 merge3.apack4 27648 13470419ec44a5d7
+conv_s96_k9_fp32 merge3.bias 96 7f3c6b1b042ab602
+conv_s96_k9_fp32 merge4.apack4 27648 fbc01c2e56eca1a9
+conv_s96_k9_fp32 merge4.bias 96 10b0c4a3256bbf62
+conv_s96_k9_fp32 seq2.apack 5632 860a6812c3217244
+conv_s96_k9_fp32 seq2.bias 32 8d4c5facced3017b
+conv_s96_k9_fp32 seq3.apack4 27648 6bc5b45ad331fa4d
+conv_s96_k9_fp32 seq3.bias 96 cdafbe44979b8ed7
+conv_s96_k9_fp32 sig3.apack4 13824 d1ccbba9cb07b988
+conv_s96_k9_fp32 sig3.bias 96 ad34a7f6321c8c64
+conv_s96_k9_fp32 w_fc 576 212f0df9616a9e2f
+"""
