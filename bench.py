@@ -6,7 +6,9 @@ synthetic chunks, inputs already resident in HBM.  One process per GPU; chunks s
 collective; the only exchange is one all-reduce of the per-label counts (RCCL over xGMI) at the end of the timed
 region.
 
-    python bench.py                          # 1 GPU: headline config + the other BASELINE configs + CPU baseline
+    python bench.py                          # 1 GPU: the headline config alone (set up, warm up, timed steps, result line)
+    python bench.py --full                   # + the side legs, the CPU baseline, the other BASELINE configs, the precision
+                                             #   check and the C-ABI collective check (the --no-* options trim it)
     python bench.py --gpus N [...]           # launches N ranks itself (torch.distributed.run) when not under torchrun
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W            # the driver's form: RANK/LOCAL_RANK/WORLD_SIZE from the env
@@ -15,8 +17,9 @@ Workloads (BASELINE.json `configs`): convlstm_c100 = configs[2] (the config the 
 conv_c100 = configs[1], convlstm_c100_bf16_10m = configs[3] (10 M chunks strong-sharded over the ranks, bf16),
 convlstm_c200_bf16 = configs[4] (3-class, 200-sample chunks, bf16).  `--dtype` overrides a workload's arithmetic.
 
-Prints ONE JSON line on rank 0 (contract in the task statement; `roofline` and `cpu_baseline` objects included).  A
-world size that differs from --gpus is an error, never a silently smaller run.
+Prints ONE JSON line on rank 0 (contract in the task statement; the `roofline` object from the timed steps' own kernel
+events; `cpu_baseline` and the CPU-checked `parity` figures with --full).  A world size that differs from --gpus is an
+error, never a silently smaller run.
 """
 import argparse
 import json
@@ -851,21 +854,25 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="convlstm_c100", choices=sorted(WORKLOADS) + ["all"],
-                    help="'all' = the default headline plus every other BASELINE config (what a plain 1-GPU run does anyway)")
+                    help="'all' = the default headline plus every other BASELINE config (implies --full)")
     ap.add_argument("--chunks", type=int, default=0, help="chunks per GPU per step (weak) / in total (strong); 0 = the workload's")
     ap.add_argument("--subbatch", type=int, default=0)
     ap.add_argument("--dtype", default=None, choices=["fp32", "bf16x6", "bf16x3", "f16x3", "bf16", "f16"],
                     help="GEMM arithmetic (default: the workload's): fp32 MFMA or bf16 MFMA with 1 / 2 / 3-part operands")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-encode", action="store_true", help="skip the standalone encode-kernel roofline leg")
-    ap.add_argument("--no-reads", action="store_true", help="skip the measured reads/sec and host-buffer legs")
-    ap.add_argument("--no-alt", "--no-others", dest="no_others", action="store_true", help="skip the other BASELINE configs / dtypes")
-    ap.add_argument("--no-refine", action="store_true", help="skip the refinement / VBZ / dataset-ETL legs")
+    ap.add_argument("--full", action="store_true",
+                    help="1 GPU: after the headline, the side legs, the CPU baseline, the other BASELINE configs / dtypes and the "
+                         "precision check; every world size: the C-ABI collective check.  Without it a run does only what its "
+                         "result line needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the CPU parity / precision checks")
+    ap.add_argument("--no-encode", action="store_true", help="--full: skip the standalone encode-kernel roofline leg")
+    ap.add_argument("--no-reads", action="store_true", help="--full: skip the measured reads/sec and host-buffer legs")
+    ap.add_argument("--no-alt", "--no-others", dest="no_others", action="store_true", help="--full: skip the other BASELINE configs / dtypes")
+    ap.add_argument("--no-refine", action="store_true", help="--full: skip the refinement / VBZ / dataset-ETL legs")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--details", default=None, help="where the full report goes (default: bench_details.json beside bench.py)")
     ap.add_argument("--dist-timeout", type=float, default=180.0, help="seconds a collective may take before the run is declared failed")
     ap.add_argument("--no-cabi-collective", action="store_true",
-                    help="multi-rank runs: skip the cross-check of the library's own RCCL communicator after the result line")
+                    help="multi-rank runs with --full: skip the cross-check of the library's own RCCL communicator after the result line")
     ap.add_argument("--dist-backend", default=None, help="torch.distributed backend (default nccl = RCCL)")
     ap.add_argument("--logits-hash", action="store_true",
                     help="testing: gather every rank's logits of the last step on rank 0 (after the timed region) and record the "
@@ -879,6 +886,8 @@ def main():
         ap.error("--gpus must be >= 1")
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.workload == "all":
+        args.full = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(sys.argv[1:], args.gpus))
 
@@ -977,13 +986,13 @@ def main():
     # the C-ABI collective (rmr_allreduce_counts: RCCL called from the library, no torch) cross-checked against the
     # torch.distributed result on the same counts — outside the timed region.  One process: before the result line (it is
     # part of it).  Several ranks: AFTER rank 0 has printed the result line, reported on stderr — whatever a second
-    # communicator does on a node this code has never seen, it cannot cost the measurement.
-    cabi = rdist.cabi_allreduce_check(job.eng, per_rank, rank, world) if world == 1 else None
+    # communicator does on a node this code has never seen, it cannot cost the measurement.  A check, not the headline: --full.
+    cabi = rdist.cabi_allreduce_check(job.eng, per_rank, rank, world) if world == 1 and args.full else None
 
     def cabi_after(details_path=None):
         """Never costs the run its exit code: the measurement was taken with torch.distributed's communicator and is already
         printed; this auxiliary communicator's failure is reported on stderr and in the details file, rc stays 0."""
-        if world == 1 or args.no_cabi_collective:
+        if world == 1 or args.no_cabi_collective or not args.full:
             return
         tq = time.perf_counter()
         try:
@@ -1027,10 +1036,11 @@ def main():
         "roofline": rep["roofline"], "whole_pipeline": rep["whole_pipeline"], "kernels": rep["kernels"],
         "label_counts": rep["label_counts"], "label_counts_match_logits_argmax": counts_exact,
         "label_counts_per_rank": [[int(x) for x in r] for r in per_rank] if per_rank is not None else None,
-        "allreduce_counts_c_abi": cabi if world == 1 else "run after the result line; result on stderr (see bench.py)",
+        "allreduce_counts_c_abi": ((cabi if world == 1 else "run after the result line; result on stderr (see bench.py)")
+                                   if args.full else "not run (--full runs it)"),
         "collective": coll, "logits_sha256": logits_sha, "outputs_dumped": dumped,
     }
-    if world == 1:
+    if world == 1 and args.full:
         legs = side_legs(job, args, job.logits)
         out.update(legs)
         note("side legs done")

@@ -47,6 +47,18 @@ def _bench(extra, env_extra=None, expect_rc=0):
         return full, p
 
 
+def test_bench_plain_run_does_only_the_headline():
+    """A run without --full: set-up, warm-up, the timed steps and the result line (roofline from the timed steps' own kernel
+    events) - none of the side legs, baselines, other configurations or checks that --full adds."""
+    plain, _ = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--chunks", "20000"])
+    for key in ("host_buffers_pcie_inclusive", "encode_roofline", "reads_pipeline", "refine_signal_map", "vbz_decode", "dataset_etl",
+                "cpu_baseline", "other_configs", "precision"):
+        assert key not in plain, key
+    assert plain["allreduce_counts_c_abi"] == "not run (--full runs it)"
+    assert sum(plain["label_counts"]) == 2 * 20000 and plain["label_counts_match_logits_argmax"] is True
+    assert plain["roofline"]["achieved"] > 0 and plain["kernels"]
+
+
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 def test_bench_two_ranks_shard_and_reduce_exactly(dtype):
     two, _ = _bench(["--gpus", "2", "--force-device", "0", "--dist-backend", "gloo", "--dtype", dtype] + FAST)
@@ -213,9 +225,9 @@ def test_bench_one_rank_through_rccl_reproduces_the_plain_run():
     """bench.py itself with its process group built over nccl for ONE rank (REMORA_AMD_DIST_SINGLE=1): the timed region's
     all-reduce of the device-resident label counts, the max-over-ranks clock and the per-rank gather run through RCCL and
     leave the numbers of the plain single-process run."""
-    plain, _ = _bench(["--gpus", "1"] + FAST)
+    plain, _ = _bench(["--gpus", "1", "--full"] + FAST)  # (--full: the C-ABI collective check)
     assert plain["allreduce_counts_c_abi"]["status"] == "ok", plain["allreduce_counts_c_abi"]
-    forced, p = _bench(["--gpus", "1"] + FAST, env_extra={"REMORA_AMD_DIST_SINGLE": "1", "RANK": "0", "WORLD_SIZE": "1",
-                                                         "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1"})
+    forced, p = _bench(["--gpus", "1", "--full"] + FAST, env_extra={"REMORA_AMD_DIST_SINGLE": "1", "RANK": "0", "WORLD_SIZE": "1",
+                                                                    "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1"})
     assert forced["label_counts"] == plain["label_counts"] and forced["label_counts_per_rank"] == plain["label_counts_per_rank"]
     assert forced["n_gpus"] == 1 and forced["value"] > 0

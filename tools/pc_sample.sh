@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 export ROCPROFILER_PC_SAMPLING_BETA_ENABLED=1
 OUT=gpurun_out/pcs_$TAG
 mkdir -p $OUT
-BENCH="python bench.py --steps 6 --warmup 1 --no-cpu-baseline --no-reads --no-others --no-refine $*"
+BENCH="python bench.py --full --steps 6 --warmup 1 --no-cpu-baseline --no-reads --no-others --no-refine $*"
 echo "$BENCH" > $OUT/command.txt
 timeout 120 rocprofv3 -L 2>&1 | grep -i -B2 -A12 "pc.sampl\|PC Sampl" | head -60 > $OUT/avail.txt
 for METHOD in stochastic host_trap; do

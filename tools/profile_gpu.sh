@@ -7,7 +7,7 @@ TAG=${1:-r2}; shift || true
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-BENCH="python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-reads --no-others --no-refine $*"
+BENCH="python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-reads --no-others --no-refine $*"
 echo "$BENCH" > $OUT/command.txt
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $BENCH > $OUT/bench_trace.json 2> $OUT/trace.err
 for C in FETCH_SIZE WRITE_SIZE; do
