@@ -22,11 +22,10 @@
 // [row][IC+4] image measured 54 % of LDS cycles lost to 2-way conflicts, profiles/r01).
 #include "rmr_internal.h"
 #include "rmr_math.h"
+#include "rmr_mma.h"
 #include "rmr_plan.h"
 
 namespace rmr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct ConvArgs {
     const float *in;

@@ -15,41 +15,9 @@
 // slots and an odd row stride => every 16-lane ds_read_b128 group hits 16 distinct slots.
 #include "rmr_internal.h"
 #include "rmr_math.h"
+#include "rmr_mma.h"
 
 namespace rmr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-// F16 (dtype f16x3, NP = 2): two IEEE half parts instead of bf16 parts (k_lstm_bf16s.hip, split_parts)
-template <int NP, bool F16 = false>
-__device__ __forceinline__ void split_parts_c(float x, unsigned (&p)[NP]) {
-    if constexpr (F16) {
-        static_assert(NP == 2, "the half split has two parts");
-        const _Float16 hi = (_Float16)x;
-        const _Float16 lo = (_Float16)(x - (float)hi);
-        p[0] = (unsigned)__builtin_bit_cast(unsigned short, hi) << 16;
-        p[1] = (unsigned)__builtin_bit_cast(unsigned short, lo) << 16;
-    } else if (NP == 1) {
-        const unsigned b = __float_as_uint(x);
-        p[0] = (b + 0x7fffu + ((b >> 16) & 1u)) & 0xffff0000u;
-    } else {
-        float r = x;
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const unsigned b = __float_as_uint(r);
-            p[i] = (i + 1 < NP || NP == 3) ? (b & 0xffff0000u) : ((b + 0x7fffu + ((b >> 16) & 1u)) & 0xffff0000u);
-            r -= __uint_as_float(p[i]);
-        }
-    }
-}
-
-template <int NP> struct ProdC;
-template <> struct ProdC<1> { static constexpr int N = 1; static constexpr int A[1] = {0}; static constexpr int B[1] = {0}; };
-template <> struct ProdC<2> { static constexpr int N = 3; static constexpr int A[3] = {0, 0, 1}; static constexpr int B[3] = {0, 1, 0}; };
-template <> struct ProdC<3> { static constexpr int N = 6; static constexpr int A[6] = {0, 0, 1, 0, 2, 1}; static constexpr int B[6] = {0, 1, 0, 2, 0, 1}; };
 
 struct ConvSArgs {
     const float *in;
@@ -71,7 +39,7 @@ __global__ __launch_bounds__(256) void conv_bf16s_kernel(ConvSArgs a) {
     constexpr int SLR = (KS % 2 == 0) ? KS + 1 : KS;   // odd row stride in slots
     constexpr int NPL = PAIR ? 2 : 4;            // planes
     constexpr int STEPS = PAIR ? (KW + 1) / 2 : KW * KS;
-    using P = ProdC<NP>;
+    using P = Prod<NP>;
     const int tid = threadIdx.x;
     const int lane = tid & 63, w = tid >> 6, q = lane >> 4, nn = lane & 15;
 
@@ -116,10 +84,10 @@ __global__ __launch_bounds__(256) void conv_bf16s_kernel(ConvSArgs a) {
 #pragma unroll
                 for (int u = 0; u < UNR; ++u) {
                     unsigned e[8][NP];
-                    split_parts_c<NP, F16>(v0[u].x, e[0]); split_parts_c<NP, F16>(v0[u].y, e[1]);
-                    split_parts_c<NP, F16>(v0[u].z, e[2]); split_parts_c<NP, F16>(v0[u].w, e[3]);
-                    split_parts_c<NP, F16>(v1[u].x, e[4]); split_parts_c<NP, F16>(v1[u].y, e[5]);
-                    split_parts_c<NP, F16>(v1[u].z, e[6]); split_parts_c<NP, F16>(v1[u].w, e[7]);
+                    split16<NP, F16>(v0[u].x, e[0]); split16<NP, F16>(v0[u].y, e[1]);
+                    split16<NP, F16>(v0[u].z, e[2]); split16<NP, F16>(v0[u].w, e[3]);
+                    split16<NP, F16>(v1[u].x, e[4]); split16<NP, F16>(v1[u].y, e[5]);
+                    split16<NP, F16>(v1[u].z, e[6]); split16<NP, F16>(v1[u].w, e[7]);
 #pragma unroll
                     for (int p = 0; p < NP; ++p)
                         sm4[(size_t)p * a.part + dsto[u]] =

@@ -25,11 +25,10 @@
 // groups + the next iteration's rows requested under the matrix phase (-> 1.00; sig -3 %).
 #include "rmr_internal.h"
 #include "rmr_math.h"
+#include "rmr_mma.h"
 #include "rmr_plan.h"
 
 namespace rmr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 

@@ -36,16 +36,11 @@
 //   different taps (2 of 7 k-steps, one extra LDS cycle).
 #include "rmr_internal.h"
 #include "rmr_math.h"
+#include "rmr_mma.h"
 
 #include <type_traits>
 
 namespace rmr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 struct FusedArgs {
     const float *signal;   // [n][L]
@@ -92,17 +87,6 @@ __device__ unsigned long long g_stage_clock[4][16];
 #define TS_FLUSH
 #endif
 
-__device__ __forceinline__ int fdiv(int x, FastDiv d) { return (int)(((float)x + 0.5f) * d.inv); }
-
-// The 16-bit operand type is a template parameter of everything below: F16 = false -> bf16 (8 exponent / 7 mantissa bits;
-// BASELINE configs[3]/[4] name it), true -> IEEE half (5 / 10 bits: eight times finer rounding at the same matrix rate
-// - v_mfma_f32_16x16x32_f16 and _bf16 are both 16 cycles; activations here are O(1..10), far from half's 65504).
-template <bool F16>
-__device__ __forceinline__ f32x4 mfma16(const uint4 a, const uint4 b, const f32x4 c) {
-    if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
 // Activations are carried SCALED by log2(e): every layer's weights/bias are prepared on the host so that the
 // accumulator holds z = log2(e) * y (y = the reference's pre-activation), and the stored activation is
 //   a' = z / (1 + 2^-z) = log2(e) * swish(y)          (src/remora/activations.py:4-18: swish(y) = y * sigmoid(y))
@@ -113,7 +97,6 @@ __device__ __forceinline__ f32x4 mfma16(const uint4 a, const uint4 b, const f32x
 // register pairs: 4 v_exp + 2 v_pk_add_f32 + 4 v_rcp + 2 v_pk_mul_f32 + 2 packs = 14 instructions; left to itself hipcc
 // paired elements (1, 2), moved them into an aligned register pair and re-assembled the result with v_perm / v_alignbit
 // (22).  Packed and scalar fp32 add / mul round alike: same bits.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 #ifndef RMR_SWISH_PAIRS
 #define RMR_SWISH_PAIRS 1
 #endif

@@ -18,11 +18,9 @@
 // one ds_read_b128 per 16-wide k group, each feeding 4 MFMAs x 4 gates.
 #include "rmr_internal.h"
 #include "rmr_math.h"
+#include "rmr_mma.h"
 
 namespace rmr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 
 struct LstmArgs {
     const float *x;  // [n][T][H] channel-last merge_conv1 output

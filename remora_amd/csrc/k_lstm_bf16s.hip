@@ -16,52 +16,13 @@
 // slots padded to an odd slot count -> conflict-free ds_read_b128 B fragments.
 #include "rmr_internal.h"
 #include "rmr_math.h"
+#include "rmr_mma.h"
 
 namespace rmr {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-// split x into NP bf16 parts, returned as fp32 bit patterns whose low 16 bits are zero.  F16 (dtype f16x3, NP = 2): two IEEE
-// half parts instead - hi = half(x), lo = half(x - hi), each in the high 16 bits of its word like the bf16 parts: 22
-// significand bits from three products (hi hi, hi lo, lo hi), where two bf16 parts carry 16
-template <int NP, bool F16 = false>
-__device__ __forceinline__ void split_parts(float x, unsigned (&p)[NP]) {
-    if constexpr (F16) {
-        static_assert(NP == 2, "the half split has two parts");
-        const _Float16 hi = (_Float16)x;
-        const _Float16 lo = (_Float16)(x - (float)hi);
-        p[0] = (unsigned)__builtin_bit_cast(unsigned short, hi) << 16;
-        p[1] = (unsigned)__builtin_bit_cast(unsigned short, lo) << 16;
-    } else if (NP == 1) {  // round to nearest even
-        const unsigned b = __float_as_uint(x);
-        p[0] = (b + 0x7fffu + ((b >> 16) & 1u)) & 0xffff0000u;
-    } else {
-        float r = x;
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const unsigned b = __float_as_uint(r);
-            if (i + 1 < NP || NP == 3) {
-                p[i] = b & 0xffff0000u;  // truncation: exact remainder chain
-            } else {
-                p[i] = (b + 0x7fffu + ((b >> 16) & 1u)) & 0xffff0000u;  // last of two: round
-            }
-            r -= __uint_as_float(p[i]);
-        }
-    }
-}
-__device__ __forceinline__ unsigned pack2(unsigned lo_elem, unsigned hi_elem) {
-    return (lo_elem >> 16) | hi_elem;  // two bf16 (given as fp32 patterns) -> one dword
-}
-
-// part-product schedule: pairs (a part, b part)
-template <int NP> struct Prod;
-template <> struct Prod<1> { static constexpr int N = 1; static constexpr int A[1] = {0}; static constexpr int B[1] = {0}; };
-template <> struct Prod<2> { static constexpr int N = 3; static constexpr int A[3] = {0, 0, 1}; static constexpr int B[3] = {0, 1, 0}; };
-template <> struct Prod<3> { static constexpr int N = 6; static constexpr int A[6] = {0, 0, 1, 0, 2, 1}; static constexpr int B[6] = {0, 1, 0, 2, 0, 1}; };
-
+// mfma16 (rmr_mma.h) with the B operand typed bf16x8.  Kept as a local form: with a uint4 B operand hipcc unrolls
+// lstm_bf16s_kernel<32, 2, true> (dtype f16x3, size 32) differently - 975 instead of 1174 instructions, one more SGPR - while
+// every other instance comes out the same; which of the two is faster has not been measured.
 template <bool F16>
 __device__ __forceinline__ f32x4 mma_part(const uint4 a, const bf16x8 b, const f32x4 c) {
     if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
@@ -141,8 +102,8 @@ __global__ __launch_bounds__(4 * H) void lstm_bf16s_kernel(LstmSArgs a) {
 
     auto stage_x = [&](int buf, const float4 v) {
         unsigned e[4][NP];
-        split_parts<NP, F16>(v.x, e[0]); split_parts<NP, F16>(v.y, e[1]);
-        split_parts<NP, F16>(v.z, e[2]); split_parts<NP, F16>(v.w, e[3]);
+        split16<NP, F16>(v.x, e[0]); split16<NP, F16>(v.y, e[1]);
+        split16<NP, F16>(v.z, e[2]); split16<NP, F16>(v.w, e[3]);
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
             uint2 wv = make_uint2(pack2(e[0][p], e[1][p]), pack2(e[2][p], e[3][p]));
@@ -210,7 +171,7 @@ __global__ __launch_bounds__(4 * H) void lstm_bf16s_kernel(LstmSArgs a) {
             {
                 unsigned e[4][NP];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) split_parts<NP, F16>(h[r], e[r]);
+                for (int r = 0; r < 4; ++r) split16<NP, F16>(h[r], e[r]);
                 const int grp8 = 2 * w + (q >> 1);
 #pragma unroll
                 for (int p = 0; p < NP; ++p) {

@@ -19,14 +19,9 @@
 
 #include "rmr_internal.h"
 #include "rmr_math.h"
+#include "rmr_mma.h"
 
 namespace rmr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 struct LstmXArgs {
     const uint16_t *x;     // bf16 [n][T][64]
@@ -38,51 +33,7 @@ struct LstmXArgs {
     int T, num_out;
 };
 
-// F16: the operands (x from the fused front kernel, h, the weights) are IEEE half instead of bf16 (k_fused.hip)
-template <bool F16>
-__device__ __forceinline__ f32x4 mfma16(const uint4 a, const uint4 b, const f32x4 c) {
-    if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-// acc rows are pre-scaled: [0] i, [1] f, [3] o by -log2(e); [2] g by 2 log2(e)
-__device__ __forceinline__ float lstm_cell(const f32x4 acc, float &c) {
-    const float ig = fast_rcp(1.0f + __builtin_amdgcn_exp2f(acc[0]));
-    const float fg = fast_rcp(1.0f + __builtin_amdgcn_exp2f(acc[1]));
-    const float gg = fmaf(-2.0f, fast_rcp(1.0f + __builtin_amdgcn_exp2f(acc[2])), 1.0f);
-    const float og = fast_rcp(1.0f + __builtin_amdgcn_exp2f(acc[3]));
-    c = fmaf(fg, c, ig * gg);
-    const float tc = fmaf(-2.0f, fast_rcp(1.0f + __builtin_amdgcn_exp2f(c * 2.8853900817779268f)), 1.0f);
-    return og * tc;
-}
-
-// The lane's TWO units at once: everything that is not an exp or a rcp works on register pairs (v_pk_add_f32,
-// v_pk_fma_f32, v_pk_mul_f32: 11 packed + 20 transcendental instructions instead of 22 + 20; the VALU is this kernel's
-// bound).  Packed and scalar fp32 operations round alike: same bits as two lstm_cell calls.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-#ifndef RMR_LSTM_PAIRS
-#define RMR_LSTM_PAIRS 1
-#endif
-__device__ __forceinline__ f32x2 exp2_2(const f32x2 v) { return f32x2{__builtin_amdgcn_exp2f(v.x), __builtin_amdgcn_exp2f(v.y)}; }
-__device__ __forceinline__ f32x2 rcp_2(const f32x2 v) { return f32x2{fast_rcp(v.x), fast_rcp(v.y)}; }
-// Tried and dropped (profiles/r03_lstm_shared_rcp_ab.log): sharing reciprocals - sig(i) tanh(g) = (G - 1) / ((1 + A)(1 + G)),
-// sig(o) tanh(c) = (C - 1) / ((1 + O)(1 + C)), 5 exp + 3 rcp per unit instead of 5 + 5 - ran 2.42 against 2.37 ns/chunk: the
-// step is bound by the recurrent chain (h -> MFMA -> gates -> h), which the extra multiply in front of each rcp lengthens.
-__device__ __forceinline__ f32x2 lstm_cell2(const f32x4 acc0, const f32x4 acc1, float &c0, float &c1) {
-    if (!RMR_LSTM_PAIRS) return f32x2{lstm_cell(acc0, c0), lstm_cell(acc1, c1)};
-    const f32x2 ig = rcp_2(exp2_2(f32x2{acc0[0], acc1[0]}) + 1.0f);
-    const f32x2 fg = rcp_2(exp2_2(f32x2{acc0[1], acc1[1]}) + 1.0f);
-    const f32x2 gr = rcp_2(exp2_2(f32x2{acc0[2], acc1[2]}) + 1.0f);
-    const f32x2 og = rcp_2(exp2_2(f32x2{acc0[3], acc1[3]}) + 1.0f);
-    const f32x2 gg = __builtin_elementwise_fma(f32x2{-2.0f, -2.0f}, gr, f32x2{1.0f, 1.0f});
-    const f32x2 c = __builtin_elementwise_fma(fg, f32x2{c0, c1}, ig * gg);
-    c0 = c.x;
-    c1 = c.y;
-    const f32x2 tr = rcp_2(exp2_2(c * 2.8853900817779268f) + 1.0f);
-    const f32x2 tc = __builtin_elementwise_fma(f32x2{-2.0f, -2.0f}, tr, f32x2{1.0f, 1.0f});
-    return og * tc;
-}
-
+// F16: the operands (x from the fused front kernel, h, the weights) are IEEE half instead of bf16 (k_fused.hip).
 // Two 16-chunk groups per block iteration (round 4; the one-group kernel it replaced - 2.38 against 2.22 ns per chunk at C100 -
 // left the library in round 6): a wave issues
 // the MFMAs of both groups before the gate math of the first, so the matrix pipe works on group B while the VALU works on

@@ -17,13 +17,9 @@
 
 #include "rmr_internal.h"
 #include "rmr_math.h"
+#include "rmr_mma.h"
 
 namespace rmr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
@@ -37,56 +33,9 @@ struct LstmXsArgs {
     int T, num_out;
 };
 
-template <int NP> struct ProdX;
-template <> struct ProdX<2> { static constexpr int N = 3; static constexpr int A[3] = {0, 0, 1}; static constexpr int B[3] = {0, 1, 0}; };
-template <> struct ProdX<3> { static constexpr int N = 6; static constexpr int A[6] = {0, 0, 1, 0, 2, 1}; static constexpr int B[6] = {0, 1, 0, 2, 0, 1}; };
-
-// x -> NP parts, each in the HIGH 16 bits of its word (split_parts of k_lstm_bf16s.hip)
-template <int NP, bool F16>
-__device__ __forceinline__ void split16(float x, unsigned (&p)[NP]) {
-    if constexpr (F16) {
-        static_assert(NP == 2, "the half split has two parts");
-        const _Float16 hi = (_Float16)x;
-        const _Float16 lo = (_Float16)(x - (float)hi);
-        p[0] = (unsigned)__builtin_bit_cast(unsigned short, hi) << 16;
-        p[1] = (unsigned)__builtin_bit_cast(unsigned short, lo) << 16;
-    } else {
-        float r = x;
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const unsigned b = __float_as_uint(r);
-            p[i] = (i + 1 < NP || NP == 3) ? (b & 0xffff0000u) : ((b + 0x7fffu + ((b >> 16) & 1u)) & 0xffff0000u);
-            r -= __uint_as_float(p[i]);
-        }
-    }
-}
-
-template <bool F16>
-__device__ __forceinline__ f32x4 mma16(const uint4 a, const uint4 b, const f32x4 c) {
-    if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-// acc rows are pre-scaled: [0] i, [1] f, [3] o by -log2(e); [2] g by 2 log2(e); the lane's two units at once
-__device__ __forceinline__ f32x2 exp2_2(const f32x2 v) { return f32x2{__builtin_amdgcn_exp2f(v.x), __builtin_amdgcn_exp2f(v.y)}; }
-__device__ __forceinline__ f32x2 rcp_2(const f32x2 v) { return f32x2{fast_rcp(v.x), fast_rcp(v.y)}; }
-__device__ __forceinline__ f32x2 cell2(const f32x4 acc0, const f32x4 acc1, float &c0, float &c1) {
-    const f32x2 ig = rcp_2(exp2_2(f32x2{acc0[0], acc1[0]}) + 1.0f);
-    const f32x2 fg = rcp_2(exp2_2(f32x2{acc0[1], acc1[1]}) + 1.0f);
-    const f32x2 gr = rcp_2(exp2_2(f32x2{acc0[2], acc1[2]}) + 1.0f);
-    const f32x2 og = rcp_2(exp2_2(f32x2{acc0[3], acc1[3]}) + 1.0f);
-    const f32x2 gg = __builtin_elementwise_fma(f32x2{-2.0f, -2.0f}, gr, f32x2{1.0f, 1.0f});
-    const f32x2 c = __builtin_elementwise_fma(fg, f32x2{c0, c1}, ig * gg);
-    c0 = c.x;
-    c1 = c.y;
-    const f32x2 tr = rcp_2(exp2_2(c * 2.8853900817779268f) + 1.0f);
-    const f32x2 tc = __builtin_elementwise_fma(f32x2{-2.0f, -2.0f}, tr, f32x2{1.0f, 1.0f});
-    return og * tc;
-}
-
 template <int NP, bool F16>
 __global__ __launch_bounds__(512, NP == 2 ? 4 : 2) void lstm_x16s_kernel(LstmXsArgs a) {
-    using P = ProdX<NP>;
+    using P = Prod<NP>;
     // B-operand images per part (8 x 16 bit = 16 B per slot): plane p = 8-channel group (channel / 8) % 4, slot = channel / 32,
     // rows = chunks; 3 slots per row (2 used) keep the 16-lane ds_read_b128 groups on distinct bank slots
     __shared__ uint4 xs[2][NP][4][16][3];
@@ -147,7 +96,7 @@ __global__ __launch_bounds__(512, NP == 2 ? 4 : 2) void lstm_x16s_kernel(LstmXsA
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-                for (int pr = 0; pr < P::N; ++pr) accN[u] = mma16<F16>(Aih[u][ks][P::A[pr]], xs[0][P::B[pr]][q][nn][ks], accN[u]);
+                for (int pr = 0; pr < P::N; ++pr) accN[u] = mfma16<F16>(Aih[u][ks][P::A[pr]], xs[0][P::B[pr]][q][nn][ks], accN[u]);
         }
         RMR_SYNC();  // x_0 read by every wave before step 0 ends with its tile overwritten (k_lstm_x16.hip)
 
@@ -176,7 +125,7 @@ __global__ __launch_bounds__(512, NP == 2 ? 4 : 2) void lstm_x16s_kernel(LstmXsA
 #pragma unroll
                     for (int pr = 0; pr < P::N; ++pr)
 #pragma unroll
-                        for (int u = 0; u < 2; ++u) acc[u] = mma16<F16>(Ahh[u][ks][P::A[pr]], bh[ks][P::B[pr]], acc[u]);
+                        for (int u = 0; u < 2; ++u) acc[u] = mfma16<F16>(Ahh[u][ks][P::A[pr]], bh[ks][P::B[pr]], acc[u]);
             }
             // input projection of the next step (in the last step it projects a stale, finite tile: dropped)
 #pragma unroll
@@ -186,8 +135,8 @@ __global__ __launch_bounds__(512, NP == 2 ? 4 : 2) void lstm_x16s_kernel(LstmXsA
 #pragma unroll
                 for (int pr = 0; pr < P::N; ++pr)
 #pragma unroll
-                    for (int u = 0; u < 2; ++u) accN[u] = mma16<F16>(Aih[u][ks][P::A[pr]], bx[ks][P::B[pr]], accN[u]);
-            const f32x2 hh = cell2(acc[0], acc[1], c[0], c[1]);
+                    for (int u = 0; u < 2; ++u) accN[u] = mfma16<F16>(Aih[u][ks][P::A[pr]], bx[ks][P::B[pr]], accN[u]);
+            const f32x2 hh = lstm_cell2(acc[0], acc[1], c[0], c[1]);
             float h0 = hh.x, h1 = hh.y;
             if constexpr (LAST) {  // lstm2 consumes swish(h1[T-1]) (models/ConvLSTM_w_ref.py:52)
                 h0 = swish_f(h0);
@@ -219,11 +168,11 @@ __global__ __launch_bounds__(512, NP == 2 ? 4 : 2) void lstm_x16s_kernel(LstmXsA
                 for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
                     for (int pr = 0; pr < P::N; ++pr)
-                        acc2[u] = mma16<F16>(a.a_ih2[((((size_t)w * 2 + u) * 2 + ks) * NP + P::A[pr]) * 64 + lane], bh[ks][P::B[pr]], acc2[u]);
+                        acc2[u] = mfma16<F16>(a.a_ih2[((((size_t)w * 2 + u) * 2 + ks) * NP + P::A[pr]) * 64 + lane], bh[ks][P::B[pr]], acc2[u]);
             }
         }
         float c2a = 0.f, c2b = 0.f;
-        const f32x2 h2 = cell2(acc2[0], acc2[1], c2a, c2b);  // c2 = sig(i) tanh(g); h2 = sig(o) tanh(c2)
+        const f32x2 h2 = lstm_cell2(acc2[0], acc2[1], c2a, c2b);  // c2 = sig(i) tanh(g); h2 = sig(o) tanh(c2)
         const float y[2] = {swish_f(h2.x), swish_f(h2.y)};
         // ---- fc: this lane's two hidden units, reduced over q (lanes) then over the 8 waves (LDS) ----
         const int u0 = 8 * w + 2 * q;

@@ -15,17 +15,14 @@
 // k-ordered fmaf chain, so a network padded from 64 to 80 channels returns the 64-channel kernels' bits.
 #include "rmr_internal.h"
 #include "rmr_math.h"
+#include "rmr_mma.h"
 
 namespace rmr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int fdiv(int x, FastDiv d) { return (int)(((float)x + 0.5f) * d.inv); }
 
 // =========================================================================================
 // convolution + folded BatchNorm + swish
 // =========================================================================================
-struct ConvSArgs {
+struct ConvStreamArgs {
     const float *in;
     float *out;
     const float *apack4;  // [oc/16][KW * ic/16 steps][64 lanes][4]: W[16 ot + m][16 g + 4 q + j][tap], step = tap * G + g
@@ -47,7 +44,7 @@ struct ConvSArgs {
 
 // One work item of a wave: output channels 16 ot .. 16 ot + 15 x NTV column tiles (16 columns each) from column tile `tile0`.
 template <int KW, int STRIDE, int NTV>
-__device__ __forceinline__ void conv_stream_item(const ConvSArgs &a, const float *smem, int64_t chunk0, int pbase, int ncols, int ot, int tile0,
+__device__ __forceinline__ void conv_stream_item(const ConvStreamArgs &a, const float *smem, int64_t chunk0, int pbase, int ncols, int ot, int tile0,
                                                  int lane, int q, int nn) {
     const int G = a.ic >> 4, RS = a.rs, S4 = KW * G;
     const f32x4 b4 = *reinterpret_cast<const f32x4 *>(a.bias + 16 * ot + 4 * q);
@@ -105,7 +102,7 @@ __device__ __forceinline__ void conv_stream_item(const ConvSArgs &a, const float
 constexpr int kConvStreamNT = 4;
 
 template <int KW, int STRIDE>
-__global__ __launch_bounds__(512) void conv_stream_kernel(ConvSArgs a) {
+__global__ __launch_bounds__(512) void conv_stream_kernel(ConvStreamArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NT = kConvStreamNT;
     const int tid = threadIdx.x, nthr = blockDim.x;
@@ -200,7 +197,7 @@ static int launch_conv_stream_t(rmr_engine *e, const ConvLayer &c, const float *
     const int plane = ((cb * pin_w * RS) + 63) & ~63;
     const size_t lds = (size_t)plane * 4 * sizeof(float) + 64;  // + trash slot for masked staging writes
     if (lds > 160 * 1024 - 256) RMR_FAIL(RMR_ERR_INVALID, "conv layer %d -> %d channels needs %zu B of LDS", c.ic, c.oc, lds);
-    ConvSArgs a;
+    ConvStreamArgs a;
     a.in = in; a.out = out; a.apack4 = c.apack4; a.bias = c.bias; a.n = n;
     a.ic = c.ic; a.oc = c.oc; a.pin = pin_w; a.pout = pout_w; a.out_row = out_row; a.out_coff = out_coff;
     a.cb = cb; a.plane = plane; a.rs = RS;
@@ -235,7 +232,7 @@ int launch_conv_stream(rmr_engine *e, const ConvLayer &c, const float *in, int i
 // =========================================================================================
 // lstm1 (T steps) + lstm2 (ONE step, see k_lstm.hip) + fc
 // =========================================================================================
-struct LstmSArgs {
+struct LstmStreamArgs {
     const float *x;  // [n][T][H] channel-last merge_conv1 output
     float *logits;   // [n][num_out]
     // a_ih1 / a_hh1: [H/16 waves][H/16 k groups][4 gates][64 lanes][4] (rows pre-scaled, rmr_pack.cpp gate_scale);
@@ -283,7 +280,7 @@ __device__ __forceinline__ void stream_mm(const float *img, int plane, int RS, i
 // One block = H/16 waves x 16 NT chunks.  Wave w owns hidden units 16 w .. 16 w + 15 of all four gates (a cell's i, f, g, o in
 // one lane: the update is lane-local, c never leaves registers), for NT column tiles.
 template <int NT, int MAXT>
-__global__ __launch_bounds__(MAXT) void lstm_stream_kernel(LstmSArgs a) {
+__global__ __launch_bounds__(MAXT) void lstm_stream_kernel(LstmStreamArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H = a.H, G = H >> 4, RS = a.rs, R4 = H >> 2;
     constexpr int ROWS = 16 * NT;
@@ -395,7 +392,7 @@ __global__ __launch_bounds__(MAXT) void lstm_stream_kernel(LstmSArgs a) {
 }
 
 template <int NT, int MAXT>
-static int launch_lstm_stream_t(rmr_model *m, const LstmSArgs &a, int64_t n) {
+static int launch_lstm_stream_t(rmr_model *m, const LstmStreamArgs &a, int64_t n) {
     rmr_engine *e = m->eng;
     const int H = a.H;
     const size_t lds = (size_t)4 * 4 * 16 * NT * a.rs * sizeof(float);
@@ -416,7 +413,7 @@ int launch_lstm_stream(rmr_model *m, const float *x, int64_t n, float *logits) {
     const int H = m->desc.size;
     if (H % 16 || H > 256 || !m->lstm.t_ih1) RMR_FAIL(RMR_ERR_INVALID, "internal: LSTM of %d units not packed for the streamed kernel", H);
     const int G = H / 16;
-    LstmSArgs a;
+    LstmStreamArgs a;
     a.x = x; a.logits = logits; a.n = n; a.T = m->T; a.num_out = m->desc.num_out; a.H = H;
     a.rs = (G % 2 == 0) ? H / 4 + 4 : H / 4;
     a.div_r4 = make_fastdiv(H / 4);

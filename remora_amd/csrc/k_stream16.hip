@@ -18,46 +18,11 @@
 // padded k read finite values (the image is zeroed once, then only ever holds finite activations).
 #include "rmr_internal.h"
 #include "rmr_math.h"
+#include "rmr_mma.h"
 
 namespace rmr {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-__device__ __forceinline__ int fdiv16(int x, FastDiv d) { return (int)(((float)x + 0.5f) * d.inv); }
-
-template <bool F16>
-__device__ __forceinline__ f32x4 mfma16(const uint4 a, const uint4 b, const f32x4 c) {
-    if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-template <bool F16>
-__device__ __forceinline__ uint2 pack4(const float a, const float b, const float c, const float d) {
-    if constexpr (F16) {
-        const f16x4 o = {(_Float16)a, (_Float16)b, (_Float16)c, (_Float16)d};
-        return __builtin_bit_cast(uint2, o);
-    } else {
-        const bf16x4 o = {(__bf16)a, (__bf16)b, (__bf16)c, (__bf16)d};
-        return __builtin_bit_cast(uint2, o);
-    }
-}
-
-// acc rows are pre-scaled: [0] i, [1] f, [3] o by -log2(e); [2] g by 2 log2(e)  (k_lstm_x16.hip lstm_cell)
-__device__ __forceinline__ float cell16(const f32x4 acc, float &c) {
-    const float ig = fast_rcp(1.0f + __builtin_amdgcn_exp2f(acc[0]));
-    const float fg = fast_rcp(1.0f + __builtin_amdgcn_exp2f(acc[1]));
-    const float gg = fmaf(-2.0f, fast_rcp(1.0f + __builtin_amdgcn_exp2f(acc[2])), 1.0f);
-    const float og = fast_rcp(1.0f + __builtin_amdgcn_exp2f(acc[3]));
-    c = fmaf(fg, c, ig * gg);
-    const float tc = fmaf(-2.0f, fast_rcp(1.0f + __builtin_amdgcn_exp2f(c * 2.8853900817779268f)), 1.0f);
-    return og * tc;
-}
 
 // =========================================================================================
 // convolution + folded BatchNorm + swish
@@ -87,7 +52,7 @@ __device__ __forceinline__ void conv16_item(const ConvS16Args &a, const unsigned
         int col = (tile0 + t) * 16 + nn;
         valid[t] = col < ncols;
         col = valid[t] ? col : ncols - 1;
-        ch[t] = fdiv16(col, a.div_pout);
+        ch[t] = fdiv(col, a.div_pout);
         pp[t] = col - ch[t] * a.pout;
         roff[t] = (ch[t] * a.pin + pp[t] * STRIDE) * a.rb;
         acc[t] = b4;
@@ -95,7 +60,7 @@ __device__ __forceinline__ void conv16_item(const ConvS16Args &a, const unsigned
     const uint4 *ap = a.apack + (size_t)ot * a.ks * 64 + lane;
     uint4 A0 = ap[0], A1 = ap[(size_t)(a.ks > 1 ? 1 : 0) * 64];
     auto koff = [&](int s) {  // byte offset of the 8-channel group k0 = 32 s + 8 q inside a column's run of rows
-        const int k0 = 32 * s + 8 * q, tap = fdiv16(k0, a.div_ic);
+        const int k0 = 32 * s + 8 * q, tap = fdiv(k0, a.div_ic);
         return tap * a.rb + (k0 - tap * a.ic) * 2;
     };
     uint4 x[NTV];
@@ -144,7 +109,7 @@ __global__ __launch_bounds__(512) void conv_stream16_kernel(ConvS16Args a) {
         {
             const int total = rows * C8;  // 16-byte pieces of 8 channels
             for (int i = tid; i < total; i += nthr) {
-                const int row = fdiv16(i, a.div_c8), c8 = i - row * C8;
+                const int row = fdiv(i, a.div_c8), c8 = i - row * C8;
                 uint4 v;
                 if constexpr (IN16) {
                     v = reinterpret_cast<const uint4 *>(reinterpret_cast<const uint16_t *>(a.in) + ((size_t)chunk0 * a.pin + row) * a.ic)[c8];
@@ -292,7 +257,7 @@ __global__ __launch_bounds__(MAXT) void lstm_stream16_kernel(LstmS16Args a) {
 #pragma unroll
     for (int u = 0; u < PIECES; ++u) {
         const int i = tid + u * nthr;
-        st_row[u] = fdiv16(i, a.div_c8);
+        st_row[u] = fdiv(i, a.div_c8);
         st_c8[u] = i - st_row[u] * C8;
     }
     f32x4 bias[4];
@@ -335,7 +300,7 @@ __global__ __launch_bounds__(MAXT) void lstm_stream16_kernel(LstmS16Args a) {
                 float h[4];
 #pragma unroll
                 for (int tt = 0; tt < 4; ++tt) {
-                    h[tt] = cell16(acc[tt][c], cst[tt][c]);
+                    h[tt] = lstm_cell(acc[tt][c], cst[tt][c]);
                     if (last) h[tt] = swish_f(h[tt]);  // lstm2 reads swish(h1[T-1]) (models/ConvLSTM_w_ref.py:52-53)
                 }
                 *reinterpret_cast<uint2 *>(hbuf + (size_t)(t & 1) * img + (size_t)(c * 16 + nn) * rb + (16 * w + 4 * q) * 2) = pack4<F16>(h[0], h[1], h[2], h[3]);
@@ -361,7 +326,7 @@ __global__ __launch_bounds__(MAXT) void lstm_stream16_kernel(LstmS16Args a) {
 #pragma unroll
             for (int tt = 0; tt < 4; ++tt) {
                 float c2 = 0.0f;
-                y[c][tt] = swish_f(cell16(acc2[tt][c], c2));
+                y[c][tt] = swish_f(lstm_cell(acc2[tt][c], c2));
             }
         RMR_SYNC();  // every wave has read h1[T-1]: its image becomes `part`
         for (int o = 0; o < a.num_out; ++o) {

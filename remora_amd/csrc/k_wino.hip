@@ -46,10 +46,9 @@
 // Columns are tracked incrementally (row of the group's first position) - one 64-bit division per thread and launch.
 #include "rmr_internal.h"
 #include "rmr_math.h"
+#include "rmr_mma.h"
 
 namespace rmr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct WinoArgs {
     const float *in;

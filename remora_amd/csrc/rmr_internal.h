@@ -68,10 +68,7 @@ struct rmr_engine {
     int device = 0;
     hipStream_t stream = nullptr;
     bool owns_stream = false;
-    // second stream + events for the two-stage sub-batch pipeline (front kernels of sub-batch
-    // i+1 run under the matrix kernels of sub-batch i)
-    hipStream_t aux = nullptr;
-    hipEvent_t ev_in = nullptr, ev_front[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
+    hipStream_t aux = nullptr;  // upload stream of rmr_infer_chunks (the pinned slots and ev_h2d below)
     hipEvent_t ev_handoff = nullptr;  // rmr_engine_wait_for: recorded on this engine's stream, waited for by another's
     int num_cus = 256;
     std::mutex mu;
@@ -127,7 +124,7 @@ namespace rmr {
 // registers of every CU with 0xFFFFFFFF (NaN as fp32 / bf16 / half, -1 as an integer).  LDS and registers keep what the
 // previous workgroup left; a kernel that reads a word it never wrote normally finds the leftovers of its own kind (often
 // the very values it would have written) and only fails next to OTHER kernels - e.g. another process's on the same GPU.
-// With the poison such a read shows up in a single process: tests/test_gpu_poison.py.
+// With the poison such a read shows up in a single process: tools/poison_check.py.
 void poison_before_launch(rmr_engine *e, hipStream_t s);
 }  // namespace rmr
 

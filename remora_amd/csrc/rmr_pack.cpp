@@ -158,7 +158,7 @@ static inline uint32_t f2u(float x) { uint32_t u; memcpy(&u, &x, 4); return u; }
 static inline float u2f(uint32_t u) { float x; memcpy(&x, &u, 4); return x; }
 static inline uint32_t rne_bf16(uint32_t b) { return (b + 0x7fffu + ((b >> 16) & 1u)) & 0xffff0000u; }
 static inline uint32_t half_hi(_Float16 h) { uint16_t b; memcpy(&b, &h, 2); return (uint32_t)b << 16; }
-// One fp32 value as np 16-bit operand parts, each in the HIGH half of its word (host twin of split_parts in k_lstm_bf16s.hip).
+// One fp32 value as np 16-bit operand parts, each in the HIGH half of its word (host twin of the device split16 in rmr_mma.h).
 // bf16: the parts before the last truncated, each taking what the previous ones left of x; the last rounded to nearest even
 // (np = 1, 2) or truncated (np = 3).  f16: hi = half(x) (round to nearest even; the compiler's conversion), np = 2 adds
 // lo = half(x - hi) (dtype f16x3).
