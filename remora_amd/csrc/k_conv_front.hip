@@ -1003,10 +1003,11 @@ int launch_sig3_front_mfma(rmr_model *m, const float *signal, int64_t n, float *
 }
 
 // sig_conv3 (+ sig_conv1/2) and seq_conv2 (+ seq_conv1) of `n` chunks into the two halves of cat [n][P3][128]
-int launch_conv_front(rmr_model *m, const float *signal, const int8_t *seqs, int seq_w, const int16_t *maps, int map_w,
-                      const int16_t *lens, int64_t n, float *cat, const FwdSwitches &sw) {
+int launch_conv_front(rmr_model *m, const ChunkArrays &c, int64_t n, float *cat, const FwdSwitches &sw) {
     rmr_engine *e = m->eng;
     if (n <= 0) return 0;
+    const float *signal = c.signal;
+    const int seq_w = c.seq_w, map_w = c.map_w;
     const int sz = m->desc.size, K = m->desc.kmer_len;
     // The matrix-core producer is the default since round 4: bit-identical to the VALU one, 5.39 against 5.47 ns per chunk at
     // C100 (12.57 against 12.03 at C200), and it is the one that stayed exact next to foreign processes on the same GPU in
@@ -1035,7 +1036,7 @@ int launch_conv_front(rmr_model *m, const float *signal, const int8_t *seqs, int
     const FrontPlan p = plan_seq2_front(m->L, m->P1, m->P3, K, seq_w, map_w, n, e->num_cus, wino);
     if (!p.ok) RMR_FAIL(RMR_ERR_INVALID, "seq2_front: max_seq_len %d needs %zu B of LDS", map_w - 1, p.lds);
     ConvFrontArgs a{};
-    a.seqs = seqs; a.maps = maps; a.lens = lens; a.wt5 = m->front.wt5_seq1; a.b_seq1 = m->front.b_seq1;
+    a.seqs = c.seqs; a.maps = c.maps; a.lens = c.lens; a.wt5 = m->front.wt5_seq1; a.b_seq1 = m->front.b_seq1;
     a.L = m->L; a.P1 = m->P1; a.seq_w = seq_w; a.map_w = map_w; a.K = K; a.maxlen = map_w - 1;
     a.out = cat; a.apack = m->seq2.apack; a.bias = m->seq2.bias; a.n = n;
     a.pin = m->P1; a.pout = m->P3; a.out_row = 2 * sz; a.out_coff = sz; a.div_pout = make_fastdiv(m->P3);

@@ -356,17 +356,16 @@ __global__ __launch_bounds__(512, 4) void front_seq_tap_kernel(FrontSeqArgs a) {
     }
 }
 
-int launch_front(rmr_model *m, hipStream_t st, const float *signal, const int8_t *seqs, int seq_w,
-                 const int16_t *maps, int map_w, const int16_t *lens, int kb, int ka, int64_t n,
-                 float *sig2, float *seq1) {
+int launch_front(rmr_model *m, hipStream_t st, const ChunkArrays &c, int64_t n, float *sig2, float *seq1) {
     rmr_engine *e = m->eng;
     if (n <= 0) return 0;
+    const int seq_w = c.seq_w, map_w = c.map_w, kb = c.kb, ka = c.ka;
     const int K = m->desc.kmer_len;
     const int kw = m->front.kw1;
     if (kw != 5 && kw != 11) RMR_FAIL(RMR_ERR_INVALID, "front kernel width %d unsupported", kw);
     if (sig2) {   // ---- signal branch (skipped when the caller folds it into sig_conv3: launch_sig3_front_mfma) ----
         FrontSigArgs a;
-        a.signal = signal; a.w_sig1 = m->front.w_sig1; a.b_sig1 = m->front.b_sig1;
+        a.signal = c.signal; a.w_sig1 = m->front.w_sig1; a.b_sig1 = m->front.b_sig1;
         a.w_sig2 = m->front.w_sig2; a.b_sig2 = m->front.b_sig2; a.sig2 = sig2; a.n = n;
         a.L = m->L; a.P1 = m->P1; a.P2 = m->P2; a.cb = 8;
         const int Lp = (m->L + 3) & ~3;
@@ -383,7 +382,7 @@ int launch_front(rmr_model *m, hipStream_t st, const float *signal, const int8_t
     if (kb + ka + 1 != K) RMR_FAIL(RMR_ERR_INVALID, "kmer context (%d,%d) != model kmer_len %d", kb, ka, K);
     if (K > 21) RMR_FAIL(RMR_ERR_INVALID, "kmer_len %d > 21 not supported by the fused encode", K);
     FrontSeqArgs a;
-    a.seqs = seqs; a.maps = maps; a.lens = lens; a.wt5 = m->front.wt5_seq1; a.b_seq1 = m->front.b_seq1;
+    a.seqs = c.seqs; a.maps = c.maps; a.lens = c.lens; a.wt5 = m->front.wt5_seq1; a.b_seq1 = m->front.b_seq1;
     a.seq1 = seq1; a.n = n; a.L = m->L; a.seq_w = seq_w; a.map_w = map_w; a.K = K; a.P1 = m->P1;
     a.maxlen = map_w - 1;
     if (seq_w < a.maxlen + K - 1) RMR_FAIL(RMR_ERR_INVALID, "sequence width %d too small for mapping width %d", seq_w, map_w);

@@ -729,12 +729,12 @@ bool fused_front_supported(const rmr_model *m, int seq_w, int map_w) {
     return fused_front_plan(m, seq_w, map_w, probe, total) >= 1 || fused_front_plan(m, seq_w, map_w, probe, total, FUSED_WINDOW_L) >= 1;
 }
 
-int launch_fused_front(rmr_model *m, const float *signal, const int8_t *seqs, int seq_w, const int16_t *maps, int map_w,
-                       const int16_t *lens, int64_t n, uint16_t *x) {
+int launch_fused_front(rmr_model *m, const ChunkArrays &c, int64_t n, uint16_t *x) {
     rmr_engine *e = m->eng;
     if (n <= 0) return 0;
+    const int seq_w = c.seq_w, map_w = c.map_w;
     FusedArgs a;
-    a.signal = signal; a.seqs = seqs; a.maps = maps; a.lens = lens;
+    a.signal = c.signal; a.seqs = c.seqs; a.maps = c.maps; a.lens = c.lens;
     a.a_sig2 = reinterpret_cast<const uint4 *>(m->fused.a_sig2); a.a_seq1 = reinterpret_cast<const uint4 *>(m->fused.a_seq1);
     a.a_sig3 = reinterpret_cast<const uint4 *>(m->fused.a_sig3); a.a_seq2 = reinterpret_cast<const uint4 *>(m->fused.a_seq2);
     a.a_merge1 = reinterpret_cast<const uint4 *>(m->fused.a_merge1);

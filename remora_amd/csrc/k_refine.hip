@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "rmr_internal.h"
+#include "rmr_stage.h"
 
 struct rmr_refiner {
     rmr_engine *e = nullptr;
@@ -1033,8 +1034,6 @@ int rmr_refine_signal_maps(rmr_refiner *rf, int64_t n_reads, const int16_t *dacs
     Bump st;
     st.base = reinterpret_cast<char *>(e->staging.ptr);
     RefineReads dr{dacs, sig_off, seq_to_sig, seq_off, int_seq, shift, scale};
-#define RMR_H2D(dst, src, b) RMR_HIP(hipMemcpyAsync((dst), (src), (b), hipMemcpyHostToDevice, e->stream))
-#define RMR_D2H(dst, src, b) RMR_HIP(hipMemcpyAsync((dst), (src), (b), hipMemcpyDeviceToHost, e->stream))
     if (mem == RMR_MEM_HOST) {
         auto *d_dacs = st.take<int16_t>(ts + 1);
         auto *d_so = st.take<int64_t>(n1);
@@ -1043,13 +1042,13 @@ int rmr_refine_signal_maps(rmr_refiner *rf, int64_t n_reads, const int16_t *dacs
         auto *d_qo = st.take<int64_t>(n1);
         auto *d_sh = st.take<double>(n1);
         auto *d_sc = st.take<double>(n1);
-        if (ts) RMR_H2D(d_dacs, dacs, (size_t)ts * 2);
-        RMR_H2D(d_so, sig_off, n1 * 8);
-        RMR_H2D(d_map, seq_to_sig, (size_t)(tb + n_reads) * 8);
-        if (tb) RMR_H2D(d_seq, int_seq, (size_t)tb);
-        RMR_H2D(d_qo, seq_off, n1 * 8);
-        RMR_H2D(d_sh, shift, (size_t)n_reads * 8);
-        RMR_H2D(d_sc, scale, (size_t)n_reads * 8);
+        H2D(d_dacs, dacs, (size_t)ts * 2);
+        H2D(d_so, sig_off, n1 * 8);
+        H2D(d_map, seq_to_sig, (size_t)(tb + n_reads) * 8);
+        H2D(d_seq, int_seq, (size_t)tb);
+        H2D(d_qo, seq_off, n1 * 8);
+        H2D(d_sh, shift, (size_t)n_reads * 8);
+        H2D(d_sc, scale, (size_t)n_reads * 8);
         dr = RefineReads{d_dacs, d_so, d_map, d_qo, d_seq, d_sh, d_sc};
     }
     RefineScratch w{};
@@ -1073,9 +1072,9 @@ int rmr_refine_signal_maps(rmr_refiner *rf, int64_t n_reads, const int16_t *dacs
     }
     std::vector<int64_t> band_len(n_reads);
     std::vector<int32_t> hstat(n_reads), maxwin(n_reads);
-    RMR_D2H(band_len.data(), w.band_len, (size_t)n_reads * 8);
-    RMR_D2H(hstat.data(), w.status, (size_t)n_reads * 4);
-    RMR_D2H(maxwin.data(), w.maxwin, (size_t)n_reads * 4);
+    D2H(band_len.data(), w.band_len, (size_t)n_reads * 8);
+    D2H(hstat.data(), w.status, (size_t)n_reads * 4);
+    D2H(maxwin.data(), w.maxwin, (size_t)n_reads * 4);
     RMR_HIP(hipStreamSynchronize(e->stream));
 
     const bool force_rowwise = tune_int("RMR_REFINE_ROWWISE", 0) != 0 || rf->sd_len > kMaxD;
@@ -1114,8 +1113,8 @@ int rmr_refine_signal_maps(rmr_refiner *rf, int64_t n_reads, const int16_t *dacs
             }
             RMR_TRY(e->ensure(e->act, (size_t)cells * 2 + 256));
             w.tb = reinterpret_cast<int16_t *>(e->act.ptr);
-            RMR_H2D(d_todo, lst.data(), lst.size() * 4);
-            RMR_H2D(d_scb, slot_base.data(), slot_base.size() * 8);
+            H2D(d_todo, lst.data(), lst.size() * 4);
+            H2D(d_scb, slot_base.data(), slot_base.size() * 8);
             if (pass == 0) {
                 if (rf->algo == RMR_REFINE_VITERBI) RMR_TRY((launch_dp<16, 0>(rf, dr, w, d_todo, (int)lst.size(), grid, d_scb, d_out)));
                 else RMR_TRY((launch_dp<16, 1>(rf, dr, w, d_todo, (int)lst.size(), grid, d_scb, d_out)));
@@ -1125,7 +1124,7 @@ int rmr_refine_signal_maps(rmr_refiner *rf, int64_t n_reads, const int16_t *dacs
             }
             RMR_HIP(hipStreamSynchronize(e->stream));  // host lists and the arena are reused by the next pass
         }
-        RMR_D2H(hstat.data(), w.status, (size_t)n_reads * 4);
+        D2H(hstat.data(), w.status, (size_t)n_reads * 4);
         RMR_HIP(hipStreamSynchronize(e->stream));
         for (int64_t r = 0; r < n_reads; ++r)
             if ((maxwin[r] > 64 || band_len[r] >= ((int64_t)1 << 31)) && hstat[r] == 0) hstat[r] = -1;  // not for the column kernel
@@ -1163,14 +1162,12 @@ int rmr_refine_signal_maps(rmr_refiner *rf, int64_t n_reads, const int16_t *dacs
         }
     }
     if (mem == RMR_MEM_HOST) {
-        RMR_D2H(out_map, d_out, (size_t)(tb + n_reads) * 8);
+        D2H(out_map, d_out, (size_t)(tb + n_reads) * 8);
         memcpy(status, hstat.data(), (size_t)n_reads * 4);
     } else {
-        RMR_H2D(status, hstat.data(), (size_t)n_reads * 4);
+        H2D(status, hstat.data(), (size_t)n_reads * 4);
     }
     RMR_HIP(hipStreamSynchronize(e->stream));
-#undef RMR_H2D
-#undef RMR_D2H
     return 0;
 }
 

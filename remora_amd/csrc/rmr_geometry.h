@@ -1,6 +1,6 @@
 // Geometry of one chunk - RemoraRead.iter_chunks + the index arithmetic of extract_chunk
 // (src/remora/data_chunks.py:443-453, :341-373) - as ONE function for the device (geometry_kernel, k_data.hip: a thread per
-// chunk of a batch) and the host (rmr_call_read, engine.hip: the chunks of a single read, computed while its arrays cross
+// chunk of a batch) and the host (rmr_call_read, api_forward.hip: the chunks of a single read, computed while its arrays cross
 // PCIe, so that the call needs no stream synchronisation between extraction and network).  Integer arithmetic only: the two
 // sides cannot differ.
 #pragma once

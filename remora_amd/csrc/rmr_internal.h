@@ -120,6 +120,7 @@ struct rmr_engine {
 };
 
 namespace rmr {
+void rccl_comm_free(void *comm);  // comm.cpp: rmr_engine_destroy drops the communicator of rmr_comm_init through it
 // Diagnostics (RMR_POISON=1): in front of EVERY kernel launch of the library a kernel fills the LDS and most of the vector
 // registers of every CU with 0xFFFFFFFF (NaN as fp32 / bf16 / half, -1 as an integer).  LDS and registers keep what the
 // previous workgroup left; a kernel that reads a word it never wrote normally finds the leftovers of its own kind (often
@@ -188,12 +189,24 @@ int launch_motif_focus(rmr_engine *e, const int8_t *seq, const int64_t *seq_off,
 int launch_motif(rmr_engine *e, const int8_t *seq, const int64_t *seq_off, int n_reads, int64_t total,
                  const rmr_motif_set &ms, uint8_t *flags);
 
+// the inputs of a forward call as the front kernels read them: the signal and either a dense one-hot tensor or the chunk arrays
+struct ChunkArrays {
+    const float *signal;  // [n][L]
+    const float *enc;     // [n][EC][L], or nullptr: the k-mers are gathered from (seqs, maps, lens)
+    const int8_t *seqs;  int seq_w;  // [n][seq_w]
+    const int16_t *maps; int map_w;  // [n][map_w]
+    const int16_t *lens; int kb, ka;  // [n]
+    // the same arrays from chunk c0 on
+    ChunkArrays at(int64_t c0, int L, int EC) const {
+        if (enc) return ChunkArrays{signal + (size_t)c0 * L, enc + (size_t)c0 * EC * L, nullptr, 0, nullptr, 0, nullptr, 0, 0};
+        return ChunkArrays{signal + (size_t)c0 * L, nullptr, seqs + (size_t)c0 * seq_w, seq_w, maps + (size_t)c0 * map_w, map_w, lens + c0, kb, ka};
+    }
+};
+
 // fused pipeline stages; all tensors channel-last in device scratch
-int launch_front(rmr_model *m, hipStream_t st, const float *signal, const int8_t *seqs, int seq_w,
-                 const int16_t *maps, int map_w, const int16_t *lens, int kb, int ka, int64_t n,
-                 float *sig2, float *seq1 /* nullptr: skip seq path */);
+int launch_front(rmr_model *m, hipStream_t st, const ChunkArrays &c, int64_t n, float *sig2, float *seq1 /* nullptr: skip seq path */);
 int launch_seq1_dense(rmr_model *m, const float *enc, int64_t n, float *seq1);
-// the kernel switches of the fp32 path: read from the environment once per forward call (run_pipeline) and passed
+// the kernel switches of the fp32 path: read from the environment once per forward call (run_pipeline, api_forward.hip) and passed
 // down, so that a change between two calls on the same model takes effect
 struct FwdSwitches {
     bool fused;       // RMR_FUSED
@@ -206,8 +219,7 @@ bool conv_front_supported(const rmr_model *m, int kb, int ka, int seq_w, int map
 // the signal half alone with sig_conv2 on the matrix cores (both architectures, 5 or 11 taps): signal -> cat channels [0, 64)
 bool sig3_front_mfma_supported(const rmr_model *m);
 int launch_sig3_front_mfma(rmr_model *m, const float *signal, int64_t n, float *cat, bool winograd);
-int launch_conv_front(rmr_model *m, const float *signal, const int8_t *seqs, int seq_w, const int16_t *maps, int map_w,
-                      const int16_t *lens, int64_t n, float *cat, const FwdSwitches &sw);
+int launch_conv_front(rmr_model *m, const ChunkArrays &c, int64_t n, float *cat, const FwdSwitches &sw);
 int launch_conv(rmr_engine *e, const ConvLayer &c, const float *in, int in_row, int pin,
                 float *out, int out_row, int out_coff, int pout, int64_t n, bool winograd);
 int launch_lstm_head(rmr_model *m, const float *x, int64_t n, float *logits);
@@ -233,8 +245,7 @@ int launch_conv_split(rmr_engine *e, const ConvLayer &c, int np, const float *in
 int launch_fc_head(rmr_model *m, const float *m4, int64_t n, float *logits);
 // fused bf16 front (k_fused.hip): chunk arrays -> x bf16[n][T][64];  lstm on that tensor (k_lstm_bf16s.hip)
 bool fused_front_supported(const rmr_model *m, int seq_w, int map_w);
-int launch_fused_front(rmr_model *m, const float *signal, const int8_t *seqs, int seq_w, const int16_t *maps, int map_w,
-                       const int16_t *lens, int64_t n, uint16_t *x);
+int launch_fused_front(rmr_model *m, const ChunkArrays &c, int64_t n, uint16_t *x);
 bool lstm_x16s_supported(const rmr_model *m);
 int launch_lstm_head_x16s(rmr_model *m, const float *x, int64_t n, float *logits);
 int launch_lstm_head_x16(rmr_model *m, const uint16_t *x, int64_t n, float *logits);

@@ -1,6 +1,6 @@
 // The weights of a model as the kernels read them: the canonical blob (include/remora_hip.h, rmr_model_create) parsed,
 // BatchNorm folded, and every layer packed into the fragment layouts of its kernels.  Plain C++, no HIP: pack_model hands
-// each finished host buffer to an `upload` callback - engine.hip copies it to the device, tests/c/model_packs.cpp digests
+// each finished host buffer to an `upload` callback - api_forward.hip copies it to the device, tests/c/model_packs.cpp digests
 // it on the CPU.  rmr_pack.cpp holds the code.
 #pragma once
 #include <cstddef>

@@ -1203,7 +1203,7 @@ def test_real_reads_reference_anchored(torch_cuda, O, tmp_path, prefix, n_chunks
 
 
 def test_motif_scan_kernel_vs_host(torch_cuda):
-    """rmr_motif_flags (through DeviceReads.motif_focus_bases) against Motif.findall on every read: IUPAC
+    """rmr_motif_focus_counts / rmr_motif_focus_fill (through DeviceReads.motif_focus_bases) against Motif.findall on every read: IUPAC
     codes, several motifs, N bases in the reads, a focus position left of the motif after N-stripping, reads
     shorter than the motif, and no hit may straddle two reads."""
     from remora_amd.data_chunks import DeviceReads, RemoraRead
@@ -1810,3 +1810,179 @@ def test_device_reads_mapping_crosses_pcie_as_int32_and_arrives_as_int64(torch_c
     monkeypatch.setenv("RMR_READS_NARROW_MAPS", "0")
     reads = batch()
     check(DeviceReads(reads), reads)
+
+
+# ---- rmr_call_read against the exact-size route, and host-memory calls against device-memory calls -------------------------
+def _zero_dwell_read(run_end):
+    """One read of 400 bases: bases 80 .. run_end - 1 share a single signal position (zero dwell), every other base has one to
+    three samples."""
+    rng = np.random.default_rng(5)
+    dwell = rng.integers(1, 4, 400)
+    dwell[80:run_end] = 0
+    s2s = np.concatenate([[0], np.cumsum(dwell)]).astype(np.int64)
+    dacs = rng.integers(300, 700, int(s2s[-1])).astype(np.int16)
+    return dacs, s2s, rng.integers(0, 4, 400).astype(np.int8)
+
+
+def _extract_and_infer(torch, model, reads, focus_per_read, kcb, mem):
+    """rmr_chunk_geometry -> rmr_chunk_fill -> rmr_infer_chunks through the ctypes binding, every array in host memory
+    (RMR_MEM_HOST) or every array in device memory: (sig, geo, max_seq_len, signal, seqs, maps, lens, read_focus_bases, logits,
+    label counts) as numpy arrays.  The row widths are the ones rmr_call_read derives: msl + kb + ka and msl + 1."""
+    import ctypes
+
+    from remora_amd import _lib as L
+
+    lib, eng, (kb, ka), Lc, no = L.lib(), model.engine, kcb, model.chunk_len, model.num_out
+    cat = lambda parts, dt: np.ascontiguousarray(np.concatenate([np.asarray(p, dt).ravel() for p in parts]))  # noqa: E731
+    off = lambda sizes: np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)  # noqa: E731
+    host = dict(dacs=cat([r[0] for r in reads], np.int16), sig_off=off([r[0].size for r in reads]), s2s=cat([r[1] for r in reads], np.int64),
+                seq=cat([r[2] for r in reads], np.int8), seq_off=off([r[2].size for r in reads]), shift=np.full(len(reads), 500.0),
+                scale=np.full(len(reads), 100.0), focus=cat(focus_per_read, np.int64), foc_off=off([len(f) for f in focus_per_read]))
+    ts, nc = int(host["sig_off"][-1]), int(host["foc_off"][-1])
+    keep = []
+
+    def buf(a):  # an input where `mem` says (device arrays with a tail the kernels' vector loads may run into)
+        if mem == L.MEM_HOST:
+            keep.append(a)
+            return a.ctypes.data
+        keep.append(torch.from_numpy(np.concatenate([a, np.zeros(16, a.dtype)])).cuda())
+        return keep[-1].data_ptr()
+
+    def out(shape, dt):
+        if mem == L.MEM_HOST:
+            a = np.zeros(shape, dt)
+            return a, a.ctypes.data
+        t = torch.zeros(shape, dtype=getattr(torch, np.dtype(dt).name), device="cuda")
+        return t, t.data_ptr()
+
+    def fetch(a):
+        return a if mem == L.MEM_HOST else a.cpu().numpy()
+
+    rs = L.Reads(len(reads), *(buf(host[k]) for k in ("dacs", "sig_off", "s2s", "seq", "seq_off", "shift", "scale", "focus", "foc_off")),
+                 Lc // 2, Lc - Lc // 2, kb, ka, 0, 0)
+    (sig, p_sig), (geo, p_geo), msl = out(ts, np.float32), out((nc, 6), np.int64), ctypes.c_int64(0)
+    L.check(lib.rmr_chunk_geometry(eng.handle, ctypes.byref(rs), p_sig, p_geo, ctypes.byref(msl), mem))
+    seq_w, map_w = int(msl.value) + kb + ka, int(msl.value) + 1
+    (signal, p_signal), (seqs, p_seqs), (maps, p_maps) = out((nc, Lc), np.float32), out((nc, seq_w), np.int8), out((nc, map_w), np.int16)
+    (lens, p_lens), (rfb, p_rfb), (logits, p_log), (counts, p_cnt) = out(nc, np.int16), out(nc, np.int64), out((nc, no), np.float32), out(no, np.int64)
+    L.check(lib.rmr_chunk_fill(eng.handle, ctypes.byref(rs), p_sig, p_geo, p_signal, p_seqs, seq_w, p_maps, map_w, p_lens, p_rfb, mem))
+    L.check(lib.rmr_infer_chunks(model._h, p_signal, p_seqs, seq_w, p_maps, map_w, p_lens, kb, ka, nc, p_log, p_cnt, mem))
+    eng.synchronize()
+    return [fetch(a) for a in (sig, geo)] + [int(msl.value)] + [fetch(a) for a in (signal, seqs, maps, lens, rfb, logits, counts)]
+
+
+@pytest.mark.parametrize("run_end,focus,restart", [(340, (150, 200, 250), True), (100, (85, 90, 95), False)])
+def test_call_read_with_chunks_wider_than_planned_equals_the_exact_size_route(torch_cuda, O, run_end, focus, restart):
+    """rmr_call_read plans its staging for rows of min(n_bases + 1, 2 L + 8) = 208 bases before it knows the chunks; a run of
+    zero-dwell bases puts more than that into a chunk of L = 100 samples, and the call plans again with the exact width.  Logits
+    and read_focus_bases equal, bit for bit, those of rmr_chunk_geometry -> rmr_chunk_fill -> rmr_infer_chunks at the widths
+    rmr_call_read derives - with the restart (run of 260 bases) and without (run of 20)."""
+    import ctypes
+
+    from remora_amd import _lib as L
+
+    g = golden("model_convlstm_s64_l100_o2.npz")
+    model, _, kcb = _model_from_golden(g, O)
+    assert model.chunk_len == 100 and model.dtype == "fp32"
+    dacs, s2s, seq = _zero_dwell_read(run_end)
+    foc = np.array(focus, np.int64)
+    want = _extract_and_infer(torch_cuda, model, [(dacs, s2s, seq)], [foc], kcb, L.MEM_HOST)
+    msl, want_rfb, want_logits = want[2], want[7], want[8]
+    assert (msl > 208) == restart, msl
+    rd = L.Read(dacs.ctypes.data, dacs.size, s2s.ctypes.data, seq.ctypes.data, 1, 0, seq.size, 500.0, 100.0, foc.ctypes.data, foc.size,
+                50, 50, kcb[0], kcb[1], 0, 0)
+    for _ in range(2):  # the second call finds the arena the first one left
+        logits, rfb = np.zeros((foc.size, model.num_out), np.float32), np.full(foc.size, -1, np.int64)
+        L.check(L.lib().rmr_call_read(model._h, ctypes.byref(rd), logits.ctypes.data, rfb.ctypes.data))
+        assert np.array_equal(rfb, want_rfb)
+        assert np.array_equal(logits.view(np.uint32), want_logits.view(np.uint32))
+    assert np.isfinite(want_logits).all() and np.abs(want_logits).max() > 0
+
+
+def test_chunk_extraction_and_inference_from_host_memory_equal_device_memory(torch_cuda, O):
+    """rmr_chunk_geometry, rmr_chunk_fill and rmr_infer_chunks (with label counts) on 3 reads / 7 chunks: every staged array of the
+    RMR_MEM_HOST calls is non-empty, and every output equals the RMR_MEM_DEVICE call's bit for bit."""
+    from remora_amd import _lib as L
+
+    g = golden("model_convlstm_s64_l100_o2.npz")
+    model, _, kcb = _model_from_golden(g, O)
+    reads = [_zero_dwell_read(100), _zero_dwell_read(80), _zero_dwell_read(340)]
+    focus = [(60, 90, 300), (200, 210), (10, 390)]
+    host = _extract_and_infer(torch_cuda, model, reads, focus, kcb, L.MEM_HOST)
+    dev = _extract_and_infer(torch_cuda, model, reads, focus, kcb, L.MEM_DEVICE)
+    assert host[2] == dev[2] > 0 and host[9].sum() == 7
+    for h, d in zip(host, dev):
+        if not isinstance(h, int):
+            assert h.shape == d.shape and h.tobytes() == d.tobytes()
+
+
+@pytest.mark.parametrize("call", ["forward", "encode_kmers", "trim_chunk_context", "count_labels", "motif_flags"])
+def test_host_memory_calls_equal_device_memory_calls(torch_cuda, O, call):
+    """The RMR_MEM_HOST form of a call stages its arrays, runs the RMR_MEM_DEVICE form's kernels and copies back: same bits."""
+    import ctypes
+
+    from remora_amd import _lib as L
+    from remora_amd.engine import get_engine
+
+    torch, lib = torch_cuda, L.lib()
+    g = golden("model_convlstm_s64_l100_o2.npz")
+    n = 5
+    seqs, maps, lens = (np.ascontiguousarray(g[k][:n]) for k in ("seqs", "maps", "lens"))
+    assert seqs.dtype == np.int8 and maps.dtype == np.int16 and lens.dtype == np.int16
+
+    def both(fn, ins, outs):
+        """fn(pointers of ins + outs, mem) with numpy arrays and with CUDA tensors: the outputs (and in-place inputs) of each"""
+        res = []
+        for mem in (L.MEM_HOST, L.MEM_DEVICE):
+            arrs = [a.copy() for a in ins + outs]
+            if mem == L.MEM_DEVICE:
+                arrs = [torch.from_numpy(a).cuda() for a in arrs]
+            fn(*[a.ctypes.data if mem == L.MEM_HOST else a.data_ptr() for a in arrs], mem)
+            get_engine(0).synchronize()
+            res.append([a if mem == L.MEM_HOST else a.cpu().numpy() for a in arrs])
+        for h, d in zip(*res):
+            assert h.tobytes() == d.tobytes()
+        return res[0]
+
+    eng = get_engine(0).handle
+    if call == "forward":
+        model, _, (kb, ka) = _model_from_golden(g, O)
+        enc = np.ascontiguousarray(O.compute_encoded_kmer_batch(kb, ka, seqs, maps, lens), np.float32)
+        sigs = np.ascontiguousarray(g["sigs"][:n], np.float32)
+        res = both(lambda s, q, o, mem: L.check(lib.rmr_forward(model._h, s, q, n, o, mem)), [sigs, enc], [np.zeros((n, 2), np.float32)])
+        assert np.abs(res[2] - g["logits"][:n]).max() <= 1e-4
+    elif call == "encode_kmers":
+        res = both(lambda s, m, l, o, mem: L.check(lib.rmr_encode_kmers(eng, 4, 4, s, seqs.shape[1], m, maps.shape[1], l, n, 100, o, mem)),
+                   [seqs, maps, lens], [np.zeros((n, 36, 100), np.float32)])
+        assert np.array_equal(res[3], O.compute_encoded_kmer_batch(4, 4, seqs, maps, lens))
+    elif call == "trim_chunk_context":
+        t = golden("trim_chunk_context.npz")
+        a = [int(x) for x in t["c0_args"]]  # stored context, new context, the samples to keep: test_trim_golden
+        tin = [np.ascontiguousarray(t["c0_in_seqs"], np.int8), (t["c0_in_maps"] - (a[0] - a[2])).astype(np.int16), np.ascontiguousarray(t["c0_in_lens"], np.int16)]
+        res = both(lambda s, m, l, mem: L.check(lib.rmr_trim_chunk_context(eng, *a, s, tin[0].shape[1], m, tin[1].shape[1], l, tin[2].size, mem)), tin, [])
+        assert all(np.array_equal(r, t[f"c0_out_{k}"]) for r, k in zip(res, ("seqs", "maps", "lens")))
+    elif call == "motif_flags":  # 3 reads with some N bases, two motifs: the flags of both calls, and Motif.findall's hits
+        from remora_amd.util import Motif
+
+        rng = np.random.default_rng(3)
+        reads = [rng.integers(0, 4, k).astype(np.int8) for k in (700, 3, 4500)]
+        reads[2][rng.integers(0, 4500, 60)] = -1
+        motifs, ms = [Motif("DRACH", 2), Motif("CG", 1)], L.MotifSet()
+        ms.n_motifs = len(motifs)
+        for m, mot in enumerate(motifs):  # as DeviceReads.motif_focus_bases fills it
+            ms.len[m], ms.focus_pos[m] = len(mot.raw_motif), int(mot.focus_pos)
+            for k, allowed in enumerate(mot.int_pattern):
+                ms.mask[m][k] = int(sum(1 << int(b) for b in allowed))
+        seq, off = np.concatenate(reads), np.concatenate([[0], np.cumsum([r.size for r in reads])]).astype(np.int64)
+        res = both(lambda s, o, f, mem: L.check(lib.rmr_motif_flags(eng, s, o, len(reads), ctypes.byref(ms), f, mem)), [seq, off],
+                   [np.zeros(seq.size, np.uint8)])
+        want = np.zeros(seq.size, np.uint8)
+        for r, o in zip(reads, off):
+            for mot in motifs:
+                fb = np.array([int(st) + mot.focus_pos for st in mot.findall(r.astype(np.int64))], np.int64)
+                want[o + fb[(fb >= 0) & (fb < r.size)]] = 1
+        assert 0 < want.sum() < seq.size and np.array_equal(res[2], want)
+    else:
+        logits = np.ascontiguousarray(g["logits"][:n], np.float32)
+        res = both(lambda x, c, mem: L.check(lib.rmr_count_labels(eng, x, n, 2, c, mem)), [logits], [np.array([3, 4], np.int64)])
+        assert np.array_equal(res[1], np.array([3, 4]) + np.bincount(logits.argmax(1), minlength=2))

@@ -50,7 +50,7 @@ def _product_env_names():
                 txt = open(os.path.join(dp, f)).read()
                 every |= set(re.findall(r'"((?:RMR|REMORA)_[A-Z0-9_]+)"', txt))
                 abl |= set(re.findall(r'abl_int\("((?:RMR|REMORA)_[A-Z0-9_]+)"', txt))
-    abl |= {"RMR_DUMP_CAT", "RMR_FUSED_DUMP_X"}  # getenv under #ifdef RMR_TIMING_ABLATIONS (engine.hip)
+    abl |= {"RMR_DUMP_CAT", "RMR_FUSED_DUMP_X"}  # getenv under #ifdef RMR_TIMING_ABLATIONS (api_forward.hip)
     return every, abl
 
 
@@ -65,7 +65,7 @@ def test_every_environment_switch_is_in_the_design_table_and_there_are_few():
     listed = set(re.findall(r"`((?:RMR|REMORA)_[A-Z0-9_]+)`", table))
     assert listed == every, (sorted(every - listed), sorted(listed - every))
     assert len(every - abl) <= 38, sorted(every - abl)
-    eng = open(os.path.join(ROOT, "remora_amd", "csrc", "engine.hip")).read()
+    eng = open(os.path.join(ROOT, "remora_amd", "csrc", "api_forward.hip")).read()  # the forward pipelines
     for name in ("RMR_DUMP_CAT", "RMR_FUSED_DUMP_X"):  # really behind the experiment-build macro
         before = eng[: eng.index(f'getenv("{name}")')]
         assert before.rfind("#ifdef RMR_TIMING_ABLATIONS") > before.rfind("#endif"), name
@@ -2800,6 +2800,23 @@ def test_chunk_geometry_searches_from_a_hint_equal_bisection(tmp_path):
     assert cc.returncode == 0, cc.stderr
     run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert run.returncode == 0 and run.stdout.strip().endswith("0 mismatches"), run.stdout + run.stderr
+
+
+def test_staging_layouts_are_aligned_disjoint_and_within_the_committed_total(tmp_path):
+    """rmr_stage.h is the ONE description of what a call keeps in the staging arena: each array is declared once with its element
+    count, and the arena's size and the pointers both come from those declarations.  tests/c/stage_layout.cpp commits layouts
+    against a fake engine: slots 256-byte aligned, disjoint and within the total; an empty slot; the layout of rmr_call_read
+    planned again for wider rows; the counts rmr_chunk_fill declares for 2 reads / 3 chunks / L 8 / seq_w 12 / map_w 5."""
+    import shutil
+
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is part of the image"
+    exe = str(tmp_path / "stage")
+    cc = subprocess.run([gxx, "-O2", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "remora_amd", "csrc"),
+                         os.path.join(ROOT, "tests", "c", "stage_layout.cpp"), "-o", exe], capture_output=True, text=True)
+    assert cc.returncode == 0 and not cc.stderr, cc.stderr
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0 and run.stdout.strip() == "0 failed checks", run.stdout + run.stderr
 
 
 def test_front_plans_fit_their_budgets_and_pin_the_benchmark_shapes(tmp_path):
