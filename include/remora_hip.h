@@ -126,6 +126,32 @@ int rmr_model_padded_size(const rmr_model_desc *desc);
 int rmr_model_pad_weights(const rmr_model_desc *desc, const float *weights, size_t n_floats, rmr_model_desc *padded_desc,
                           float *out, size_t out_cap, size_t *out_n);
 
+/* The form the fp32 kernels run this model's Winograd-capable layers in.  A fp32 model of which at least one layer has a
+ * Winograd kernel (merge_conv1 / merge_conv2 as F(4,5), sig_conv3 / seq_conv2 / seq_conv3 as polyphase F(4,3) / F(4,5)) is
+ * screened by rmr_model_create: a fixed batch of probe chunks at the model's own chunk and k-mer length goes through the
+ * network twice on the device, once in the Winograd and once in the direct form, and the Winograd kernels stay in use only
+ * if every logit of both runs is finite and the two differ by at most `tol` (default 2e-5).  Every forward entry of the
+ * model (rmr_forward, rmr_infer_chunks, rmr_call_read) follows the decision; RMR_WINOGRAD=0 still selects the direct form
+ * per call.  A screen on 256 chunks, not a proof.  Models without a Winograd layer (the 16-bit and split dtypes, sizes
+ * other than 64) are not screened: checked = 0, winograd = 0.
+ * replaces: nothing (torch.nn.Conv1d has one form; the layers concerned are models/ConvLSTM_w_ref.py:36-37,50 and
+ *           models/Conv_w_ref.py:35-38,54-55). */
+typedef struct rmr_model_numerics {
+    int32_t checked;        /* 1: the probe ran for this model */
+    int32_t winograd;       /* 1: fp32 Winograd kernels in use; 0: direct forms */
+    int32_t probe_chunks;
+    int32_t nonfinite;      /* non-finite logits seen in either form */
+    float   max_abs_diff;   /* max |winograd - direct| over the probe's logits (entries finite in both forms) */
+    float   tol;
+} rmr_model_numerics;
+int rmr_model_numerics_get(const rmr_model *m, rmr_model_numerics *out);
+/* re-run the probe with another tolerance and adopt its decision; tol < 0 restores the default.  tol = 0 forces the direct
+ * forms unless the two are bit-equal; tol = INFINITY forces Winograd (non-finite logits still select the direct forms).  A
+ * model that is not screened keeps checked = 0.  Synchronises the engine's stream; leaves its sub-batch setting and its
+ * profiler counters as they were.
+ * replaces: nothing (as above). */
+int rmr_model_check_winograd(rmr_model *m, float tol, rmr_model_numerics *out);
+
 /* ---- E1: k-mer one-hot encode with move-table expansion ------------------------------ */
 /* replaces: encoded_kmers.compute_encoded_kmer_batch, src/remora/encoded_kmers.pyx:13-45.
  * out: f32[n, 4*(kb+ka+1), sig_len].  The reference takes sig_len from chunk 0

@@ -19,13 +19,15 @@ def _validate(args):
     import torch
 
     from .data_chunks import CoreRemoraDataset, RemoraDataset, load_dataset
-    from .model_util import load_torchscript_model
+    from .model_util import load_torchscript_model, winograd_guard_message
     from .validate import ValidationLogger
 
     from . import dist as rdist
 
     rank, world, dev = rdist.setup_ranks(args.gpus, args.procs_per_gpu)
     model, md = load_torchscript_model(args.model, device=args.device if dev is None else dev, eval_only=True, dtype=args.dtype)
+    if rank == 0 and winograd_guard_message(model, os.path.basename(args.model)):
+        print(winograd_guard_message(model, os.path.basename(args.model)), file=sys.stderr)
     over = {"extra_arrays": {}, "kmer_context_bases": md["kmer_context_bases"], "chunk_context": md["chunk_context"]}
     paths, props, hashes = load_dataset(args.remora_dataset_path)
     dataset = RemoraDataset([CoreRemoraDataset(p, override_metadata=dict(over), infinite_iter=False,
@@ -227,7 +229,7 @@ def _dataset_copy(args):
 def _infer(args):
     from . import dist as rdist
     from .inference import infer_from_pod5_and_bam
-    from .model_util import load_torchscript_model
+    from .model_util import load_torchscript_model, winograd_guard_message
 
     # this rank's share of the BAM, found in a thread under the model load.  By byte range (default): where the share and
     # the next one begin is read off the bytes there (io.bam_byte_shard - no pass over the file, and the rank in front
@@ -244,6 +246,9 @@ def _infer(args):
     loaded = [load_torchscript_model(m, device=args.device if dev is None else dev, eval_only=True, dtype=args.dtype)
               for m in args.model]
     model, md = [x[0] for x in loaded], [x[1] for x in loaded]
+    for name, mdl in zip(args.model, model):
+        if rank == 0 and winograd_guard_message(mdl, os.path.basename(name)):
+            print(winograd_guard_message(mdl, os.path.basename(name)), file=sys.stderr)
     if len({m["can_base"] for m in md}) != len(md):
         raise RemoraError("Only one model per canonical base allowed.")
     import time

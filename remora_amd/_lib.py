@@ -24,6 +24,13 @@ class ModelDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("arch", "size", "kmer_len", "num_out", "chunk_len", "dtype")]
 
 
+class ModelNumerics(ctypes.Structure):
+    """rmr_model_numerics of include/remora_hip.h: the record of the load-time Winograd probe."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("checked", "winograd", "probe_chunks", "nonfinite")] + [
+        ("max_abs_diff", ctypes.c_float), ("tol", ctypes.c_float)]
+
+
 class BamBatch(ctypes.Structure):
     """rmr_bam_batch of include/remora_hip.h."""
 
@@ -72,6 +79,8 @@ SIGNATURES = {
     "rmr_model_padded_size": (c_int, [ctypes.POINTER(ModelDesc)]),
     "rmr_model_pad_weights": (c_int, [ctypes.POINTER(ModelDesc), c_vp, ctypes.c_size_t, ctypes.POINTER(ModelDesc), c_vp, ctypes.c_size_t,
                                       ctypes.POINTER(ctypes.c_size_t)]),
+    "rmr_model_numerics_get": (c_int, [c_vp, ctypes.POINTER(ModelNumerics)]),
+    "rmr_model_check_winograd": (c_int, [c_vp, ctypes.c_float, ctypes.POINTER(ModelNumerics)]),
     "rmr_encode_kmers": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_i64, c_int, c_vp, c_int]),
     "rmr_trim_chunk_context": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_i64, c_int]),
     "rmr_parse_moves": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_vp, ctypes.POINTER(c_i64), c_int]),

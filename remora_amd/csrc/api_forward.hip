@@ -2,11 +2,14 @@
 // then upload), the three forward pipelines over the kernels of k_*.hip, rmr_forward, rmr_infer_chunks and rmr_call_read.
 #include <algorithm>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <thread>
+#include <tuple>
 
 #include "rmr_internal.h"
 #include "rmr_geometry.h"
+#include "rmr_probe.h"
 #include "rmr_stage.h"
 
 using namespace rmr;
@@ -53,6 +56,17 @@ int rmr_model_pad_weights(const rmr_model_desc *desc, const float *weights, size
 }
 
 static int model_create_at_kernel_size(rmr_engine *e, const rmr_model_desc *desc, const float *weights, size_t n_floats, rmr_model **out);
+static int model_probe_winograd(rmr_model *m, float tol);
+
+// the load-time screen of the Winograd kernels (below, behind the pipelines); a model whose probe fails to run is not handed out
+static int model_probe_or_destroy(rmr_model **out) {
+    const int rc = model_probe_winograd(*out, -1.0f);
+    if (rc != 0) {
+        rmr_model_destroy(*out);
+        *out = nullptr;
+    }
+    return rc;
+}
 
 int rmr_model_create(rmr_engine *e, const rmr_model_desc *desc, const float *weights,
                      size_t n_floats, rmr_model **out) {
@@ -67,13 +81,16 @@ int rmr_model_create(rmr_engine *e, const rmr_model_desc *desc, const float *wei
     const size_t want = rmr_model_weight_count(desc);
     if (want != n_floats) RMR_FAIL(RMR_ERR_INVALID, "weight blob has %zu floats, expected %zu", n_floats, want);
     const int sp = padded_size(desc->size, desc->dtype);
-    if (sp == desc->size) return model_create_at_kernel_size(e, desc, weights, n_floats, out);
+    if (sp == desc->size) {
+        RMR_TRY(model_create_at_kernel_size(e, desc, weights, n_floats, out));
+        return model_probe_or_destroy(out);
+    }
     rmr_model_desc pd = *desc;
     pd.size = sp;
     const std::vector<float> blob = pad_model_blob(*desc, weights, sp);
     RMR_TRY(model_create_at_kernel_size(e, &pd, blob.data(), blob.size(), out));
     (*out)->true_size = desc->size;
-    return 0;
+    return model_probe_or_destroy(out);
 }
 
 // `desc->size` is a size the kernels run at (padded_size is the identity on it)
@@ -251,8 +268,8 @@ int pipeline_fp32(rmr_model *m, const ChunkArrays &in, int64_t n, float *logits,
 int run_pipeline(rmr_model *m, const ChunkArrays &in, int64_t n, float *logits) {
     if (n <= 0) return 0;
     // the switches of every kernel choice below, read once per call
-    const FwdSwitches sw{tune_int("RMR_FUSED", 1) != 0, tune_int("RMR_CONV_FRONT", 1) != 0, tune_int("RMR_WINOGRAD", 1) != 0,
-                         tune_int("RMR_SIG3_MFMA", 1) != 0};
+    const FwdSwitches sw{tune_int("RMR_FUSED", 1) != 0, tune_int("RMR_CONV_FRONT", 1) != 0,
+                         tune_int("RMR_WINOGRAD", 1) != 0 && m->use_winograd, tune_int("RMR_SIG3_MFMA", 1) != 0};
     if (m->nparts == 1 && m->desc.size > 64) return pipeline_stream16(m, in, n, logits);
     if (m->f16 && (in.enc || !fused_front_supported(m, in.seq_w, in.map_w)))
         RMR_FAIL(RMR_ERR_INVALID, "dtype f16 runs on the fused kernels only: chunk arrays (not a dense one-hot tensor), sequence rows of at "
@@ -261,9 +278,122 @@ int run_pipeline(rmr_model *m, const ChunkArrays &in, int64_t n, float *logits) 
     return pipeline_fp32(m, in, n, logits, sw);
 }
 
+// ---- the Winograd guard (include/remora_hip.h, rmr_model_numerics) ---------------------------------------------------------
+constexpr float kWinogradTol = 2e-5f;  // what tests/test_gpu_wino.py allows the two forms on the reference-generated models
+
+// Whether a forward call of this model launches a kernel in a Winograd form: the question pipeline_fp32 and launch_conv answer
+// per launch, asked for the layers of the architecture at once.  `seq_w`, `map_w`, `n`: the probe's chunk arrays (the fronts'
+// plans depend on them only through what fits the LDS; a dense one-hot call takes a subset of these kernels).
+bool model_takes_winograd(const rmr_model *m, int kb, int ka, int seq_w, int map_w, int64_t n) {
+    if (m->desc.dtype != 0 || m->nparts != 0 || m->f16) return false;
+    auto conv = [](const ConvLayer &c, int pin, int pout) { return conv_wino_supported(c, pin, pout) || conv_wino_s3_supported(c, pin, pout); };
+    const bool sw_front = tune_int("RMR_CONV_FRONT", 1) != 0, sw_mfma = tune_int("RMR_SIG3_MFMA", 1) != 0;
+    const bool fold = sw_front && conv_front_supported(m, kb, ka, seq_w, map_w);
+    bool any = fold ? seq2_front_takes_winograd(m, seq_w, map_w, n) : false;
+    if (sw_mfma && sig3_front_mfma_supported(m)) any |= sig3_front_takes_winograd(m, n);
+    else if (!fold) any |= conv(m->sig3, m->P2, m->P3);
+    any |= conv(m->merge1, m->P3, m->T);
+    if (m->desc.arch == RMR_ARCH_CONV_LSTM) return any || (!fold && conv(m->seq2, m->P1, m->P3));
+    return any || conv(m->seq2, m->P1, m->PQ2) || conv(m->seq3, m->PQ2, m->P3) || conv(m->merge2, m->T, m->T2) ||
+           conv(m->merge3, m->T2, m->T3) || conv(m->merge4, m->T3, m->T4);
+}
+
 }  // namespace
 
+// The probe batch (rmr_probe.h) through pipeline_fp32 in both forms, everything on the device, and the decision of
+// include/remora_hip.h.  tol < 0: the default.  On the engine's stream, synchronised before returning; the engine's sub-batch
+// setting and its profiler are put aside for the two runs (no record of the probe reaches rmr_profile_get).
+static int model_probe_winograd(rmr_model *m, float tol) {
+    rmr_engine *e = m->eng;
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    rmr_model_numerics &nm = m->numerics;
+    nm = rmr_model_numerics{};
+    nm.tol = tol < 0.0f ? kWinogradTol : tol;
+    m->use_winograd = true;
+    const int K = m->desc.kmer_len, kb = (K - 1) / 2, ka = K - 1 - kb, L = m->L, no = m->desc.num_out;
+    const int max_len = probe_max_len(L);
+    if (!model_takes_winograd(m, kb, ka, max_len + kb + ka, max_len + 1, PROBE_CHUNKS)) return 0;
+    // the batch is generated once per geometry and kept as ONE host blob in the layout of the staging slots below: one upload
+    struct Packed { ProbeBatch pb; std::vector<char> blob; };
+    static std::mutex cache_mu;
+    static std::map<std::tuple<int, int, int>, Packed> cache;
+    const Packed *pk;
+    {
+        std::lock_guard<std::mutex> ck(cache_mu);
+        Packed &c = cache[std::make_tuple(L, kb, ka)];
+        if (c.blob.empty()) {
+            c.pb = make_probe_batch(L, kb, ka);
+            const size_t o_seq = Stage::pad(c.pb.signal.size() * sizeof(float)), o_map = o_seq + Stage::pad(c.pb.seqs.size());
+            const size_t o_len = o_map + Stage::pad(c.pb.maps.size() * sizeof(int16_t));
+            c.blob.assign(o_len + Stage::pad(c.pb.lens.size() * sizeof(int16_t)), 0);
+            memcpy(c.blob.data(), c.pb.signal.data(), c.pb.signal.size() * sizeof(float));
+            memcpy(c.blob.data() + o_seq, c.pb.seqs.data(), c.pb.seqs.size());
+            memcpy(c.blob.data() + o_map, c.pb.maps.data(), c.pb.maps.size() * sizeof(int16_t));
+            memcpy(c.blob.data() + o_len, c.pb.lens.data(), c.pb.lens.size() * sizeof(int16_t));
+        }
+        pk = &c;  // (std::map: the node stays where it is)
+    }
+    const ProbeBatch &pb = pk->pb;
+    const int64_t n = pb.n;
+    Stage st;
+    float *dsig, *dw, *dd;
+    int8_t *ds;
+    int16_t *dm, *dl;
+    unsigned *dred;
+    st.add(&dsig, pb.signal.size()).add(&ds, pb.seqs.size()).add(&dm, pb.maps.size()).add(&dl, pb.lens.size());
+    if (st.total != pk->blob.size()) RMR_FAIL(RMR_ERR_INVALID, "internal: probe blob of %zu bytes, slots of %zu", pk->blob.size(), st.total);
+    st.add(&dw, (size_t)n * no).add(&dd, (size_t)n * no).add(&dred, 2);
+    RMR_TRY(st.commit(e));
+    H2D(dsig, pk->blob.data(), pk->blob.size());
+    const ChunkArrays in{dsig, nullptr, ds, pb.seq_w, dm, pb.map_w, dl, kb, ka};
+    const bool profiling = e->profiling;
+    const int64_t subbatch = e->subbatch;
+    e->profiling = false;
+    e->subbatch = 0;
+    unsigned red[2] = {0, 0};
+    auto run = [&]() -> int {
+        FwdSwitches sw{false, tune_int("RMR_CONV_FRONT", 1) != 0, true, tune_int("RMR_SIG3_MFMA", 1) != 0};
+        RMR_TRY(pipeline_fp32(m, in, n, dw, sw));
+        sw.winograd = false;
+        RMR_TRY(pipeline_fp32(m, in, n, dd, sw));
+        RMR_TRY(launch_probe_compare(e, dw, dd, n * no, dred));
+        D2H(red, dred, sizeof(red));
+        RMR_HIP(hipStreamSynchronize(e->stream));
+        return 0;
+    };
+    const int rc = run();
+    e->profiling = profiling;
+    e->subbatch = subbatch;
+    if (rc != 0) {
+        (void)hipStreamSynchronize(e->stream);
+        return rc;
+    }
+    nm.checked = 1;
+    nm.probe_chunks = (int32_t)n;
+    memcpy(&nm.max_abs_diff, &red[0], sizeof(float));
+    nm.nonfinite = (int32_t)red[1];
+    m->use_winograd = nm.nonfinite == 0 && nm.max_abs_diff <= nm.tol;
+    nm.winograd = m->use_winograd ? 1 : 0;
+    return 0;
+}
+
 extern "C" {
+
+int rmr_model_numerics_get(const rmr_model *m, rmr_model_numerics *out) {
+    if (!m || !out) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(m->eng->mu);
+    *out = m->numerics;
+    return 0;
+}
+
+int rmr_model_check_winograd(rmr_model *m, float tol, rmr_model_numerics *out) {
+    if (!m) RMR_FAIL(RMR_ERR_INVALID, "model is NULL");
+    if (tol != tol) RMR_FAIL(RMR_ERR_INVALID, "tol is NaN");
+    RMR_TRY(model_probe_winograd(m, tol));
+    if (out) *out = m->numerics;
+    return 0;
+}
 
 int rmr_forward(rmr_model *m, const float *sigs, const float *seqs, int64_t n, float *logits, int mem) {
     if (!m || !sigs || !seqs || !logits) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");

@@ -977,6 +977,14 @@ bool sig3_front_mfma_supported(const rmr_model *m) {
     return sig3_mfma_plan(m, 1, false).ok;
 }
 
+bool sig3_front_takes_winograd(const rmr_model *m, int64_t n) {
+    return sig3_front_mfma_supported(m) && m->sig3.wpack && sig3_mfma_plan(m, n, true).wino;
+}
+
+bool seq2_front_takes_winograd(const rmr_model *m, int seq_w, int map_w, int64_t n) {
+    return m->seq2.wpack && plan_seq2_front(m->L, m->P1, m->P3, m->desc.kmer_len, seq_w, map_w, n, m->eng->num_cus, true).wino;
+}
+
 // sig_conv1 -> sig_conv2 (matrix cores) -> sig_conv3 of `n` chunks into channels [0, 64) of cat [n][P3][out_row]; sig_conv3 in
 // polyphase Winograd form (sig3_front_wino_kernel) where its x-domain image fits beside the rows (rmr_plan.h), the direct form
 // for !winograd (RMR_WINOGRAD=0) and long chunk contexts
@@ -997,6 +1005,7 @@ int launch_sig3_front_mfma(rmr_model *m, const float *signal, int64_t n, float *
     void (*kern)(ConvFrontArgs) = sig3_mfma_kernel(m->front.kw1, p.wino);
     RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(kern)));
     ProfScope ps(e, K_SIG3_FRONT);
+    if (p.wino) e->prof_count(K_WINO_FORM);
     hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(256), p.lds, e->stream, a);
     RMR_HIP(hipGetLastError());
     return 0;
@@ -1047,6 +1056,7 @@ int launch_conv_front(rmr_model *m, const ChunkArrays &c, int64_t n, float *cat,
     void (*kern)(ConvFrontArgs) = p.wino ? seq2_front_wino_kernel<9> : seq2_front_kernel<9>;
     RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(kern)));
     ProfScope ps(e, K_SEQ2_FRONT);
+    if (p.wino) e->prof_count(K_WINO_FORM);
     hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(256), p.lds, e->stream, a);
     RMR_HIP(hipGetLastError());
     return 0;

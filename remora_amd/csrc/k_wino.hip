@@ -292,6 +292,7 @@ static int launch_wino_t(rmr_engine *e, const ConvLayer &c, const float *in, int
     auto kern = wino_conv_kernel<IC>;
     RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(kern)));
     ProfScope ps(e, c.kid);
+    e->prof_count(K_WINO_FORM);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, e->stream, a);
     RMR_HIP(hipGetLastError());
     return 0;
@@ -514,6 +515,7 @@ static int launch_wino_s3_t(rmr_engine *e, const ConvLayer &c, const float *in, 
     auto kern = wino_s3_kernel<IC>;
     RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(kern)));
     ProfScope ps(e, c.kid);
+    e->prof_count(K_WINO_FORM);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, e->stream, a);
     RMR_HIP(hipGetLastError());
     return 0;

@@ -57,6 +57,9 @@ enum KernelId {
     K_RESCALE_Q,
     K_SIG3_FRONT,
     K_SEQ2_FRONT,
+    K_PROBE_DIFF,
+    K_PROBE_NONFINITE,
+    K_WINO_FORM,  // a launch count without a time: every kernel launched in a Winograd form is ALSO counted here (its time stays under its layer's id)
     K_NUM
 };
 const char *kernel_name(int id);
@@ -116,6 +119,7 @@ struct rmr_engine {
     double acc_ms[rmr::K_NUM] = {};
     int64_t acc_n[rmr::K_NUM] = {};
     int prof_begin(int id, hipEvent_t *t1, hipStream_t s);
+    void prof_count(int id) { if (profiling) acc_n[id] += 1; }  // a launch counted beside its timed record (K_WINO_FORM)
     int prof_collect();
 };
 
@@ -151,6 +155,11 @@ struct rmr_model : rmr::ModelWeights {
     rmr_engine *eng = nullptr;
     int true_size = 0;      // the network's own `size` (model_params["size"]); channels beyond it carry zero weights
     std::vector<void *> dev_allocs;
+    // the Winograd guard (include/remora_hip.h, rmr_model_numerics): the decision of the load-time probe.  `use_winograd` is what
+    // the forward entries read beside RMR_WINOGRAD; it stays true for a model that is not screened (none of its layers has a
+    // Winograd kernel, so nothing reads it), whose record says checked = 0, winograd = 0
+    bool use_winograd = true;
+    rmr_model_numerics numerics{};
 };
 
 // ---- kernel launchers (defined in k_*.hip) ------------------------------------------------
@@ -180,6 +189,8 @@ int launch_fill(rmr_engine *e, const rmr_reads &d, int64_t n_chunks, const int32
                 int16_t *maps, int map_w, int16_t *lens, int64_t *rfb);
 int launch_chunk_read(rmr_engine *e, const int64_t *focus_off, int64_t n_reads, int64_t n_chunks, int32_t *out);
 int launch_count(rmr_engine *e, const float *logits, int64_t n, int num_out, int64_t *counts);
+// k_probe.hip: out[0] = bits of max |a - b| over the entries finite in both, out[1] = non-finite entries of a and b
+int launch_probe_compare(rmr_engine *e, const float *a, const float *b, int64_t n, unsigned *out);
 int launch_validation_tally(rmr_engine *e, const float *logits, const int64_t *labels, int64_t n, int km, int kf, const int *colmap,
                             int64_t *conf, float *win, uint8_t *pred, double *loss_sum);
 int launch_vbz(rmr_engine *e, const uint8_t *svb, const int64_t *row_off, const int32_t *row_n, const int64_t *out_off,
@@ -211,7 +222,7 @@ int launch_seq1_dense(rmr_model *m, const float *enc, int64_t n, float *seq1);
 struct FwdSwitches {
     bool fused;       // RMR_FUSED
     bool conv_front;  // RMR_CONV_FRONT
-    bool winograd;    // RMR_WINOGRAD
+    bool winograd;    // RMR_WINOGRAD and the model's own decision (rmr_model::use_winograd)
     bool sig3_mfma;   // RMR_SIG3_MFMA
 };
 // k_conv_front.hip: fp32 sig_conv3 / seq_conv2 with their producers (sig_conv1/2, seq_conv1) folded into the staging
@@ -219,6 +230,9 @@ bool conv_front_supported(const rmr_model *m, int kb, int ka, int seq_w, int map
 // the signal half alone with sig_conv2 on the matrix cores (both architectures, 5 or 11 taps): signal -> cat channels [0, 64)
 bool sig3_front_mfma_supported(const rmr_model *m);
 int launch_sig3_front_mfma(rmr_model *m, const float *signal, int64_t n, float *cat, bool winograd);
+// whether the plans of the two folded fronts take their Winograd kernels for a batch of n chunks (the guard's question)
+bool sig3_front_takes_winograd(const rmr_model *m, int64_t n);
+bool seq2_front_takes_winograd(const rmr_model *m, int seq_w, int map_w, int64_t n);
 int launch_conv_front(rmr_model *m, const ChunkArrays &c, int64_t n, float *cat, const FwdSwitches &sw);
 int launch_conv(rmr_engine *e, const ConvLayer &c, const float *in, int in_row, int pin,
                 float *out, int out_row, int out_coff, int pout, int64_t n, bool winograd);

@@ -238,6 +238,10 @@ class HipModel:
         L.check(lib.rmr_model_create(self.engine.handle, ctypes.byref(desc), blob.ctypes.data, blob.size, ctypes.byref(h)))
         self._h, self._lib = h, lib
         self.kernel_size = int(lib.rmr_model_padded_size(ctypes.byref(desc)))  # channels the kernels run at (zero-weight padding)
+        # the record of the load-time Winograd probe (rmr_model_numerics): which form the fp32 kernels run this model in
+        rec = L.ModelNumerics()
+        L.check(lib.rmr_model_numerics_get(h, ctypes.byref(rec)))
+        self.numerics = self._numerics_dict(rec)
         # a device-resident token so that `next(model.parameters()).device` works
         self._param = torch.nn.Parameter(torch.zeros(1, device=self.engine.torch_device), requires_grad=False)
         self.training = False
@@ -249,6 +253,26 @@ class HipModel:
                 self._lib.rmr_model_destroy(h)
             except Exception:
                 pass
+
+    @staticmethod
+    def _numerics_dict(rec):
+        return {name: getattr(rec, name) for name, _ in L.ModelNumerics._fields_}
+
+    @property
+    def winograd_form(self):
+        """"winograd" / "direct": the form the probe chose for the fp32 Winograd-capable layers; "n/a": the model has none."""
+        if not self.numerics["checked"]:
+            return "n/a"
+        return "winograd" if self.numerics["winograd"] else "direct"
+
+    def check_winograd(self, tol=None):
+        """Re-run the probe (rmr_model_check_winograd) with tolerance `tol` on max |winograd - direct| over its logits and
+        adopt the decision; None restores the default.  0.0 forces the direct kernels, inf the Winograd ones.  Returns the
+        refreshed `numerics`."""
+        rec = L.ModelNumerics()
+        L.check(self._lib.rmr_model_check_winograd(self._h, -1.0 if tol is None else float(tol), ctypes.byref(rec)))
+        self.numerics = self._numerics_dict(rec)
+        return self.numerics
 
     # ---- torch.nn.Module-like surface ----
     def parameters(self):

@@ -8,6 +8,7 @@ HIP engine (BatchNorm folding and MFMA packing happen inside rmr_model_create) a
 returned in place of the ScriptModule is a `HipModel`.
 """
 import json
+import logging
 import os
 from os.path import isfile
 
@@ -16,6 +17,25 @@ import numpy as np
 from . import RemoraError
 from .engine import HipModel, _torch
 from .refine_signal_map import SigMapRefiner
+
+LOGGER = logging.getLogger("Remora")
+
+
+def winograd_guard_message(model, name):
+    """The one line said about a model whose load-time probe took the fp32 Winograd kernels out of use (None otherwise)."""
+    rec = model.numerics
+    if not rec["checked"] or rec["winograd"]:
+        return None
+    return (f"model {name}: fp32 Winograd kernels off, direct forms in use (probe of {rec['probe_chunks']} chunks: "
+            f"max_abs_diff {rec['max_abs_diff']:.3g} against tol {rec['tol']:.3g}, {rec['nonfinite']} non-finite logits)")
+
+
+def _record_winograd(model, md, name):
+    """metadata["winograd"] = "winograd" / "direct" / "n/a"; one INFO line when the guard tripped."""
+    md["winograd"] = model.winograd_form
+    msg = winograd_guard_message(model, name)
+    if msg is not None:
+        LOGGER.info(msg)
 
 
 def add_derived_metadata(md):
@@ -77,6 +97,7 @@ def load_torchscript_model(model_filename, device=None, quiet=False, eval_only=F
     model = HipModel(state, md["chunk_len"], device=device, dtype=dtype)
     if model.kmer_len != md["kmer_len"]:
         raise RemoraError(f"model weights expect kmer_len {model.kmer_len}, metadata says {md['kmer_len']}")
+    _record_winograd(model, md, os.path.basename(str(model_filename)))
     return model.eval(), md
 
 
@@ -105,10 +126,12 @@ def load_model(model_filename=None, *, pore=None, basecall_model_type=None, base
 
 def model_from_state(state, model_metadata, device=None, engine=None, dtype="fp32"):
     """HipModel straight from a state_dict-like {name: array} (numpy or torch) — the entry point
-    for callers that already hold the weights."""
+    for callers that already hold the weights.  The form the fp32 kernels run it in goes into `model_metadata["winograd"]`."""
     st = {}
     for k, v in state.items():
         if k.endswith("num_batches_tracked"):
             continue
         st[k] = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
-    return HipModel(st, int(sum(model_metadata["chunk_context"])), device=device, engine=engine, dtype=dtype)
+    model = HipModel(st, int(sum(model_metadata["chunk_context"])), device=device, engine=engine, dtype=dtype)
+    _record_winograd(model, model_metadata, f"{model.arch} size {model.size} (from state)")
+    return model

@@ -516,6 +516,81 @@ def gen_model_logits(R, out):
         print("model", name, "logit range", float(logits.min()), float(logits.max()))
 
 
+def gen_trained(R, out):
+    """The two architectures at size 64 TRAINED by this tool, so that the weights and the BatchNorm running statistics are
+    those of a network that learned something (every other model fixture is a freshly initialised one with drawn statistics):
+    models/ConvLSTM_w_ref.py and models/Conv_w_ref.py, chunk context (50, 50), k-mer context (4, 4), 2 outputs; Adam on the
+    CPU, BatchNorm in train mode, synthetic labelled chunks of remora_amd.synth in which a label-1 chunk has a constant
+    offset added to the signal samples of its focus base.  Written only if the trained network calls >= 0.9 of 2 000 fresh
+    chunks correctly; then exported (export_model_torchscript), reloaded (load_model) and run on the fixture's chunks."""
+    import tempfile
+
+    import torch
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    from remora_amd import synth
+
+    OFFSET, STEPS, BATCH, LR = 3.0, 400, 256, 2e-3
+    kb, ka, L, size, num_out, n_fix = 4, 4, 100, 64, 2, 48
+    K = kb + ka + 1
+
+    def labelled(n, shard):
+        d = synth.synth_chunks_config("C100", n, seed=20250117, shard=shard)
+        sig, mp, lab = d["signal"].copy(), d["sequence_to_signal_mapping"].astype(np.int64), d["labels"]
+        sl = d["sequence_lengths"].astype(np.int64)
+        inside = (mp[:, :-1] <= L // 2) & (np.arange(mp.shape[1] - 1)[None, :] < sl[:, None])
+        pstar = inside.sum(axis=1) - 1  # the base whose samples contain L // 2 (synth.synth_chunks)
+        rows = np.arange(n)
+        pos = np.arange(L)[None, :]
+        focus = (pos >= mp[rows, pstar][:, None]) & (pos < mp[rows, pstar + 1][:, None])
+        sig[:, 0][focus & (lab == 1)[:, None]] += np.float32(OFFSET)
+        enc = R.encoded_kmers.compute_encoded_kmer_batch(kb, ka, d["sequence"], d["sequence_to_signal_mapping"], d["sequence_lengths"])
+        return d, torch.from_numpy(sig), torch.from_numpy(enc), torch.from_numpy(lab)
+
+    for si, (name, arch) in enumerate((("convlstm_s64_l100_o2_trained", "ConvLSTM_w_ref"), ("conv_s64_l100_o2_trained", "Conv_w_ref"))):
+        torch.manual_seed(700 + si)
+        net = R.model_util._load_python_model(f"{REF}/models/{arch}.py", size=size, kmer_len=K, num_out=num_out)
+        net.train()
+        opt = torch.optim.Adam(net.parameters(), lr=LR)
+        loss_fn = torch.nn.CrossEntropyLoss()
+        losses = []
+        for step in range(STEPS):
+            _, sig, enc, lab = labelled(BATCH, shard=1000 * si + step)
+            opt.zero_grad()
+            loss = loss_fn(net(sig, enc), lab)
+            loss.backward()
+            opt.step()
+            losses.append(float(loss.detach()))
+        net.eval()
+        _, sig, enc, lab = labelled(2000, shard=900_000 + si)
+        with torch.no_grad():
+            acc = float((net(sig, enc).argmax(dim=1) == lab).float().mean())
+        print("trained", name, "loss", losses[0], "->", losses[-1], "held-out accuracy", acc)
+        if acc < 0.9:
+            raise SystemExit(f"{name}: held-out accuracy {acc:.3f} < 0.9 - fixture not written")
+        ckpt = _ckpt((kb, ka), (L // 2, L - L // 2), ["m"], ["5mC"], [("CG", 0)], size, K, num_out)
+        with tempfile.TemporaryDirectory() as td:
+            pt = os.path.join(td, "m.pt")
+            R.model_util.export_model_torchscript(ckpt, net, pt)
+            model, _ = R.model_util.load_model(pt, quiet=True, eval_only=True)
+        d, sig, enc, _ = labelled(n_fix, shard=950_000 + si)
+        rng = np.random.default_rng(18 + si)
+        dense = rng.standard_normal((8, 4 * K, L)).astype(np.float32)
+        with torch.no_grad():
+            logits = model(sig, enc).numpy()
+            dense_logits = model(sig[:8], torch.from_numpy(dense)).numpy()
+            assert np.abs(logits - net(sig, enc).numpy()).max() < 1e-5
+        fx = state_to_np(net)
+        fx.update(arch=np.asarray(arch), params=np.asarray([size, kb, ka, L, num_out], np.int64), sigs=sig.numpy(),
+                  seqs=d["sequence"], maps=d["sequence_to_signal_mapping"], lens=d["sequence_lengths"], logits=logits,
+                  dense_seqs=dense, dense_logits=dense_logits,
+                  meta_txt=np.asarray(json.dumps(dict(trained=True, offset=OFFSET, steps=STEPS, batch=BATCH, lr=LR, optimiser="Adam",
+                                                      first_loss=losses[0], last_loss=losses[-1], held_out_chunks=2000,
+                                                      held_out_accuracy=acc))))
+        np.savez_compressed(os.path.join(out, f"model_{name}.npz"), **fx)
+        print("model", name, "logit range", float(logits.min()), float(logits.max()))
+
+
 def _ckpt(kcb, cc, mod_bases, mod_long_names, motifs, size, kmer_len, num_out, bsj=False, off=0):
     return dict(
         kmer_context_bases=kcb,
@@ -1382,6 +1457,7 @@ def main():
         encode_kmers=gen_encode_kmers,
         trim=gen_trim,
         model_logits=gen_model_logits,
+        trained=gen_trained,
         call_read_mods=gen_call_read_mods,
         post=gen_post,
         dataset_batches=gen_dataset_batches,
@@ -1396,6 +1472,8 @@ def main():
     )
     for name, fn in gens.items():
         if args.only and name not in args.only.split(","):
+            continue
+        if name == "trained" and not args.only:  # minutes of CPU training: on request (--only trained)
             continue
         fn(R, out)
 
