@@ -573,6 +573,45 @@ int rmr_rescale_quantiles(rmr_refiner *r, int64_t n_reads, const int16_t *dacs, 
                           const double *shift, const double *scale, int64_t max_read_bases, int clip_bases,
                           int n_quants, const double *quants, double *sig_q, double *lvl_q, int32_t *status);
 
+/* ---- P1: per-base signal metrics and the k-mer level table estimated from them ------------ */
+/* replaces, for a batch of reads in one launch: metrics.METRIC_FUNCS (src/remora/metrics.py:45-117: compute_dwell,
+ * compute_dwell_mean, compute_dwell_mean_sd, compute_trimmean, compute_trimmean_trimsd with clip_sig :7-9) as
+ * io.Read.compute_per_base_metric applies them to one read's normalised signal (src/remora/io.py:2394-2480).
+ * Reads laid out as in rmr_reads (dacs / sig_off / seq_to_sig / seq_off / shift / scale), DEVICE pointers; max_read_bases: the
+ * longest read of the batch (sizes the launch).  Per base b of the concatenated reads (any output may be NULL):
+ *   dwell f32    seq_to_sig[b + 1] - seq_to_sig[b]
+ *   mean, sd     f64, over the base's samples (dacs - shift) / scale evaluated in float64 as Read.norm_signal does (io.py:1842-1849);
+ *                sd = sqrt(max(0, E[x^2] - mean^2)); NaN for a base without samples (the reference's inf becomes NaN too)
+ *   trimmean, trimsd   the same over the samples left after dropping start_trim at the base's start and end_trim at its end;
+ *                NaN when max(0, dwell - start_trim - end_trim) is 0
+ * Every base's samples are summed directly in float64 (error <= dwell * 2^-53 * sum|x|) where the reference takes differences
+ * of a whole-read cumulative sum; a base's result does not depend on the other reads of the batch or on the read's place in it.
+ * A mapping entry outside the read's own signal gives NaN for the bases it bounds.  Asynchronous on the engine's stream. */
+int rmr_base_metrics(rmr_engine *e, int64_t n_reads, const int16_t *dacs, const int64_t *sig_off, const int64_t *seq_to_sig,
+                     const int64_t *seq_off, const double *shift, const double *scale, int64_t max_read_bases, int start_trim,
+                     int end_trim, float *dwell, double *mean, double *sd, double *trimmean, double *trimsd);
+/* replaces: io.get_region_kmers (src/remora/io.py:930-982; sequence from get_ref_seq_from_reads :671-703) over every region
+ * of io.get_site_kmer_levels (:991-1044) and the median per k-mer of `remora analyze estimate_kmer_levels`
+ * (src/remora/parsers.py:2296-2331).  The bases of n_reads reference-anchored reads, concatenated (seq_off i64[n_reads + 1]), are
+ * the observations: base i of read r lies on site site0[r] + i - a caller-chosen 64-bit key that encodes contig, strand and the
+ * reference position counted in READ orientation, so that the next base of a read is the next site on either strand, and that
+ * differs by more than kmer_before + kmer_after between the last site of one contig / strand and the first of another -,
+ * carries trimmean[i] (rmr_base_metrics) and int_seq[i] (-1..3, read orientation).  Per site the non-finite values are dropped,
+ * at least max(1, min_cov) values are required, and the median (numpy's: the mean of the two middle values of an even count) is
+ * the site's level; its k-mer is made of the bases of sites key - kmer_before .. key + kmer_after, each known from any read
+ * that covers it, and a window with a site no read covers or a base outside ACGT is skipped.  levels f64[4^k]: the median of
+ * the site levels of every k-mer (index = sum base_j * 4^(k-1-j)), NaN for a k-mer without site; kmer_sites i64[4^k] (nullable):
+ * how many sites; site_kmer i32 / site_level f64 (nullable, both or none, capacity n_bases): the *n_sites (host) reported sites
+ * ordered by (k-mer, level).  k = kmer_before + 1 + kmer_after <= RMR_MAX_LEVEL_KMER.  Sorting and selection run on the device
+ * (four radix sorts of 16 bytes per observation; 32 bytes of scratch per observation, plus the sorts' own, are allocated for
+ * the call, so n_bases is bounded by device memory: RMR_ERR_HIP when it does not fit).
+ * remora_amd.metrics.site_key0 is the key the package uses: sample (8 bits) | contig (20) | strand (1) | position (34).
+ * All array pointers are DEVICE memory.  Synchronous. */
+#define RMR_MAX_LEVEL_KMER 8
+int rmr_site_kmer_levels(rmr_engine *e, int64_t n_reads, const int64_t *seq_off, const int64_t *site0, int64_t n_bases,
+                         const double *trimmean, const int8_t *int_seq, int kmer_before, int kmer_after, int64_t min_cov,
+                         double *levels, int64_t *kmer_sites, int32_t *site_kmer, double *site_level, int64_t *n_sites);
+
 /* ---- measurement: HIP-event timing of every kernel launch on the engine stream ----------- */
 int rmr_profile_enable(rmr_engine *e, int on);
 int rmr_profile_reset(rmr_engine *e);

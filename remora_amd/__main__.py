@@ -276,7 +276,49 @@ def _infer(args):
     return 0
 
 
-def main(argv=None):
+def _estimate_kmer_levels(args):
+    """src/remora/parsers.py:2268-2333."""
+    import logging
+
+    import numpy as np
+
+    from .engine import get_engine
+    from .io import add_site_levels, read_bam_header_bytes
+    from .metrics import SiteLevels, kmer_strings
+    from .refine_signal_map import SigMapRefiner
+
+    log = logging.getLogger("Remora")
+    if args.log_filename is not None:
+        log.addHandler(logging.FileHandler(args.log_filename, mode="w"))
+        log.setLevel(logging.INFO)
+    out_fh = open(args.levels_filename, "w")  # opened first: no long run without write access
+    refiner = SigMapRefiner(kmer_model_filename=args.refine_kmer_level_table, do_rough_rescale=args.refine_rough_rescale,
+                            scale_iters=args.refine_scale_iters, algo=args.refine_algo, half_bandwidth=args.refine_half_bandwidth,
+                            sd_params=args.refine_short_dwell_parameters, do_fix_guage=True)
+    if not refiner.is_loaded or refiner.scale_iters < 0:
+        log.warning("It is highly recommended to apply signal mapping refinement in order to output a valid kmer level table.")
+    log.info("--chunk-width, --max-chunk-coverage and --num-workers are ignored: the BAM is streamed once and every read is used")
+    acc = SiteLevels(get_engine(args.device), args.kmer_context_bases, args.min_coverage)
+    for sample, (pod5_path, bam_path) in enumerate(args.pod5_and_bam):
+        hdr = read_bam_header_bytes(bam_path)
+        l_text = int.from_bytes(hdr[4:8], "little")
+        if int.from_bytes(hdr[8 + l_text : 12 + l_text], "little") == 0:
+            log.warning("Cannot estimate levels from BAM file without mappings or index")
+            continue
+        log.info(f"Extracting levels from {pod5_path} and {bam_path}")
+        add_site_levels(acc, pod5_path, bam_path, refiner, sample=sample, reads_per_batch=args.reads_per_batch, device=args.device)
+    log.info("Aggregating and outputting levels")
+    levels, _ = acc.levels()
+    if np.isnan(levels).any():
+        log.warning("Some k-mers not observed.")
+    for kmer, level in zip(kmer_strings(acc.kmer_len), levels.tolist()):
+        out_fh.write(f"{kmer}\tnan\n" if level != level else f"{kmer}\t{np.float64(level)}\n")
+    out_fh.close()
+    log.info("Done")
+    return 0
+
+
+def build_parser():
     ap = argparse.ArgumentParser(prog="remora_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
     infer = sub.add_parser("infer").add_subparsers(dest="sub", required=True)
@@ -379,6 +421,32 @@ def main(argv=None):
     dc.add_argument("--overwrite", action="store_true")
     dc.set_defaults(func=_dataset_copy)
 
+    ana = sub.add_parser("analyze").add_subparsers(dest="sub", required=True)
+    k = ana.add_parser("estimate_kmer_levels", help="Estimate k-mer level table (per-base trimmed means and both medians on the GPU)")
+    k.add_argument("--pod5-and-bam", required=True, nargs=2, metavar=("POD5", "BAM"), action="append",
+                   help="POD5 signal path and BAM path; the BAM holds mapped reads with move tables and MD tags (no index needed); "
+                        "repeat for several samples, which are aggregated after the site level")
+    k.add_argument("--refine-kmer-level-table")
+    k.add_argument("--refine-rough-rescale", action="store_true")
+    k.add_argument("--refine-scale-iters", default=0, type=int)
+    k.add_argument("--refine-half-bandwidth", default=5, type=int)
+    k.add_argument("--refine-algo", default="dwell_penalty", choices=("Viterbi", "dwell_penalty"))
+    k.add_argument("--refine-short-dwell-parameters", default=[4, 3, 0.5], type=float, nargs=3, metavar=("TARGET", "LIMIT", "WEIGHT"))
+    k.add_argument("--min-coverage", type=int, default=10, help="Minimum coverage to include a site.")
+    k.add_argument("--kmer-context-bases", nargs=2, default=(2, 2), type=int, metavar=("BASES_BEFORE", "BASES_AFTER"))
+    k.add_argument("--levels-filename", default="remora_kmer_levels.txt")
+    k.add_argument("--log-filename")
+    k.add_argument("--num-workers", type=int, default=1, help="accepted for the reference's command lines; ignored")
+    k.add_argument("--chunk-width", type=int, default=1_000, help="accepted for the reference's command lines; ignored")
+    k.add_argument("--max-chunk-coverage", type=int, default=100, help="accepted for the reference's command lines; ignored")
+    k.add_argument("--reads-per-batch", type=int, default=256)
+    k.add_argument("--device", type=int, default=0)
+    k.set_defaults(func=_estimate_kmer_levels)
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
     nranks = getattr(args, "gpus", 1) * max(getattr(args, "procs_per_gpu", 1), 1)
     if nranks > 1 and "WORLD_SIZE" not in os.environ:

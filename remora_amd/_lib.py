@@ -130,6 +130,9 @@ SIGNATURES = {
     "rmr_refine_signal_maps": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int]),
     "rmr_rescale_quantiles": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp,
                                       c_vp, c_vp]),
+    "rmr_base_metrics": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rmr_site_kmer_levels": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                     ctypes.POINTER(c_i64)]),
     "rmr_profile_enable": (c_int, [c_vp, c_int]),
     "rmr_profile_reset": (c_int, [c_vp]),
     "rmr_profile_num_kernels": (c_int, []),

@@ -527,7 +527,7 @@ __global__ __launch_bounds__(256) void normalise_kernel(const int16_t *__restric
         const int16_t *d = reinterpret_cast<const int16_t *>(&raw);
         float o[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = (float)(((double)d[k] - sh) / sc);
+        for (int k = 0; k < 8; ++k) o[k] = (float)norm_sample_f64(d[k], sh, sc);
         reinterpret_cast<float4 *>(sig + i0)[0] = make_float4(o[0], o[1], o[2], o[3]);
         reinterpret_cast<float4 *>(sig + i0)[1] = make_float4(o[4], o[5], o[6], o[7]);
         return;
@@ -535,7 +535,7 @@ __global__ __launch_bounds__(256) void normalise_kernel(const int16_t *__restric
     for (int k = 0; k < nv; ++k) {
         const int64_t i = i0 + k;
         while (i >= r_end) { ++r; r_end = sig_off[r + 1]; sh = shift[r]; sc = scale[r]; }  // empty reads are skipped too
-        sig[i] = (float)(((double)dacs[i] - sh) / sc);
+        sig[i] = (float)norm_sample_f64(dacs[i], sh, sc);
     }
 }
 

@@ -1,0 +1,359 @@
+// k_metrics.hip - per-base signal metrics of a batch of reads and the k-mer level table estimated from them:
+//   rmr_base_metrics       src/remora/metrics.py:45-117 (METRIC_FUNCS) as io.Read.compute_per_base_metric applies them
+//                          (src/remora/io.py:2394-2480), for every base of every read of a batch in one launch
+//   rmr_site_kmer_levels   io.get_region_kmers (src/remora/io.py:930-982) + the aggregation of `remora analyze
+//                          estimate_kmer_levels` (src/remora/parsers.py:2296-2331): median per reference site, then per k-mer
+//
+// base_metrics_kernel.  One wave owns 64 consecutive bases of ONE read, counted from the read's first base, so what a base's
+// sums look like depends on its read alone and not on where the read stands in the batch (the results are the same bits for a
+// read alone and inside any batch).  The wave does not walk its bases: it walks the SAMPLES those 64 bases own, 64 at a time,
+// lane j taking sample j.  Each lane finds its sample's base by bisecting the wave's prefix sum of dwells in LDS (6 steps),
+// normalises the sample in float64 (norm_sample_f64: the expression of normalise_kernel), and a segmented inclusive scan
+// across the lanes, keyed by the base, leaves every base's partial sums in the last lane of its segment, which adds them
+// to the base's accumulators in LDS.  A stalled base of 5000 samples is 79 such rounds shared by all lanes, not one lane's
+// serial loop; a typical group (64 bases x 5-15 samples) is 5-15 rounds.  The sums are direct float64 sums of the base's own
+// samples - no whole-read cumulative sum, whose rounding grows with the read.
+// Traffic: 2 B per sample in (plus 8 B per base of mapping), 36 B per base out: HBM-bound by design, see DESIGN.md.
+//
+// The level table.  Every base of every reference-anchored read is one observation: (site, trimmean, base), `site` a 64-bit
+// key that grows by one per base in READ orientation on both strands.  Two stable LSD radix sorts (rocPRIM, by value, then by
+// site) order the observations by (site, value) with the non-finite values last in their site; a thread per site takes the
+// median of the finite ones (numpy's: mean of the two middle values for an even count) and looks its k-mer window up among
+// the sorted sites - the union of the reads of that strand, as get_ref_seq_from_reads assembles it; the same two sorts by
+// (k-mer, site median) and a thread per k-mer give the table.  Nothing but the 4^k results crosses PCIe.
+#include <cstring>
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "rmr_geometry.h"
+#include "rmr_internal.h"
+
+namespace rmr {
+
+struct BaseMetricsArgs {
+    const int16_t *dacs;
+    const int64_t *sig_off, *seq_to_sig, *seq_off;
+    const double *shift, *scale;
+    float *dwell;
+    double *mean, *sd, *trimmean, *trimsd;
+    int start_trim, end_trim;
+};
+
+// 64-bit values across lanes as two 32-bit shuffles
+__device__ __forceinline__ double shfl_up_f64(double v, int off) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __shfl_up(lo, off);
+    hi = __shfl_up(hi, off);
+    return __hiloint2double(hi, lo);
+}
+
+// LDS hand-over between the lanes of ONE wave: what every lane wrote is visible to every lane behind it (the LDS serves a wave's
+// instructions in order; the fences keep the compiler from moving accesses across)
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+constexpr int BM_WAVES = 4;  // waves (groups of 64 bases) per block
+
+__global__ __launch_bounds__(64 * BM_WAVES) void base_metrics_kernel(BaseMetricsArgs a) {
+    __shared__ int64_t s_pre[BM_WAVES][65];    // prefix sum of the group's dwells; [64] = the group's samples
+    __shared__ int64_t s_start[BM_WAVES][64];  // first sample of every base, read-local
+    __shared__ double s_acc[BM_WAVES][4][64];  // per base: sum x, sum x^2, and the same inside the trims
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t r = blockIdx.x;
+    const int64_t b0 = a.seq_off[r], nb = a.seq_off[r + 1] - b0;
+    const int64_t g0 = ((int64_t)blockIdx.y * BM_WAVES + wave) * 64;  // the group's first base, read-local
+    if (g0 >= nb) return;                                               // (wave-uniform; no block barrier below)
+    const int64_t *map = a.seq_to_sig + b0 + r;  // nb + 1 entries
+    const int64_t s0 = a.sig_off[r], sig_len = a.sig_off[r + 1] - s0;
+    const int16_t *dacs = a.dacs + s0;
+    const double sh = a.shift[r], sc = a.scale[r];
+    const int64_t bi = g0 + lane;
+    const bool live = bi < nb;
+    int64_t ms = 0, me = 0;
+    if (live) { ms = map[bi]; me = map[bi + 1]; }
+    // the samples that are summed never leave the read's own signal, whatever the mapping says
+    const int64_t cs = min(max(ms, (int64_t)0), sig_len), ce = min(max(me, cs), sig_len);
+    const int64_t dw = ce - cs;
+    int64_t inc = dw;  // inclusive prefix sum across the wave
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        int lo = (int)(uint32_t)inc, hi = (int)(inc >> 32);
+        lo = __shfl_up(lo, off);
+        hi = __shfl_up(hi, off);
+        if (lane >= off) inc += (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
+    }
+    s_pre[wave][lane + 1] = inc;
+    if (lane == 0) s_pre[wave][0] = 0;
+    s_start[wave][lane] = cs;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s_acc[wave][q][lane] = 0.0;
+    wave_lds_sync();
+    const int64_t total = s_pre[wave][64];
+    const int st = a.start_trim, en = a.end_trim;
+    for (int64_t j0 = 0; j0 < total; j0 += 64) {
+        const int64_t j = j0 + lane;
+        const bool valid = j < total;
+        int b = 64;
+        double x = 0.0, xx = 0.0, tx = 0.0, txx = 0.0;
+        if (valid) {
+            int lo = 0, hi = 64;  // the base that owns sample j: the first b with pre[b + 1] > j
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (s_pre[wave][mid + 1] <= j) lo = mid + 1; else hi = mid;
+            }
+            b = lo;
+            const int64_t k = j - s_pre[wave][b], n = s_pre[wave][b + 1] - s_pre[wave][b];
+            x = norm_sample_f64(dacs[s_start[wave][b] + k], sh, sc);
+            xx = __dmul_rn(x, x);
+            if (k >= st && k < n - en) { tx = x; txx = xx; }
+        }
+        // segmented inclusive scan: lanes of one base are neighbours, b never decreases with the lane
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int pb = __shfl_up(b, off);
+            const double px = shfl_up_f64(x, off), pxx = shfl_up_f64(xx, off), ptx = shfl_up_f64(tx, off), ptxx = shfl_up_f64(txx, off);
+            if (lane >= off && pb == b) { x = __dadd_rn(x, px); xx = __dadd_rn(xx, pxx); tx = __dadd_rn(tx, ptx); txx = __dadd_rn(txx, ptxx); }
+        }
+        const int nxt = __shfl_down(b, 1);
+        if (valid && (lane == 63 || nxt != b)) {  // one lane per base and round: a plain read-modify-write
+            s_acc[wave][0][b] = __dadd_rn(s_acc[wave][0][b], x);
+            s_acc[wave][1][b] = __dadd_rn(s_acc[wave][1][b], xx);
+            s_acc[wave][2][b] = __dadd_rn(s_acc[wave][2][b], tx);
+            s_acc[wave][3][b] = __dadd_rn(s_acc[wave][3][b], txx);
+        }
+        wave_lds_sync();
+    }
+    if (!live) return;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const float dwell_f = (float)(me - ms);                     // np.diff(seq_to_sig).astype(float32)
+    const float tdwell_f = fmaxf(0.f, dwell_f - (float)st - (float)en);  // np.maximum(0, dwells - st - en), float32 as there
+    const int64_t out = b0 + bi;
+    const bool has = dw > 0 && me - ms == dw, has_t = has && tdwell_f > 0.f;  // (a mapping that leaves the signal: NaN, nothing half-summed)
+    if (a.dwell) a.dwell[out] = dwell_f;
+    const double sx = s_acc[wave][0][lane], sxx = s_acc[wave][1][lane], stx = s_acc[wave][2][lane], stxx = s_acc[wave][3][lane];
+    const double m = has ? sx / (double)dwell_f : nan;
+    const double tm = has_t ? stx / (double)tdwell_f : nan;
+    if (a.mean) a.mean[out] = m;
+    if (a.trimmean) a.trimmean[out] = tm;
+    if (a.sd) a.sd[out] = has ? sqrt(fmax(__dsub_rn(sxx / (double)dwell_f, __dmul_rn(m, m)), 0.0)) : nan;
+    if (a.trimsd) a.trimsd[out] = has_t ? sqrt(fmax(__dsub_rn(stxx / (double)tdwell_f, __dmul_rn(tm, tm)), 0.0)) : nan;
+}
+
+int launch_base_metrics(rmr_engine *e, int64_t n_reads, int64_t max_read_bases, const BaseMetricsArgs &a) {
+    const int64_t per_block = 64 * BM_WAVES;
+    const int64_t gy = (max_read_bases + per_block - 1) / per_block;
+    if (gy > 65535) RMR_FAIL(RMR_ERR_INVALID, "rmr_base_metrics: a read of %lld bases is beyond the launch grid (16.7 M)", (long long)max_read_bases);
+    ProfScope ps(e, K_BASE_METRICS);
+    hipLaunchKernelGGL(base_metrics_kernel, dim3((unsigned)n_reads, (unsigned)gy), dim3(64 * BM_WAVES), 0, e->stream, a);
+    RMR_HIP(hipGetLastError());
+    return 0;
+}
+
+// ======================================================================================
+// site and k-mer aggregation
+// ======================================================================================
+// float64 -> uint64 whose unsigned order is the order of the values; every non-finite value becomes the largest key
+__device__ __forceinline__ uint64_t sortable_f64(double v) {
+    if (!(fabs(v) <= 1.7976931348623157e308)) return ~0ULL;
+    const uint64_t u = (uint64_t)__double_as_longlong(v + 0.0);  // (-0.0 + 0.0 = +0.0: one key for both zeros)
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ULL);
+}
+__device__ __forceinline__ double unsortable_f64(uint64_t k) {
+    const uint64_t u = (k >> 63) ? (k & 0x7fffffffffffffffULL) : ~k;
+    return __longlong_as_double((long long)u);
+}
+constexpr uint64_t NOT_A_SITE = ~0ULL;
+
+// observation i (base i of the concatenated reads): key of its value, its own index as payload
+__global__ void obs_value_keys_kernel(const double *__restrict__ vals, int64_t n, uint64_t *__restrict__ vkey, uint64_t *__restrict__ idx) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    vkey[i] = sortable_f64(vals[i]);
+    idx[i] = (uint64_t)i;
+}
+// the site of observation idx[p]: site0 of its read + its place in the read
+__global__ void obs_site_keys_kernel(const uint64_t *__restrict__ idx, int64_t n, const int64_t *__restrict__ seq_off, int64_t n_reads,
+                                     const int64_t *__restrict__ site0, uint64_t *__restrict__ skey) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const int64_t i = (int64_t)idx[p];
+    const int64_t r = ub_right(seq_off, n_reads + 1, i) - 1;  // last read with seq_off[r] <= i (empty reads are passed over)
+    skey[p] = (uint64_t)(site0[r] + (i - seq_off[r]));
+}
+
+__device__ __forceinline__ int64_t lb_u64(const uint64_t *a, int64_t n, uint64_t v) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a[mid] < v) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+
+// skey / idx: the observations ordered by (site, value).  The first observation of every site writes the site's k-mer and the
+// key of its median; every other position (and a site that is not reported) writes NOT_A_SITE.
+__global__ void site_median_kernel(const uint64_t *__restrict__ skey, const uint64_t *__restrict__ idx, int64_t n, const double *__restrict__ vals,
+                                   const int8_t *__restrict__ int_seq, int kb, int ka, int64_t min_cov, uint64_t *__restrict__ kkey,
+                                   uint64_t *__restrict__ mkey) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    uint64_t kk = NOT_A_SITE, mk = NOT_A_SITE;
+    const uint64_t key = skey[p];
+    if (p == 0 || skey[p - 1] != key) {
+        const int64_t end = lb_u64(skey, n, key + 1);
+        int64_t lo = p, hi = end;  // the finite values stand in front: first position of the site whose value is not finite
+        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (sortable_f64(vals[idx[mid]]) != ~0ULL) lo = mid + 1; else hi = mid; }
+        const int64_t c = lo - p;
+        if (c >= 1 && c >= min_cov) {
+            uint64_t code = 0;
+            bool ok = true;
+            for (int j = -kb; j <= ka && ok; ++j) {  // the bases around the site in read orientation, from whichever read covers them
+                const uint64_t want = key + (uint64_t)(int64_t)j;
+                const int64_t q = (j == 0) ? p : lb_u64(skey, n, want);
+                if (q >= n || skey[q] != want) { ok = false; break; }
+                const int b = int_seq[idx[q]];
+                if (b < 0 || b > 3) { ok = false; break; }
+                code = code * 4 + (uint64_t)b;
+            }
+            if (ok) {
+                const double lo_v = vals[idx[p + (c - 1) / 2]], hi_v = vals[idx[p + c / 2]];
+                kk = code;
+                mk = sortable_f64((c & 1) ? lo_v : __dadd_rn(lo_v, hi_v) / 2.0);
+            }
+        }
+    }
+    kkey[p] = kk;
+    mkey[p] = mk;
+}
+
+// kkey / mkey ordered by (k-mer, site median): a thread per k-mer
+__global__ void kmer_median_kernel(const uint64_t *__restrict__ kkey, const uint64_t *__restrict__ mkey, int64_t n, int64_t n_kmers,
+                                   double *__restrict__ levels, int64_t *__restrict__ counts) {
+    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_kmers) return;
+    const int64_t lo = lb_u64(kkey, n, (uint64_t)m), hi = lb_u64(kkey, n, (uint64_t)m + 1);
+    const int64_t c = hi - lo;
+    double lv = __longlong_as_double(0x7ff8000000000000LL);
+    if (c > 0) {
+        const double a = unsortable_f64(mkey[lo + (c - 1) / 2]), b = unsortable_f64(mkey[lo + c / 2]);
+        lv = (c & 1) ? a : __dadd_rn(a, b) / 2.0;
+    }
+    levels[m] = lv;
+    if (counts) counts[m] = c;
+}
+
+// the reported sites in the order of the table: site_kmer / site_level [n_sites]
+__global__ void site_list_kernel(const uint64_t *__restrict__ kkey, const uint64_t *__restrict__ mkey, int64_t n_sites, int32_t *__restrict__ site_kmer,
+                                 double *__restrict__ site_level) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_sites) return;
+    site_kmer[p] = (int32_t)kkey[p];
+    site_level[p] = unsortable_f64(mkey[p]);
+}
+
+// keys / vals sorted by `keys` (stable) into keys_out / vals_out
+static int sort_pairs(rmr_engine *e, void *tmp, size_t tmp_bytes, uint64_t *keys, uint64_t *keys_out, uint64_t *vals, uint64_t *vals_out, int64_t n) {
+    RMR_HIP(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys_out, vals, vals_out, (size_t)n, 0, 64, e->stream));
+    return 0;
+}
+
+struct DevFree {  // the temporaries of one call
+    std::vector<void *> ptrs;
+    ~DevFree() { for (void *p : ptrs) (void)hipFree(p); }
+    int get(void **out, size_t bytes) {
+        RMR_HIP(hipMalloc(out, bytes ? bytes : 1));
+        ptrs.push_back(*out);
+        return 0;
+    }
+};
+
+int run_site_kmer_levels(rmr_engine *e, int64_t n_reads, const int64_t *seq_off, const int64_t *site0, int64_t n, const double *vals,
+                         const int8_t *int_seq, int kb, int ka, int64_t min_cov, double *levels, int64_t *counts, int32_t *site_kmer,
+                         double *site_level, int64_t *n_sites) {
+    const int64_t n_kmers = (int64_t)1 << (2 * (kb + ka + 1));
+    const unsigned T = 256;
+    uint64_t *A = nullptr, *B = nullptr, *C = nullptr, *D = nullptr;
+    void *tmp = nullptr;
+    size_t tmp_bytes = 0;
+    DevFree pool;
+    int64_t sites = 0;
+    if (n > 0) {
+        RMR_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, A, B, C, D, (size_t)n, 0, 64, e->stream));
+        RMR_TRY(pool.get((void **)&A, n * 8));
+        RMR_TRY(pool.get((void **)&B, n * 8));
+        RMR_TRY(pool.get((void **)&C, n * 8));
+        RMR_TRY(pool.get((void **)&D, n * 8));
+        RMR_TRY(pool.get(&tmp, tmp_bytes));
+        const dim3 grid((unsigned)((n + T - 1) / T));
+        ProfScope ps(e, K_SITE_KMER_LEVELS);
+        // by value (A: value keys, C: indices -> B, D), then by site (A: site keys of D -> C keys, B indices)
+        hipLaunchKernelGGL(obs_value_keys_kernel, grid, dim3(T), 0, e->stream, vals, n, A, C);
+        RMR_TRY(sort_pairs(e, tmp, tmp_bytes, A, B, C, D, n));
+        hipLaunchKernelGGL(obs_site_keys_kernel, grid, dim3(T), 0, e->stream, D, n, seq_off, n_reads, site0, A);
+        RMR_TRY(sort_pairs(e, tmp, tmp_bytes, A, C, D, B, n));
+        // C: sites, B: indices, ordered by (site, value) -> A: k-mer of every site, D: key of its median
+        hipLaunchKernelGGL(site_median_kernel, grid, dim3(T), 0, e->stream, C, B, n, vals, int_seq, kb, ka, min_cov, A, D);
+        // by median (D keys, A payload -> B, C), then by k-mer (C keys, B payload -> A, D)
+        RMR_TRY(sort_pairs(e, tmp, tmp_bytes, D, B, A, C, n));
+        RMR_TRY(sort_pairs(e, tmp, tmp_bytes, C, A, B, D, n));
+        RMR_HIP(hipGetLastError());
+    }
+    // A: k-mers ascending (NOT_A_SITE last), D: their sites' medians ascending inside each k-mer
+    int64_t *cnt = counts;
+    if (!cnt) RMR_TRY(pool.get((void **)&cnt, n_kmers * 8));
+    {
+        ProfScope ps(e, K_SITE_KMER_LEVELS);
+        hipLaunchKernelGGL(kmer_median_kernel, dim3((unsigned)((n_kmers + T - 1) / T)), dim3(T), 0, e->stream, A, D, n, n_kmers, levels, cnt);
+        RMR_HIP(hipGetLastError());
+    }
+    if (n > 0 && (site_kmer || n_sites)) {  // the reported sites stand in front of A / D: as many as the k-mers count together
+        std::vector<int64_t> h((size_t)n_kmers);
+        RMR_HIP(hipMemcpyAsync(h.data(), cnt, n_kmers * 8, hipMemcpyDeviceToHost, e->stream));
+        RMR_HIP(hipStreamSynchronize(e->stream));
+        for (int64_t c : h) sites += c;
+        if (site_kmer && sites > 0) {
+            hipLaunchKernelGGL(site_list_kernel, dim3((unsigned)((sites + T - 1) / T)), dim3(T), 0, e->stream, A, D, sites, site_kmer, site_level);
+            RMR_HIP(hipGetLastError());
+        }
+    }
+    if (n_sites) *n_sites = sites;
+    RMR_HIP(hipStreamSynchronize(e->stream));  // the temporaries are freed on return
+    return 0;
+}
+
+}  // namespace rmr
+
+using namespace rmr;
+
+extern "C" {
+
+int rmr_base_metrics(rmr_engine *e, int64_t n_reads, const int16_t *dacs, const int64_t *sig_off, const int64_t *seq_to_sig,
+                     const int64_t *seq_off, const double *shift, const double *scale, int64_t max_read_bases, int start_trim,
+                     int end_trim, float *dwell, double *mean, double *sd, double *trimmean, double *trimsd) {
+    if (!e || !dacs || !sig_off || !seq_to_sig || !seq_off || !shift || !scale) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if (n_reads < 0 || n_reads > 0x7fffffffLL) RMR_FAIL(RMR_ERR_INVALID, "bad n_reads");
+    if (max_read_bases < 0) RMR_FAIL(RMR_ERR_INVALID, "bad max_read_bases");
+    if (start_trim < 0 || end_trim < 0) RMR_FAIL(RMR_ERR_INVALID, "trims must not be negative");
+    if (n_reads == 0 || max_read_bases == 0) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    BaseMetricsArgs a{dacs, sig_off, seq_to_sig, seq_off, shift, scale, dwell, mean, sd, trimmean, trimsd, start_trim, end_trim};
+    return launch_base_metrics(e, n_reads, max_read_bases, a);
+}
+
+int rmr_site_kmer_levels(rmr_engine *e, int64_t n_reads, const int64_t *seq_off, const int64_t *site0, int64_t n_bases,
+                         const double *trimmean, const int8_t *int_seq, int kmer_before, int kmer_after, int64_t min_cov,
+                         double *levels, int64_t *kmer_sites, int32_t *site_kmer, double *site_level, int64_t *n_sites) {
+    if (!e || !levels) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if (kmer_before < 0 || kmer_after < 0 || kmer_before + kmer_after + 1 > RMR_MAX_LEVEL_KMER)
+        RMR_FAIL(RMR_ERR_INVALID, "k-mers of 1 to %d bases are supported, got %d + 1 + %d", RMR_MAX_LEVEL_KMER, kmer_before, kmer_after);
+    if (n_reads < 0 || n_bases < 0 || n_bases > 0x7fffffffLL * 256) RMR_FAIL(RMR_ERR_INVALID, "bad n_reads / n_bases");
+    if (n_bases > 0 && (!seq_off || !site0 || !trimmean || !int_seq || n_reads == 0)) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if ((site_kmer == nullptr) != (site_level == nullptr)) RMR_FAIL(RMR_ERR_INVALID, "site_kmer and site_level go together");
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    return run_site_kmer_levels(e, n_reads, seq_off, site0, n_bases, trimmean, int_seq, kmer_before, kmer_after, min_cov, levels, kmer_sites,
+                                site_kmer, site_level, n_sites);
+}
+
+}  // extern "C"

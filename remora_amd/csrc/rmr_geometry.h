@@ -10,6 +10,10 @@
 
 namespace rmr {
 
+// One sample normalised as RemoraRead.sig (src/remora/data_chunks.py:191-197) and io.Read.norm_signal (src/remora/io.py:1842-1849)
+// do before any rounding to float32: (dacs - shift) / scale in float64, two IEEE operations - the same bits as numpy's.
+__host__ __device__ inline double norm_sample_f64(int16_t dac, double shift, double scale) { return ((double)dac - shift) / scale; }
+
 // first index with a[idx] > v  (np.searchsorted side="right")
 __host__ __device__ inline int64_t ub_right(const int64_t *a, int64_t n, int64_t v) {
     int64_t lo = 0, hi = n;

@@ -60,6 +60,8 @@ enum KernelId {
     K_PROBE_DIFF,
     K_PROBE_NONFINITE,
     K_WINO_FORM,  // a launch count without a time: every kernel launched in a Winograd form is ALSO counted here (its time stays under its layer's id)
+    K_BASE_METRICS,
+    K_SITE_KMER_LEVELS,  // its kernels and the four radix sorts between them, bracketed in two pieces
     K_NUM
 };
 const char *kernel_name(int id);

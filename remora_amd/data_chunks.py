@@ -450,6 +450,13 @@ class DeviceReads:
         self.shift = torch.from_numpy(np.asarray(shift, np.float64)).to(dev)
         self.scale = torch.from_numpy(np.asarray(scale, np.float64)).to(dev)
 
+    def per_base_metrics(self, metric, start_trim=1, end_trim=1):
+        """A named per-base metric (metrics.METRIC_FUNCS) for every base of the batch in one launch: {key: device tensor over
+        the concatenated bases}.  The batch form of io.Read.compute_per_base_metric (src/remora/io.py:2394-2480)."""
+        from .metrics import base_metrics
+
+        return base_metrics(self, metric, start_trim, end_trim)
+
     def motif_focus_bases(self, motifs):
         """Focus bases of all motif hits, ascending inside each read: (focus i64[F] read-local, on the device;
         foc_off i64[n_reads+1] on the host).  GPU counterpart of RemoraRead.set_motif_focus_bases for a batch

@@ -1332,6 +1332,100 @@ class Read:
     def pa_signal(self):
         return (self.dacs - self.shift_dacs_to_pa) / self.scale_dacs_to_pa
 
+    @property
+    def norm_signal(self):
+        """src/remora/io.py:1842-1849."""
+        if self.scale_dacs_to_norm is None or self.shift_dacs_to_norm is None:
+            raise RemoraError("Norm scaling factors not set")
+        return (self.dacs - self.shift_dacs_to_norm) / self.scale_dacs_to_norm
+
+    def _sig_scaling(self, signal_type):
+        """(shift, scale) with signal = (dacs - shift) / scale for a signal type of get_sig_type (src/remora/io.py:2294-2308)."""
+        if signal_type == "norm":
+            if self.scale_dacs_to_norm is None or self.shift_dacs_to_norm is None:
+                raise RemoraError("Norm scaling factors not set")
+            return self.shift_dacs_to_norm, self.scale_dacs_to_norm
+        if signal_type == "pa":
+            if self.scale_dacs_to_pa is None or self.shift_dacs_to_pa is None:
+                raise RemoraError("pA scaling factors not set")
+            return self.shift_dacs_to_pa, self.scale_dacs_to_pa
+        if signal_type == "zc_pa":
+            if self.shift_pa_to_zc_pa is None or self.scale_pa_to_zc_pa is None:
+                raise RemoraError("Zero-centred pA scaling factors not set")
+            return (self.shift_dacs_to_pa + self.scale_dacs_to_pa * self.shift_pa_to_zc_pa,
+                    self.scale_dacs_to_pa * self.scale_pa_to_zc_pa)
+        if signal_type == "dac":
+            return 0.0, 1.0
+        raise RemoraError(f"Invalid signal_type: {signal_type}")
+
+    def get_sig_type(self, signal_type):
+        shift, scale = self._sig_scaling(signal_type)
+        return self.dacs if signal_type == "dac" else (self.dacs - shift) / scale
+
+    def set_refine_signal_mapping(self, sig_map_refiner, ref_mapping=False):
+        """Refine the reference (`ref_mapping`) or basecall mapping and take over the refiner's scaling
+        (src/remora/io.py:2179-2213)."""
+        if sig_map_refiner is None:
+            return
+        remora_read = self.into_remora_read(ref_mapping)
+        remora_read.refine_signal_mapping(sig_map_refiner)
+        if ref_mapping:
+            self.ref_to_signal = remora_read.seq_to_sig_map + self.ref_to_signal[0]
+        else:
+            self.query_to_signal = remora_read.seq_to_sig_map + self.query_to_signal[0]
+        self.shift_dacs_to_norm, self.scale_dacs_to_norm = remora_read.shift, remora_read.scale
+        self.shift_pa_to_norm = (self.shift_dacs_to_norm - self.shift_dacs_to_pa) / self.scale_dacs_to_pa
+        self.scale_pa_to_norm = self.scale_dacs_to_norm / self.scale_dacs_to_pa
+
+    def compute_per_base_metric(self, metric=None, metric_func=None, ref_anchored=True, region=None, signal_type="norm", **kwargs):
+        """A per-base metric of this read (src/remora/io.py:2394-2479): `metric` names one of metrics.METRIC_FUNCS and runs
+        on the GPU (rmr_base_metrics on the read's int16 samples: the same bits as DeviceReads.per_base_metrics gives the read
+        inside a batch); `metric_func(sig, seq_to_sig, **kwargs)` is called on the host with the float signal.  `region`
+        (RefRegion; basecall coordinates when not `ref_anchored`) selects the bases; positions of the region the read does not
+        cover are NaN.  Read-oriented, as in the reference."""
+        from . import metrics
+
+        if metric is not None and metric not in metrics.METRIC_FUNCS:
+            raise RemoraError(f"Unknown per-base metric: {metric}")
+        if metric is None and metric_func is None:
+            raise RemoraError("Must provide either metric or metric_func")
+        full_map = self.ref_to_signal if ref_anchored else self.query_to_signal
+        if full_map is None:
+            raise RemoraError("Missing move table" if region is None else
+                              f"Missing {'ref' if ref_anchored else 'query'}_to_signal (move table)")
+        n_bases = full_map.size - 1
+        # bases [first, last) of the read are asked for; `lead` positions of the region lie before the read's first base
+        first, last, lead = 0, n_bases, 0
+        if region is not None and ref_anchored:
+            mine = self.ref_reg
+            if (mine.ctg, mine.strand) != (region.ctg, region.strand):
+                raise RemoraError("Region contig/strand do not match read")
+            if min(mine.end, region.end) <= max(mine.start, region.start):
+                raise RemoraError("Region does not overlap read.")
+            # read-oriented offset of the region's first position from the read's first base: the strand decides which end that is
+            offset = region.start - mine.start if mine.strand == "+" else mine.end - region.end
+            first, last, lead = max(offset, 0), min(offset + region.len, n_bases), max(-offset, 0)
+        elif region is not None:
+            if not 0 <= region.start <= len(self.seq):
+                raise RemoraError("Region does not overlap read.")
+            # (the reference slices the mapping with the region's own bounds here: one base fewer than the region names)
+            first, last = region.start, max(region.start, min(region.end - 1, n_bases))
+        if metric is not None:
+            # the whole read goes through the kernel and the region is cut from its results: a base's sums are grouped from the
+            # read's first base on, so a region returns the very bits the whole read (and the read inside a batch) gives
+            shift, scale = self._sig_scaling(signal_type)
+            vals = metrics.read_base_metrics(self.dacs, shift, scale, full_map, metric, kwargs.get("start_trim", metrics.DEFAULT_START_TRIM),
+                                             kwargs.get("end_trim", metrics.DEFAULT_END_TRIM))
+            vals = {name: v[first:last] for name, v in vals.items()}
+        else:
+            vals = metric_func(self.get_sig_type(signal_type), full_map[first : last + 1], **kwargs)
+        if region is not None and ref_anchored and last - first < region.len:  # the region reaches past the read: NaN there
+            wide = {name: np.full(region.len, np.nan) for name in vals}
+            for name, v in vals.items():
+                wide[name][lead : lead + v.size] = v
+            vals = wide
+        return vals
+
     def compute_pa_to_norm_scaling(self, factor=PA_TO_NORM_SCALING_FACTOR):
         """src/remora/io.py:1851-1856 (median / MAD)."""
         pa = self.pa_signal
@@ -1972,6 +2066,80 @@ def iter_ingest_batches(pod5_path, bam_path, pa_scaling=None, skip_non_primary=T
             continue
         got.per_read = per_read  # for a consumer that finds it cannot use the batch after all (dataset prepare: a refiner's band error)
         yield got
+
+
+def add_site_levels(acc, pod5_path, bam_path, sig_map_refiner, start_trim=1, end_trim=1, sample=0, reads_per_batch=256, device=None):
+    """One streaming pass over `bam_path`: every primary, mapped read with a move table and an MD tag is anchored on its
+    reference bases (iter_ingest_batches, ref_anchored), its signal mapping refined as Read.set_refine_signal_mapping(..,
+    ref_mapping=True) does (src/remora/io.py:861-863), and the trimmed mean of every base joins `acc` (metrics.SiteLevels) on
+    the device.  A batch the array ingest or the resident refinement does not cover (the iterative refiner, a read whose band
+    the refiner rejects) goes read by read through the same kernels; a read that cannot be anchored or refined is left out,
+    as `missing_ok` / the reference's per-read errors leave it out.  -> number of reads used."""
+    from .data_chunks import DeviceReads
+    from .metrics import site_key0
+
+    refiner = sig_map_refiner
+    loaded = refiner is not None and getattr(refiner, "is_loaded", False)
+    used = 0
+    for item in iter_ingest_batches(pod5_path, bam_path, batch=reads_per_batch, device=device, ref_anchored=True):
+        if isinstance(item, IngestBatch) and not (loaded and refiner.scale_iters > 0):
+            if not item.good.size:
+                continue
+            dr, stubs = item.dr, item.reads
+            try:
+                if loaded and refiner.do_rough_rescale:
+                    refiner.rough_rescale_device(dr, stubs)
+                if loaded and refiner.scale_iters == 0:
+                    refiner.refine_device_reads(dr, stubs)
+            except RemoraError:
+                pairs = item.per_read()
+            else:
+                rb, gk, lens = item.rb, item.keep[item.good], np.diff(item.seq_off)
+                acc.add(dr.per_base_metrics("dwell_trimmean", start_trim, end_trim)["trimmean"], dr.iseq,
+                        site_key0(sample, rb.ref_id[gk], (rb.flag[gk] & 16) != 0, rb.pos[gk], lens), lens)
+                used += int(lens.size)
+                continue
+        else:
+            pairs = item.per_read() if isinstance(item, IngestBatch) else item
+        rrs, recs = [], []
+        for io_read, err in pairs:
+            if err is not None or io_read.ref_to_signal is None:
+                continue
+            try:
+                rrs.append(io_read.into_remora_read(True))
+            except RemoraError:
+                continue
+            recs.append(io_read.record)
+        if loaded and rrs:
+            errs = refiner.refine_reads(rrs)
+            rrs, recs = [r for r, e in zip(rrs, errs) if e is None], [c for c, e in zip(recs, errs) if e is None]
+        if not rrs:
+            continue
+        dr = DeviceReads(rrs, get_engine(device))
+        lens = np.diff(dr.seq_off)
+        acc.add(dr.per_base_metrics("dwell_trimmean", start_trim, end_trim)["trimmean"], dr.iseq,
+                site_key0(sample, [c.reference_id for c in recs], [c.is_reverse for c in recs], [c.reference_start for c in recs], lens), lens)
+        used += int(lens.size)
+    return used
+
+
+def get_site_kmer_levels(pod5_path, bam_path, sig_map_refiner, kmer_context_bases, min_cov=10, chunk_len=None, max_chunk_cov=None,
+                         start_trim=1, end_trim=1, num_workers=1, reverse_signal=False, device=None):
+    """{k-mer: float64 array of the levels of its reference sites, ascending} for every k-mer over ACGT
+    (src/remora/io.py:991-1044).  A site's level is the median over the reads of the trimmed mean of the base on it; sites with
+    fewer than `min_cov` finite values are left out.  Computed on the GPU in one streaming pass over the BAM (add_site_levels,
+    metrics.SiteLevels), every read used: where the reference walks an indexed BAM in regions of `chunk_len` bases and
+    sub-samples a region whose mean coverage exceeds `max_chunk_cov`, both arguments are accepted and ignored here (no index is
+    needed; the results are the reference's whenever no region exceeds that coverage); `num_workers` likewise."""
+    from .metrics import SiteLevels, kmer_strings
+
+    if reverse_signal:
+        raise RemoraError("k-mer levels from reverse signal are not supported")
+    acc = SiteLevels(get_engine(device), kmer_context_bases, min_cov)
+    add_site_levels(acc, pod5_path, bam_path, sig_map_refiner, start_trim, end_trim, device=device)
+    _, counts, _, site_level = acc.levels(want_sites=True)
+    bounds = np.concatenate([[0], np.cumsum(counts)])
+    return {kmer: site_level[bounds[i] : bounds[i + 1]] for i, kmer in enumerate(kmer_strings(acc.kmer_len))}
 
 
 # ---- BAM output (SURVEY §8f row N3): the reference writes `pysam.AlignedSegment.from_dict(
