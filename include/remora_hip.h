@@ -204,6 +204,18 @@ int rmr_signal_histograms(rmr_engine *e, const int16_t *signal, const int64_t *s
 int rmr_assemble_reads(rmr_engine *e, int64_t n_reads, const int16_t *signal, const int64_t *src_start, const int64_t *q2s,
                        const int64_t *q2s_off, const int64_t *seq_len, int16_t *dacs, int64_t dacs_cap, int64_t *s2s,
                        int64_t *d_sig_off, int64_t *d_seq_off, int64_t *sig_off);
+/* The same with a direction.  replaces: the `reverse_signal` branches of that tail (src/remora/io.py:2001-2010: the signal of
+ * an alignment is dacs[::-1][sp:][ts:ns][::-1] of the already reversed dacs, i.e. the SAME window of the raw signal, reversed;
+ * :401-402: query_to_signal = sig_len - q2s[::-1]; :2123-2177 as above) - the reads of models whose metadata says
+ * reverse_signal (direct RNA).  span_len[i] (host) is the length of read i's trimmed window, signal[src_start[i] ..
+ * src_start[i] + span_len[i]); with reverse_signal != 0 the coordinates q = q2s[q2s_off[i] ...] are those of the reversed
+ * window (rmr_parse_moves_batch with reverse_signal = 1, or the composition rmr_ref_anchor_batch_dir wrote) and the read keeps
+ *     dacs_i[k] = signal[src_start[i] + span_len[i] - 1 - (q[0] + k)],  0 <= k < q[last] - q[0];   s2s_i[k] = q[k] - q[0].
+ * A mapping outside [0, span_len[i]] fails the call (RMR_ERR_INVALID) before anything is copied.  With reverse_signal == 0
+ * span_len is not read (NULL allowed) and the call IS rmr_assemble_reads, which forwards here. */
+int rmr_assemble_reads_dir(rmr_engine *e, int64_t n_reads, const int16_t *signal, const int64_t *src_start, const int64_t *span_len,
+                           int reverse_signal, const int64_t *q2s, const int64_t *q2s_off, const int64_t *seq_len, int16_t *dacs,
+                           int64_t dacs_cap, int64_t *s2s, int64_t *d_sig_off, int64_t *d_seq_off, int64_t *sig_off);
 
 /* ---- N1: BAM records for the POD5+BAM ingest (host code: BGZF inflate + record / tag decode) ---------- */
 /* replaces: what ReadIndexedBam / pysam hand to io.Read.add_alignment (src/remora/io.py:184-358, :1972-2084):
@@ -315,6 +327,15 @@ int rmr_ref_to_signal(const uint32_t *cigar, int64_t n_ops, int reverse, const i
 int rmr_ref_anchor_batch(int64_t n, const int8_t *mv, const int64_t *mv_off, const int64_t *sig_len, const int64_t *seq_len,
                          const uint32_t *cigar, const int64_t *cigar_off, const uint8_t *reverse, const int64_t *ref_len,
                          int64_t *r2s, const int64_t *r2s_off, int32_t *status, int threads);
+/* The same for signal recorded 3'->5' (`reverse_signal` models).  replaces: the reverse_signal branch of io.parse_move_tag
+ * (src/remora/io.py:401-402: query_to_signal = sig_len - query_to_signal[::-1], after the two checks) inside the composition
+ * above - with reverse_signal != 0 the CIGAR walk interpolates in those reversed coordinates, exactly as Read.add_alignment +
+ * compute_ref_to_signal do for a read built with reverse_signal=True.  Same arguments otherwise, same status codes;
+ * reverse_signal == 0 IS rmr_ref_anchor_batch, which forwards here.  (`reverse` is the strand of the alignment, per record;
+ * `reverse_signal` the direction of the signal, per call.) */
+int rmr_ref_anchor_batch_dir(int64_t n, const int8_t *mv, const int64_t *mv_off, const int64_t *sig_len, const int64_t *seq_len,
+                             const uint32_t *cigar, const int64_t *cigar_off, const uint8_t *reverse, const int64_t *ref_len,
+                             int64_t *r2s, const int64_t *r2s_off, int32_t *status, int reverse_signal, int threads);
 
 /* The native BAM reader's own inflater for BGZF members, alone (host code; replaces zlib's inflate under
  * rmr_bam_read_batch, which itself stands in for htslib below pysam, src/remora/io.py:184-358): a raw RFC 1951 stream

@@ -306,7 +306,8 @@ def _estimate_kmer_levels(args):
             log.warning("Cannot estimate levels from BAM file without mappings or index")
             continue
         log.info(f"Extracting levels from {pod5_path} and {bam_path}")
-        add_site_levels(acc, pod5_path, bam_path, refiner, sample=sample, reads_per_batch=args.reads_per_batch, device=args.device)
+        add_site_levels(acc, pod5_path, bam_path, refiner, sample=sample, reads_per_batch=args.reads_per_batch, device=args.device,
+                        reverse_signal=args.reverse_signal)
     log.info("Aggregating and outputting levels")
     levels, _ = acc.levels()
     if np.isnan(levels).any():
@@ -439,6 +440,9 @@ def build_parser():
     k.add_argument("--num-workers", type=int, default=1, help="accepted for the reference's command lines; ignored")
     k.add_argument("--chunk-width", type=int, default=1_000, help="accepted for the reference's command lines; ignored")
     k.add_argument("--max-chunk-coverage", type=int, default=100, help="accepted for the reference's command lines; ignored")
+    k.add_argument("--reverse-signal", action="store_true",
+                   help="the signal was recorded 3'->5' (direct RNA): build the reads as models with reverse_signal read them. "
+                        "The reference's get_site_kmer_levels takes this argument, its command line does not expose it")
     k.add_argument("--reads-per-batch", type=int, default=256)
     k.add_argument("--device", type=int, default=0)
     k.set_defaults(func=_estimate_kmer_levels)

@@ -392,12 +392,15 @@ int launch_moves_batch(rmr_engine *e, const int8_t *mv_tags, const int64_t *mv_o
 // its move table maps, signal[src_start[i] + q2s_i[0] .. src_start[i] + q2s_i[last]), and its mapping re-based to 0.
 // Pass 1 (one thread per read): the kept length; pass 2 (grid = reads x segments): the copies, coalesced.
 // ---------------------------------------------------------------------------------------
-__global__ void assemble_lengths_kernel(const int64_t *q2s, const int64_t *q2s_off, const int64_t *seq_len, int64_t n,
-                                        int64_t *len_out) {
+// `span_len` (reversed signal only, else NULL): a mapping that leaves its window [0, span_len[i]] is reported as INT64_MIN -
+// the reversed copy addresses the signal from the window's END, so the window has to hold the mapping
+__global__ void assemble_lengths_kernel(const int64_t *q2s, const int64_t *q2s_off, const int64_t *seq_len, const int64_t *span_len,
+                                        int64_t n, int64_t *len_out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int64_t *q = q2s + q2s_off[i];
-    len_out[i] = q[seq_len[i]] - q[0];
+    const int64_t q0 = q[0], q1 = q[seq_len[i]];
+    len_out[i] = (span_len && (q0 < 0 || q1 > span_len[i])) ? INT64_MIN : q1 - q0;
 }
 
 __global__ __launch_bounds__(256) void assemble_reads_kernel(const int16_t *signal, const int64_t *src_start, const int64_t *q2s,
@@ -410,6 +413,40 @@ __global__ __launch_bounds__(256) void assemble_reads_kernel(const int16_t *sign
     int16_t *dst = dacs + sig_off[i];
     const int64_t step = (int64_t)gridDim.y * blockDim.x, t0 = (int64_t)blockIdx.y * blockDim.x + threadIdx.x;
     for (int64_t k = t0; k < n_sig; k += step) dst[k] = src[k];
+    int64_t *m = s2s + seq_off[i] + i;
+    for (int64_t k = t0; k < n_map; k += step) m[k] = q[k] - first;
+}
+
+// The same for signal recorded 3'->5' (`reverse_signal` models, src/remora/io.py:2001-2010, :401-402): the read's signal is its
+// trimmed window REVERSED, q holds coordinates of that reversed window (moves_batch_kernel, reverse), so with
+// hi = signal + src_start[i] + span_len[i] - q[0] the read keeps dacs[k] = hi[-1 - k], 0 <= k < q[last] - q[0].
+// Same grid.  A thread moves four samples at a time: one 8-byte load (2-byte aligned: the source run ends wherever the window
+// does), the four samples swapped end for end in registers, one 8-byte store aligned on the destination; a wave reads a
+// contiguous 512 bytes and writes a contiguous 512 bytes, only the order inside the run flips.  The up to three samples in
+// front of the first aligned destination word and behind the last whole one go one by one.
+__global__ __launch_bounds__(256) void assemble_reads_rev_kernel(const int16_t *signal, const int64_t *src_start, const int64_t *span_len,
+                                                                 const int64_t *q2s, const int64_t *q2s_off, const int64_t *sig_off,
+                                                                 const int64_t *seq_off, int16_t *dacs, int64_t *s2s) {
+    const int64_t i = blockIdx.x;
+    const int64_t *q = q2s + q2s_off[i];
+    const int64_t first = q[0], n_sig = sig_off[i + 1] - sig_off[i], n_map = seq_off[i + 1] - seq_off[i] + 1;
+    const int16_t *hi = signal + src_start[i] + span_len[i] - first;  // one past the last sample kept
+    int16_t *dst = dacs + sig_off[i];
+    const int64_t step = (int64_t)gridDim.y * blockDim.x, t0 = (int64_t)blockIdx.y * blockDim.x + threadIdx.x;
+    int64_t head = (int64_t)((0 - ((uintptr_t)dst >> 1)) & 3);  // samples in front of the first 8-byte boundary of dst
+    head = head < n_sig ? head : n_sig;
+    const int64_t n_quad = (n_sig - head) >> 2, tail0 = head + 4 * n_quad;
+    if (t0 < head) dst[t0] = hi[-1 - t0];
+    if (t0 < n_sig - tail0) dst[tail0 + t0] = hi[-1 - tail0 - t0];
+    for (int64_t g = t0; g < n_quad; g += step) {
+        const int64_t k = head + 4 * g;
+        uint2 v;
+        __builtin_memcpy(&v, hi - k - 4, 8);  // samples k+3, k+2, k+1, k of the read, in that order
+        uint2 o;
+        o.x = (v.y >> 16) | (v.y << 16);
+        o.y = (v.x >> 16) | (v.x << 16);
+        *reinterpret_cast<uint2 *>(dst + k) = o;
+    }
     int64_t *m = s2s + seq_off[i] + i;
     for (int64_t k = t0; k < n_map; k += step) m[k] = q[k] - first;
 }
@@ -487,16 +524,23 @@ int launch_signal_hist(rmr_engine *e, const int16_t *signal, const int64_t *star
     return 0;
 }
 
-int launch_assemble_lengths(rmr_engine *e, const int64_t *q2s, const int64_t *q2s_off, const int64_t *seq_len, int64_t n, int64_t *len_out) {
-    hipLaunchKernelGGL(assemble_lengths_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, q2s, q2s_off, seq_len, n, len_out);
+int launch_assemble_lengths(rmr_engine *e, const int64_t *q2s, const int64_t *q2s_off, const int64_t *seq_len, const int64_t *span_len,
+                            int64_t n, int64_t *len_out) {
+    hipLaunchKernelGGL(assemble_lengths_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, q2s, q2s_off, seq_len, span_len, n,
+                       len_out);
     RMR_HIP(hipGetLastError());
     return 0;
 }
 
-int launch_assemble_reads(rmr_engine *e, const int16_t *signal, const int64_t *src_start, const int64_t *q2s, const int64_t *q2s_off,
-                          const int64_t *sig_off, const int64_t *seq_off, int64_t n, int16_t *dacs, int64_t *s2s) {
-    hipLaunchKernelGGL(assemble_reads_kernel, dim3((unsigned)n, 16), dim3(256), 0, e->stream, signal, src_start, q2s, q2s_off, sig_off,
-                       seq_off, dacs, s2s);
+// span_len != NULL: the reversed copy (signal recorded 3'->5')
+int launch_assemble_reads(rmr_engine *e, const int16_t *signal, const int64_t *src_start, const int64_t *span_len, const int64_t *q2s,
+                          const int64_t *q2s_off, const int64_t *sig_off, const int64_t *seq_off, int64_t n, int16_t *dacs, int64_t *s2s) {
+    if (span_len)
+        hipLaunchKernelGGL(assemble_reads_rev_kernel, dim3((unsigned)n, 16), dim3(256), 0, e->stream, signal, src_start, span_len, q2s, q2s_off,
+                           sig_off, seq_off, dacs, s2s);
+    else
+        hipLaunchKernelGGL(assemble_reads_kernel, dim3((unsigned)n, 16), dim3(256), 0, e->stream, signal, src_start, q2s, q2s_off, sig_off,
+                           seq_off, dacs, s2s);
     RMR_HIP(hipGetLastError());
     return 0;
 }

@@ -120,9 +120,11 @@ extern "C" int rmr_ref_to_signal(const uint32_t *cigar, int64_t n_ops, int rever
 // rmr_parse_moves_batch; 1 "Discordant ref seq lengths" (io.py:2078-2079); 2 "Invalid cigar op(s)"; 3 "No match operations
 // found in alignment cigar"; 4 a CIGAR with an empty match run (the caller's array form handles it); 8 no move table;
 // 9 move table fine, no reference sequence.
-extern "C" int rmr_ref_anchor_batch(int64_t n, const int8_t *mv, const int64_t *mv_off, const int64_t *sig_len, const int64_t *seq_len,
-                                    const uint32_t *cigar, const int64_t *cigar_off, const uint8_t *reverse, const int64_t *ref_len,
-                                    int64_t *r2s, const int64_t *r2s_off, int32_t *status, int threads) {
+// `reverse_signal` (signal recorded 3'->5'): query_to_signal = sig_len - query_to_signal[::-1] once the move table has passed
+// its checks (io.py:401-402), and the walk interpolates in those coordinates.
+extern "C" int rmr_ref_anchor_batch_dir(int64_t n, const int8_t *mv, const int64_t *mv_off, const int64_t *sig_len, const int64_t *seq_len,
+                                        const uint32_t *cigar, const int64_t *cigar_off, const uint8_t *reverse, const int64_t *ref_len,
+                                        int64_t *r2s, const int64_t *r2s_off, int32_t *status, int reverse_signal, int threads) {
     if (n < 0 || !mv_off || !sig_len || !seq_len || !cigar_off || !reverse || !ref_len || !r2s_off || !status || (n > 0 && (!mv || !r2s)))
         RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
     auto work = [&](int64_t i0, int64_t i1) {
@@ -141,6 +143,13 @@ extern "C" int rmr_ref_anchor_batch(int64_t n, const int8_t *mv, const int64_t *
             if (seq_len[i] >= 0 && cnt != seq_len[i]) { status[i] = RMR_ERR_DISCORDANT_SEQ; continue; }
             if (nmv != sig_len[i] / stride) { status[i] = RMR_ERR_DISCORDANT_SIG; continue; }
             if (ref_len[i] < 0) { status[i] = 9; continue; }  // (the move table is checked first, as add_alignment does)
+            if (reverse_signal) {
+                for (int64_t a = 0, b = cnt; a <= b; ++a, --b) {
+                    const int64_t lo = sig_len[i] - q2s[(size_t)b], hi = sig_len[i] - q2s[(size_t)a];
+                    q2s[(size_t)a] = lo;
+                    q2s[(size_t)b] = hi;
+                }
+            }
             int64_t n_out = 0;
             const int rc = ref_to_signal_core(cigar + cigar_off[i], cigar_off[i + 1] - cigar_off[i], reverse[i] != 0, q2s.data(), (int64_t)q2s.size(),
                                               r2s + r2s_off[i], ref_len[i] + 1, &n_out);
@@ -157,4 +166,10 @@ extern "C" int rmr_ref_anchor_batch(int64_t n, const int8_t *mv, const int64_t *
     for (int t = 0; t < threads; ++t) pool.emplace_back(work, n * t / threads, n * (t + 1) / threads);
     for (auto &th : pool) th.join();
     return RMR_OK;
+}
+
+extern "C" int rmr_ref_anchor_batch(int64_t n, const int8_t *mv, const int64_t *mv_off, const int64_t *sig_len, const int64_t *seq_len,
+                                    const uint32_t *cigar, const int64_t *cigar_off, const uint8_t *reverse, const int64_t *ref_len,
+                                    int64_t *r2s, const int64_t *r2s_off, int32_t *status, int threads) {
+    return rmr_ref_anchor_batch_dir(n, mv, mv_off, sig_len, seq_len, cigar, cigar_off, reverse, ref_len, r2s, r2s_off, status, 0, threads);
 }

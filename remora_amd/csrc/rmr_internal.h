@@ -180,9 +180,10 @@ int launch_moves_batch(rmr_engine *e, const int8_t *mv_tags, const int64_t *mv_o
 int launch_signal_range(rmr_engine *e, const int16_t *signal, const int64_t *start, const int64_t *len, int64_t n, int32_t *lo, int32_t *hi);
 int launch_signal_hist(rmr_engine *e, const int16_t *signal, const int64_t *start, const int64_t *len, const int32_t *lo,
                        const int64_t *hist_off, int64_t n, unsigned int *hist);
-int launch_assemble_lengths(rmr_engine *e, const int64_t *q2s, const int64_t *q2s_off, const int64_t *seq_len, int64_t n, int64_t *len_out);
-int launch_assemble_reads(rmr_engine *e, const int16_t *signal, const int64_t *src_start, const int64_t *q2s, const int64_t *q2s_off,
-                          const int64_t *sig_off, const int64_t *seq_off, int64_t n, int16_t *dacs, int64_t *s2s);
+int launch_assemble_lengths(rmr_engine *e, const int64_t *q2s, const int64_t *q2s_off, const int64_t *seq_len, const int64_t *span_len,
+                            int64_t n, int64_t *len_out);
+int launch_assemble_reads(rmr_engine *e, const int16_t *signal, const int64_t *src_start, const int64_t *span_len, const int64_t *q2s,
+                          const int64_t *q2s_off, const int64_t *sig_off, const int64_t *seq_off, int64_t n, int16_t *dacs, int64_t *s2s);
 int launch_geometry(rmr_engine *e, const rmr_reads &d, int64_t n_chunks, const int32_t *chunk_read,
                     float *sig_out, int64_t total_sig, const int32_t *sig_read, int64_t *geo,
                     int *d_max_seq_len);

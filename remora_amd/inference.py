@@ -562,12 +562,12 @@ def infer_from_pod5_and_bam(pod5_path, in_bam_path, model, model_metadata, out_b
 
     refiner0 = mds[0].get("sig_map_refiner")
     iterative = refiner0 is not None and getattr(refiner0, "is_loaded", False) and refiner0.scale_iters > 0
-    # forward signal, either anchor: the batch ingest (io.iter_ingest_batches) - trimming, move tables, scaling and the read
-    # arrays of a whole BAM batch on the GPU, no Python object per read.  Several models (one per canonical base,
+    # either signal direction, either anchor: the batch ingest (io.iter_ingest_batches) - trimming, move tables, scaling and the
+    # read arrays of a whole BAM batch on the GPU, no Python object per read.  Several models (one per canonical base,
     # src/remora/inference.py:286,311-315) share the resident reads when none of them refines the mapping (refinement rewrites
-    # it per model: those, reverse signal and iterative re-scaling go read by read)
+    # it per model: those and iterative re-scaling go read by read)
     any_refiner = any(getattr(md.get("sig_map_refiner"), "is_loaded", False) for md in mds)
-    batch_ingest = ((len(models) == 1 or not any_refiner) and not reverse_signal and not iterative
+    batch_ingest = ((len(models) == 1 or not any_refiner) and not iterative
                     and os.environ.get("RMR_INFER_BATCH_INGEST", "1") != "0")
 
     def batches():
@@ -575,7 +575,7 @@ def infer_from_pod5_and_bam(pod5_path, in_bam_path, model, model_metadata, out_b
             seen = 0
             for ib in rio.iter_ingest_batches(pod5_path, in_bam_path, pa_scaling=pa_scaling, skip_non_primary=skip_non_primary,
                                               batch=reads_per_batch, shard=shard, device=models[0].engine.device,
-                                              ref_anchored=ref_anchored):
+                                              ref_anchored=ref_anchored, reverse_signal=reverse_signal):
                 if num_reads is not None and seen + len(ib) >= num_reads:
                     left = num_reads - seen
                     if left > 0:

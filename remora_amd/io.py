@@ -1789,10 +1789,16 @@ def _section_clock():
     return clock
 
 
-def _ingest_batch(rb, records, signals, eng, pa_scaling, skip_non_primary, ref_anchored=False):
+def _ingest_batch(rb, records, signals, eng, pa_scaling, skip_non_primary, ref_anchored=False, reverse_signal=False):
     """IngestBatch of one raw BAM batch, or None when nothing of it is kept.  Everything Read.from_pod5 + add_alignment +
-    into_remora_read (forward signal) do per read, for the batch: trimming by sp / ts / ns, strand-aware
+    into_remora_read do per read, for the batch: trimming by sp / ts / ns, strand-aware
     sequence, move tables -> query_to_signal (one launch), sm / sd composed with the calibration, the trim to the mapped span.
+    `reverse_signal` (models of signal recorded 3'->5', src/remora/io.py:2001-2010, :401-402): the trimmed window is the same
+    window of the raw signal, the read's samples are that window reversed and the move-table coordinates
+    sig_len - query_to_signal[::-1]; the expansion (rmr_parse_moves_batch), the reference-anchor composition
+    (rmr_ref_anchor_batch_dir) and the assembly (rmr_assemble_reads_dir) take the flag, everything else - median / MAD
+    scaling (an order statistic of the window), calibration, base orientation, the error texts and their order - is as for
+    forward signal.
     `ref_anchored` (`infer --reference-anchored`; `rb` read with want_ref): the reads are anchored on the reference bases of
     their alignments instead of their basecalls - move table and CIGAR composed per record by native threads
     (rmr_ref_anchor_batch: src/remora/io.py:2066-2084), the reference sequence rebuilt from MD by the native reader, and
@@ -1879,10 +1885,11 @@ def _ingest_batch(rb, records, signals, eng, pa_scaling, skip_non_primary, ref_a
         mv_arr = rb.mv if total_mv else np.zeros(1, np.int8)
         cig_arr = np.ascontiguousarray(rb.cigar, np.uint32) if rb.cigar.size else np.zeros(1, np.uint32)
         rev8 = np.ascontiguousarray(is_rev_all, np.uint8)
-        L.check(L.lib().rmr_ref_anchor_batch(n_all, pp(mv_arr), pp(np.ascontiguousarray(rb.mv_off, np.int64)), pp(sl_all),
-                                             pp(np.ascontiguousarray(seq_len_all, np.int64)), pp(cig_arr),
-                                             pp(np.ascontiguousarray(rb.cigar_off, np.int64)), pp(rev8), pp(ref_len_all), pp(r2s),
-                                             pp(r2s_off), pp(status_all), int(os.environ.get("RMR_PACK_THREADS", "8"))))
+        L.check(L.lib().rmr_ref_anchor_batch_dir(n_all, pp(mv_arr), pp(np.ascontiguousarray(rb.mv_off, np.int64)), pp(sl_all),
+                                                 pp(np.ascontiguousarray(seq_len_all, np.int64)), pp(cig_arr),
+                                                 pp(np.ascontiguousarray(rb.cigar_off, np.int64)), pp(rev8), pp(ref_len_all), pp(r2s),
+                                                 pp(r2s_off), pp(status_all), int(bool(reverse_signal)),
+                                                 int(os.environ.get("RMR_PACK_THREADS", "8"))))
         status = status_all[keep]
         if (status == 4).any():
             return "slow"  # a CIGAR with an empty match run: the array form of the per-read path does what numpy does with it
@@ -1896,8 +1903,8 @@ def _ingest_batch(rb, records, signals, eng, pa_scaling, skip_non_primary, ref_a
         # record, tables of length 0 included
         d_cnt = torch.empty(n_all, dtype=torch.int64, device=dev)
         d_st = torch.empty(n_all, dtype=torch.int32, device=dev)
-        L.check(L.lib().rmr_parse_moves_batch(eng.handle, d_mv.data_ptr(), d_off.data_ptr(), d_sl.data_ptr(), d_ql.data_ptr(), n_all, 1, 0,
-                                              d_q2s.data_ptr(), d_cnt.data_ptr(), d_st.data_ptr(), L.MEM_DEVICE))
+        L.check(L.lib().rmr_parse_moves_batch(eng.handle, d_mv.data_ptr(), d_off.data_ptr(), d_sl.data_ptr(), d_ql.data_ptr(), n_all, 1,
+                                              int(bool(reverse_signal)), d_q2s.data_ptr(), d_cnt.data_ptr(), d_st.data_ptr(), L.MEM_DEVICE))
         eng.synchronize()
         status = d_st.cpu().numpy()[keep]
     clock("moves_or_ref_anchor")
@@ -1965,7 +1972,8 @@ def _ingest_batch(rb, records, signals, eng, pa_scaling, skip_non_primary, ref_a
     else:
         sm, sd = np.full(good.size, float(pa_scaling[0])), np.full(good.size, float(pa_scaling[1]))
     shift, scale = cal_off + cal_scale * sm, cal_scale * sd
-    # ---- dacs = trimmed[map[0]:map[-1]], mapping re-based: assembled where the pieces already are ----
+    # ---- dacs = trimmed[map[0]:map[-1]] (reverse signal: of the reversed window), mapping re-based: assembled where the
+    #      pieces already are ----
     n_good = int(good.size)
     n_seq = int(out.seq_off[-1])
     if ref_anchored:  # ref_to_signal of the good records takes query_to_signal's place
@@ -1983,8 +1991,10 @@ def _ingest_batch(rb, records, signals, eng, pa_scaling, skip_non_primary, ref_a
     sig_off = np.zeros(n_good + 1, np.int64)
     p = lambda x: x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
     ss = np.ascontiguousarray(src_start[good], np.int64)
-    L.check(L.lib().rmr_assemble_reads(eng.handle, n_good, flat.data_ptr(), p(ss), d_q2s.data_ptr(), p(map_off), p(seq_len), dacs.data_ptr(),
-                                       dacs.numel(), s2s.data_ptr(), d_sig_off.data_ptr(), d_seq_off.data_ptr(), p(sig_off)))
+    span = np.ascontiguousarray(sig_len[good], np.int64)
+    L.check(L.lib().rmr_assemble_reads_dir(eng.handle, n_good, flat.data_ptr(), p(ss), p(span), int(bool(reverse_signal)), d_q2s.data_ptr(),
+                                           p(map_off), p(seq_len), dacs.data_ptr(), dacs.numel(), s2s.data_ptr(), d_sig_off.data_ptr(),
+                                           d_seq_off.data_ptr(), p(sig_off)))
     clock("assemble_launch")
     d_iseq = torch.from_numpy(iseq).to(dev)
     eng.synchronize()
@@ -2044,9 +2054,9 @@ def _readahead(gen, depth=2):
 
 
 def iter_ingest_batches(pod5_path, bam_path, pa_scaling=None, skip_non_primary=True, batch=256, shard=None, device=None,
-                        ref_anchored=False):
-    """The batch form of iter_reads_from_pod5_and_bam for calling of forward signal, anchored on the basecalls or (`ref_anchored`)
-    on the reference bases of the alignments: IngestBatch objects
+                        ref_anchored=False, reverse_signal=False):
+    """The batch form of iter_reads_from_pod5_and_bam for calling of forward or (`reverse_signal`) reversed signal, anchored on
+    the basecalls or (`ref_anchored`) on the reference bases of the alignments: IngestBatch objects
     (arrays on the GPU) instead of (io.Read, error) pairs; a batch the array form does not cover comes as the list of
     (io.Read, error) pairs the per-read path yields for its records."""
     from .engine import get_ingest_engine
@@ -2056,10 +2066,11 @@ def iter_ingest_batches(pod5_path, bam_path, pa_scaling=None, skip_non_primary=T
     raw_batches = iter_bam_raw_batches(bam_path, want_ref=bool(ref_anchored), batch=batch, shard=shard)
     raw_batches = _readahead(raw_batches, 2)  # the native parser releases the GIL: BAM batches are read one ahead
     for rb, records in raw_batches:
-        got = _ingest_batch(rb, records, signals, eng, pa_scaling, skip_non_primary, ref_anchored=ref_anchored)
+        got = _ingest_batch(rb, records, signals, eng, pa_scaling, skip_non_primary, ref_anchored=ref_anchored,
+                            reverse_signal=reverse_signal)
         if got is None:
             continue
-        per_read = lambda rb=rb: list(_reads_of_records(records(rb), signals, eng, False, pa_scaling, skip_non_primary,  # noqa: E731
+        per_read = lambda rb=rb: list(_reads_of_records(records(rb), signals, eng, bool(reverse_signal), pa_scaling, skip_non_primary,  # noqa: E731
                                                         max(batch, 2), bool(ref_anchored)))
         if isinstance(got, str):  # "slow": the per-read path for the records of this batch
             yield per_read()
@@ -2068,20 +2079,23 @@ def iter_ingest_batches(pod5_path, bam_path, pa_scaling=None, skip_non_primary=T
         yield got
 
 
-def add_site_levels(acc, pod5_path, bam_path, sig_map_refiner, start_trim=1, end_trim=1, sample=0, reads_per_batch=256, device=None):
+def add_site_levels(acc, pod5_path, bam_path, sig_map_refiner, start_trim=1, end_trim=1, sample=0, reads_per_batch=256, device=None,
+                    reverse_signal=False):
     """One streaming pass over `bam_path`: every primary, mapped read with a move table and an MD tag is anchored on its
     reference bases (iter_ingest_batches, ref_anchored), its signal mapping refined as Read.set_refine_signal_mapping(..,
     ref_mapping=True) does (src/remora/io.py:861-863), and the trimmed mean of every base joins `acc` (metrics.SiteLevels) on
     the device.  A batch the array ingest or the resident refinement does not cover (the iterative refiner, a read whose band
     the refiner rejects) goes read by read through the same kernels; a read that cannot be anchored or refined is left out,
-    as `missing_ok` / the reference's per-read errors leave it out.  -> number of reads used."""
+    as `missing_ok` / the reference's per-read errors leave it out.  `reverse_signal`: the reads are built as
+    io.Read.from_pod5 / add_alignment build them with reverse_signal=True (signal recorded 3'->5').  -> number of reads used."""
     from .data_chunks import DeviceReads
     from .metrics import site_key0
 
     refiner = sig_map_refiner
     loaded = refiner is not None and getattr(refiner, "is_loaded", False)
     used = 0
-    for item in iter_ingest_batches(pod5_path, bam_path, batch=reads_per_batch, device=device, ref_anchored=True):
+    for item in iter_ingest_batches(pod5_path, bam_path, batch=reads_per_batch, device=device, ref_anchored=True,
+                                    reverse_signal=reverse_signal):
         if isinstance(item, IngestBatch) and not (loaded and refiner.scale_iters > 0):
             if not item.good.size:
                 continue
@@ -2130,13 +2144,12 @@ def get_site_kmer_levels(pod5_path, bam_path, sig_map_refiner, kmer_context_base
     fewer than `min_cov` finite values are left out.  Computed on the GPU in one streaming pass over the BAM (add_site_levels,
     metrics.SiteLevels), every read used: where the reference walks an indexed BAM in regions of `chunk_len` bases and
     sub-samples a region whose mean coverage exceeds `max_chunk_cov`, both arguments are accepted and ignored here (no index is
-    needed; the results are the reference's whenever no region exceeds that coverage); `num_workers` likewise."""
+    needed; the results are the reference's whenever no region exceeds that coverage); `num_workers` likewise.
+    `reverse_signal` (src/remora/io.py:1002): the levels of reads built with reverse_signal=True - direct RNA."""
     from .metrics import SiteLevels, kmer_strings
 
-    if reverse_signal:
-        raise RemoraError("k-mer levels from reverse signal are not supported")
     acc = SiteLevels(get_engine(device), kmer_context_bases, min_cov)
-    add_site_levels(acc, pod5_path, bam_path, sig_map_refiner, start_trim, end_trim, device=device)
+    add_site_levels(acc, pod5_path, bam_path, sig_map_refiner, start_trim, end_trim, device=device, reverse_signal=reverse_signal)
     _, counts, _, site_level = acc.levels(want_sites=True)
     bounds = np.concatenate([[0], np.cumsum(counts)])
     return {kmer: site_level[bounds[i] : bounds[i + 1]] for i, kmer in enumerate(kmer_strings(acc.kmer_len))}

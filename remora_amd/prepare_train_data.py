@@ -404,15 +404,16 @@ def extract_chunk_dataset(bam_path, pod5_path, out_path, mod_base, mod_base_cont
             next_save += save_every
 
     refiner_iterative = (sig_map_refiner is not None and getattr(sig_map_refiner, "is_loaded", False) and sig_map_refiner.scale_iters > 0)
-    # reference anchor, motif-selected focus bases, forward signal: the batch ingest of `infer --reference-anchored`
+    # reference anchor, motif-selected focus bases, either signal direction: the batch ingest of `infer --reference-anchored`
     # (io.iter_ingest_batches: the reads of a BAM batch assembled on the GPU) - everything else read by read
-    if (not basecall_anchor and focus_ref_pos is None and not rev_sig and not refiner_iterative and
+    if (not basecall_anchor and focus_ref_pos is None and not refiner_iterative and
             os.environ.get("RMR_PREPARE_BATCH_INGEST", "1") != "0"):
         seen, t_loop = 0, _time.perf_counter()
         # (pa_scaling only travels in the dataset's metadata: training reads are scaled by sm / sd, prepare_train_data.py:66-72)
         dev_idx = engine.device if engine is not None else _torch().cuda.current_device()
         for ib in _prefetched(rio.iter_ingest_batches(pod5_path, bam_path, pa_scaling=None, skip_non_primary=skip_non_primary,
-                                                      batch=reads_per_batch, shard=shard, device=dev_idx, ref_anchored=True), dev_idx):
+                                                      batch=reads_per_batch, shard=shard, device=dev_idx, ref_anchored=True,
+                                                      reverse_signal=rev_sig), dev_idx):
             if seen >= num_reads:
                 break
             if seen + len(ib) > num_reads:
