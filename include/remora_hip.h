@@ -305,6 +305,77 @@ int rmr_records_with_mod_tags_ref(int64_t n_reads, const uint8_t *const *raw, co
                                   const uint8_t *has_tags, const char *ref_seq, const int64_t *ref_off, uint8_t *out, int64_t out_cap,
                                   int64_t *out_len);
 
+/* ---- `validate from_modbams`: modified-base calls read back from a BAM and joined with ground-truth sites -------------- */
+/* The MM / ML tokeniser (host code, native threads).
+ * replaces: htslib's bam_parse_basemod below pysam.AlignedSegment.modified_bases, which validate.check_mod_strand and
+ * validate.parse_mod_read consume per read (src/remora/validate.py:414-446, :322-335) - the text half of it: tags found,
+ * text turned into numbers; the walk along the read's bases is rmr_modbam_site_counts' (GPU).
+ * Records as rmr_bam_batch delivers them: record r = raw[raw_off[r] .. raw_off[r+1]), its tag region tags_off[r] bytes in.
+ * MM / Mm (type Z) and ML / Ml (type B, subtype C) are looked for; one MM entry is
+ *     ([ACGTUN])([+-])([a-z]+|[0-9]+)([.?]?)(,[0-9]+)*;
+ * a run of letters is that many single-letter codes (at most RMR_MOD_MAX_CODES), a run of digits one ChEBI code.  An entry
+ * of c codes and n deltas owns c * n ML bytes, call-major (per call the codes in listed order); ML is consumed in entry order.
+ * status[r]: 0 ok; 1 no MM tag; 2 malformed (tag region does not parse, MM / ML of another type, bad grammar, a number
+ * beyond int32, ML shorter or longer than the entries need, ML absent while an entry has deltas).  Records with a status
+ * other than 0 own no entries, deltas or ML bytes.
+ * rmr_mod_tags_sizes counts per record (n_entries, n_deltas, n_ml: int64[n]); the caller's exclusive prefix sums are the
+ * [n+1] offset tables of rmr_mod_tags_fill, which writes the entry table, the flat int32 deltas and the flat ML bytes
+ * (RMR_ERR_INVALID when the tables are not the counts of these records).  delta_off / ml_off inside an entry index the
+ * flat arrays of the batch. */
+#define RMR_MOD_MAX_CODES 16
+typedef struct rmr_mod_entry {
+    int64_t delta_off;               /* deltas[delta_off .. delta_off + n_deltas) */
+    int64_t ml_off;                  /* ml[ml_off .. ml_off + n_codes * n_deltas) */
+    int32_t n_deltas, n_codes;
+    int32_t chebi;                   /* the ChEBI code of a numeric entry (n_codes = 1, codes[0] = 0), else 0 */
+    char base, strand, flag, pad;    /* [ACGTUN], [+-], '.', '?' or 0 (absent) */
+    char codes[RMR_MOD_MAX_CODES];   /* single-letter codes in listed order */
+} rmr_mod_entry;
+int rmr_mod_tags_sizes(int64_t n, const uint8_t *raw, const int64_t *raw_off, const int64_t *tags_off, int32_t *status,
+                       int64_t *n_entries, int64_t *n_deltas, int64_t *n_ml, int threads);
+int rmr_mod_tags_fill(int64_t n, const uint8_t *raw, const int64_t *raw_off, const int64_t *tags_off, const int32_t *status,
+                      const int64_t *ent_off, const int64_t *delta_off, const int64_t *ml_off, rmr_mod_entry *entries, int32_t *deltas,
+                      uint8_t *ml, int threads);
+
+/* The site join (GPU; DEVICE pointers only, asynchronous on the engine's stream).
+ * replaces: validate.check_mod_strand + validate.parse_mod_read for a batch of records (src/remora/validate.py:296-446):
+ * the loop over pysam's get_aligned_pairs(with_seq=True) with a dictionary lookup per pair, and the base walk of
+ * modified_bases.  Per record, one workgroup:
+ *   - skipped whole, status set: 1 / 2 the tokeniser's status, 3 ref_id < 0, 4 no MD tag (has bit 7; the reference returns
+ *     nothing for such a read, :309-313), 5 no entry that counts (check_mod_strand), 2 also for a call beyond the last
+ *     occurrence of its base (any entry) and for a CIGAR whose query length is not the read's;
+ *   - the original sequence is the stored one, reverse-complemented for flag 0x10; call k of an entry sits on occurrence
+ *     d_0 + .. + d_k + k of the entry's base in it (N: every base; U counts T); its stored position is L-1-p there;
+ *   - entries that count: strand '+', and of their codes those among mod_codes (the alphabet's modified bases, n_mods <= 7;
+ *     ChEBI entries never count); p = (ML + 0.5) / 256 per code, the later entry wins where two give one code at one
+ *     position, other columns 0, column 0 = 1 - sum (all multiples of 1/512: exact);
+ *   - stored position -> reference position through the CIGAR (inside M / = / X only); the position is kept when the truth
+ *     table of (ref_id, strand of the record) holds it.
+ * Truth table: positions i64 ascending per (ref_id, strand) slice with their label u8, slice 2 * ref_id + (reverse ? 1 : 0)
+ * = [truth_off[s], truth_off[s+1]); a ref_id >= n_refs has no truth.
+ * rmr_modbam_site_counts writes counts i64[n] and status i32[n] and fills the workspaces ords i32[total deltas], cig_q /
+ * cig_r i64[total CIGAR words]; the caller's exclusive prefix sum of counts is out_off i64[n+1] of rmr_modbam_site_fill
+ * (same batch, same workspaces, same status), which writes probs f32[][n_mods + 1], label u8[], qpos i64[] (stored
+ * coordinate), rpos i64[]: records in batch order, ascending stored position inside a record (the order of aligned_pairs). */
+typedef struct rmr_modbam_batch {
+    int64_t n_records;
+    const uint8_t *seq;      const int64_t *seq_off;     /* ASCII bases as stored */
+    const uint32_t *cigar;   const int64_t *cigar_off;   /* BAM CIGAR words */
+    const int32_t *flag, *ref_id, *pos;
+    const uint8_t *has;                                  /* rmr_bam_batch.has */
+    const int32_t *tok_status;                           /* rmr_mod_tags_sizes */
+    const int64_t *ent_off;  const rmr_mod_entry *entries;
+    const int32_t *deltas;   const uint8_t *ml;
+    int64_t n_deltas, n_ml;                              /* sizes of the two flat arrays (bounds of the entries' ranges) */
+    int32_t n_mods; char mod_codes[8];
+    int64_t n_refs;          const int64_t *truth_off;   /* [2 * n_refs + 1] */
+    const int64_t *truth_pos; const uint8_t *truth_label;
+} rmr_modbam_batch;
+int rmr_modbam_site_counts(rmr_engine *e, const rmr_modbam_batch *b, int32_t *ords, int64_t *cig_q, int64_t *cig_r, int64_t *counts,
+                           int32_t *status);
+int rmr_modbam_site_fill(rmr_engine *e, const rmr_modbam_batch *b, const int32_t *ords, const int64_t *cig_q, const int64_t *cig_r,
+                         const int32_t *status, const int64_t *out_off, float *probs, uint8_t *label, int64_t *qpos, int64_t *rpos);
+
 /* The signal coordinate of every reference position of one alignment (host code).
  * replaces: compute_ref_to_signal = map_ref_to_signal(make_sequence_coordinate_mapping(cigar)), src/remora/data_chunks.py:60-122
  * (called from io.Read.add_alignment, src/remora/io.py:2070-2080), with np.interp's float64 arithmetic: the same integers.

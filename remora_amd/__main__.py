@@ -53,6 +53,37 @@ def _validate(args):
     return 0
 
 
+_IMPLICIT_TAGS = ("If implicit modified tag types (`.`) are included (from all-context modified base models) results from this command "
+                  "will be invalid: only the positions an MM tag lists are read, for `.` and `?` alike (what htslib reports; pysam "
+                  "issue 1123), so a skipped canonical site of a `.` entry is not counted as a canonical call.")
+
+
+def _validate_modbams(args):
+    """src/remora/parsers.py:1759-1798."""
+    import logging
+
+    from .validate import FULL_RESULTS_REFUSAL, validate_modbams
+
+    log = logging.getLogger("Remora")
+    log.setLevel(logging.INFO)
+    log.addHandler(logging.StreamHandler(sys.stderr))
+    if args.explicit_mod_tag_used:
+        log.warning(_IMPLICIT_TAGS)
+    else:
+        log.error(_IMPLICIT_TAGS + " To force the usage of this command please specify the --explicit-mod-tag-used argument")
+        return 1
+    if args.full_results_filename is not None:
+        raise RemoraError(FULL_RESULTS_REFUSAL)
+    if args.log_filename is not None:
+        log.addHandler(logging.FileHandler(args.log_filename, mode="w"))
+    line = validate_modbams(bams_and_beds=args.bam_and_bed, full_results_path=None, name=args.name, pct_filt=args.pct_filt,
+                            allow_unbalanced=args.allow_unbalanced, seed=args.seed, extra_bases=args.extra_bases,
+                            max_sites_per_read=args.max_sites_per_read, device=args.device)
+    sys.stdout.write(line.lstrip("\n"))
+    log.info("Done")
+    return 0
+
+
 def _dataset_prepare(args):
     """src/remora/parsers.py:281-337."""
     from .engine import get_engine
@@ -359,6 +390,28 @@ def build_parser():
     v.add_argument("--batch-size", type=int, default=131072)
     v.add_argument("--dtype", default=None)
     v.set_defaults(func=_validate)
+
+    vm = val.add_parser("from_modbams", help="Validation with ground truth samples: the MM/ML calls of mapped BAM files scored at "
+                        "the sites of ground-truth BED files (tags tokenised on native threads, calls, alignment and sites joined on the GPU)")
+    vm.add_argument("--bam-and-bed", required=True, nargs=2, metavar=("BAM", "GROUND_TRUTH_BED"), action="append",
+                    help="BAM file with modified base tags (mapped, with MD tags) and a BED file with ground truth reference positions, "
+                         "whose name field is the single letter code of a modified base or of the canonical base; repeat for several samples")
+    vm.add_argument("--full-results-filename", help="the reference's per-pair alignment-context TSV: not built here, refused")
+    vm.add_argument("--name", default="sample", help="Name of this sample/comparison. Useful when tabulating several runs.")
+    vm.add_argument("--pct-filt", type=float, default=10.0, help="Filter a specified percentage (or less given ties) of calls.")
+    vm.add_argument("--allow-unbalanced", action="store_true", help="Allow classes to be unbalanced for metric computation.")
+    vm.add_argument("--max-sites-per-read", type=int, help="Maximum number of sites to extract from a single read.")
+    vm.add_argument("--seed", type=int,
+                    help="Seed value. Default: Random seed.  Applied (np.random.seed) before anything is drawn, so that the sites "
+                         "drawn under --max-sites-per-read and the balancing repeat; the reference logs its seed without applying it")
+    vm.add_argument("--extra-bases", help="Extra canonical or modified base single letter codes not in the ground truth bed files "
+                                          "which should be added to the accepted alphabet, e.g. `--extra-bases mh` for a canonical "
+                                          "ground truth (C) and 5mC and 5hmC calls")
+    vm.add_argument("--log-filename", help="Log filename. (default: Don't output log file)")
+    vm.add_argument("--explicit-mod-tag-used", action="store_true",
+                    help="Specify that the user has checked that the modified base tag (MM) uses the explicit (`?`) specifier")
+    vm.add_argument("--device", type=int, default=0)
+    vm.set_defaults(func=_validate_modbams)
 
     dset = sub.add_parser("dataset").add_subparsers(dest="sub", required=True)
     d = dset.add_parser("prepare", help="POD5 + BAM -> labelled chunk dataset directory")

@@ -40,6 +40,21 @@ class BamBatch(ctypes.Structure):
         "md", "ref_ok", "refseq_off", "refseq", "voffset")]
 
 
+class ModbamBatch(ctypes.Structure):
+    """rmr_modbam_batch of include/remora_hip.h (device pointers)."""
+
+    _fields_ = [("n_records", c_i64)] + [(n, c_vp) for n in (
+        "seq", "seq_off", "cigar", "cigar_off", "flag", "ref_id", "pos", "has", "tok_status", "ent_off", "entries", "deltas", "ml")] + [
+        ("n_deltas", c_i64), ("n_ml", c_i64), ("n_mods", ctypes.c_int32), ("mod_codes", ctypes.c_char * 8), ("n_refs", c_i64),
+        ("truth_off", c_vp), ("truth_pos", c_vp), ("truth_label", c_vp)]
+
+
+MOD_MAX_CODES = 16
+# rmr_mod_entry of include/remora_hip.h as a numpy record (48 bytes)
+MOD_ENTRY_FIELDS = [("delta_off", "<i8"), ("ml_off", "<i8"), ("n_deltas", "<i4"), ("n_codes", "<i4"), ("chebi", "<i4"), ("base", "S1"),
+                    ("strand", "S1"), ("flag", "S1"), ("pad", "S1"), ("codes", "S16")]
+
+
 class MotifSet(ctypes.Structure):
     _fields_ = [("n_motifs", ctypes.c_int32), ("len", ctypes.c_int32 * 8), ("focus_pos", ctypes.c_int32 * 8),
                 ("mask", (ctypes.c_uint8 * 16) * 8)]
@@ -100,6 +115,10 @@ SIGNATURES = {
                                  c_vp, c_vp, c_i64, c_vp]),
     "rmr_records_with_mod_tags": (c_int, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(c_i64)]),
     "rmr_records_with_mod_tags_ref": (c_int, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "rmr_mod_tags_sizes": (c_int, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int]),
+    "rmr_mod_tags_fill": (c_int, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int]),
+    "rmr_modbam_site_counts": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rmr_modbam_site_fill": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rmr_inflate_raw": (c_int, [c_vp, c_i64, c_vp, c_i64]),
     "rmr_bgzf_huffman": (c_int, [c_vp, c_i64, c_int, c_vp, c_i64, ctypes.POINTER(c_i64)]),
     "rmr_zstd_frame_sizes": (c_int, [c_vp, c_vp, c_i64, c_vp]),

@@ -1,6 +1,6 @@
 // api_data.hip — the data entry points of the C ABI: k-mer encoding, context trimming, move tables, signal histograms, read
-// assembly, chunk extraction, label counts, the validation tally, motif scans and the VBZ decode.  Each RMR_MEM_HOST call
-// declares its arrays in a Stage (rmr_stage.h), uploads, launches (k_data.hip, k_vbz.hip) and copies back.
+// assembly, chunk extraction, label counts, the validation tally, motif scans, the VBZ decode and the site join of `validate from_modbams`.  Each RMR_MEM_HOST call
+// declares its arrays in a Stage (rmr_stage.h), uploads, launches (k_data.hip, k_vbz.hip, k_modbam.hip) and copies back.
 #include <cstring>
 
 #include "rmr_internal.h"
@@ -444,6 +444,16 @@ int rmr_motif_flags(rmr_engine *e, const int8_t *int_seq, const int64_t *seq_off
     return 0;
 }
 
+static int check_modbam_batch(const rmr_modbam_batch *b) {
+    if (b->n_records < 0 || b->n_records > (int64_t)1 << 30) RMR_FAIL(RMR_ERR_INVALID, "bad n_records");
+    if (b->n_mods < 1 || b->n_mods > 7) RMR_FAIL(RMR_ERR_INVALID, "1..7 modified-base codes supported, got %d", b->n_mods);
+    if (b->n_refs < 0 || b->n_deltas < 0 || b->n_ml < 0) RMR_FAIL(RMR_ERR_INVALID, "bad sizes");
+    if (b->n_records > 0 && (!b->seq_off || !b->cigar_off || !b->flag || !b->ref_id || !b->pos || !b->has || !b->tok_status || !b->ent_off ||
+                             !b->truth_off))
+        RMR_FAIL(RMR_ERR_INVALID, "NULL array in the batch");
+    return 0;
+}
+
 int rmr_vbz_decode(rmr_engine *e, const uint8_t *svb, const int64_t *row_off, const int32_t *row_samples,
                    int64_t n_rows, int16_t *out, int mem) {
     if (!e || !svb || !row_off || !row_samples || !out) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
@@ -492,6 +502,29 @@ int rmr_vbz_decode(rmr_engine *e, const uint8_t *svb, const int64_t *row_off, co
     for (int64_t r = 0; r < n_rows; ++r)
         if (hst[r]) RMR_FAIL(RMR_ERR_INVALID, "corrupt VBZ signal block (row %lld)", (long long)r);
     return 0;
+}
+
+int rmr_modbam_site_counts(rmr_engine *e, const rmr_modbam_batch *b, int32_t *ords, int64_t *cig_q, int64_t *cig_r, int64_t *counts,
+                           int32_t *status) {
+    if (!e || !b || !counts || !status) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    RMR_TRY(check_modbam_batch(b));
+    if ((b->n_deltas > 0 && !ords) || !cig_q || !cig_r) RMR_FAIL(RMR_ERR_INVALID, "NULL workspace");
+    if (b->n_records == 0) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    return launch_modbam_sites(e, *b, ords, cig_q, cig_r, counts, status, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+int rmr_modbam_site_fill(rmr_engine *e, const rmr_modbam_batch *b, const int32_t *ords, const int64_t *cig_q, const int64_t *cig_r,
+                         const int32_t *status, const int64_t *out_off, float *probs, uint8_t *label, int64_t *qpos, int64_t *rpos) {
+    if (!e || !b || !status || !out_off || !probs || !label || !qpos || !rpos) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    RMR_TRY(check_modbam_batch(b));
+    if ((b->n_deltas > 0 && !ords) || !cig_q || !cig_r) RMR_FAIL(RMR_ERR_INVALID, "NULL workspace");
+    if (b->n_records == 0) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    return launch_modbam_sites(e, *b, const_cast<int32_t *>(ords), const_cast<int64_t *>(cig_q), const_cast<int64_t *>(cig_r), nullptr,
+                               const_cast<int32_t *>(status), out_off, probs, label, qpos, rpos);
 }
 
 }  // extern "C"

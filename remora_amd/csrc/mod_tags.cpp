@@ -8,6 +8,11 @@
 // The reference flags this stage as slow in its source (inference.py:55); per read it is a handful of numpy calls and string
 // joins - 90 us of interpreter time per 7 kb read here, the largest single item on the consumer thread of a file-to-file run.
 // One call per batch, no GPU.  Byte-for-byte the output of the Python implementations it replaces (tests/test_host_cpu.py).
+// And the way back, for `validate from_modbams`:
+//   rmr_mod_tags_sizes / rmr_mod_tags_fill: the MM:Z / ML:B:C tags of a batch of stored records -> an entry table, a flat
+//                             delta array and the ML bytes (what htslib's bam_parse_basemod reads below pysam's
+//                             AlignedSegment.modified_bases, src/remora/validate.py:326, :420); the walk along the bases is
+//                             the GPU's (k_modbam.hip)
 #include "../../include/remora_hip.h"
 #include "rmr_internal.h"
 
@@ -18,6 +23,7 @@
 #include <cstring>
 #include <numeric>
 #include <string>
+#include <thread>
 #include <vector>
 
 using namespace rmr;
@@ -263,6 +269,173 @@ int rmr_records_with_mod_tags_ref(int64_t n_reads, const uint8_t *const *raw, co
                                   int64_t *out_len) {
     if (n_reads > 0 && (!ref_seq || !ref_off)) RMR_FAIL(RMR_ERR_INVALID, "bad argument");
     return rewrite_records(n_reads, raw, raw_len, tags_off, mm, mm_off, ml, ml_off, has_tags, ref_seq, ref_off, out, out_cap, out_len);
+}
+
+}  // extern "C"
+
+// ---- MM / ML tokeniser -------------------------------------------------------------------------------------------------
+namespace {
+
+struct ModTagView {
+    const char *mm = nullptr, *mm_end = nullptr;  // the MM string without its NUL
+    const uint8_t *ml = nullptr;                  // the ML bytes
+    int64_t ml_n = -1;                            // -1: no ML tag
+    bool corrupt = false;                         // tag region does not parse / MM or ML of another type
+};
+
+ModTagView find_mod_tags(const uint8_t *tags, const uint8_t *end) {
+    ModTagView v;
+    const uint8_t *p = tags;
+    while (p + 3 <= end) {
+        const char t = (char)p[2];
+        const int64_t sz = value_size(t, p + 3, end);
+        if (sz < 0 || p + 3 + sz > end) {
+            v.corrupt = true;
+            return v;
+        }
+        if (p[0] == 'M' && (p[1] == 'M' || p[1] == 'm') && !v.mm) {
+            if (t != 'Z') v.corrupt = true;
+            else v.mm = (const char *)p + 3, v.mm_end = (const char *)p + 3 + sz - 1;
+        } else if (p[0] == 'M' && (p[1] == 'L' || p[1] == 'l') && v.ml_n < 0) {
+            if (t != 'B' || p[3] != 'C') v.corrupt = true;
+            else v.ml = p + 8, v.ml_n = rd32(p + 4);
+        }
+        p += 3 + sz;
+    }
+    if (p != end) v.corrupt = true;
+    return v;
+}
+
+// One record's tags.  ents / deltas / ml == nullptr: count only.  Returns the status (0 ok, 1 no MM tag, 2 malformed) and,
+// for status 0, the numbers of entries, deltas and ML bytes; the entries' offsets start at d0 / m0.
+int tokenise_record(const uint8_t *rec, int64_t len, int64_t to, rmr_mod_entry *ents, int32_t *deltas, uint8_t *ml, int64_t d0,
+                    int64_t m0, int64_t *n_ent, int64_t *n_delta, int64_t *n_ml) {
+    *n_ent = *n_delta = *n_ml = 0;
+    if (to < 0 || to > len) return 2;
+    const ModTagView v = find_mod_tags(rec + to, rec + len);
+    if (v.corrupt) return 2;
+    if (!v.mm) return 1;
+    int64_t ne = 0, nd = 0, nm = 0;
+    const char *s = v.mm, *e = v.mm_end;
+    while (s < e) {
+        rmr_mod_entry en;
+        memset(&en, 0, sizeof en);
+        if (!memchr("ACGTUN", *s, 6)) return 2;
+        en.base = *s++;
+        if (s >= e || (*s != '+' && *s != '-')) return 2;
+        en.strand = *s++;
+        if (s < e && *s >= 'a' && *s <= 'z') {
+            while (s < e && *s >= 'a' && *s <= 'z') {
+                if (en.n_codes >= RMR_MOD_MAX_CODES) return 2;
+                en.codes[en.n_codes++] = *s++;
+            }
+        } else if (s < e && *s >= '0' && *s <= '9') {
+            int64_t c = 0;
+            while (s < e && *s >= '0' && *s <= '9') {
+                c = c * 10 + (*s++ - '0');
+                if (c > INT32_MAX) return 2;
+            }
+            en.chebi = (int32_t)c;
+            en.n_codes = 1;
+        } else {
+            return 2;
+        }
+        if (s < e && (*s == '.' || *s == '?')) en.flag = *s++;
+        en.delta_off = d0 + nd;
+        en.ml_off = m0 + nm;
+        int64_t k = 0;
+        while (s < e && *s == ',') {
+            ++s;
+            if (s >= e || *s < '0' || *s > '9') return 2;
+            int64_t d = 0;
+            while (s < e && *s >= '0' && *s <= '9') {
+                d = d * 10 + (*s++ - '0');
+                if (d > INT32_MAX) return 2;
+            }
+            if (deltas) deltas[d0 + nd + k] = (int32_t)d;
+            ++k;
+        }
+        if (s >= e || *s != ';') return 2;
+        ++s;
+        if (k > INT32_MAX) return 2;
+        en.n_deltas = (int32_t)k;
+        if (ents) ents[ne] = en;
+        ++ne;
+        nd += k;
+        nm += k * en.n_codes;
+    }
+    if (v.ml_n < 0 ? nm != 0 : nm != v.ml_n) return 2;
+    if (ml && nm) memcpy(ml + m0, v.ml, (size_t)nm);
+    *n_ent = ne, *n_delta = nd, *n_ml = nm;
+    return 0;
+}
+
+template <class F>
+void over_records(int64_t n, int threads, F work) {
+    if (threads < 1) threads = 1;
+    if (threads > 32) threads = 32;
+    if (threads == 1 || n < 4 * threads) {
+        work((int64_t)0, n);
+        return;
+    }
+    std::vector<std::thread> pool;
+    for (int t = 0; t < threads; ++t) pool.emplace_back(work, n * t / threads, n * (t + 1) / threads);
+    for (auto &th : pool) th.join();
+}
+
+}  // namespace
+
+extern "C" {
+
+int rmr_mod_tags_sizes(int64_t n, const uint8_t *raw, const int64_t *raw_off, const int64_t *tags_off, int32_t *status,
+                       int64_t *n_entries, int64_t *n_deltas, int64_t *n_ml, int threads) {
+    if (n < 0 || (n > 0 && (!raw_off || !tags_off || !status || !n_entries || !n_deltas || !n_ml))) RMR_FAIL(RMR_ERR_INVALID, "bad argument");
+    for (int64_t r = 0; r < n; ++r)
+        if (raw_off[r + 1] < raw_off[r] || raw_off[r] < 0 || (raw_off[r + 1] > raw_off[r] && !raw))
+            RMR_FAIL(RMR_ERR_INVALID, "record %lld: bad offsets", (long long)r);
+    over_records(n, threads, [=](int64_t r0, int64_t r1) {
+        for (int64_t r = r0; r < r1; ++r)
+            status[r] = tokenise_record(raw + raw_off[r], raw_off[r + 1] - raw_off[r], tags_off[r], nullptr, nullptr, nullptr, 0, 0,
+                                        n_entries + r, n_deltas + r, n_ml + r);
+    });
+    return 0;
+}
+
+int rmr_mod_tags_fill(int64_t n, const uint8_t *raw, const int64_t *raw_off, const int64_t *tags_off, const int32_t *status,
+                      const int64_t *ent_off, const int64_t *delta_off, const int64_t *ml_off, rmr_mod_entry *entries, int32_t *deltas,
+                      uint8_t *ml, int threads) {
+    if (n < 0 || (n > 0 && (!raw_off || !tags_off || !status || !ent_off || !delta_off || !ml_off))) RMR_FAIL(RMR_ERR_INVALID, "bad argument");
+    for (int64_t r = 0; r < n; ++r) {
+        if (raw_off[r + 1] < raw_off[r] || raw_off[r] < 0 || (raw_off[r + 1] > raw_off[r] && !raw))
+            RMR_FAIL(RMR_ERR_INVALID, "record %lld: bad offsets", (long long)r);
+        if (ent_off[r + 1] < ent_off[r] || delta_off[r + 1] < delta_off[r] || ml_off[r + 1] < ml_off[r] || ent_off[0] != 0 ||
+            delta_off[0] != 0 || ml_off[0] != 0)
+            RMR_FAIL(RMR_ERR_INVALID, "record %lld: output offsets not ascending from 0", (long long)r);
+    }
+    if (n > 0 && ((ent_off[n] && !entries) || (delta_off[n] && !deltas) || (ml_off[n] && !ml))) RMR_FAIL(RMR_ERR_INVALID, "NULL output");
+    std::vector<int64_t> bad((size_t)(n > 0 ? 1 : 0), (int64_t)-1);
+    int64_t *badp = bad.data();
+    over_records(n, threads, [=](int64_t r0, int64_t r1) {
+        for (int64_t r = r0; r < r1; ++r) {
+            const int64_t we = ent_off[r + 1] - ent_off[r], wd = delta_off[r + 1] - delta_off[r], wm = ml_off[r + 1] - ml_off[r];
+            int64_t ne = 0, nd = 0, nm = 0;
+            if (status[r] == 0) {
+                // the counting pass over the same bytes first: nothing is written unless the caller's ranges are this record's
+                const int st = tokenise_record(raw + raw_off[r], raw_off[r + 1] - raw_off[r], tags_off[r], nullptr, nullptr, nullptr, 0, 0,
+                                               &ne, &nd, &nm);
+                if (st != 0 || ne != we || nd != wd || nm != wm) {
+                    __atomic_store_n(badp, r, __ATOMIC_RELAXED);
+                    continue;
+                }
+                tokenise_record(raw + raw_off[r], raw_off[r + 1] - raw_off[r], tags_off[r], entries ? entries + ent_off[r] : nullptr,
+                                deltas, ml, delta_off[r], ml_off[r], &ne, &nd, &nm);
+            } else if (we || wd || wm) {
+                __atomic_store_n(badp, r, __ATOMIC_RELAXED);
+            }
+        }
+    });
+    if (n > 0 && bad[0] >= 0) RMR_FAIL(RMR_ERR_INVALID, "record %lld: offsets do not match what rmr_mod_tags_sizes counted", (long long)bad[0]);
+    return 0;
 }
 
 }  // extern "C"

@@ -62,6 +62,7 @@ enum KernelId {
     K_WINO_FORM,  // a launch count without a time: every kernel launched in a Winograd form is ALSO counted here (its time stays under its layer's id)
     K_BASE_METRICS,
     K_SITE_KMER_LEVELS,  // its kernels and the four radix sorts between them, bracketed in two pieces
+    K_MODBAM_SITES,
     K_NUM
 };
 const char *kernel_name(int id);
@@ -200,6 +201,9 @@ int launch_vbz(rmr_engine *e, const uint8_t *svb, const int64_t *row_off, const 
                int64_t n_rows, int16_t *out, int32_t *status);
 int launch_motif_focus(rmr_engine *e, const int8_t *seq, const int64_t *seq_off, int n_reads, const rmr_motif_set &ms,
                        int64_t *counts, const int64_t *foc_off, int64_t *focus);
+// k_modbam.hip: the site join of `validate from_modbams` (count pass: out_off == nullptr)
+int launch_modbam_sites(rmr_engine *e, const rmr_modbam_batch &b, int32_t *ords, int64_t *cig_q, int64_t *cig_r, int64_t *counts,
+                        int32_t *status, const int64_t *out_off, float *probs, uint8_t *label, int64_t *qpos, int64_t *rpos);
 int launch_motif(rmr_engine *e, const int8_t *seq, const int64_t *seq_off, int n_reads, int64_t total,
                  const rmr_motif_set &ms, uint8_t *flags);
 

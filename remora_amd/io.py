@@ -1267,6 +1267,39 @@ def parse_bed(bed_path):
     return regs
 
 
+def parse_mods_bed(bed_path):
+    """Ground-truth sites of `validate from_modbams` (src/remora/io.py:129-144): ({(contig, strand): {position: code}}, the set
+    of codes).  The name column is the single-letter code of a modified base or of the canonical base; a line without a
+    strand column (or with anything but + / - there) stands for both strands."""
+    from collections import defaultdict
+
+    regs, all_mods = defaultdict(dict), set()
+    with open(bed_path) as fh:
+        for line in fh:
+            fields = line.split()
+            ctg, st, en, mod = fields[:4]
+            all_mods.add(mod)
+            strands = "+-" if len(fields) < 6 or fields[5] not in "+-" else fields[5]
+            for strand in strands:
+                for pos in range(int(st), int(en)):
+                    regs[(ctg, strand)][pos] = mod
+    return regs, all_mods
+
+
+def bam_reference_names(bam_path):
+    """The reference dictionary's names in ref_id order."""
+    hdr = read_bam_header_bytes(bam_path)
+    at = 8 + struct.unpack_from("<i", hdr, 4)[0]
+    n_ref = struct.unpack_from("<i", hdr, at)[0]
+    at += 4
+    names = []
+    for _ in range(n_ref):
+        ln = struct.unpack_from("<i", hdr, at)[0]
+        names.append(hdr[at + 4 : at + 4 + ln - 1].decode())
+        at += 8 + ln
+    return names
+
+
 def _ref_to_signal_of_bam_cigar(cig, is_reverse, query_to_signal, expect):
     """compute_ref_to_signal for a CIGAR in BAM's uint32 form: one native walk (rmr_ref_to_signal, np.interp's arithmetic: the
     same integers) instead of two interpolations over arrays of the read's length.  `expect`: the usual size of the result

@@ -3,13 +3,16 @@ fused extraction-free inference kernels and the reference's validation summary o
 matrix, cross-entropy loss, confidence-filtered accuracy).  Mirrors src/remora/validate.py:17-293 for the
 dataset flavour: VAL_METRICS, mat_to_str, compute_metrics (:42-66), add_unmodeled_labels (:69-99),
 ValidationLogger (:168-293).  The host part is numpy on N x num_labels arrays; the model forward is
-HipModel.infer_chunks on the stored rows (no one-hot tensor is materialised)."""
+HipModel.infer_chunks on the stored rows (no one-hot tensor is materialised).
+`remora validate from_modbams` (src/remora/validate.py:296-594) is in the second half of the file: parse_mod_bam,
+process_mods_probs, validate_modbams."""
 import json
+import logging
 from collections import namedtuple
 
 import numpy as np
 
-from . import constants
+from . import RemoraError, constants
 from .engine import HipModel, _torch
 from .util import softmax_axis1
 
@@ -333,3 +336,274 @@ class ValidationLogger:
                       f"{ms.num_calls}\t{ms.filt_frac:.4f}\t{ms.filt_acc:.6f}\t{mat_to_str(ms.filt_conf_mat)}\t"
                       f"{ms.filt_thresh}\n")
         return ms
+
+
+# ---- `validate from_modbams` (src/remora/validate.py:296-594): modified-base calls read back from BAM files and scored at
+# ground-truth sites.  The reference loops over get_aligned_pairs(with_seq=True) per base of every read in Python; here a
+# batch of records is tokenised on native threads (rmr_mod_tags_sizes / _fill) and joined with the alignment and the truth
+# table on the GPU (rmr_modbam_site_counts / _fill, csrc/k_modbam.hip). ----
+LOGGER = logging.getLogger("Remora")
+
+MODBAM_STATUS = {1: "no MM tag", 2: "malformed modified-base tags", 3: "unmapped", 4: "no MD tag", 5: "no modified base of the alphabet"}
+FULL_RESULTS_REFUSAL = ("--full-results-filename (the per-pair alignment-context table) is not built for `validate from_modbams`: "
+                        "run without it")
+
+
+def _upload(torch, dev, arrays):
+    """Host arrays -> ONE device buffer (a single copy across PCIe); returns the buffer and each array's device address."""
+    offs, total = [], 0
+    for a in arrays:
+        offs.append(total)
+        total += (a.nbytes + 15) // 16 * 16
+    host = np.empty(max(total, 16), np.uint8)
+    for a, o in zip(arrays, offs):
+        if a.nbytes:
+            host[o : o + a.nbytes] = a.reshape(-1).view(np.uint8)
+    buf = torch.from_numpy(host).to(dev)
+    return buf, [buf.data_ptr() + o for o in offs]
+
+
+class ModBamTruth:
+    """The ground-truth sites of one BAM's reference dictionary, resident on the device: per (ref_id, strand) an ascending
+    int64 position array with the label (index into `alphabet`) of every site."""
+
+    def __init__(self, ref_names, gt_sites, alphabet, device):
+        torch = _torch()
+        index = {m: i for i, m in enumerate(alphabet)}
+        off, pos, lab = [0], [], []
+        for name in ref_names:
+            for strand in "+-":
+                sites = gt_sites.get((name, strand)) if hasattr(gt_sites, "get") else None
+                if sites:
+                    p = np.fromiter(sites.keys(), np.int64, len(sites))
+                    try:
+                        v = np.fromiter((index[m] for m in sites.values()), np.uint8, len(sites))
+                    except KeyError as e:
+                        raise RemoraError(f"Ground truth label {e} is not in the alphabet {alphabet}")
+                    order = np.argsort(p, kind="stable")
+                    pos.append(p[order])
+                    lab.append(v[order])
+                off.append(off[-1] + (len(sites) if sites else 0))
+        self.n_refs = len(ref_names)
+        self.off = torch.from_numpy(np.asarray(off, np.int64)).to(device)
+        self.pos = torch.from_numpy(np.concatenate(pos) if pos else np.zeros(1, np.int64)).to(device)
+        self.lab = torch.from_numpy(np.concatenate(lab) if lab else np.zeros(1, np.uint8)).to(device)
+
+
+def tokenise_mod_tags(raw, raw_off, tags_off, threads=None):
+    """rmr_mod_tags_sizes + rmr_mod_tags_fill for the records of a batch: (status i32[n], ent_off, delta_off, ml_off i64[n+1],
+    entries (numpy records, _lib.MOD_ENTRY_FIELDS), deltas i32, ml u8)."""
+    import ctypes
+
+    from . import _lib as L
+    from .util import effective_cpu_count
+
+    lib = L.lib()
+    # a batch of 512 records is half a millisecond of parsing: beyond four threads their start costs more than they save
+    threads = max(1, min(4, effective_cpu_count())) if threads is None else int(threads)
+    raw_off, tags_off = np.ascontiguousarray(raw_off, np.int64), np.ascontiguousarray(tags_off, np.int64)
+    n = int(tags_off.size)
+    raw_arr = np.frombuffer(raw, np.uint8) if len(raw) else np.zeros(1, np.uint8)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    status = np.zeros(n, np.int32)
+    sizes = np.zeros((3, max(n, 1)), np.int64)
+    L.check(lib.rmr_mod_tags_sizes(n, p(raw_arr), p(raw_off), p(tags_off), p(status), p(sizes[0]), p(sizes[1]), p(sizes[2]), threads))
+    offs = np.zeros((3, n + 1), np.int64)
+    np.cumsum(sizes[:, :n], axis=1, out=offs[:, 1:])
+    entries = np.zeros(max(int(offs[0, n]), 1), np.dtype(L.MOD_ENTRY_FIELDS))
+    deltas = np.zeros(max(int(offs[1, n]), 1), np.int32)
+    ml = np.zeros(max(int(offs[2, n]), 1), np.uint8)
+    L.check(lib.rmr_mod_tags_fill(n, p(raw_arr), p(raw_off), p(tags_off), p(status), p(offs[0]), p(offs[1]), p(offs[2]), p(entries),
+                                  p(deltas), p(ml), threads))
+    return status, offs[0], offs[1], offs[2], entries[: int(offs[0, n])], deltas[: int(offs[1, n])], ml[: int(offs[2, n])]
+
+
+def modbam_batch_sites(eng, truth, mod_codes, seq, seq_off, cigar, cigar_off, flag, ref_id, pos, has, tok):
+    """The site join of one batch (rmr_modbam_site_counts, prefix sum, rmr_modbam_site_fill): device tensors probs f32[n, 1 +
+    len(mod_codes)], label u8[n], qpos, rpos i64[n], and on the host the calls per record (i64) and the records' status."""
+    import ctypes
+
+    from . import _lib as L
+
+    torch, lib, dev = _torch(), L.lib(), eng.torch_device
+    status, ent_off, _, _, entries, deltas, ml = tok
+    n, n_alpha = int(np.asarray(flag).size), len(mod_codes) + 1
+    i32 = lambda a: np.ascontiguousarray(a, np.int32)  # noqa: E731
+    i64 = lambda a: np.ascontiguousarray(a, np.int64)  # noqa: E731
+    seq_arr = np.frombuffer(seq, np.uint8) if not isinstance(seq, np.ndarray) else seq
+    arrays = [seq_arr, i64(seq_off), np.ascontiguousarray(cigar, np.uint32), i64(cigar_off), i32(flag), i32(ref_id), i32(pos),
+              np.ascontiguousarray(has, np.uint8), i32(status), i64(ent_off), entries.view(np.uint8), i32(deltas),
+              np.ascontiguousarray(ml, np.uint8)]
+    buf, ptrs = _upload(torch, dev, arrays)
+    b = L.ModbamBatch()
+    b.n_records = n
+    for name, ptr in zip(("seq", "seq_off", "cigar", "cigar_off", "flag", "ref_id", "pos", "has", "tok_status", "ent_off", "entries",
+                          "deltas", "ml"), ptrs):
+        setattr(b, name, ptr)
+    b.n_deltas, b.n_ml, b.n_mods, b.mod_codes = int(deltas.size), int(ml.size), len(mod_codes), "".join(mod_codes).encode()
+    b.n_refs, b.truth_off, b.truth_pos, b.truth_label = truth.n_refs, truth.off.data_ptr(), truth.pos.data_ptr(), truth.lab.data_ptr()
+    n_cig = int(np.asarray(cigar).size)
+    ords = torch.empty(max(int(deltas.size), 1), dtype=torch.int32, device=dev)
+    cig_qr = torch.empty((2, max(n_cig, 1)), dtype=torch.int64, device=dev)
+    counts = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    d_status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    L.check(lib.rmr_modbam_site_counts(eng.handle, ctypes.byref(b), ords.data_ptr(), cig_qr[0].data_ptr(), cig_qr[1].data_ptr(),
+                                       counts.data_ptr(), d_status.data_ptr()))
+    eng.synchronize()
+    h_counts, h_status = counts[:n].cpu().numpy(), d_status[:n].cpu().numpy()
+    out_off = np.zeros(n + 1, np.int64)
+    np.cumsum(h_counts, out=out_off[1:])
+    total = int(out_off[n])
+    probs = torch.empty((max(total, 1), n_alpha), dtype=torch.float32, device=dev)
+    label = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    qr = torch.empty((2, max(total, 1)), dtype=torch.int64, device=dev)
+    if total:
+        d_off = torch.from_numpy(out_off).to(dev)
+        L.check(lib.rmr_modbam_site_fill(eng.handle, ctypes.byref(b), ords.data_ptr(), cig_qr[0].data_ptr(), cig_qr[1].data_ptr(),
+                                         d_status.data_ptr(), d_off.data_ptr(), probs.data_ptr(), label.data_ptr(), qr[0].data_ptr(),
+                                         qr[1].data_ptr()))
+        eng.synchronize()  # the inputs (buf, the workspaces) may go once the kernels are through
+    return probs[:total], label[:total], qr[0, :total], qr[1, :total], h_counts, h_status
+
+
+def parse_mod_bam(bam_path, gt_sites, gt_ranges, alphabet, full_fh, context_bases=5, max_sites=None, device=None, batch=512,
+                  return_sites=False):
+    """Probabilities and ground-truth labels of every modified-base call of `bam_path` that falls on a ground-truth site
+    (src/remora/validate.py:449-510): (probs float64[n, len(alphabet)], labels int64[n]), reads in file order, a read's calls
+    in the order of its aligned pairs.  `alphabet`: the canonical base followed by the modified bases' single-letter codes;
+    other modified bases in the BAM are ignored.  `max_sites`: at most that many calls per read, drawn with
+    np.random.choice(len, size=max_sites, replace=False) read by read as the reference does.  `full_fh` must be None (the
+    per-pair table is not built); `gt_ranges` and `context_bases` only serve that table.  `return_sites`: also the stored query
+    position and the reference position of every call and the calls per record (before `max_sites`)."""
+    from .engine import get_engine
+    from .io import _readahead, bam_reference_names, iter_bam_raw_batches
+
+    if full_fh is not None:
+        raise RemoraError(FULL_RESULTS_REFUSAL)
+    mods = list(alphabet[1:])
+    if not 1 <= len(mods) <= 7 or any(len(m) != 1 for m in alphabet):
+        raise RemoraError(f"validate from_modbams takes 1 to 7 single-letter modified bases beside the canonical base, got {alphabet}")
+    torch = _torch()
+    eng = get_engine(device)
+    truth = ModBamTruth(bam_reference_names(bam_path), gt_sites, list(alphabet), eng.torch_device)
+    parts, counts, skipped, n_records = [], [], {}, 0
+    warn_mod = warn_strand = True
+    def tokenised():  # the reader and the tokeniser of batch k + 1 run on a thread of their own beside the join of batch k
+        for rb, _ in iter_bam_raw_batches(bam_path, want_ref=False, batch=int(batch)):
+            yield rb, tokenise_mod_tags(rb.raw, rb.raw_off, rb.tags_off)
+
+    for rb, tok in _readahead(tokenised(), depth=2):
+        entries = tok[4]
+        if warn_strand and entries.size and (entries["strand"] == b"-").any():
+            LOGGER.warning("Reverse strand (duplex) mods not supported ")
+            warn_strand = False
+        if warn_mod and entries.size:
+            fwd = entries[entries["strand"] == b"+"]
+            seen = set(np.unique(np.frombuffer(fwd["codes"].tobytes(), np.uint8)).tobytes().decode("latin-1")) - {"\x00"}
+            seen |= {str(c) for c in np.unique(fwd["chebi"]).tolist() if c}
+            for mod_name in sorted(seen - set(alphabet)):
+                LOGGER.warning(f"Modified base found in BAM ({mod_name}) not found in ground truth. If this should be included in "
+                               "validation, add with --extra-bases.")
+                warn_mod = False
+                break
+        out = modbam_batch_sites(eng, truth, mods, rb.seq, rb.seq_off, rb.cigar, rb.cigar_off, rb.flag, rb.ref_id, rb.pos, rb.has, tok)
+        parts.append(out[:4])
+        counts.append(out[4])
+        n_records += rb.n
+        for st, k in zip(*np.unique(out[5], return_counts=True)):
+            if st:
+                skipped[int(st)] = skipped.get(int(st), 0) + int(k)
+    for st, k in sorted(skipped.items()):
+        LOGGER.info(f"{k} of {n_records} records skipped: {MODBAM_STATUS.get(st, st)} ({bam_path})")
+    counts = np.concatenate(counts) if counts else np.zeros(0, np.int64)
+    if int(counts.sum()) < 1:
+        raise RemoraError(f"No valid modification calls from {bam_path}. Confirm that contig names from reference FASTA and ground "
+                          "truth BED match.")
+    probs = torch.cat([p[0] for p in parts]).cpu().numpy().astype(np.float64)
+    labels = torch.cat([p[1] for p in parts]).cpu().numpy().astype(np.int64)
+    keep = None
+    if max_sites is not None and counts.size and int(counts.max()) > max_sites:
+        start = np.concatenate([[0], np.cumsum(counts)])
+        pieces = []
+        for r in range(counts.size):  # read by read in file order: the reference's sequence of draws
+            k = int(counts[r])
+            pieces.append(start[r] + (np.random.choice(k, size=max_sites, replace=False) if k > max_sites else np.arange(k)))
+        keep = np.concatenate(pieces).astype(np.int64)
+    LOGGER.debug(f"Parsed {labels.size if keep is None else keep.size} modified base calls from file: {bam_path}")
+    if return_sites:
+        qpos = torch.cat([p[2] for p in parts]).cpu().numpy()
+        rpos = torch.cat([p[3] for p in parts]).cpu().numpy()
+        if keep is not None:
+            return probs[keep], labels[keep], qpos[keep], rpos[keep], counts
+        return probs, labels, qpos, rpos, counts
+    return (probs, labels) if keep is None else (probs[keep], labels[keep])
+
+
+def process_mods_probs(probs, labels, allow_unbalanced, pct_filt, name):
+    """The summary line of `validate from_modbams` (src/remora/validate.py:102-154): classes balanced to the smallest one that
+    occurs (np.random.shuffle of the larger ones) unless `allow_unbalanced`, then compute_metrics.  Logged as the reference
+    logs it; the text is returned as well."""
+    if not allow_unbalanced:
+        nlabs = max(labels.max() + 1, probs.shape[1])
+        labels_probs = [probs[labels == mod_idx] for mod_idx in range(nlabs)]
+        lab_sizes = [lp.shape[0] for lp in labels_probs]
+        if len(lab_sizes) == 1:
+            raise RemoraError("Cannot balance dataset with 1 label. Consider running with `--allow-unbalanced`")
+        LOGGER.debug(f"Balancing labels. Starting from: {lab_sizes}")
+        min_size = min([s for s in lab_sizes if s > 0])
+        bal_probs, bal_labels = [], []
+        for lab_idx, label_probs in enumerate(labels_probs):
+            if label_probs.shape[0] == 0:  # labels not included in ground truth
+                continue
+            if label_probs.shape[0] > min_size:
+                np.random.shuffle(label_probs)
+            bal_probs.append(label_probs[:min_size])
+            bal_labels.append(np.full(min_size, lab_idx, dtype=labels.dtype))
+        probs, labels = np.concatenate(bal_probs), np.concatenate(bal_labels)
+    acc, conf_mat, filt_frac, filt_acc, filt_conf_mat, filt_thr = compute_metrics(probs, labels, pct_filt / 100)
+    val_output = (f"\n{ValidationLogger.HEADER}\n{name}\t0\t0\t{acc:.6f}\t{mat_to_str(conf_mat)}\tNAN\t{labels.size}\t{filt_frac:.4f}\t"
+                  f"{filt_acc:.6f}\t{mat_to_str(filt_conf_mat)}\t{filt_thr}\n")
+    LOGGER.info(val_output)
+    return val_output
+
+
+def validate_modbams(bams_and_beds, full_results_path, name, pct_filt, allow_unbalanced=False, seed=None, extra_bases=None,
+                     max_sites_per_read=None, device=None):
+    """`validate from_modbams` (src/remora/validate.py:513-594).  The reference draws and logs `seed` without applying it; here
+    np.random.seed(seed) is called once, first of all, so that the draws of --max-sites-per-read and of the balancing repeat
+    under the same seed.  Returns the summary text."""
+    from .io import parse_mods_bed
+
+    seed = int(np.random.randint(0, np.iinfo(np.uint32).max, dtype=np.uint32)) if seed is None else seed
+    LOGGER.debug(f"Seed selected is {seed}")
+    np.random.seed(seed)
+    if full_results_path is not None:
+        raise RemoraError(FULL_RESULTS_REFUSAL)
+    LOGGER.info("Parsing ground truth BED files")
+    bams, beds = zip(*bams_and_beds)
+    parsed, all_gt_sites, all_gt_ranges, all_mods = {}, [], [], set()
+    for bed_path in beds:
+        if bed_path not in parsed:
+            parsed[bed_path] = parse_mods_bed(bed_path)
+            tot_sites = sum(len(cs_sites) for cs_sites in parsed[bed_path][0].values())
+            LOGGER.info(f"Parsed {tot_sites} total sites with labels {parsed[bed_path][1]} from {bed_path}")
+        gt_sites, samp_mods = parsed[bed_path]
+        all_gt_sites.append(gt_sites)
+        all_gt_ranges.append(dict((cs, (min(poss), max(poss))) for cs, poss in gt_sites.items()))
+        all_mods.update(samp_mods)
+    if extra_bases is not None:
+        all_mods.update(extra_bases)
+    can_base = all_mods.intersection("ACGTU")
+    if len(can_base) > 1:
+        raise RemoraError(f"More than one canonical base found: {can_base}")
+    if len(can_base) == 0:
+        raise RemoraError("No canonical bases found in ground truth.")
+    alphabet = list(can_base) + sorted(all_mods.difference("ACGTU"))
+    LOGGER.info("Parsing modBAM files")
+    all_probs, all_labels = [], []
+    for bam_path, gt_sites, gt_ranges in zip(bams, all_gt_sites, all_gt_ranges):
+        probs, labels = parse_mod_bam(bam_path, gt_sites, gt_ranges, alphabet, None, max_sites=max_sites_per_read, device=device)
+        all_probs.append(probs)
+        all_labels.append(labels)
+    LOGGER.info(f"Alphabet used (and order of reported metrics): {alphabet}")
+    return process_mods_probs(np.vstack(all_probs), np.concatenate(all_labels), allow_unbalanced, pct_filt, name)

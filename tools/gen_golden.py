@@ -1441,6 +1441,128 @@ def gen_batch_params(R, out):
     shutil.rmtree(td)
 
 
+def gen_modbams(R, out):
+    """`validate from_modbams` (src/remora/validate.py:296-594) on tagged copies of the reference's test alignments.
+    The records of data/{can,mod}_mappings.bam are parsed by remora_amd.io (pysam is not installed here), get seeded
+    probabilities at the CG sites of their read-oriented sequence - one modified base (m) in the `can` file, two (h, m) in the
+    `mod` file - formatted by the REFERENCE's util.format_mm_ml_tags, and are written to data/{can,mod}_modbam.bam with
+    BamWriter (fixed fields, name, CIGAR and bases as stored; qualities blanked; of the tags only MD kept).  Duck-typed read
+    objects then go through the REFERENCE's check_mod_strand, parse_mod_read and process_mods_probs; their `modified_bases`
+    and `get_aligned_pairs(with_seq=True)` are pysam restated (tests/modbam_restate.py)."""
+    import logging
+    import struct
+
+    sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
+    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tests"))
+    import modbam_restate as mr
+    from remora_amd import io as rio
+
+    data = os.path.join(out, "data")
+    V = R.validate
+    if not hasattr(np, "NAN"):  # the reference predates numpy 2 (validate.py:138)
+        np.NAN = np.nan
+    lines = []
+
+    class Grab(logging.Handler):
+        def emit(self, record):
+            lines.append(record.getMessage())
+
+    V.LOGGER.addHandler(Grab())
+    V.LOGGER.setLevel(logging.INFO)
+    ops = "MIDNSHP=X"
+    rng = np.random.default_rng(20240607)
+    d, reads = {}, {}
+    for prefix, mods in (("can", ["m"]), ("mod", ["h", "m"])):
+        recs = list(rio.iter_bam_records(os.path.join(data, f"{prefix}_mappings.bam")))
+        reads[prefix] = []
+        with rio.BamWriter(os.path.join(data, f"{prefix}_modbam.bam"), rio.read_bam_header_bytes(os.path.join(data, f"{prefix}_mappings.bam")),
+                           threads=1) as w:
+            for rec in recs:
+                seq, rev = rec.query_sequence, bool(rec.flag & 0x10)
+                orig = mr.original_sequence(seq, rev)
+                poss = [p for p in range(len(orig) - 1) if orig[p : p + 2] == "CG"]
+                probs = rng.dirichlet(np.ones(len(mods) + 1) * 0.5, size=len(poss))[:, 1:]
+                mm, ml = R.util.format_mm_ml_tags(orig, poss, probs, mods, "C")
+                ml = bytes(ml)
+                raw = bytes(rec.raw)
+                l_name, n_cig, l_seq = raw[8], struct.unpack_from("<H", raw, 12)[0], struct.unpack_from("<i", raw, 16)[0]
+                core_end = 32 + l_name + 4 * n_cig + (l_seq + 1) // 2
+                md = rec.get_tag("MD")
+                body = raw[:core_end] + b"\xff" * l_seq + b"MDZ" + md.encode() + b"\x00" + mr.mod_tags(mm, ml)
+                w.write(struct.pack("<i", len(body)) + body)
+                cigar = [(ops[op], n) for op, n in rec.cigartuples]
+                read = types.SimpleNamespace(
+                    is_reverse=rev, reference_name=rec.reference_name, query_name=rec.query_name, query_sequence=seq,
+                    modified_bases=mr.modified_bases(seq, rev, mm, ml),
+                    get_aligned_pairs=lambda with_seq=True, c=cigar, p=rec.reference_start: mr.aligned_pairs(c, p))
+                reads[prefix].append(read)
+
+    def run(prefix, bed, alphabet, max_sites=None):
+        gt_sites, _ = R.io.parse_mods_bed(os.path.join(data, bed))
+        per_probs, per_labels = [], []
+        for read in reads[prefix]:
+            _, _, valid = V.check_mod_strand(read, prefix, alphabet, True, True)
+            if not valid:
+                per_probs.append(np.zeros((0, len(alphabet))))
+                per_labels.append(np.zeros(0, np.int64))
+                continue
+            pr, lb = V.parse_mod_read(read, gt_sites, {}, alphabet, None, max_sites=max_sites)
+            per_probs.append(np.array(pr, np.float64).reshape(-1, len(alphabet)))
+            per_labels.append(np.array(lb, np.int64))
+        return per_probs, per_labels
+
+    def summary(probs, labels, allow_unbalanced, seed, name):
+        del lines[:]
+        np.random.seed(seed)
+        V.process_mods_probs(probs, labels, allow_unbalanced, 10.0, name)
+        return lines[-1]
+
+    seed = 42
+    for tag, alphabet in (("two", ["C", "m"]), ("three", ["C", "h", "m"])):
+        cat_p, cat_l = [], []
+        for prefix in ("can", "mod"):
+            pp, pl = run(prefix, f"{prefix}_gt.bed", alphabet)
+            d[f"{tag}__{prefix}__counts"] = np.array([len(x) for x in pl], np.int64)
+            d[f"{tag}__{prefix}__probs"] = np.concatenate(pp)
+            d[f"{tag}__{prefix}__labels"] = np.concatenate(pl)
+            cat_p.append(d[f"{tag}__{prefix}__probs"])
+            cat_l.append(d[f"{tag}__{prefix}__labels"])
+        d[f"{tag}__probs"], d[f"{tag}__labels"] = np.vstack(cat_p), np.concatenate(cat_l)
+        for bal in ("balanced", "unbalanced"):
+            d[f"{tag}__line_{bal}"] = np.array(summary(d[f"{tag}__probs"].copy(), d[f"{tag}__labels"].copy(), bal == "unbalanced", seed,
+                                                       f"{tag}_{bal}"))
+    # --max-sites-per-read 5, two labels: the draws of both files and of the balancing in ONE stream seeded once, as
+    # validate_modbams runs them
+    np.random.seed(seed)
+    cat_p, cat_l = [], []
+    for prefix in ("can", "mod"):
+        pp, pl = run(prefix, f"{prefix}_gt.bed", ["C", "m"], max_sites=5)
+        cat_p.append(np.concatenate(pp))
+        cat_l.append(np.concatenate(pl))
+    d["max5__probs"], d["max5__labels"] = np.vstack(cat_p), np.concatenate(cat_l)
+    del lines[:]
+    V.process_mods_probs(d["max5__probs"].copy(), d["max5__labels"].copy(), False, 10.0, "max5")
+    d["max5__line"] = np.array(lines[-1])
+    # the positions of the calls (restated walk; the reference's loop does not return them)
+    for prefix, alphabet in (("can", ["C", "m"]), ("mod", ["C", "h", "m"])):
+        gt_sites, _ = R.io.parse_mods_bed(os.path.join(data, f"{prefix}_gt.bed"))
+        qp, rp = [], []
+        for read in reads[prefix]:
+            called = set()
+            for (_, strand, name), vals in read.modified_bases.items():
+                if strand == int(read.is_reverse) and str(name) in alphabet:
+                    called |= {p for p, _ in vals}
+            truth = gt_sites.get((read.reference_name, "-" if read.is_reverse else "+"), {})
+            for q, r, _ in read.get_aligned_pairs():
+                if q in called and r in truth:
+                    qp.append(q)
+                    rp.append(r)
+        d[f"{prefix}__qpos"], d[f"{prefix}__rpos"] = np.array(qp, np.int64), np.array(rp, np.int64)
+    d["seed"] = np.array(seed)
+    np.savez_compressed(os.path.join(out, "modbams.npz"), **d)
+    print("modbams:", {k: (v.shape if v.ndim else str(v)[:60]) for k, v in d.items()})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(__file__), "..", "tests", "golden"))
@@ -1469,6 +1591,7 @@ def main():
         prepare=gen_prepare,
         remora_dataset=gen_remora_dataset,
         batch_params=gen_batch_params,
+        modbams=gen_modbams,
     )
     for name, fn in gens.items():
         if args.only and name not in args.only.split(","):
