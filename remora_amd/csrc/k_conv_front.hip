@@ -28,6 +28,8 @@
 #include "rmr_mma.h"
 #include "rmr_plan.h"
 
+#include <type_traits>
+
 namespace rmr {
 
 namespace {
@@ -346,6 +348,91 @@ __global__ __launch_bounds__(256, (KW1 <= 5 ? 3 : 2)) void sig3_front_mfma_kerne
 }
 
 // ---------------------------------------------------------------------------------------
+// rows -> V of the two Winograd kernels below: one plane of the staged rows into one plane of the x-domain image.  An item =
+// (column, phase) reads NJ rows 12 t + 3 j + phase of the column's chunk; rows behind the chunk's last enter as zeros.  Whether ANY
+// item of a launch reaches behind its chunk follows from the geometry alone (the last group's last phase: 12 (ngrp - 1) + 2 +
+// 3 (NJ - 1) against pin - 1), so the kernels choose once, by a scalar branch, between the body with the zero selects (TAIL) and
+// one without them: at C100 no group does, and the selects were a third of the transform's vector instructions.  Both bodies
+// do the same arithmetic on the same values.
+// ---------------------------------------------------------------------------------------
+template <int NJ>
+__device__ __forceinline__ bool rows_reach_behind(const ConvFrontArgs &a) {
+    return 12 * (a.ngrp - 1) + 2 + 3 * (NJ - 1) > a.pin - 1;
+}
+
+template <bool TAIL, int NJ>
+__device__ __forceinline__ void load_rows(const ConvFrontArgs &a, const float *img, int c, int t, int ph, f32x4 (&d)[NJ]) {
+    const float *rp = img + (size_t)(c * a.pin + 12 * t + ph) * 4;
+    if (TAIL) {
+        const int lim = a.pin - 1 - ph - 12 * t;  // highest row offset 3 j inside the chunk (>= 0)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            d[j] = *reinterpret_cast<const f32x4 *>(rp + (3 * j <= lim ? 3 * j : 0) * 4);
+            if (3 * j > lim) d[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) d[j] = *reinterpret_cast<const f32x4 *>(rp + 3 * j * 4);
+    }
+}
+
+// F(4, 3): six rows -> six points (sig3_front_wino_kernel)
+template <bool TAIL>
+__device__ __forceinline__ void rows_to_v_f43(const ConvFrontArgs &a, const float *img, float *vq, int XIV, int ncols, int lane) {
+    for (int i = lane; i < 3 * ncols; i += 64) {
+        const int col = i / 3, ph = i - 3 * col;
+        const int c = (int)(((float)col + 0.5f) * a.div_ngrp.inv), t = col - c * a.ngrp;
+        f32x4 d[6];
+        load_rows<TAIL, 6>(a, img, c, t, ph, d);
+        // BT d of F(4, 3), natural point order (0, 1, -1, 2, -2, inf)
+        f32x4 v[6];
+        const f32x4 c4 = {4.0f, 4.0f, 4.0f, 4.0f}, m5 = {-5.0f, -5.0f, -5.0f, -5.0f}, c2 = {2.0f, 2.0f, 2.0f, 2.0f};
+        v[0] = __builtin_elementwise_fma(m5, d[2], __builtin_elementwise_fma(c4, d[0], d[4]));
+        const f32x4 ea = __builtin_elementwise_fma(c4, d[2], -d[4]), eb = __builtin_elementwise_fma(c4, d[1], -d[3]);
+        v[1] = ea + eb;
+        v[2] = ea - eb;
+        const f32x4 ec = d[4] - d[2], ee = d[3] - d[1];
+        v[3] = __builtin_elementwise_fma(c2, ee, ec);
+        v[4] = __builtin_elementwise_fma(-c2, ee, ec);
+        v[5] = __builtin_elementwise_fma(m5, d[3], __builtin_elementwise_fma(c4, d[1], d[5]));
+        float *dst = vq + (size_t)ph * 4 * a.vplane + (size_t)((col & ~15) + ((col + 4 * ph) & 15)) * 4;
+#pragma unroll
+        for (int x = 0; x < 6; ++x) *reinterpret_cast<f32x4 *>(dst + (size_t)x * XIV) = v[x];
+    }
+}
+
+// F(4, 5): eight rows -> eight points (seq2_front_wino_kernel)
+template <bool TAIL>
+__device__ __forceinline__ void rows_to_v_f45(const ConvFrontArgs &a, const float *img, float *vq, int XIV, int ncols, int lane) {
+    for (int i = lane; i < 3 * ncols; i += 64) {
+        const int col = i / 3, ph = i - 3 * col;
+        const int c = (int)(((float)col + 0.5f) * a.div_ngrp.inv), t = col - c * a.ngrp;
+        f32x4 d[8];
+        load_rows<TAIL, 8>(a, img, c, t, ph, d);
+        // BT d of F(4, 5), natural point order (0, 1, -1, 2, -2, 1/2, -1/2, inf); k_wino.hip wino_in_transform has the derivation
+        auto f4 = [](float cst, f32x4 x, f32x4 y) { return __builtin_elementwise_fma(f32x4{cst, cst, cst, cst}, x, y); };
+        f32x4 v[8];
+        const f32x4 e1 = f4(-4.0f, d[2] + d[6], f32x4{17.0f, 17.0f, 17.0f, 17.0f} * d[4]);
+        const f32x4 o1 = f4(-4.0f, d[1] + d[5], f32x4{17.0f, 17.0f, 17.0f, 17.0f} * d[3]);
+        v[1] = e1 + o1;
+        v[2] = e1 - o1;
+        const f32x4 e2 = f4(-5.0f, d[4], f4(4.0f, d[6], d[2]));
+        const f32x4 o2 = f4(-5.0f, d[3], f4(4.0f, d[5], d[1]));
+        v[3] = f4(2.0f, o2, e2);
+        v[4] = f4(-2.0f, o2, e2);
+        v[0] = f4(-21.0f, d[2] - d[4], f32x4{4.0f, 4.0f, 4.0f, 4.0f} * (d[0] - d[6]));
+        const f32x4 e3 = f4(-5.0f, d[4], f4(4.0f, d[2], d[6]));
+        const f32x4 o3 = f4(-5.0f, d[3], f4(4.0f, d[1], d[5]));
+        v[5] = f4(2.0f, e3, o3);
+        v[6] = f4(2.0f, e3, -o3);
+        v[7] = f4(21.0f, d[3] - d[5], f32x4{4.0f, 4.0f, 4.0f, 4.0f} * (d[7] - d[1]));
+        float *dst = vq + (size_t)ph * 4 * a.vplane + (size_t)((col & ~15) + ((col + 4 * ph) & 15)) * 4;
+#pragma unroll
+        for (int x = 0; x < 8; ++x) *reinterpret_cast<f32x4 *>(dst + (size_t)x * XIV) = v[x];
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // The same kernel with sig_conv3 in minimal form (round 6; k_wino.hip has the algebra and the stride-1 kernels).  Stride 3 = three
 // stride-1 phase filters of three taps on d_r[i] = sig2[3 i + r]; each over groups of four outputs as F(4, 3) at 0, +-1, +-2, inf:
 // 6 products per 4 outputs where the direct form has 12, the three phases accumulating into the same x-domain accumulators
@@ -437,47 +524,23 @@ __global__ __launch_bounds__(256, 2) void sig3_front_wino_kernel(ConvFrontArgs a
         RMR_SYNC();
         // ---- rows -> V: wave w takes plane w; an item = (column, phase): six rows 12 t + 3 j + phase of the column's chunk
         const int ncols = nch * a.ngrp;
-        {
-            const float *img = smem + (size_t)w * a.plane;
-            float *vq = V + (size_t)w * a.vplane;
-            for (int i = lane; i < 3 * ncols; i += 64) {
-                const int col = i / 3, ph = i - 3 * col;
-                const int c = (int)(((float)col + 0.5f) * a.div_ngrp.inv), t = col - c * a.ngrp;
-                const int lim = a.pin - 1 - ph - 12 * t;  // highest row offset 3 j inside the chunk (>= 0)
-                const float *rp = img + (size_t)(c * a.pin + 12 * t + ph) * 4;
-                f32x4 d[6];
-#pragma unroll
-                for (int j = 0; j < 6; ++j) {
-                    d[j] = *reinterpret_cast<const f32x4 *>(rp + (3 * j <= lim ? 3 * j : 0) * 4);
-                    if (3 * j > lim) d[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-                }
-                // BT d of F(4, 3), natural point order (0, 1, -1, 2, -2, inf)
-                f32x4 v[6];
-                const f32x4 c4 = {4.0f, 4.0f, 4.0f, 4.0f}, m5 = {-5.0f, -5.0f, -5.0f, -5.0f}, c2 = {2.0f, 2.0f, 2.0f, 2.0f};
-                v[0] = __builtin_elementwise_fma(m5, d[2], __builtin_elementwise_fma(c4, d[0], d[4]));
-                const f32x4 ea = __builtin_elementwise_fma(c4, d[2], -d[4]), eb = __builtin_elementwise_fma(c4, d[1], -d[3]);
-                v[1] = ea + eb;
-                v[2] = ea - eb;
-                const f32x4 ec = d[4] - d[2], ee = d[3] - d[1];
-                v[3] = __builtin_elementwise_fma(c2, ee, ec);
-                v[4] = __builtin_elementwise_fma(-c2, ee, ec);
-                v[5] = __builtin_elementwise_fma(m5, d[3], __builtin_elementwise_fma(c4, d[1], d[5]));
-                float *dst = vq + (size_t)ph * 4 * a.vplane + (size_t)((col & ~15) + ((col + 4 * ph) & 15)) * 4;
-#pragma unroll
-                for (int x = 0; x < 6; ++x) *reinterpret_cast<f32x4 *>(dst + (size_t)x * XIV) = v[x];
-            }
-        }
+        if (rows_reach_behind<6>(a)) rows_to_v_f43<true>(a, smem + (size_t)w * a.plane, V + (size_t)w * a.vplane, XIV, ncols, lane);
+        else rows_to_v_f43<false>(a, smem + (size_t)w * a.plane, V + (size_t)w * a.vplane, XIV, ncols, lane);
         RMR_SYNC();
         // ---- six GEMMs of K = 48 per column tile; steps = (phase, half of the points); AT m, bias, swish, four stores per column
         if (CF_ABL(2)) continue;
         const int ntl = (ncols + 15) >> 4;
+        float *const obase = a.out + (size_t)chunk0 * a.pout * a.out_row + a.out_coff;  // the iteration's first output row (block-uniform)
+        auto tiles = [&](auto vpl) {
+        constexpr int VPL = decltype(vpl)::value;
+        const int vplane = VPL ? VPL : a.vplane, XIV = 12 * vplane;
         for (int tile = 0; tile < ntl; ++tile) {
             const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
             f32x4 acc[6] = {b4, zero, zero, zero, zero, b4};  // AT[0][0] = AT[3][5] = 1: the bias of y0 and y3
-            const float *r = V + (size_t)q * a.vplane + (size_t)tile * 64;
+            const float *r = V + q * vplane + tile * 64;
             f32x4 xv[3];
 #pragma unroll
-            for (int k = 0; k < 3; ++k) xv[k] = *reinterpret_cast<const f32x4 *>(r + (size_t)k * XIV + nn * 4);
+            for (int k = 0; k < 3; ++k) xv[k] = *reinterpret_cast<const f32x4 *>(r + k * XIV + nn * 4);
 #pragma unroll
             for (int st = 0; st < 6; ++st) {
                 const int p = st >> 1, x0 = (st & 1) * 3;
@@ -486,7 +549,7 @@ __global__ __launch_bounds__(256, 2) void sig3_front_wino_kernel(ConvFrontArgs a
                     const int p1 = (st + 1) >> 1, x1 = ((st + 1) & 1) * 3;
 #pragma unroll
                     for (int k = 0; k < 3; ++k)
-                        yv[k] = *reinterpret_cast<const f32x4 *>(r + (size_t)(x1 + k) * XIV + (size_t)p1 * 4 * a.vplane + ((nn + 4 * p1) & 15) * 4);
+                        yv[k] = *reinterpret_cast<const f32x4 *>(r + (x1 + k) * XIV + p1 * 4 * vplane + ((nn + 4 * p1) & 15) * 4);
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
@@ -515,7 +578,7 @@ __global__ __launch_bounds__(256, 2) void sig3_front_wino_kernel(ConvFrontArgs a
                 yo[1] = __builtin_elementwise_fma(c2, d34, d12) + b4;
                 yo[2] = __builtin_elementwise_fma(c4, s34, s12) + b4;
                 yo[3] = __builtin_elementwise_fma(c8, d34, d12) + acc[5];
-                float *dst = a.out + ((size_t)(chunk0 + c) * a.pout + 4 * t) * a.out_row + a.out_coff + 16 * w + 4 * q;
+                float *dst = obase + (unsigned)((c * a.pout + 4 * t) * a.out_row + 16 * w + 4 * q);
                 const int nvalid = a.pout - 4 * t;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -527,6 +590,11 @@ __global__ __launch_bounds__(256, 2) void sig3_front_wino_kernel(ConvFrontArgs a
                 }
             }
         }
+        };
+        // V's plane size known at compile time (four chunks of 5..8 groups per iteration: every C100-class launch but a small
+        // batch's): every read of a tile is one of three lane bases plus an immediate offset, no address arithmetic per read
+        if (a.vplane == 128) tiles(std::integral_constant<int, 128>{});
+        else tiles(std::integral_constant<int, 0>{});
     }
 }
 
@@ -844,52 +912,22 @@ __global__ __launch_bounds__(256, 2) void seq2_front_wino_kernel(ConvFrontArgs a
         RMR_SYNC();
         // ---- rows -> V (over the table and the scratch): wave w takes plane w; an item = (column, phase): eight rows 12 t + 3 j + phase
         const int ncols = nch * a.ngrp;
-        {
-            const float *img = smem + (size_t)w * a.plane;
-            float *vq = V + (size_t)w * a.vplane;
-            for (int i = lane; i < 3 * ncols; i += 64) {
-                const int col = i / 3, ph = i - 3 * col;
-                const int c = (int)(((float)col + 0.5f) * a.div_ngrp.inv), t = col - c * a.ngrp;
-                const int lim = a.pin - 1 - ph - 12 * t;  // highest row offset 3 j inside the chunk (>= 0)
-                const float *rp = img + (size_t)(c * a.pin + 12 * t + ph) * 4;
-                f32x4 d[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    d[j] = *reinterpret_cast<const f32x4 *>(rp + (3 * j <= lim ? 3 * j : 0) * 4);
-                    if (3 * j > lim) d[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-                }
-                // BT d of F(4, 5), natural point order (0, 1, -1, 2, -2, 1/2, -1/2, inf); k_wino.hip wino_in_transform has the derivation
-                auto f4 = [](float cst, f32x4 x, f32x4 y) { return __builtin_elementwise_fma(f32x4{cst, cst, cst, cst}, x, y); };
-                f32x4 v[8];
-                const f32x4 e1 = f4(-4.0f, d[2] + d[6], f32x4{17.0f, 17.0f, 17.0f, 17.0f} * d[4]);
-                const f32x4 o1 = f4(-4.0f, d[1] + d[5], f32x4{17.0f, 17.0f, 17.0f, 17.0f} * d[3]);
-                v[1] = e1 + o1;
-                v[2] = e1 - o1;
-                const f32x4 e2 = f4(-5.0f, d[4], f4(4.0f, d[6], d[2]));
-                const f32x4 o2 = f4(-5.0f, d[3], f4(4.0f, d[5], d[1]));
-                v[3] = f4(2.0f, o2, e2);
-                v[4] = f4(-2.0f, o2, e2);
-                v[0] = f4(-21.0f, d[2] - d[4], f32x4{4.0f, 4.0f, 4.0f, 4.0f} * (d[0] - d[6]));
-                const f32x4 e3 = f4(-5.0f, d[4], f4(4.0f, d[2], d[6]));
-                const f32x4 o3 = f4(-5.0f, d[3], f4(4.0f, d[1], d[5]));
-                v[5] = f4(2.0f, e3, o3);
-                v[6] = f4(2.0f, e3, -o3);
-                v[7] = f4(21.0f, d[3] - d[5], f32x4{4.0f, 4.0f, 4.0f, 4.0f} * (d[7] - d[1]));
-                float *dst = vq + (size_t)ph * 4 * a.vplane + (size_t)((col & ~15) + ((col + 4 * ph) & 15)) * 4;
-#pragma unroll
-                for (int x = 0; x < 8; ++x) *reinterpret_cast<f32x4 *>(dst + (size_t)x * XIV) = v[x];
-            }
-        }
+        if (rows_reach_behind<8>(a)) rows_to_v_f45<true>(a, smem + (size_t)w * a.plane, V + (size_t)w * a.vplane, XIV, ncols, lane);
+        else rows_to_v_f45<false>(a, smem + (size_t)w * a.plane, V + (size_t)w * a.vplane, XIV, ncols, lane);
         RMR_SYNC();
         // ---- eight GEMMs of K = 48 per column tile; steps = (phase, half of the points); AT m, bias, swish, four stores per column
         const int ntl = (ncols + 15) >> 4;
+        float *const obase = a.out + (size_t)chunk0 * a.pout * a.out_row + a.out_coff;  // the iteration's first output row (block-uniform)
+        auto tiles = [&](auto vpl) {  // (see sig3_front_wino_kernel)
+        constexpr int VPL = decltype(vpl)::value;
+        const int vplane = VPL ? VPL : a.vplane, XIV = 12 * vplane;
         for (int tile = 0; tile < ntl; ++tile) {
             const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
             f32x4 acc[8] = {b4, zero, zero, zero, zero, zero, zero, b4};  // AT[0][0] = AT[3][7] = 1: the bias of y0 and y3
-            const float *r = V + (size_t)q * a.vplane + (size_t)tile * 64;
+            const float *r = V + q * vplane + tile * 64;
             f32x4 xv[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) xv[k] = *reinterpret_cast<const f32x4 *>(r + (size_t)k * XIV + nn * 4);
+            for (int k = 0; k < 4; ++k) xv[k] = *reinterpret_cast<const f32x4 *>(r + k * XIV + nn * 4);
 #pragma unroll
             for (int st = 0; st < 6; ++st) {
                 const int p = st >> 1, x0 = (st & 1) * 4;
@@ -898,7 +936,7 @@ __global__ __launch_bounds__(256, 2) void seq2_front_wino_kernel(ConvFrontArgs a
                     const int p1 = (st + 1) >> 1, x1 = ((st + 1) & 1) * 4;
 #pragma unroll
                     for (int k = 0; k < 4; ++k)
-                        yv[k] = *reinterpret_cast<const f32x4 *>(r + (size_t)(x1 + k) * XIV + (size_t)p1 * 4 * a.vplane + ((nn + 4 * p1) & 15) * 4);
+                        yv[k] = *reinterpret_cast<const f32x4 *>(r + (x1 + k) * XIV + p1 * 4 * vplane + ((nn + 4 * p1) & 15) * 4);
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
@@ -927,7 +965,7 @@ __global__ __launch_bounds__(256, 2) void seq2_front_wino_kernel(ConvFrontArgs a
                 yo[1] = f4(0.5f, d56, f4(2.0f, d34, d12)) + b4;
                 yo[2] = f4(0.25f, s56, f4(4.0f, s34, s12)) + b4;
                 yo[3] = f4(0.125f, d56, f4(8.0f, d34, d12)) + acc[7];
-                float *dst = a.out + ((size_t)(chunk0 + c) * a.pout + 4 * t) * a.out_row + a.out_coff + 16 * w + 4 * q;
+                float *dst = obase + (unsigned)((c * a.pout + 4 * t) * a.out_row + 16 * w + 4 * q);
                 const int nvalid = a.pout - 4 * t;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -939,6 +977,9 @@ __global__ __launch_bounds__(256, 2) void seq2_front_wino_kernel(ConvFrontArgs a
                 }
             }
         }
+        };
+        if (a.vplane == 128) tiles(std::integral_constant<int, 128>{});
+        else tiles(std::integral_constant<int, 0>{});
     }
 }
 

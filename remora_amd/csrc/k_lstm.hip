@@ -64,8 +64,10 @@ __device__ __forceinline__ void gates(const f32x4 (&acc)[4], f32x4 &c, f32x4 &h)
 }
 
 // One LSTM step for this wave's 16 hidden units x 16 chunks.
-//   acc  = accN (bias + W_ih x_t, computed during the previous step) [+ W_hh h_{t-1} if HAS_H]
+//   acc  (in: bias + W_ih x_t, computed during the previous step) [+= W_hh h_{t-1} if HAS_H]
 //   accN = bias + W_ih x_{t+1}   [if HAS_X]   -- independent of h_t
+// acc and accN are two register sets that the caller swaps from step to step: the recurrent MFMAs accumulate where the
+// projection left its sums and the next projection starts from bias as its C operand, so no accumulator is ever copied.
 // The fp32 MFMA shares the SIMD's fp32 datapath with ordinary VALU work (ablation: removing
 // the gate transcendentals raised the kernel from 114 to 134 TFLOP/s), so the gate math is
 // kept minimal: the i/f/o rows of W and b are pre-scaled by -log2(e) and the g rows by
@@ -77,10 +79,9 @@ template <int H, bool HAS_H, bool HAS_X, int ABL>
 __device__ __forceinline__ void lstm_step(const float (&xb_img)[4][16][(H / 16 % 2 == 0) ? H / 4 + 4 : H / 4],
                                           const float (&hb_img)[4][16][(H / 16 % 2 == 0) ? H / 4 + 4 : H / 4],
                                           int q, int nn, const float (&Aih)[4][H / 4], const float (&Ahh)[4][H / 4],
-                                          const f32x4 (&bias)[4], f32x4 (&accN)[4], f32x4 &c, f32x4 &h) {
+                                          const f32x4 (&bias)[4], f32x4 (&acc)[4], f32x4 (&accN)[4], f32x4 &c, f32x4 &h) {
     constexpr int KS = H / 4, G = H / 16;
     constexpr int RS = (G % 2 == 0) ? H / 4 + 4 : H / 4;
-    f32x4 acc[4] = {accN[0], accN[1], accN[2], accN[3]};
     f32x4 bx[G];
     if (HAS_X) {  // B fragments of x_{t+1} first (LDS latency hidden behind the recurrent MFMAs)
         const float *xb = &xb_img[q][nn][0];
@@ -187,26 +188,42 @@ __global__ __launch_bounds__(4 * H, 2) void lstm_head_kernel(LstmArgs a) {
         // non-linearities of step t and keep the matrix pipe busy while the VALU/transcendental
         // work runs; only W_hh h_{t-1} (4*KS MFMAs) sits on the recurrent critical path.
         f32x4 c = {0.f, 0.f, 0.f, 0.f};
-        f32x4 accN[4] = {bias[0], bias[1], bias[2], bias[3]};
-        xproj<KS, G, RS>(xbuf[0], q, nn, Aih, accN);
+        f32x4 accA[4] = {bias[0], bias[1], bias[2], bias[3]}, accB[4];
+        xproj<KS, G, RS>(xbuf[0], q, nn, Aih, accA);
         // step 0 ends with xbuf[0] overwritten (x_2): every wave has to be past its x_0 reads first (k_lstm_x16.hip has the
         // account of what happened without this barrier when processes shared the GPU)
         RMR_SYNC();
-        for (int t = 0; t < a.T; ++t) {
-            // x_{t+2} (clamped: the last two fetches are redundant re-reads, never consumed)
-            const int tf = (t + 2 < a.T) ? t + 2 : a.T - 1;
-            const float4 xnext = xsrc[(size_t)tf * (H / 4)];
-            f32x4 h;
-            if (t == 0)
-                lstm_step<H, false, true, ABL>(xbuf[1], hbuf[1], q, nn, Aih, Ahh, bias, accN, c, h);
-            else if (t + 1 < a.T)
-                lstm_step<H, true, true, ABL>(xbuf[(t + 1) & 1], hbuf[(t + 1) & 1], q, nn, Aih, Ahh, bias, accN, c, h);
-            else
-                lstm_step<H, true, false, ABL>(xbuf[(t + 1) & 1], hbuf[(t + 1) & 1], q, nn, Aih, Ahh, bias, accN, c, h);
-            *reinterpret_cast<f32x4 *>(&hbuf[t & 1][q][nn][4 * w]) = h;
-            *reinterpret_cast<float4 *>(&xbuf[t & 1][st_q][st_row][4 * st_g]) = xnext;
-            if (!(ABL & 2)) RMR_SYNC();  // ABL&2: timing ablation without the per-step barrier
+        // One step t: fetch x_{t+2} (clamped: the last two fetches are redundant re-reads, never consumed), run the cell on
+        // `in` while `out` collects the projection of x_{t+1}, publish h_t and x_{t+2} in the images of parity p = t & 1.
+#define RMR_LSTM_STEP(HAS_H, HAS_X, t_, p_, in, out)                                                                   \
+    do {                                                                                                               \
+        const int tt = (t_), pp = (p_);                                                                                \
+        const int tf = (tt + 2 < a.T) ? tt + 2 : a.T - 1;                                                              \
+        const float4 xnext = xsrc[(size_t)tf * (H / 4)];                                                               \
+        f32x4 h;                                                                                                       \
+        lstm_step<H, HAS_H, HAS_X, ABL>(xbuf[pp ^ 1], hbuf[pp ^ 1], q, nn, Aih, Ahh, bias, in, out, c, h);             \
+        *reinterpret_cast<f32x4 *>(&hbuf[pp][q][nn][4 * w]) = h;                                                       \
+        *reinterpret_cast<float4 *>(&xbuf[pp][st_q][st_row][4 * st_g]) = xnext;                                        \
+        if (!(ABL & 2)) RMR_SYNC(); /* ABL&2: timing ablation without the per-step barrier */                          \
+    } while (0)
+        // The time loop runs two steps per trip with the roles of the two accumulator sets exchanged between them: a loop
+        // of single steps has to hand accN over to acc in registers, 16 v_mov per step beside the MFMAs (and the three-way
+        // choice of step kind in its body cost 20 more where the branches met).  Steps: 0 (no h yet), 1 .. T-2 in pairs,
+        // one odd middle step if T is odd, T-1 (no x_{t+1} to project).
+        RMR_LSTM_STEP(false, true, 0, 0, accA, accB);
+        int t = 1;
+        for (; t + 2 < a.T; t += 2) {  // t odd
+            RMR_LSTM_STEP(true, true, t, 1, accB, accA);
+            RMR_LSTM_STEP(true, true, t + 1, 0, accA, accB);
         }
+        if (t + 1 < a.T) {  // odd middle step: its sums move back to accB, once per 16-chunk group
+            RMR_LSTM_STEP(true, true, t, 1, accB, accA);
+#pragma unroll
+            for (int gt = 0; gt < 4; ++gt) accB[gt] = accA[gt];
+            ++t;
+        }
+        if (t < a.T) RMR_LSTM_STEP(true, false, t, t & 1, accB, accA);
+#undef RMR_LSTM_STEP
 
         // ---- lstm2: one step on swish(h1[T-1]), gates i, g, o only (c0 = 0 kills f) ----
         f32x4 acc2[3];
