@@ -682,6 +682,36 @@ int rmr_rescale_quantiles(rmr_refiner *r, int64_t n_reads, const int16_t *dacs, 
 int rmr_base_metrics(rmr_engine *e, int64_t n_reads, const int16_t *dacs, const int64_t *sig_off, const int64_t *seq_to_sig,
                      const int64_t *seq_off, const double *shift, const double *scale, int64_t max_read_bases, int start_trim,
                      int end_trim, float *dwell, double *mean, double *sd, double *trimmean, double *trimsd);
+/* replaces, for a list of (read, region) pairs of one resident batch in one launch: io.Read.compute_per_base_metric(metric,
+ * region=...) as io.get_ref_reg_sample_metrics stacks it (src/remora/io.py:840-886, :2394-2479) - the metrics of only the bases of
+ * a read that lie in a reference region, NaN where the read does not cover the region (:2471-2478), the row reversed for reference
+ * orientation on the reverse strand (:879-885).  Reads as in rmr_base_metrics.  pairs i64[n_pairs][8]: read (index into the
+ * batch), first, last (bases [first, last) of the read, read-local), lead (region positions in front of the read's first base),
+ * row, region length, flip (0 / 1), 0; max_pair_bases >= every last - first (sizes the launch).  Outputs f64[rows][width], any may
+ * be NULL (dwell is the float32 value of rmr_base_metrics, widened): base first + i of the pair goes to column lead + i of its row,
+ * or, flipped, region length - 1 - (lead + i); every other column of the row is NaN.  The values are the bits rmr_base_metrics
+ * gives for the same bases: the 64-base groups of the read that meet [first, last) are summed, counted from the read's first base.
+ * A pair is used only if 0 <= first < last <= bases of its read, lead + (last - first) <= region length <= width and 0 <= row <
+ * rows; otherwise nothing is written for it and status[pair] = 1 (0: done).  status i32[n_pairs].  Two pairs must not share a
+ * row.  All array pointers are DEVICE memory.  Asynchronous on the engine's stream. */
+int rmr_region_base_metrics(rmr_engine *e, int64_t n_reads, const int16_t *dacs, const int64_t *sig_off, const int64_t *seq_to_sig,
+                            const int64_t *seq_off, const double *shift, const double *scale, int64_t n_pairs, const int64_t *pairs,
+                            int64_t max_pair_bases, int start_trim, int end_trim, int64_t rows, int64_t width, double *dwell, double *mean,
+                            double *sd, double *trimmean, double *trimsd, int32_t *status);
+/* replaces, for the same pairs: Read.extract_ref_reg (src/remora/io.py:2342-2392; the signal of Read.get_sig_type :2294-2308).
+ * Per pair, with map = seq_to_sig of its read: the samples [map[first], map[last]) as (dacs - shift[read]) / scale[read] in float64
+ * (raw = 0: sig_out is f64; the caller's shift / scale arrays choose "norm", "pa" or "zc_pa") or the int16 samples themselves (raw =
+ * 1: sig_out is i16, "dac"), at sig_out[sig_out_off[pair] ..]; the last - first + 1 entries map[first .. last] - map[first] at
+ * map_out[map_out_off[pair] ..]; sig_start[pair] = map[first] (read-local).  flip: the samples back to front and the mapping as
+ * map[-1] - map[::-1] (:2376-2379).  sig_out_off / map_out_off i64[n_pairs + 1]: the pairs back to back; the caller reads map[first]
+ * and map[last] to lay them out, and a pair whose slots are not exactly its sizes, or end beyond sig_capacity / map_capacity
+ * (items), or whose read, first or last fail the checks of rmr_region_base_metrics, writes nothing: status[pair] = 1; a mapping that
+ * leaves the read's signal there: status 2.  A pair's lead, row and region length are not looked at by this call.  All array pointers
+ * are DEVICE memory.  Asynchronous on the engine's stream. */
+int rmr_region_signals(rmr_engine *e, int64_t n_reads, const int16_t *dacs, const int64_t *sig_off, const int64_t *seq_to_sig,
+                       const int64_t *seq_off, const double *shift, const double *scale, int64_t n_pairs, const int64_t *pairs,
+                       const int64_t *sig_out_off, const int64_t *map_out_off, int raw, void *sig_out, int64_t sig_capacity, int64_t *map_out,
+                       int64_t map_capacity, int64_t *sig_start, int32_t *status);
 /* replaces: io.get_region_kmers (src/remora/io.py:930-982; sequence from get_ref_seq_from_reads :671-703) over every region
  * of io.get_site_kmer_levels (:991-1044) and the median per k-mer of `remora analyze estimate_kmer_levels`
  * (src/remora/parsers.py:2296-2331).  The bases of n_reads reference-anchored reads, concatenated (seq_off i64[n_reads + 1]), are

@@ -152,6 +152,10 @@ SIGNATURES = {
     "rmr_rescale_quantiles": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp,
                                       c_vp, c_vp]),
     "rmr_base_metrics": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rmr_region_base_metrics": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_i64, c_i64, c_vp, c_vp,
+                                        c_vp, c_vp, c_vp, c_vp]),
+    "rmr_region_signals": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_i64,
+                                   c_vp, c_vp]),
     "rmr_site_kmer_levels": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_vp,
                                      ctypes.POINTER(c_i64)]),
     "rmr_profile_enable": (c_int, [c_vp, c_int]),

@@ -1,6 +1,9 @@
 // k_metrics.hip - per-base signal metrics of a batch of reads and the k-mer level table estimated from them:
 //   rmr_base_metrics       src/remora/metrics.py:45-117 (METRIC_FUNCS) as io.Read.compute_per_base_metric applies them
 //                          (src/remora/io.py:2394-2480), for every base of every read of a batch in one launch
+//   rmr_region_base_metrics / rmr_region_signals   the same metrics, and the normalised samples, of only the bases of a read that lie
+//                          in a reference region (io.get_ref_reg_sample_metrics :840-886, Read.extract_ref_reg :2342-2392), for a
+//                          list of (read, region) pairs of a resident batch
 //   rmr_site_kmer_levels   io.get_region_kmers (src/remora/io.py:930-982) + the aggregation of `remora analyze
 //                          estimate_kmer_levels` (src/remora/parsers.py:2296-2331): median per reference site, then per k-mer
 //
@@ -57,19 +60,16 @@ __device__ __forceinline__ void wave_lds_sync() {
 
 constexpr int BM_WAVES = 4;  // waves (groups of 64 bases) per block
 
-__global__ __launch_bounds__(64 * BM_WAVES) void base_metrics_kernel(BaseMetricsArgs a) {
-    __shared__ int64_t s_pre[BM_WAVES][65];    // prefix sum of the group's dwells; [64] = the group's samples
-    __shared__ int64_t s_start[BM_WAVES][64];  // first sample of every base, read-local
-    __shared__ double s_acc[BM_WAVES][4][64];  // per base: sum x, sum x^2, and the same inside the trims
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t r = blockIdx.x;
-    const int64_t b0 = a.seq_off[r], nb = a.seq_off[r + 1] - b0;
-    const int64_t g0 = ((int64_t)blockIdx.y * BM_WAVES + wave) * 64;  // the group's first base, read-local
-    if (g0 >= nb) return;                                               // (wave-uniform; no block barrier below)
-    const int64_t *map = a.seq_to_sig + b0 + r;  // nb + 1 entries
-    const int64_t s0 = a.sig_off[r], sig_len = a.sig_off[r + 1] - s0;
-    const int16_t *dacs = a.dacs + s0;
-    const double sh = a.shift[r], sc = a.scale[r];
+// One wave, one group of 64 bases: bases g0 .. g0 + 63 of a read of nb bases whose mapping (nb + 1 entries) is `map` and whose
+// own signal is dacs[0 .. sig_len).  The summation of base_metrics_kernel and region_metrics_kernel: what a base's sums look like
+// depends on the read and on g0 alone, and both kernels hand over g0 = a multiple of 64 counted from the read's first base, so a
+// base has the same bits wherever it is asked for.  `Sink::put(bi, dwell, mean, has, sum x^2, trimmean, has_t, trimmed sum x^2,
+// trimmed dwell)` is called by the lane of every base bi < nb of the group and decides where (and whether) the results go; it
+// forms the two sd itself (sd_of), and only where somebody wants them.  s_pre / s_start / s_acc: this wave's LDS.
+template <class Sink>
+__device__ __forceinline__ void base_group_metrics(const int16_t *dacs, int64_t sig_len, const int64_t *map, int64_t nb, int64_t g0, double sh,
+                                                   double sc, int st, int en, int lane, int64_t *s_pre, int64_t *s_start, double (*s_acc)[64],
+                                                   const Sink &sink) {
     const int64_t bi = g0 + lane;
     const bool live = bi < nb;
     int64_t ms = 0, me = 0;
@@ -85,14 +85,13 @@ __global__ __launch_bounds__(64 * BM_WAVES) void base_metrics_kernel(BaseMetrics
         hi = __shfl_up(hi, off);
         if (lane >= off) inc += (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
     }
-    s_pre[wave][lane + 1] = inc;
-    if (lane == 0) s_pre[wave][0] = 0;
-    s_start[wave][lane] = cs;
+    s_pre[lane + 1] = inc;
+    if (lane == 0) s_pre[0] = 0;
+    s_start[lane] = cs;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) s_acc[wave][q][lane] = 0.0;
+    for (int q = 0; q < 4; ++q) s_acc[q][lane] = 0.0;
     wave_lds_sync();
-    const int64_t total = s_pre[wave][64];
-    const int st = a.start_trim, en = a.end_trim;
+    const int64_t total = s_pre[64];
     for (int64_t j0 = 0; j0 < total; j0 += 64) {
         const int64_t j = j0 + lane;
         const bool valid = j < total;
@@ -102,11 +101,11 @@ __global__ __launch_bounds__(64 * BM_WAVES) void base_metrics_kernel(BaseMetrics
             int lo = 0, hi = 64;  // the base that owns sample j: the first b with pre[b + 1] > j
             while (lo < hi) {
                 const int mid = (lo + hi) >> 1;
-                if (s_pre[wave][mid + 1] <= j) lo = mid + 1; else hi = mid;
+                if (s_pre[mid + 1] <= j) lo = mid + 1; else hi = mid;
             }
             b = lo;
-            const int64_t k = j - s_pre[wave][b], n = s_pre[wave][b + 1] - s_pre[wave][b];
-            x = norm_sample_f64(dacs[s_start[wave][b] + k], sh, sc);
+            const int64_t k = j - s_pre[b], n = s_pre[b + 1] - s_pre[b];
+            x = norm_sample_f64(dacs[s_start[b] + k], sh, sc);
             xx = __dmul_rn(x, x);
             if (k >= st && k < n - en) { tx = x; txx = xx; }
         }
@@ -119,10 +118,10 @@ __global__ __launch_bounds__(64 * BM_WAVES) void base_metrics_kernel(BaseMetrics
         }
         const int nxt = __shfl_down(b, 1);
         if (valid && (lane == 63 || nxt != b)) {  // one lane per base and round: a plain read-modify-write
-            s_acc[wave][0][b] = __dadd_rn(s_acc[wave][0][b], x);
-            s_acc[wave][1][b] = __dadd_rn(s_acc[wave][1][b], xx);
-            s_acc[wave][2][b] = __dadd_rn(s_acc[wave][2][b], tx);
-            s_acc[wave][3][b] = __dadd_rn(s_acc[wave][3][b], txx);
+            s_acc[0][b] = __dadd_rn(s_acc[0][b], x);
+            s_acc[1][b] = __dadd_rn(s_acc[1][b], xx);
+            s_acc[2][b] = __dadd_rn(s_acc[2][b], tx);
+            s_acc[3][b] = __dadd_rn(s_acc[3][b], txx);
         }
         wave_lds_sync();
     }
@@ -130,16 +129,44 @@ __global__ __launch_bounds__(64 * BM_WAVES) void base_metrics_kernel(BaseMetrics
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     const float dwell_f = (float)(me - ms);                     // np.diff(seq_to_sig).astype(float32)
     const float tdwell_f = fmaxf(0.f, dwell_f - (float)st - (float)en);  // np.maximum(0, dwells - st - en), float32 as there
-    const int64_t out = b0 + bi;
     const bool has = dw > 0 && me - ms == dw, has_t = has && tdwell_f > 0.f;  // (a mapping that leaves the signal: NaN, nothing half-summed)
-    if (a.dwell) a.dwell[out] = dwell_f;
-    const double sx = s_acc[wave][0][lane], sxx = s_acc[wave][1][lane], stx = s_acc[wave][2][lane], stxx = s_acc[wave][3][lane];
+    const double sx = s_acc[0][lane], sxx = s_acc[1][lane], stx = s_acc[2][lane], stxx = s_acc[3][lane];
     const double m = has ? sx / (double)dwell_f : nan;
     const double tm = has_t ? stx / (double)tdwell_f : nan;
-    if (a.mean) a.mean[out] = m;
-    if (a.trimmean) a.trimmean[out] = tm;
-    if (a.sd) a.sd[out] = has ? sqrt(fmax(__dsub_rn(sxx / (double)dwell_f, __dmul_rn(m, m)), 0.0)) : nan;
-    if (a.trimsd) a.trimsd[out] = has_t ? sqrt(fmax(__dsub_rn(stxx / (double)tdwell_f, __dmul_rn(tm, tm)), 0.0)) : nan;
+    sink.put(bi, dwell_f, m, has, sxx, tm, has_t, stxx, tdwell_f);
+}
+
+// sd = sqrt(max(0, E[x^2] - mean^2)), evaluated only where somebody wants it
+__device__ __forceinline__ double sd_of(bool has, double sxx, double n, double m) {
+    return has ? sqrt(fmax(__dsub_rn(sxx / n, __dmul_rn(m, m)), 0.0)) : __longlong_as_double(0x7ff8000000000000LL);
+}
+
+struct BatchSink {  // base bi of the read -> entry b0 + bi of the batch's per-base arrays
+    const BaseMetricsArgs &a;
+    int64_t b0;
+    __device__ __forceinline__ void put(int64_t bi, float dwell_f, double m, bool has, double sxx, double tm, bool has_t, double stxx,
+                                        float tdwell_f) const {
+        const int64_t out = b0 + bi;
+        if (a.dwell) a.dwell[out] = dwell_f;
+        if (a.mean) a.mean[out] = m;
+        if (a.trimmean) a.trimmean[out] = tm;
+        if (a.sd) a.sd[out] = sd_of(has, sxx, (double)dwell_f, m);
+        if (a.trimsd) a.trimsd[out] = sd_of(has_t, stxx, (double)tdwell_f, tm);
+    }
+};
+
+__global__ __launch_bounds__(64 * BM_WAVES) void base_metrics_kernel(BaseMetricsArgs a) {
+    __shared__ int64_t s_pre[BM_WAVES][65];    // prefix sum of the group's dwells; [64] = the group's samples
+    __shared__ int64_t s_start[BM_WAVES][64];  // first sample of every base, read-local
+    __shared__ double s_acc[BM_WAVES][4][64];  // per base: sum x, sum x^2, and the same inside the trims
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t r = blockIdx.x;
+    const int64_t b0 = a.seq_off[r], nb = a.seq_off[r + 1] - b0;
+    const int64_t g0 = ((int64_t)blockIdx.y * BM_WAVES + wave) * 64;  // the group's first base, read-local
+    if (g0 >= nb) return;                                               // (wave-uniform; no block barrier below)
+    const int64_t s0 = a.sig_off[r];
+    base_group_metrics(a.dacs + s0, a.sig_off[r + 1] - s0, a.seq_to_sig + b0 + r, nb, g0, a.shift[r], a.scale[r], a.start_trim, a.end_trim, lane,
+                       s_pre[wave], s_start[wave], s_acc[wave], BatchSink{a, b0});
 }
 
 int launch_base_metrics(rmr_engine *e, int64_t n_reads, int64_t max_read_bases, const BaseMetricsArgs &a) {
@@ -150,6 +177,147 @@ int launch_base_metrics(rmr_engine *e, int64_t n_reads, int64_t max_read_bases, 
     hipLaunchKernelGGL(base_metrics_kernel, dim3((unsigned)n_reads, (unsigned)gy), dim3(64 * BM_WAVES), 0, e->stream, a);
     RMR_HIP(hipGetLastError());
     return 0;
+}
+
+// ======================================================================================
+// regions: the bases (and the samples) of a read that lie in a reference region, for a list of (read, region) pairs
+// ======================================================================================
+// A pair, 8 x int64: the read (index into the batch), [first, last) its bases inside the region (read-local), `lead` region
+// positions in front of the read's first base, the pair's `row` of the output, the region's length, `flip` (the row is written
+// back to front: reference orientation on the reverse strand), one spare.  The host plans the pairs (io.plan_region_pairs).
+constexpr int RP_READ = 0, RP_FIRST = 1, RP_LAST = 2, RP_LEAD = 3, RP_ROW = 4, RP_RLEN = 5, RP_FLIP = 6, RP_WORDS = 8;
+
+struct RegionMetricsArgs {
+    const int16_t *dacs;
+    const int64_t *sig_off, *seq_to_sig, *seq_off;
+    const double *shift, *scale;
+    const int64_t *pairs;
+    int64_t n_reads, rows, width;
+    double *dwell, *mean, *sd, *trimmean, *trimsd;  // [rows][width] each, any may be NULL
+    int32_t *status;
+    int start_trim, end_trim;
+};
+
+struct RegionPair {
+    int64_t read, first, last, lead, row, rlen;
+    bool flip;
+};
+__device__ __forceinline__ RegionPair load_pair(const int64_t *pairs, int64_t p) {
+    const int64_t *w = pairs + p * RP_WORDS;
+    return RegionPair{w[RP_READ], w[RP_FIRST], w[RP_LAST], w[RP_LEAD], w[RP_ROW], w[RP_RLEN], w[RP_FLIP] != 0};
+}
+// what the wrapper checks before the launch, once more where an index would be formed from it: the pair's span inside its read
+// (all rmr_region_signals uses of a pair beside its flip), and its place in the region and in the output
+__device__ __forceinline__ bool span_fits(const RegionPair &q, int64_t n_reads, const int64_t *seq_off) {
+    if (q.read < 0 || q.read >= n_reads) return false;
+    const int64_t nb = seq_off[q.read + 1] - seq_off[q.read];
+    return q.first >= 0 && q.first < q.last && q.last <= nb;
+}
+__device__ __forceinline__ bool pair_fits(const RegionPair &q, int64_t n_reads, const int64_t *seq_off, int64_t rows, int64_t width) {
+    return span_fits(q, n_reads, seq_off) && q.lead >= 0 && q.rlen > 0 && q.rlen <= width && q.last - q.first <= q.rlen &&
+           q.lead <= q.rlen - (q.last - q.first) && q.row >= 0 && q.row < rows;
+}
+
+struct RegionSink {  // base bi of the read -> column lead + bi - first of the pair's row (counted from the row's end when flipped)
+    const RegionMetricsArgs &a;
+    const RegionPair &q;
+    __device__ __forceinline__ void put(int64_t bi, float dwell_f, double m, bool has, double sxx, double tm, bool has_t, double stxx,
+                                        float tdwell_f) const {
+        if (bi < q.first || bi >= q.last) return;  // (the rest of the 64-base group: summed for the grouping's sake, not asked for)
+        const int64_t pos = q.lead + (bi - q.first);
+        const int64_t out = q.row * a.width + (q.flip ? q.rlen - 1 - pos : pos);
+        if (a.dwell) a.dwell[out] = (double)dwell_f;
+        if (a.mean) a.mean[out] = m;
+        if (a.trimmean) a.trimmean[out] = tm;
+        if (a.sd) a.sd[out] = sd_of(has, sxx, (double)dwell_f, m);
+        if (a.trimsd) a.trimsd[out] = sd_of(has_t, stxx, (double)tdwell_f, tm);
+    }
+};
+
+// grid (pairs, groups of BM_WAVES 64-base groups): wave w of block y runs group first / 64 + y * BM_WAVES + w of the pair's read.
+// Block y = 0 also writes the NaN of every column of the row that the read does not cover, and the pair's status word.
+__global__ __launch_bounds__(64 * BM_WAVES) void region_metrics_kernel(RegionMetricsArgs a) {
+    __shared__ int64_t s_pre[BM_WAVES][65];
+    __shared__ int64_t s_start[BM_WAVES][64];
+    __shared__ double s_acc[BM_WAVES][4][64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const RegionPair q = load_pair(a.pairs, blockIdx.x);
+    const bool fits = pair_fits(q, a.n_reads, a.seq_off, a.rows, a.width);
+    if (blockIdx.y == 0 && threadIdx.x == 0) a.status[blockIdx.x] = fits ? 0 : 1;
+    if (!fits) return;  // (block-uniform) a pair that does not fit writes nothing
+    if (blockIdx.y == 0) {
+        const double nan = __longlong_as_double(0x7ff8000000000000LL);
+        const int64_t covered = q.last - q.first;
+        for (int64_t c = threadIdx.x; c < a.width; c += 64 * BM_WAVES) {
+            const int64_t pos = c < q.rlen ? (q.flip ? q.rlen - 1 - c : c) : -1;
+            if (pos >= q.lead && pos < q.lead + covered) continue;
+            const int64_t out = q.row * a.width + c;
+            if (a.dwell) a.dwell[out] = nan;
+            if (a.mean) a.mean[out] = nan;
+            if (a.sd) a.sd[out] = nan;
+            if (a.trimmean) a.trimmean[out] = nan;
+            if (a.trimsd) a.trimsd[out] = nan;
+        }
+    }
+    const int64_t r = q.read;
+    const int64_t b0 = a.seq_off[r], nb = a.seq_off[r + 1] - b0;
+    const int64_t g0 = (q.first / 64 + (int64_t)blockIdx.y * BM_WAVES + wave) * 64;  // a group of base_metrics_kernel: counted from base 0
+    if (g0 >= q.last) return;                                                          // (wave-uniform; no block barrier below)
+    const int64_t s0 = a.sig_off[r];
+    base_group_metrics(a.dacs + s0, a.sig_off[r + 1] - s0, a.seq_to_sig + b0 + r, nb, g0, a.shift[r], a.scale[r], a.start_trim, a.end_trim, lane,
+                       s_pre[wave], s_start[wave], s_acc[wave], RegionSink{a, q});
+}
+
+struct RegionSignalsArgs {
+    const int16_t *dacs;
+    const int64_t *sig_off, *seq_to_sig, *seq_off;
+    const double *shift, *scale;
+    const int64_t *pairs, *sig_out_off, *map_out_off;  // offsets: [n_pairs + 1], the pairs' samples / map entries back to back
+    int64_t n_reads, sig_capacity, map_capacity;
+    void *sig_out;  // f64 (normalised) or i16 (RAW)
+    int64_t *map_out, *sig_start;
+    int32_t *status;
+};
+
+// grid (pairs, slices): the samples map[first] .. map[last] of the pair's read, (dacs - shift) / scale in float64 (RAW: the int16
+// samples themselves), and the last - first + 1 mapping entries re-based on the first sample; flipped: samples back to front and
+// map[-1] - map[::-1].  status 1: the pair or its slots do not fit; 2: the mapping leaves the read's signal there.
+template <bool RAW>
+__global__ __launch_bounds__(256) void region_signals_kernel(RegionSignalsArgs a) {
+    const int64_t p = blockIdx.x;
+    const RegionPair q = load_pair(a.pairs, p);
+    int st = 0;
+    int64_t ms = 0, me = 0, so = 0, mo = 0;
+    const int64_t *map = nullptr;
+    const int16_t *dacs = nullptr;
+    if (!span_fits(q, a.n_reads, a.seq_off)) st = 1;  // (lead, row and region length are the metrics kernel's business)
+    if (!st) {
+        const int64_t r = q.read, b0 = a.seq_off[r], s0 = a.sig_off[r], sig_len = a.sig_off[r + 1] - s0;
+        map = a.seq_to_sig + b0 + r;
+        dacs = a.dacs + s0;
+        ms = map[q.first];
+        me = map[q.last];
+        so = a.sig_out_off[p];
+        mo = a.map_out_off[p];
+        if (ms < 0 || me < ms || me > sig_len) st = 2;
+        else if (so < 0 || a.sig_out_off[p + 1] - so != me - ms || a.sig_out_off[p + 1] > a.sig_capacity || mo < 0 ||
+                 a.map_out_off[p + 1] - mo != q.last - q.first + 1 || a.map_out_off[p + 1] > a.map_capacity)
+            st = 1;
+    }
+    if (blockIdx.y == 0 && threadIdx.x == 0) {
+        a.status[p] = st;
+        if (!st) a.sig_start[p] = ms;
+    }
+    if (st) return;
+    const int64_t n = me - ms, nm = q.last - q.first + 1;
+    const int64_t t0 = (int64_t)blockIdx.y * blockDim.x + threadIdx.x, step = (int64_t)gridDim.y * blockDim.x;
+    const double sh = a.shift[q.read], sc = a.scale[q.read];
+    for (int64_t i = t0; i < n; i += step) {
+        const int16_t d = dacs[ms + (q.flip ? n - 1 - i : i)];
+        if (RAW) ((int16_t *)a.sig_out)[so + i] = d;
+        else ((double *)a.sig_out)[so + i] = norm_sample_f64(d, sh, sc);
+    }
+    for (int64_t k = t0; k < nm; k += step) a.map_out[mo + k] = q.flip ? me - map[q.last - k] : map[q.first + k] - ms;
 }
 
 // ======================================================================================
@@ -339,6 +507,51 @@ int rmr_base_metrics(rmr_engine *e, int64_t n_reads, const int16_t *dacs, const 
     RMR_HIP(hipSetDevice(e->device));
     BaseMetricsArgs a{dacs, sig_off, seq_to_sig, seq_off, shift, scale, dwell, mean, sd, trimmean, trimsd, start_trim, end_trim};
     return launch_base_metrics(e, n_reads, max_read_bases, a);
+}
+
+int rmr_region_base_metrics(rmr_engine *e, int64_t n_reads, const int16_t *dacs, const int64_t *sig_off, const int64_t *seq_to_sig,
+                            const int64_t *seq_off, const double *shift, const double *scale, int64_t n_pairs, const int64_t *pairs,
+                            int64_t max_pair_bases, int start_trim, int end_trim, int64_t rows, int64_t width, double *dwell, double *mean,
+                            double *sd, double *trimmean, double *trimsd, int32_t *status) {
+    if (!e || !dacs || !sig_off || !seq_to_sig || !seq_off || !shift || !scale) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if (n_reads < 0 || n_reads > 0x7fffffffLL || n_pairs < 0 || n_pairs > 0x7fffffffLL) RMR_FAIL(RMR_ERR_INVALID, "bad n_reads / n_pairs");
+    if (start_trim < 0 || end_trim < 0) RMR_FAIL(RMR_ERR_INVALID, "trims must not be negative");
+    if (n_pairs == 0) return 0;
+    if (!pairs || !status || n_reads == 0) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if (rows <= 0 || width <= 0 || max_pair_bases <= 0) RMR_FAIL(RMR_ERR_INVALID, "bad rows / width / max_pair_bases");
+    // a span of n bases touches at most (n + 62) / 64 + 1 groups of 64 counted from the read's first base
+    const int64_t groups = (max_pair_bases + 62) / 64 + 1, gy = (groups + BM_WAVES - 1) / BM_WAVES;
+    if (gy > 65535) RMR_FAIL(RMR_ERR_INVALID, "rmr_region_base_metrics: a region of %lld bases is beyond the launch grid", (long long)max_pair_bases);
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    RegionMetricsArgs a{dacs, sig_off, seq_to_sig, seq_off, shift, scale, pairs, n_reads, rows, width, dwell, mean, sd, trimmean, trimsd, status,
+                        start_trim, end_trim};
+    ProfScope ps(e, K_REGION_METRICS);
+    hipLaunchKernelGGL(region_metrics_kernel, dim3((unsigned)n_pairs, (unsigned)gy), dim3(64 * BM_WAVES), 0, e->stream, a);
+    RMR_HIP(hipGetLastError());
+    return 0;
+}
+
+int rmr_region_signals(rmr_engine *e, int64_t n_reads, const int16_t *dacs, const int64_t *sig_off, const int64_t *seq_to_sig,
+                       const int64_t *seq_off, const double *shift, const double *scale, int64_t n_pairs, const int64_t *pairs,
+                       const int64_t *sig_out_off, const int64_t *map_out_off, int raw, void *sig_out, int64_t sig_capacity, int64_t *map_out,
+                       int64_t map_capacity, int64_t *sig_start, int32_t *status) {
+    if (!e || !dacs || !sig_off || !seq_to_sig || !seq_off || !shift || !scale) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if (n_reads < 0 || n_reads > 0x7fffffffLL || n_pairs < 0 || n_pairs > 0x7fffffffLL) RMR_FAIL(RMR_ERR_INVALID, "bad n_reads / n_pairs");
+    if (n_pairs == 0) return 0;
+    if (!pairs || !sig_out_off || !map_out_off || !sig_out || !map_out || !sig_start || !status || n_reads == 0)
+        RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if (sig_capacity < 0 || map_capacity < 0) RMR_FAIL(RMR_ERR_INVALID, "bad capacity");
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    RegionSignalsArgs a{dacs, sig_off, seq_to_sig, seq_off, shift, scale, pairs, sig_out_off, map_out_off, n_reads, sig_capacity, map_capacity,
+                        sig_out, map_out, sig_start, status};
+    ProfScope ps(e, K_REGION_SIGNALS);
+    const dim3 grid((unsigned)n_pairs, 8), block(256);
+    if (raw) hipLaunchKernelGGL(region_signals_kernel<true>, grid, block, 0, e->stream, a);
+    else hipLaunchKernelGGL(region_signals_kernel<false>, grid, block, 0, e->stream, a);
+    RMR_HIP(hipGetLastError());
+    return 0;
 }
 
 int rmr_site_kmer_levels(rmr_engine *e, int64_t n_reads, const int64_t *seq_off, const int64_t *site0, int64_t n_bases,

@@ -61,6 +61,8 @@ enum KernelId {
     K_PROBE_NONFINITE,
     K_WINO_FORM,  // a launch count without a time: every kernel launched in a Winograd form is ALSO counted here (its time stays under its layer's id)
     K_BASE_METRICS,
+    K_REGION_METRICS,
+    K_REGION_SIGNALS,
     K_SITE_KMER_LEVELS,  // its kernels and the four radix sorts between them, bracketed in two pieces
     K_MODBAM_SITES,
     K_NUM

@@ -457,6 +457,23 @@ class DeviceReads:
 
         return base_metrics(self, metric, start_trim, end_trim)
 
+    def region_metrics(self, pairs, metric, start_trim=1, end_trim=1, rows=None, width=None, shift=None, scale=None):
+        """A named per-base metric for only the bases of (read, region) pairs, one launch (rmr_region_base_metrics): {key:
+        float64 device tensor [rows, width]}, NaN where a read does not cover its region.  `pairs`: int64 [n, 7] - read, first,
+        last, lead, row, region length, flip (the columns io.plan_region_pairs returns, stacked in this order, `read` counted inside this batch).  The values are the bits per_base_metrics gives the same
+        bases.  A pair that does not fit its read, its region or the output is refused before anything is launched."""
+        from .region_metrics import device_region_metrics
+
+        return device_region_metrics(self, pairs, metric, start_trim, end_trim, rows, width, shift, scale)
+
+    def region_signals(self, pairs, shift=None, scale=None, raw=False):
+        """The samples and the region-local mapping of (read, region) pairs, one launch (rmr_region_signals): numpy arrays
+        (signal, sig_off, seq_to_sig, map_off, sig_start) - the pairs' float64 samples (dacs - shift) / scale (`raw`: the int16
+        samples) and mapping entries back to back.  `shift` / `scale`: float64 per read (default: the batch's own)."""
+        from .region_metrics import device_region_signals
+
+        return device_region_signals(self, pairs, shift, scale, raw)
+
     def motif_focus_bases(self, motifs):
         """Focus bases of all motif hits, ascending inside each read: (focus i64[F] read-local, on the device;
         foc_off i64[n_reads+1] on the host).  GPU counterpart of RemoraRead.set_motif_focus_bases for a batch

@@ -115,6 +115,16 @@ class BamRecord:
     def is_supplementary(self):
         return bool(self.flag & 0x800)
 
+    @property
+    def is_forward(self):
+        return not self.is_reverse
+
+    @property
+    def reference_end(self):
+        """One past the last reference position of the alignment (pysam's: None for a record that consumes no reference)."""
+        span = sum(ln for op, ln in (self.cigartuples or ()) if op in (0, 2, 3, 7, 8))
+        return self.reference_start + span if span else None
+
     def get_tag(self, name):
         for k, v in self.tags:
             if k == name:
@@ -1240,11 +1250,30 @@ class RefRegion:
 
     @property
     def len(self):
-        return self.end - self.start
+        return 1 if self.end is None else self.end - self.start
+
+    @classmethod
+    def parse_ref_region_str(cls, ref_reg_str, req_strand=True):
+        """`ctg:start-end:strand` with a 1-based closed span (the strand optional unless `req_strand`), src/remora/io.py:58-76."""
+        mat = re.match(r"^(?P<ctg>.+):(?P<st>\d+)-(?P<en>\d+):(?P<strand>[\+\-])$" if req_strand
+                       else r"^(?P<ctg>.+):(?P<st>\d+)-(?P<en>\d+)(:(?P<strand>[\+\-]))?$", ref_reg_str)
+        if mat is None:
+            raise RemoraError(f"Invalid reference region: {ref_reg_str}")
+        start = int(mat.group("st")) - 1
+        if start < 0:
+            raise RemoraError("Invalid reference start coordinate")
+        return cls(ctg=mat.group("ctg"), strand=mat.group("strand"), start=start, end=int(mat.group("en")))
 
     @property
     def coord_range(self):
         return range(self.start, self.end)
+
+    def adjust(self, start_adjust=0, end_adjust=0, ref_orient=True):
+        """A copy moved by the two amounts; read-oriented (`ref_orient=False`) on the reverse strand the amounts swap ends
+        (src/remora/io.py:82-102)."""
+        if ref_orient or self.strand == "+":
+            return RefRegion(self.ctg, self.strand, self.start + start_adjust, None if self.end is None else self.end + end_adjust)
+        return RefRegion(self.ctg, self.strand, self.start - end_adjust, None if self.end is None else self.end - start_adjust)
 
 
 def parse_bed_lines(bed_path):
@@ -1458,6 +1487,47 @@ class Read:
                 wide[name][lead : lead + v.size] = v
             vals = wide
         return vals
+
+    def extract_basecall_region(self, start_base=None, end_base=None, signal_type="norm"):
+        """The signal and mapping of basecalls [start_base, end_base) as a ReadBasecallRegion (src/remora/io.py:2310-2340)."""
+        from .region_metrics import ReadBasecallRegion
+
+        if self.query_to_signal is None:
+            raise RemoraError("Missing query_to_signal (move table)")
+        start_base = start_base or 0
+        end_base = end_base or len(self.seq)
+        reg_seq_to_sig = self.query_to_signal[start_base : end_base + 1].copy()
+        reg_sig = self.get_sig_type(signal_type)[reg_seq_to_sig[0] : reg_seq_to_sig[-1]]
+        sig_start = reg_seq_to_sig[0]
+        reg_seq_to_sig -= sig_start
+        return ReadBasecallRegion(read_id=self.read_id, norm_signal=reg_sig, seq=self.seq[start_base:end_base],
+                                  seq_to_sig_map=reg_seq_to_sig, start=start_base, sig_start=sig_start)
+
+    def extract_ref_reg(self, ref_reg, signal_type="norm"):
+        """The part of this read inside a reference region as a ReadRefReg, reverse-strand reads turned onto the reference
+        (src/remora/io.py:2342-2392).  Host numpy; io.get_reads_reference_regions is the batch form (rmr_region_signals)."""
+        from .region_metrics import ReadRefReg
+
+        if self.ref_to_signal is None:
+            raise RemoraError("Missing ref_to_signal (move table)")
+        if ref_reg.start >= self.ref_reg.start + len(self.ref_seq):
+            raise RemoraError("Reference region starts after read ends")
+        if ref_reg.end < self.ref_reg.start:
+            raise RemoraError("Reference region ends before read starts")
+        if self.ref_reg.strand == "+":
+            first, last = max(0, ref_reg.start - self.ref_reg.start), ref_reg.end - self.ref_reg.start
+        else:
+            first, last = max(0, self.ref_reg.end - ref_reg.end), self.ref_reg.end - ref_reg.start
+        reg_seq_to_sig = self.ref_to_signal[first : last + 1].copy()
+        reg_sig = self.get_sig_type(signal_type)[reg_seq_to_sig[0] : reg_seq_to_sig[-1]]
+        reg_seq = self.ref_seq[first:last]
+        sig_start = reg_seq_to_sig[0]
+        reg_seq_to_sig -= sig_start
+        ref_st = max(self.ref_reg.start, ref_reg.start)
+        if self.ref_reg.strand == "-":
+            reg_sig, reg_seq, reg_seq_to_sig = reg_sig[::-1], reg_seq[::-1], reg_seq_to_sig[-1] - reg_seq_to_sig[::-1]
+        return ReadRefReg(read_id=self.read_id, norm_signal=reg_sig, seq=reg_seq, seq_to_sig_map=reg_seq_to_sig,
+                          ref_reg=RefRegion(self.ref_reg.ctg, self.ref_reg.strand, ref_st, ref_st + len(reg_seq)), sig_start=sig_start)
 
     def compute_pa_to_norm_scaling(self, factor=PA_TO_NORM_SCALING_FACTOR):
         """src/remora/io.py:1851-1856 (median / MAD)."""
@@ -1703,10 +1773,13 @@ class IngestBatch:
     (ReadStub per good read), `seq` (their strand-oriented bases, ASCII, back to back) and `seq_off`.  Reference-anchored
     batches: `seq` holds the reference bases of the alignments in read orientation (what the reads are anchored on), and
     `ref_fwd` / `ref_fwd_off` (int64[len(keep) + 1]) the same bases in forward-strand orientation per KEPT record (empty for
-    records that cannot be called) - what the output records are rewritten with; None otherwise.  `per_read()` - the same
+    records that cannot be called) - what the output records are rewritten with; None otherwise.  `map0` (reference-anchored
+    batches, int64 per good read): the sample of the read's trimmed signal its first base starts on (ref_to_signal[0] of the
+    io.Read), which `dr`'s mapping is re-based on; `cal_off` / `cal_scale` (float64 per good read): the pA calibration.  `per_read()` - the same
     records as (io.Read, error) pairs of the per-read path, built on demand."""
 
-    __slots__ = ("rb", "keep", "err", "good", "dr", "reads", "seq", "iseq", "seq_off", "records", "ref_fwd", "ref_fwd_off", "per_read")
+    __slots__ = ("rb", "keep", "err", "good", "dr", "reads", "seq", "iseq", "seq_off", "records", "ref_fwd", "ref_fwd_off", "per_read", "map0",
+                 "cal_off", "cal_scale")
 
     def __len__(self):
         return int(self.keep.size)
@@ -1721,6 +1794,7 @@ class IngestBatch:
         out.ref_fwd, out.ref_fwd_off = self.ref_fwd, (None if self.ref_fwd_off is None else self.ref_fwd_off[: k + 1])
         out.per_read = (lambda pr=self.per_read, kk=k: pr()[:kk]) if self.per_read is not None else None
         g = int(np.searchsorted(self.good, k))
+        out.map0, out.cal_off, out.cal_scale = (None if x is None else x[:g] for x in (self.map0, self.cal_off, self.cal_scale))
         out.good, out.reads, out.seq_off = self.good[:g], self.reads[:g], self.seq_off[: g + 1]
         out.seq = self.seq[: int(self.seq_off[g])]
         out.iseq = self.iseq[: int(self.seq_off[g])]
@@ -1822,7 +1896,7 @@ def _section_clock():
     return clock
 
 
-def _ingest_batch(rb, records, signals, eng, pa_scaling, skip_non_primary, ref_anchored=False, reverse_signal=False):
+def _ingest_batch(rb, records, signals, eng, pa_scaling, skip_non_primary, ref_anchored=False, reverse_signal=False, select=None):
     """IngestBatch of one raw BAM batch, or None when nothing of it is kept.  Everything Read.from_pod5 + add_alignment +
     into_remora_read do per read, for the batch: trimming by sp / ts / ns, strand-aware
     sequence, move tables -> query_to_signal (one launch), sm / sd composed with the calibration, the trim to the mapped span.
@@ -1837,6 +1911,7 @@ def _ingest_batch(rb, records, signals, eng, pa_scaling, skip_non_primary, ref_a
     (rmr_ref_anchor_batch: src/remora/io.py:2066-2084), the reference sequence rebuilt from MD by the native reader, and
     the same assembly kernel cuts signal and mapping (ref_to_signal in place of query_to_signal).
     Reads without sm / sd tags get the median / MAD scaling from GPU histograms of their trimmed signal (_median_mad_scaling).
+    `select` (bool per record of `rb`): only these records are looked at - the signals of the others are never read.
     A batch that holds something the array form does not reproduce (negative trim tags, bases outside A-Z, an aligned record
     without a move table) is returned as the string "slow": the caller sends its records through the per-read path.
     RMR_INFER_TIMING=1: seconds per section accumulate in io.INGEST_CLOCK (tools/prof_ingest_batches.py prints them)."""
@@ -1848,6 +1923,8 @@ def _ingest_batch(rb, records, signals, eng, pa_scaling, skip_non_primary, ref_a
     n_all = rb.n
     flag = rb.flag
     keep_mask = np.ones(n_all, bool) if not skip_non_primary else (flag & 0x900) == 0
+    if select is not None:
+        keep_mask = keep_mask & np.asarray(select, bool)
     # the read a record's signal belongs to: the parent (pi) of a split read, else the record's name
     names, pi = rb.names, rb.pi
     row_of, kept = signals._row, []
@@ -1968,6 +2045,7 @@ def _ingest_batch(rb, records, signals, eng, pa_scaling, skip_non_primary, ref_a
     out.dr, out.reads, out.seq, out.seq_off, out.iseq = None, [], b"", np.zeros(1, np.int64), np.zeros(0, np.int8)
     out.ref_fwd, out.ref_fwd_off = (b"", np.zeros(nk + 1, np.int64)) if ref_anchored else (None, None)
     out.per_read = None
+    out.map0 = out.cal_off = out.cal_scale = None
     if not good.size:
         return out
     gk = keep[good]
@@ -2005,6 +2083,7 @@ def _ingest_batch(rb, records, signals, eng, pa_scaling, skip_non_primary, ref_a
     else:
         sm, sd = np.full(good.size, float(pa_scaling[0])), np.full(good.size, float(pa_scaling[1]))
     shift, scale = cal_off + cal_scale * sm, cal_scale * sd
+    out.cal_off, out.cal_scale = cal_off, cal_scale
     # ---- dacs = trimmed[map[0]:map[-1]] (reverse signal: of the reversed window), mapping re-based: assembled where the
     #      pieces already are ----
     n_good = int(good.size)
@@ -2013,6 +2092,7 @@ def _ingest_batch(rb, records, signals, eng, pa_scaling, skip_non_primary, ref_a
         d_q2s = torch.from_numpy(r2s).to(dev)
         map_off = np.ascontiguousarray(r2s_off[gk], np.int64)
         sig_total = int((r2s[r2s_off[gk] + seq_len] - r2s[r2s_off[gk]]).sum())
+        out.map0 = r2s[r2s_off[gk]].copy()
     else:
         map_off = np.ascontiguousarray(rb.mv_off[gk], np.int64)
         sig_total = int(sig_len[good].sum())
@@ -2488,3 +2568,21 @@ def concat_bam_parts(out_path, part_paths, remove=True):
         for p in part_paths:
             os.remove(p)
     return how
+
+
+# ---- the region API (src/remora/io.py:579-922): remora_amd/region_metrics.py, under the reference's names ----
+from .region_metrics import (  # noqa: E402
+    ReadBasecallRegion,
+    ReadRefReg,
+    compute_base_space_sig_coords,
+    get_reads_reference_regions,
+    get_reads_reference_regions_many,
+    get_ref_int_seq_from_reads,
+    get_ref_reg_sample_metrics,
+    get_ref_reg_samples_metrics,
+    get_ref_regs_samples_metrics,
+    get_ref_seq_and_levels_from_reads,
+    get_ref_seq_from_reads,
+    plan_region_pairs,
+    strands_match,
+)

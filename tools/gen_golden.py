@@ -80,6 +80,7 @@ def import_reference():
         inference,
         io,
         model_util,
+        refine_signal_map,
         util,
         validate,
     )
@@ -92,6 +93,7 @@ def import_reference():
         inference=inference,
         io=io,
         model_util=model_util,
+        refine_signal_map=refine_signal_map,
         util=util,
         validate=validate,
     )
@@ -1562,6 +1564,143 @@ def gen_modbams(R, out):
     np.savez_compressed(os.path.join(out, "modbams.npz"), **d)
     print("modbams:", {k: (v.shape if v.ndim else str(v)[:60]) for k, v in d.items()})
 
+# the regions of tests/golden/region_metrics.npz: name -> (contig, strand, start, end); chosen on the record spans of
+# data/{can,mod}_mappings.bam (tests/test_gpu_region_metrics.py says what each exercises)
+REGIONS = {
+    "a_fwd": ("chr13", "+", 52310000, 52310100), "a_rev": ("chr13", "-", 52310000, 52310100),
+    "b_fwd": ("chr13", "+", 52308990, 52309050), "b_rev": ("chr13", "-", 52308990, 52309050),
+    "one_read": ("chr13", "+", 52317000, 52317050), "nobody": ("chr13", "+", 52300000, 52300100),
+    "one_base": ("chr13", "+", 52310000, 52310001), "wide": ("chr13", "+", 52310000, 52310200),
+}
+REGION_METRICS = (("dwell_mean_sd", {}), ("dwell_trimmean_trimsd", {"start_trim": 1, "end_trim": 1}),
+                  ("dwell_trimmean", {"start_trim": 2, "end_trim": 2}))
+
+
+class _Reciprocal:
+    """calibration.scale of a stubbed POD5 record: Read.from_pod5_and_alignment takes 1 / scale, which gives back the very
+    float64 gen_real_reads hands to io.Read (1 / (1 / x) need not)."""
+
+    def __init__(self, value):
+        self.value = value
+
+    def __rtruediv__(self, one):
+        assert one == 1
+        return self.value
+
+
+def gen_regions(R, out):
+    """The reference's region API (src/remora/io.py:579-922) on its own test data -> region_metrics.npz.  Its functions run as
+    they are, on reference io.Read objects that get_io_reads builds with the values gen_real_reads uses; only the two handles are
+    stubbed (pysam / pod5 are not installed here): the BAM handle's fetch returns the records remora_amd.io parsed that overlap
+    as htslib defines it, in file order (the files are coordinate-sorted: asserted), the POD5 reader's reads() the CPU-decoded
+    signals.  Per case: read ids in row order and every returned matrix; the ReadRefReg fields; the sampled rows under
+    random.seed(7); sequences and levels from reads."""
+    import random
+
+    sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
+    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tests"))
+    from golden_util import pod5_reads_cpu
+    from remora_amd import io as rio
+
+    data = os.path.join(out, "data")
+    if not hasattr(np, "NAN"):  # the reference spells it np.NAN (io.py:748, :2474), which numpy 2 no longer has
+        np.NAN = np.nan
+
+    class Bam:
+        def __init__(self, path):
+            self.recs = list(rio.iter_bam_records(path, want_ref=True))
+            starts = [r.reference_start for r in self.recs if not r.is_unmapped]
+            assert starts == sorted(starts), "fetch order is file order only for a coordinate-sorted BAM"
+
+        def has_index(self):
+            return True
+
+        def fetch(self, ctg, start, end):
+            return [r for r in self.recs if not r.is_unmapped and r.reference_name == ctg and r.reference_start < end
+                    and r.reference_end > start]
+
+    class Pod5:
+        def __init__(self, path):
+            self.pods = {p.read_id: p for p in pod5_reads_cpu(path)}
+
+        def reads(self, selection=None, preload=None):
+            for rid in selection:
+                p = self.pods[rid]
+                yield types.SimpleNamespace(read_id=p.read_id, signal=p.signal, calibration=types.SimpleNamespace(
+                    offset=-p.calibration_offset, scale=_Reciprocal(p.calibration_scale)))
+
+    pairs = {k: (Pod5(os.path.join(data, f"{k}_reads.pod5")), Bam(os.path.join(data, f"{k}_mappings.bam"))) for k in ("can", "mod")}
+    reg = lambda name: R.io.RefRegion(*REGIONS[name])  # noqa: E731
+    d = {"region_names": np.asarray(list(REGIONS)), "regions": np.asarray([[str(v) for v in REGIONS[k]] for k in REGIONS])}
+    shutil.copy(os.path.join(REF, "tests", "data", "ref_regions.bed"), os.path.join(data, "ref_regions.bed"))
+
+    def put_metrics(key, samples_metrics, all_bam_reads):
+        d[f"{key}_n_samples"] = np.asarray(len(samples_metrics))
+        for s, (mets, recs) in enumerate(zip(samples_metrics, all_bam_reads)):
+            d[f"{key}_s{s}_ids"] = np.asarray([r.query_name for r in recs])
+            d[f"{key}_s{s}_keys"] = np.asarray(list(mets))
+            for name, mat in mets.items():
+                d[f"{key}_s{s}_{name}"] = np.ascontiguousarray(mat)
+
+    # ---- metrics: one sample, every region, both orientations; two samples on region a ----
+    n_cases = 0
+    for name in REGIONS:
+        for samples in (("can",), ("can", "mod")):
+            if len(samples) == 2 and not name.startswith("a_"):
+                continue
+            for metric, kw in REGION_METRICS:
+                for orient in (True, False):
+                    key = f"m_{name}_{'+'.join(samples)}_{metric}_{'ref' if orient else 'read'}"
+                    try:
+                        got = R.io.get_ref_reg_samples_metrics(reg(name), [pairs[k] for k in samples], metric=metric, ref_orient=orient, **kw)
+                    except R.remora.RemoraError as e:
+                        d[f"{key}_error"] = np.asarray(str(e))
+                        continue
+                    put_metrics(key, *got)
+                    n_cases += 1
+    assert str(d["m_nobody_can_dwell_mean_sd_ref_error"]) == "No reads covering region"
+    # ---- sampling: two regions and two samples in one run of the random numbers, for region: for sample: ----
+    random.seed(7)
+    for name in ("a_fwd", "a_rev"):
+        put_metrics(f"sampled_{name}", *R.io.get_ref_reg_samples_metrics(reg(name), [pairs["can"], pairs["mod"]], max_reads=3,
+                                                                           metric="dwell_trimmean", start_trim=1, end_trim=1))
+    # ---- ReadRefReg: signal, mapping and sequence of every read in the region ----
+    for name in ("a_fwd", "a_rev", "b_fwd", "b_rev", "one_base"):
+        regs, recs = R.io.get_reads_reference_regions(reg(name), [pairs["can"]], max_reads=None)
+        d[f"x_{name}_ids"] = np.asarray([r.query_name for r in recs[0]])
+        for i, rr in enumerate(regs[0]):
+            k = f"x_{name}_r{i}"
+            assert rr.norm_signal.dtype == np.float64
+            d[f"{k}_read_id"], d[f"{k}_seq"], d[f"{k}_sig"] = np.asarray(rr.read_id), np.asarray(rr.seq), np.ascontiguousarray(rr.norm_signal)
+            d[f"{k}_map"], d[f"{k}_sig_start"] = np.asarray(rr.seq_to_sig_map, np.int64), np.asarray(int(rr.sig_start))
+            d[f"{k}_ref_reg"] = np.asarray([rr.ref_reg.ctg, rr.ref_reg.strand, str(rr.ref_reg.start), str(rr.ref_reg.end)])
+            d[f"{k}_coords"] = np.asarray(rr.ref_sig_coords)
+    # ---- sequences and levels from the records (levels_4mer.txt: written by the `refine` group) ----
+    refiner = R.refine_signal_map.SigMapRefiner(kmer_model_filename=os.path.join(data, "levels_4mer.txt"), do_rough_rescale=True,
+                                                scale_iters=0, do_fix_guage=True)
+    d["levels_context"] = np.asarray([refiner.bases_before, refiner.bases_after])
+    for name in ("a_fwd", "a_rev", "b_fwd", "b_rev"):
+        recs = R.io.get_reg_bam_reads(reg(name), pairs["can"][1])
+        for orient in (True, False):
+            k = f"q_{name}_{'ref' if orient else 'read'}"
+            d[f"{k}_int_seq"] = R.io.get_ref_int_seq_from_reads(reg(name), recs, ref_orient=orient)
+            if name.endswith("_rev"):
+                # the reference complements through an unsigned table (util.NP_COMP_BASES, uintp) and then assigns -1 into the
+                # result, which numpy 2 refuses: on the reverse strand only the integer form can be recorded
+                continue
+            d[f"{k}_seq"] = np.asarray(R.io.get_ref_seq_from_reads(reg(name), recs, ref_orient=orient))
+            ctx = R.io.get_ref_int_seq_from_reads(reg(name).adjust(-refiner.bases_before, refiner.bases_after, ref_orient=False), recs,
+                                                  ref_orient=False)
+            # the reference's table lookup is defined only where the whole k-mer is covered ACGT: these regions are chosen so
+            # that this holds everywhere (a lookup with a -1 / -2 base runs without bounds checks)
+            assert ctx.min() >= 0, (name, "a position of the context is not covered ACGT")
+            seq, levels = R.io.get_ref_seq_and_levels_from_reads(reg(name), recs, refiner, ref_orient=orient)
+            assert np.isfinite(levels).all()
+            d[f"{k}_lv_seq"], d[f"{k}_levels"] = np.asarray(seq), np.asarray(levels)
+            d[f"{k}_seq_only"] = np.asarray(R.io.get_ref_seq_and_levels_from_reads(reg(name), recs, None, ref_orient=orient)[0])
+    np.savez_compressed(os.path.join(out, "region_metrics.npz"), **d)
+    print("regions:", n_cases, "metric cases,", os.path.getsize(os.path.join(out, "region_metrics.npz")), "bytes")
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -1592,6 +1731,7 @@ def main():
         remora_dataset=gen_remora_dataset,
         batch_params=gen_batch_params,
         modbams=gen_modbams,
+        regions=gen_regions,
     )
     for name, fn in gens.items():
         if args.only and name not in args.only.split(","):
