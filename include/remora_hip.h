@@ -664,6 +664,37 @@ int rmr_rescale_quantiles(rmr_refiner *r, int64_t n_reads, const int16_t *dacs, 
                           const int64_t *seq_to_sig, const int8_t *int_seq, const int64_t *seq_off,
                           const double *shift, const double *scale, int64_t max_read_bases, int clip_bases,
                           int n_quants, const double *quants, double *sig_q, double *lvl_q, int32_t *status);
+/* The points the precise re-scale of an iterative refiner (scale_iters > 0) fits its line through: SigMapRefiner.rescale up
+ * to its call of rescale_theil_sen (src/remora/refine_signal_map.py:406-469) for every read of a resident batch.  Reads laid
+ * out as above, DEVICE pointers, no limit on the read length.  Per read, with dwells = diff(seq_to_sig): dwell_min / dwell_max
+ * = np.percentile(dwells, (10, 90)) ("linear": the difference of the two order statistics in int64, numpy's two-sided lerp in
+ * float64); base b is kept when dwell_min < dwell < dwell_max, level_ok[b] != 0, its dwell is not 0 and
+ * edge_filter_bases <= b < n - edge_filter_bases.  levels f32 / level_ok u8 per base of the concatenated reads: the expected
+ * level (extract_levels) and numpy's |level - mean(levels)| > min_abs_level, which no round changes.  live u8[n_reads] or
+ * NULL: reads with live == 0 are not touched.  count i32[n_reads]: kept bases; x f64 / y f32, written from the read's seq_off
+ * on, in base order: ((double)(sum of the base's samples) / dwell - shift) / scale and the base's level.  Asynchronous on the
+ * engine's stream. */
+int rmr_rescale_points(rmr_refiner *r, int64_t n_reads, const int16_t *dacs, const int64_t *sig_off,
+                       const int64_t *seq_to_sig, const int64_t *seq_off, const double *shift, const double *scale,
+                       const float *levels, const uint8_t *level_ok, const uint8_t *live, int edge_filter_bases,
+                       int32_t *count, double *x, float *y);
+/* theil_sen (src/remora/refine_signal_map.py:83-103) for every live read, one block per read: slope = np.median of
+ * (double)(y[i] - y[j]) / (x[i] - x[j]) over the pairs with x[i] - x[j] > 0 (a radix select on the quotients, which are
+ * recomputed in every pass and never stored), inter = np.median of (double)y[i] - slope * x[i].  x / y / count / seq_off as
+ * rmr_rescale_points leaves them.  A read with count > 1000 (MAX_POINTS_FOR_THEIL_SEN) is fitted through the 1000 points
+ * samp[samp_off[read] ..] names (i32 indices into its points, drawn by the host as rescale_theil_sen :106-114 draws them;
+ * samp_off i64[n_reads], negative: none; n_samp: the length of samp, which every block of 1000 must lie inside; both NULL and
+ * n_samp 0 when no read needs one).  slope / inter f64[n_reads], status i32[n_reads] (rmr_theil_sen_status); reads with live == 0 are not touched.  All DEVICE pointers; asynchronous on the
+ * engine's stream. */
+enum rmr_theil_sen_status {
+    RMR_THEIL_SEN_OK = 0,
+    RMR_THEIL_SEN_NO_PAIR = 1,     /* no pair with dx > 0: slope and inter are NaN, as the reference's median of nothing */
+    RMR_THEIL_SEN_ZERO_SLOPE = 2,  /* RemoraError("Theil-Sen slope is zero: cannot re-scale"); either sign of zero */
+    RMR_THEIL_SEN_BAD_INPUT = 3    /* count outside 0..bases, more than 1000 points without a sample inside samp, index outside the points */
+};
+int rmr_theil_sen_fit(rmr_refiner *r, int64_t n_reads, const double *x, const float *y, const int32_t *count,
+                      const int64_t *seq_off, const int32_t *samp, const int64_t *samp_off, int64_t n_samp,
+                      const uint8_t *live, double *slope, double *inter, int32_t *status);
 
 /* ---- P1: per-base signal metrics and the k-mer level table estimated from them ------------ */
 /* replaces, for a batch of reads in one launch: metrics.METRIC_FUNCS (src/remora/metrics.py:45-117: compute_dwell,

@@ -25,7 +25,7 @@ static const char *k_names[K_NUM] = {
     "conv_merge1", "conv_merge2", "conv_merge3", "conv_merge4", "lstm_head", "fc_head",
     "count_labels", "motif_scan", "vbz_decode", "refine_band", "refine_dp", "refine_dp_rowwise",
     "fused_front", "rescale_quantiles", "sig3_front", "seq2_front", "probe_max_diff", "probe_nonfinite", "winograd_form",
-    "base_metrics", "region_metrics", "region_signals", "site_kmer_levels", "modbam_sites"};
+    "base_metrics", "region_metrics", "region_signals", "site_kmer_levels", "modbam_sites", "rescale_points", "theil_sen_fit"};
 const char *kernel_name(int id) { return (id >= 0 && id < K_NUM) ? k_names[id] : "?"; }
 
 }  // namespace rmr

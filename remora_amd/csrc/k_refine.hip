@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "rmr_internal.h"
+#include "rmr_math.h"
 #include "rmr_stage.h"
 
 struct rmr_refiner {
@@ -927,6 +928,319 @@ __global__ __launch_bounds__(256) void rescale_quantiles_kernel(RefineReads a, c
     lerp_quantiles(lv, cnt, quants, nq, lvl_q + (size_t)r * nq, tid);
 }
 
+// ---------------------------------------------------------------------------------------
+// precise re-scale of the iterative refiner: the points of SigMapRefiner.rescale and the Theil-Sen fit through them
+// (src/remora/refine_signal_map.py:406-469 and :83-103)
+// ---------------------------------------------------------------------------------------
+// Both kernels take order statistics with the same block-wide radix select (256 threads, 11 bits a pass, 6 passes over
+// the 64-bit keys): every pass recomputes the keys, counts the digit of those that still match the prefix in an LDS
+// histogram, and the bin holding rank k extends the prefix.  Nothing is sorted or stored, so neither kernel has a limit on
+// the read length, and the half million pairwise slopes of a read never leave the registers.
+constexpr int kSelBits = 11, kSelBins = 1 << kSelBits, kSelPasses = 6;
+constexpr int kTsMax = 1000;  // MAX_POINTS_FOR_THEIL_SEN
+
+struct SelLds {
+    uint32_t hist[kSelBins];
+    uint32_t wsum[4], wmin_lo[4], wmin_hi[4];
+    uint32_t ctl[2];
+};
+
+// float64 -> uint64 whose unsigned order is the order of the values (-inf lowest, +inf highest, one key for both zeros);
+// NaN becomes the largest key
+__device__ __forceinline__ uint64_t order_key_f64(double v) {
+    if (v != v) return ~0ULL;
+    const uint64_t u = (uint64_t)__double_as_longlong(v + 0.0);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ULL);
+}
+__device__ __forceinline__ double order_unkey_f64(uint64_t k) {
+    const uint64_t u = (k >> 63) ? (k & 0x7fffffffffffffffULL) : ~k;
+    return __longlong_as_double((long long)u);
+}
+
+// one count per valid lane into hist[digit]; called by whole waves.  The first passes of a select see a handful of digits
+// (slopes share sign and exponent), so the lanes of the two most frequent leaders are counted with one atomic each.
+__device__ __forceinline__ void hist_add(uint32_t *hist, bool valid, uint32_t digit) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(valid);
+    for (int round = 0; round < 2 && todo; ++round) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const uint32_t d0 = (uint32_t)__shfl((int)digit, leader);
+        const unsigned long long same = __ballot(valid && digit == d0);
+        if (lane == leader) atomicAdd(&hist[d0], (uint32_t)__popcll(same));
+        if (digit == d0) valid = false;
+        todo &= ~same;
+    }
+    if (valid) atomicAdd(&hist[digit], 1u);
+}
+
+// key of rank k (0-based, k < number of valid keys) among the keys `each` emits.  `each(emit)` calls emit(valid, key) the
+// same number of times in every thread of the block (a thread without an element passes valid = false).
+template <typename Each>
+__device__ uint64_t block_select(SelLds &s, Each each, uint32_t k) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    uint64_t prefix = 0, pmask = 0;
+    for (int pass = 0; pass < kSelPasses; ++pass) {
+        const int shift = (kSelPasses - 1 - pass) * kSelBits;  // 55: the first pass takes the 9 leading bits
+        for (int b = tid; b < kSelBins; b += 256) s.hist[b] = 0;
+        if (tid == 0) { s.ctl[0] = 0; s.ctl[1] = 0; }
+        RMR_SYNC();
+        each([&](bool valid, uint64_t key) {
+            hist_add(s.hist, valid && (key & pmask) == prefix, (uint32_t)(key >> shift) & (kSelBins - 1));
+        });
+        RMR_SYNC();
+        // thread t owns bins 8t .. 8t+7: block-wide exclusive scan of their sums, then the owner of rank k names the bin
+        uint32_t sum = 0;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) sum += s.hist[tid * 8 + q];
+        uint32_t inc = sum;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t t = (uint32_t)__shfl_up((int)inc, o);
+            if (lane >= o) inc += t;
+        }
+        if (lane == 63) s.wsum[wv] = inc;
+        RMR_SYNC();
+        uint32_t excl = inc - sum;
+        for (int w = 0; w < wv; ++w) excl += s.wsum[w];
+        if (k >= excl && k - excl < sum) {
+            uint32_t kk = k - excl;
+            int q = 0;
+            while (q < 7 && kk >= s.hist[tid * 8 + q]) { kk -= s.hist[tid * 8 + q]; ++q; }
+            s.ctl[0] = (uint32_t)(tid * 8 + q);
+            s.ctl[1] = kk;
+        }
+        RMR_SYNC();
+        const uint32_t bin = s.ctl[0];
+        k = s.ctl[1];
+        prefix |= (uint64_t)bin << shift;
+        pmask |= (uint64_t)(kSelBins - 1) << shift;
+        RMR_SYNC();  // ctl and wsum are rewritten by the next pass
+    }
+    return prefix;
+}
+
+// key of rank k2 when `key1` is the key of rank k2 - 1: key1 again when more than k2 keys are <= key1, else the smallest
+// key above it
+template <typename Each>
+__device__ uint64_t block_next_key(SelLds &s, Each each, uint64_t key1, uint32_t k2) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    uint32_t le = 0;
+    uint64_t mn = ~0ULL;
+    each([&](bool valid, uint64_t key) {
+        if (valid) {
+            if (key <= key1) ++le;
+            else mn = key < mn ? key : mn;
+        }
+    });
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+        le += (uint32_t)__shfl_xor((int)le, o);
+        const uint64_t other = ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(mn >> 32), o) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)mn, o);
+        mn = other < mn ? other : mn;
+    }
+    if (lane == 0) { s.wsum[wv] = le; s.wmin_lo[wv] = (uint32_t)mn; s.wmin_hi[wv] = (uint32_t)(mn >> 32); }
+    RMR_SYNC();
+    le = 0;
+    mn = ~0ULL;
+    for (int w = 0; w < 4; ++w) {
+        le += s.wsum[w];
+        const uint64_t other = ((uint64_t)s.wmin_hi[w] << 32) | s.wmin_lo[w];
+        mn = other < mn ? other : mn;
+    }
+    RMR_SYNC();
+    return le > k2 ? key1 : mn;
+}
+
+// sum of a per-thread count over the block
+__device__ uint32_t block_sum_u32(SelLds &s, uint32_t v) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+    if (lane == 0) s.wsum[wv] = v;
+    RMR_SYNC();
+    v = s.wsum[0] + s.wsum[1] + s.wsum[2] + s.wsum[3];
+    RMR_SYNC();
+    return v;
+}
+
+// SigMapRefiner.rescale up to its call of rescale_theil_sen, one block per read: np.percentile(dwells, (10, 90)) from four
+// order statistics of the integer dwells (numpy's "linear" arithmetic: virtual index (n - 1) * q, b - a in int64, the
+// two-sided lerp in float64), then the bases that pass the dwell, level and edge filters in base order:
+// x = (sum of the base's samples / dwell - shift) / scale in float64, y = the base's level.
+__global__ __launch_bounds__(256) void rescale_points_kernel(RefineReads a, const float *__restrict__ lv,
+                                                             const uint8_t *__restrict__ level_ok, const uint8_t *__restrict__ live,
+                                                             int edge, int32_t *__restrict__ count, double *__restrict__ px,
+                                                             float *__restrict__ py) {
+    __shared__ SelLds s;
+    __shared__ uint32_t wcnt[4];
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (live && !live[r]) return;
+    const int64_t q0 = a.seq_off[r];
+    const int n = (int)(a.seq_off[r + 1] - q0);
+    if (n < 1) {
+        if (tid == 0) count[r] = 0;
+        return;
+    }
+    const int64_t *m = a.s2s + q0 + r;
+    const int64_t nsig = a.sig_off[r + 1] - a.sig_off[r];
+    const int16_t *dac = a.dacs + a.sig_off[r];
+    auto each = [&](auto emit) {
+        for (int b0 = 0; b0 < n; b0 += 256) {
+            const int b = b0 + tid;
+            const bool v = b < n;
+            const int64_t d = v ? m[b + 1] - m[b] : 0;
+            emit(v, (uint64_t)d ^ 0x8000000000000000ULL);
+        }
+    };
+    double lim[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const double q = h == 0 ? 10.0 / 100.0 : 90.0 / 100.0;
+        const double top = (double)(n - 1);
+        const double vi = top * q;
+        const double prev = floor(vi);
+        const double gamma = vi - prev;
+        int pi = (int)prev, ni = pi + 1;
+        if (vi >= top) pi = ni = n - 1;
+        const uint64_t k1 = block_select(s, each, (uint32_t)pi);
+        const uint64_t k2 = ni != pi ? block_next_key(s, each, k1, (uint32_t)ni) : k1;
+        const int64_t lo = (int64_t)(k1 ^ 0x8000000000000000ULL), hi = (int64_t)(k2 ^ 0x8000000000000000ULL);
+        const int64_t diff = hi - lo;
+        const double scaled_lo = (double)diff * gamma, scaled_hi = (double)diff * (1.0 - gamma);
+        lim[h] = gamma >= 0.5 ? (double)hi - scaled_hi : (double)lo + scaled_lo;
+    }
+    const double dmin = lim[0], dmax = lim[1];
+    const double sh = a.shift[r], sc = a.scale[r];
+    int total = 0;
+    for (int b0 = 0; b0 < n; b0 += 256) {
+        const int b = b0 + tid;
+        bool v = b < n && b >= edge && b < n - edge;
+        int64_t st = 0, d = 0;
+        if (v) {
+            st = m[b];
+            d = m[b + 1] - st;
+            // a base without samples has no mean (the reference's 0 / 0 = NaN); a base outside the read's signal cannot be summed
+            v = d > 0 && st >= 0 && d <= nsig && st <= nsig - d && (double)d > dmin && (double)d < dmax && level_ok[q0 + b] != 0;
+        }
+        const unsigned long long bal = __ballot(v);
+        if (lane == 0) wcnt[wv] = (uint32_t)__popcll(bal);
+        RMR_SYNC();
+        int pos = total;
+        for (int w = 0; w < wv; ++w) pos += (int)wcnt[w];
+        total += (int)(wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3]);
+        if (v) {
+            pos += __popcll(bal & ((1ull << lane) - 1ull));
+            int64_t sum = 0;
+            for (int64_t i = 0; i < d; ++i) sum += dac[st + i];
+            const double mean = (double)sum / (double)d;
+            px[q0 + pos] = (mean - sh) / sc;
+            py[q0 + pos] = lv[q0 + b];
+        }
+        RMR_SYNC();
+    }
+    if (tid == 0) count[r] = total;
+}
+
+// theil_sen (src/remora/refine_signal_map.py:83-103), one block per read: the read's points (at most 1000, the host-drawn
+// sub-sample of a larger set) in LDS, the median of dy / dx over the pairs with dx > 0 by a radix select that recomputes the
+// quotients in every pass, then the median of y - slope * x.
+__global__ __launch_bounds__(256) void theil_sen_kernel(const double *__restrict__ px, const float *__restrict__ py,
+                                                        const int32_t *__restrict__ count, const int64_t *__restrict__ seq_off,
+                                                        const int32_t *__restrict__ samp, const int64_t *__restrict__ samp_off,
+                                                        int64_t n_samp, const uint8_t *__restrict__ live, double *__restrict__ slope_out,
+                                                        double *__restrict__ inter_out, int32_t *__restrict__ status) {
+    __shared__ SelLds s;
+    __shared__ double xs[kTsMax];
+    __shared__ float ys[kTsMax];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    if (live && !live[r]) return;
+    const int64_t q0 = seq_off[r];
+    const int64_t n = seq_off[r + 1] - q0;
+    const int c = count[r];
+    const int64_t so = (samp && samp_off) ? samp_off[r] : -1;
+    if (c < 0 || c > n || (c > kTsMax && (so < 0 || so > n_samp - kTsMax))) {
+        if (tid == 0) status[r] = RMR_THEIL_SEN_BAD_INPUT;
+        return;
+    }
+    const int m = c < kTsMax ? c : kTsMax;
+    uint32_t bad = 0;
+    for (int t = tid; t < m; t += 256) {
+        int idx = c > kTsMax ? samp[so + t] : t;
+        if (idx < 0 || idx >= c) { bad = 1; idx = 0; }
+        xs[t] = px[q0 + idx];
+        ys[t] = py[q0 + idx];
+    }
+    if (block_sum_u32(s, bad)) {  // (the barriers inside also publish xs / ys)
+        if (tid == 0) status[r] = RMR_THEIL_SEN_BAD_INPUT;
+        return;
+    }
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    // rows i and m - 2 - i of the pair triangle (i < j) together hold m pairs: every sweep is evenly filled
+    const int rows = m - 1;
+    auto each_pair = [&](auto emit) {
+        for (int t = 0; t < (rows + 1) / 2; ++t) {
+            const int i1 = t, len1 = m - 1 - t;
+            const int i2 = rows - 1 - t, len2 = i2 > i1 ? m - 1 - i2 : 0;
+            for (int c0 = 0; c0 < len1 + len2; c0 += 256) {
+                const int cc = c0 + tid;
+                bool v = cc < len1 + len2;
+                const int i = cc < len1 ? i1 : i2;
+                const int j = v ? (cc < len1 ? i1 + 1 + cc : i2 + 1 + (cc - len1)) : i;
+                double xa = xs[i], xb = xs[j];
+                float ya = ys[i], yb = ys[j];
+                if (xa < xb) {  // the ordered pair with dx > 0
+                    const double tx = xa; xa = xb; xb = tx;
+                    const float ty = ya; ya = yb; yb = ty;
+                }
+                const double dx = xa - xb;
+                v = v && dx > 0.0;
+                const float dy = ya - yb;
+                emit(v, v ? order_key_f64((double)dy / dx) : 0ULL);
+            }
+        }
+    };
+    uint32_t mine = 0, nans = 0;
+    each_pair([&](bool v, uint64_t key) {
+        if (v) { ++mine; if (key == ~0ULL) ++nans; }
+    });
+    const uint32_t np_ = block_sum_u32(s, mine);
+    const uint32_t nn = block_sum_u32(s, nans);
+    double slope = nan, inter = nan;
+    int st = RMR_THEIL_SEN_OK;
+    if (np_ == 0) {
+        st = RMR_THEIL_SEN_NO_PAIR;  // np.median of nothing
+    } else if (nn == 0) {
+        const uint32_t k1 = (np_ - 1) / 2, k2 = np_ / 2;
+        const uint64_t key1 = block_select(s, each_pair, k1);
+        const uint64_t key2 = k2 != k1 ? block_next_key(s, each_pair, key1, k2) : key1;
+        const double va = order_unkey_f64(key1), vb = order_unkey_f64(key2);
+        slope = k2 != k1 ? __dadd_rn(va, vb) / 2.0 : va;
+        if (slope == 0.0) st = RMR_THEIL_SEN_ZERO_SLOPE;
+        auto each_pt = [&](auto emit) {
+            for (int t0 = 0; t0 < m; t0 += 256) {
+                const int t = t0 + tid;
+                const bool v = t < m;
+                const double prod = v ? slope * xs[t] : 0.0;
+                emit(v, v ? order_key_f64((double)ys[t] - prod) : 0ULL);
+            }
+        };
+        uint32_t pn = 0;
+        each_pt([&](bool v, uint64_t key) { if (v && key == ~0ULL) ++pn; });
+        if (block_sum_u32(s, pn) == 0) {
+            const uint32_t j1 = (uint32_t)(m - 1) / 2, j2 = (uint32_t)m / 2;
+            const uint64_t ik1 = block_select(s, each_pt, j1);
+            const uint64_t ik2 = j2 != j1 ? block_next_key(s, each_pt, ik1, j2) : ik1;
+            const double ia = order_unkey_f64(ik1), ib = order_unkey_f64(ik2);
+            inter = j2 != j1 ? __dadd_rn(ia, ib) / 2.0 : ia;
+        }
+    }
+    if (tid == 0) {
+        slope_out[r] = slope;
+        inter_out[r] = inter;
+        status[r] = st;
+    }
+}
+
 }  // namespace
 }  // namespace rmr
 
@@ -1205,6 +1519,43 @@ int rmr_rescale_quantiles(rmr_refiner *rf, int64_t n_reads, const int16_t *dacs,
         RMR_HIP(hipGetLastError());
     }
     RMR_HIP(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+int rmr_rescale_points(rmr_refiner *rf, int64_t n_reads, const int16_t *dacs, const int64_t *sig_off, const int64_t *seq_to_sig,
+                       const int64_t *seq_off, const double *shift, const double *scale, const float *levels,
+                       const uint8_t *level_ok, const uint8_t *live, int edge_filter_bases, int32_t *count, double *x, float *y) {
+    if (!rf || !dacs || !sig_off || !seq_to_sig || !seq_off || !shift || !scale || !levels || !level_ok || !count || !x || !y)
+        RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if (n_reads < 0 || n_reads > (int64_t)1 << 30) RMR_FAIL(RMR_ERR_INVALID, "bad n_reads");
+    if (edge_filter_bases < 0) RMR_FAIL(RMR_ERR_INVALID, "bad edge_filter_bases");
+    if (n_reads == 0) return 0;
+    rmr_engine *e = rf->e;
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    rmr::RefineReads dr{dacs, sig_off, seq_to_sig, seq_off, nullptr, shift, scale};
+    ProfScope ps(e, K_RESCALE_POINTS);
+    hipLaunchKernelGGL(rmr::rescale_points_kernel, dim3((unsigned)n_reads), dim3(256), 0, e->stream, dr, levels, level_ok, live,
+                       edge_filter_bases, count, x, y);
+    RMR_HIP(hipGetLastError());
+    return 0;
+}
+
+int rmr_theil_sen_fit(rmr_refiner *rf, int64_t n_reads, const double *x, const float *y, const int32_t *count,
+                      const int64_t *seq_off, const int32_t *samp, const int64_t *samp_off, int64_t n_samp, const uint8_t *live,
+                      double *slope, double *inter, int32_t *status) {
+    if (!rf || !x || !y || !count || !seq_off || !slope || !inter || !status) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if ((samp == nullptr) != (samp_off == nullptr)) RMR_FAIL(RMR_ERR_INVALID, "samp and samp_off go together");
+    if (n_samp < 0 || (!samp && n_samp != 0)) RMR_FAIL(RMR_ERR_INVALID, "bad n_samp");
+    if (n_reads < 0 || n_reads > (int64_t)1 << 30) RMR_FAIL(RMR_ERR_INVALID, "bad n_reads");
+    if (n_reads == 0) return 0;
+    rmr_engine *e = rf->e;
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    ProfScope ps(e, K_THEIL_SEN);
+    hipLaunchKernelGGL(rmr::theil_sen_kernel, dim3((unsigned)n_reads), dim3(256), 0, e->stream, x, y, count, seq_off, samp,
+                       samp_off, n_samp, live, slope, inter, status);
+    RMR_HIP(hipGetLastError());
     return 0;
 }
 

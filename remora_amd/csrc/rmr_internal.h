@@ -65,6 +65,8 @@ enum KernelId {
     K_REGION_SIGNALS,
     K_SITE_KMER_LEVELS,  // its kernels and the four radix sorts between them, bracketed in two pieces
     K_MODBAM_SITES,
+    K_RESCALE_POINTS,
+    K_THEIL_SEN,
     K_NUM
 };
 const char *kernel_name(int id);

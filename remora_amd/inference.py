@@ -83,8 +83,7 @@ def iter_call_reads_mods(read_batches, model, model_metadata, return_mod_probs=F
     call_reads_mods returns them.  Without a loaded refiner the batches go through the three-thread pipeline of
     `_pipelined_parts` (staging, extraction and the per-read split of neighbouring batches run under each other's
     inference); with one, the host staging of batch k+1 (own thread, own HIP stream) runs under the GPU work of batch
-    k; batches whose refiner re-scales iteratively (scale_iters > 0) are staged inline, because that refinement
-    rewrites the reads first."""
+    k (single-pass and iterative refiners alike: every refinement round runs on the resident arrays)."""
     from concurrent.futures import ThreadPoolExecutor
 
     from .data_chunks import DeviceReads
@@ -95,13 +94,12 @@ def iter_call_reads_mods(read_batches, model, model_metadata, return_mod_probs=F
     if not loaded and os.environ.get("RMR_READS_SUBBATCH", "512") != "0":
         yield from _pipelined_parts(read_batches, model, model_metadata, return_mod_probs)
         return
-    inline = loaded and refiner.scale_iters > 0
     engine = getattr(model, "engine", None)
     upload_stream = None
 
     def stage(reads):
         nonlocal upload_stream
-        if inline or len(reads) == 0:
+        if len(reads) == 0:
             return None
         if upload_stream is None:
             upload_stream = torch.cuda.Stream(device=(engine.torch_device if engine is not None else None))
@@ -139,9 +137,9 @@ def _pipelined_parts(parts, model, model_metadata, return_mod_probs):
     (motif scan, extraction, inference, per-read split), so that the kernels of one batch run under the host work of
     its neighbours.  Each engine serialises its GPU calls (one mutex per engine: extraction runs on a second engine
     with its own stream); every C call and every copy releases the GIL.  Yields (batch, results) in order, results
-    identical to the unpipelined call.  At most five batches are resident and six in flight at a time.  A single-pass
-    signal-mapping refiner (scale_iters <= 0) can run per batch inside the workers (opt-in, see call_reads_mods);
-    iterative re-scaling (scale_iters > 0) rewrites the reads on the host first and never comes here."""
+    identical to the unpipelined call.  At most five batches are resident and six in flight at a time.  A
+    signal-mapping refiner can run per batch inside the workers (opt-in, see call_reads_mods); an iterative one
+    (scale_iters > 0) on reads above 1000 re-scaling points then draws its sub-samples in the workers' order."""
     import collections
     import queue
     from concurrent.futures import ThreadPoolExecutor
@@ -281,20 +279,16 @@ def call_reads_mods(reads, model, model_metadata, return_mod_probs=False, device
     sub = int(os.environ.get("RMR_READS_SUBBATCH", "512"))
     # with a loaded refiner the batch stays whole by default: the banded DP of a call costs one read's latency whatever the
     # batch size (18 ms for 2048 or for 512 reads of 5 kb), so sub-batches multiply it (RMR_READS_PIPELINE_REFINER=1 opts in)
-    piped_refiner = loaded and refiner.scale_iters <= 0 and os.environ.get("RMR_READS_PIPELINE_REFINER") == "1"
+    piped_refiner = loaded and os.environ.get("RMR_READS_PIPELINE_REFINER") == "1"
     if device_reads is None and (not loaded or piped_refiner) and sub > 0 and len(reads) >= 2 * sub:
         return _call_reads_mods_pipelined(reads, sub, model, model_metadata, return_mod_probs)
-    if loaded and refiner.scale_iters > 0:
-        for err in refiner.refine_reads(reads):  # DP rounds interleaved with host re-scaling
-            if err is not None:
-                raise err
-    dr = device_reads if device_reads is not None and not (loaded and refiner.scale_iters > 0) else \
-        DeviceReads(reads, getattr(model, "engine", None))
+    dr = device_reads if device_reads is not None else DeviceReads(reads, getattr(model, "engine", None))
     dr.wait_ready()
-    if loaded and refiner.scale_iters <= 0 and refiner.do_rough_rescale:
+    if loaded and refiner.do_rough_rescale:
         refiner.rough_rescale_device(dr, reads)  # sorts + gathers on the GPU, 19-point fits on the host
-    if loaded and refiner.scale_iters == 0:
-        refiner.refine_device_reads(dr, reads)  # one banded-DP pass on the resident arrays
+    if loaded and refiner.scale_iters >= 0:
+        # the banded-DP passes and, for an iterative refiner, the precise re-scale between them, on the resident arrays
+        refiner.refine_device_reads(dr, reads)
     focus, foc_off = dr.motif_focus_bases(motifs)
     handoff = hasattr(model, "engine") and model.engine is not dr.engine  # extraction and network on engines of their own
     arrs, _ = _extract_device(dr, focus, foc_off, model_metadata["chunk_context"], model_metadata["kmer_context_bases"],
@@ -560,14 +554,12 @@ def infer_from_pod5_and_bam(pod5_path, in_bam_path, model, model_metadata, out_b
 
     label_counts = [np.zeros(len(md["mod_bases"]) + 1, np.int64) for md in mds]
 
-    refiner0 = mds[0].get("sig_map_refiner")
-    iterative = refiner0 is not None and getattr(refiner0, "is_loaded", False) and refiner0.scale_iters > 0
     # either signal direction, either anchor: the batch ingest (io.iter_ingest_batches) - trimming, move tables, scaling and the
     # read arrays of a whole BAM batch on the GPU, no Python object per read.  Several models (one per canonical base,
     # src/remora/inference.py:286,311-315) share the resident reads when none of them refines the mapping (refinement rewrites
-    # it per model: those and iterative re-scaling go read by read)
+    # it per model: those go read by read)
     any_refiner = any(getattr(md.get("sig_map_refiner"), "is_loaded", False) for md in mds)
-    batch_ingest = ((len(models) == 1 or not any_refiner) and not iterative
+    batch_ingest = ((len(models) == 1 or not any_refiner)
                     and os.environ.get("RMR_INFER_BATCH_INGEST", "1") != "0")
 
     def batches():

@@ -2197,7 +2197,7 @@ def add_site_levels(acc, pod5_path, bam_path, sig_map_refiner, start_trim=1, end
     """One streaming pass over `bam_path`: every primary, mapped read with a move table and an MD tag is anchored on its
     reference bases (iter_ingest_batches, ref_anchored), its signal mapping refined as Read.set_refine_signal_mapping(..,
     ref_mapping=True) does (src/remora/io.py:861-863), and the trimmed mean of every base joins `acc` (metrics.SiteLevels) on
-    the device.  A batch the array ingest or the resident refinement does not cover (the iterative refiner, a read whose band
+    the device.  A batch the array ingest or the resident refinement does not cover (a read whose band
     the refiner rejects) goes read by read through the same kernels; a read that cannot be anchored or refined is left out,
     as `missing_ok` / the reference's per-read errors leave it out.  `reverse_signal`: the reads are built as
     io.Read.from_pod5 / add_alignment build them with reverse_signal=True (signal recorded 3'->5').  -> number of reads used."""
@@ -2209,14 +2209,14 @@ def add_site_levels(acc, pod5_path, bam_path, sig_map_refiner, start_trim=1, end
     used = 0
     for item in iter_ingest_batches(pod5_path, bam_path, batch=reads_per_batch, device=device, ref_anchored=True,
                                     reverse_signal=reverse_signal):
-        if isinstance(item, IngestBatch) and not (loaded and refiner.scale_iters > 0):
+        if isinstance(item, IngestBatch):
             if not item.good.size:
                 continue
             dr, stubs = item.dr, item.reads
             try:
                 if loaded and refiner.do_rough_rescale:
                     refiner.rough_rescale_device(dr, stubs)
-                if loaded and refiner.scale_iters == 0:
+                if loaded and refiner.scale_iters >= 0:
                     refiner.refine_device_reads(dr, stubs)
             except RemoraError:
                 pairs = item.per_read()

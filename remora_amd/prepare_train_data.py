@@ -51,18 +51,21 @@ def _refine(reads, sig_map_refiner, engine):
     refiner = sig_map_refiner
     loaded = refiner is not None and getattr(refiner, "is_loaded", False)
     errs = {}
-    if loaded and refiner.scale_iters > 0:
-        for i, err in enumerate(refiner.refine_reads(reads)):
-            if err is not None:
-                errs[i] = str(err)
-        alive = [r for i, r in enumerate(reads) if i not in errs]
-        return (DeviceReads(alive, engine) if alive else None), alive, errs
     alive = list(reads)
     if not alive:
         return None, alive, errs
     dr = DeviceReads(alive, engine)
     if loaded and refiner.do_rough_rescale:
         refiner.rough_rescale_device(dr, alive)
+    if loaded and refiner.scale_iters > 0:
+        # every round on the resident batch, with the per-read errors refine_reads returns
+        for i, err in enumerate(refiner.refine_device_reads(dr, alive, errors="collect")):
+            if err is not None:
+                errs[i] = str(err)
+        if errs:
+            alive = [r for i, r in enumerate(alive) if i not in errs]
+            dr = DeviceReads(alive, engine) if alive else None
+        return dr, alive, errs
     if loaded and refiner.scale_iters == 0:
         try:
             refiner.refine_device_reads(dr, alive)
@@ -208,7 +211,7 @@ def extract_chunk_arrays_from_ingest(ib, int_label, motifs, sig_map_refiner, max
         try:
             if refiner.do_rough_rescale:
                 refiner.rough_rescale_device(dr, stubs)
-            if refiner.scale_iters == 0:
+            if refiner.scale_iters >= 0:
                 refiner.refine_device_reads(dr, stubs)
         except RemoraError:
             return None
@@ -403,10 +406,9 @@ def extract_chunk_dataset(bam_path, pod5_path, out_path, mod_base, mod_base_cont
             dataset.flush()
             next_save += save_every
 
-    refiner_iterative = (sig_map_refiner is not None and getattr(sig_map_refiner, "is_loaded", False) and sig_map_refiner.scale_iters > 0)
     # reference anchor, motif-selected focus bases, either signal direction: the batch ingest of `infer --reference-anchored`
     # (io.iter_ingest_batches: the reads of a BAM batch assembled on the GPU) - everything else read by read
-    if (not basecall_anchor and focus_ref_pos is None and not refiner_iterative and
+    if (not basecall_anchor and focus_ref_pos is None and
             os.environ.get("RMR_PREPARE_BATCH_INGEST", "1") != "0"):
         seen, t_loop = 0, _time.perf_counter()
         # (pa_scaling only travels in the dataset's metadata: training reads are scaled by sm / sd, prepare_train_data.py:66-72)

@@ -10,8 +10,12 @@ What runs where:
   * the scalar re-scaling estimators: `rough_rescale` / `rescale` are float64 numpy on the host as in
     the reference (the quantiles through a one-sort replica of numpy's arithmetic);
     `rough_rescale_device` does the per-base level lookup, the centre-sample gather and the two sorts
-    of a whole batch on the GPU and leaves only the 19-point line fit of every read on the host -
-    bit-identical results."""
+    of a whole batch on the GPU and leaves only the 19-point line fit of every read on the host;
+    `rescale_device` does the precise re-scale of an iterative refiner (scale_iters > 0) for a resident
+    batch - dwell percentiles, per-base mean signal, the filters and both Theil-Sen medians in two HIP
+    kernels (`rmr_rescale_points`, `rmr_theil_sen_fit`) - and leaves the host the random sub-sample of
+    reads above 1000 points and the last two-line scaling arithmetic.  Bit-identical results, so
+    `refine_device_reads` runs every refiner (any scale_iters >= 0) on a resident batch."""
 import ctypes
 import dataclasses
 import os
@@ -620,29 +624,208 @@ class SigMapRefiner:
 
         return quantiles(norm, torch.float64), quantiles(levels, torch.float32)
 
-    def refine_device_reads(self, dr, reads):
-        """One DP pass (scale_iters 0 or 1 round of it) on reads that are already resident (`DeviceReads`):
-        the refined mappings replace `dr.s2s` on the device and are copied back into the read objects.
-        Raises the RemoraError of the first read whose band is invalid."""
+    # ---- the precise re-scale of an iterative refiner on a resident batch -----------------------------------------
+    @staticmethod
+    def level_ok(levels, min_abs_level=0.2):
+        """The level term of `rescale`'s mask for one read (uint8 per base): float32 levels against numpy's float32 mean,
+        evaluated by numpy itself - the term depends on the bases alone, so a batch uploads it once."""
+        return (np.abs(levels - np.mean(levels)) > min_abs_level).astype(np.uint8)
+
+    def _rescale_context(self, dr):
+        """What every round of `rescale_device` reuses for one resident batch: per-base levels and `level_ok` (from the
+        batch's own base codes through `extract_levels`, uploaded once) and the output arrays of the two kernels."""
+        import torch
+
+        ctx = getattr(dr, "_rescale_ctx", None)
+        if ctx is not None and ctx["owner"] is self:
+            return ctx
+        tdev = dr.s2s.device
+        nr, total = dr.n_reads, int(dr.seq_off[-1])
+        iseq = dr.iseq.cpu().numpy()
+        levels = np.zeros(max(total, 1), np.float32)
+        ok = np.zeros(max(total, 1), np.uint8)
+        so = dr.seq_off.tolist()
+        for i in range(nr):
+            if so[i + 1] > so[i]:
+                lv = self.extract_levels(iseq[so[i] : so[i + 1]])
+                levels[so[i] : so[i + 1]] = lv
+                ok[so[i] : so[i + 1]] = self.level_ok(lv)
+        ctx = dict(owner=self, levels=torch.from_numpy(levels).to(tdev), level_ok=torch.from_numpy(ok).to(tdev),
+                   x=torch.empty(max(total, 1), dtype=torch.float64, device=tdev),
+                   y=torch.empty(max(total, 1), dtype=torch.float32, device=tdev),
+                   count=torch.zeros(max(nr, 1), dtype=torch.int32, device=tdev),
+                   slope=torch.zeros(max(nr, 1), dtype=torch.float64, device=tdev),
+                   inter=torch.zeros(max(nr, 1), dtype=torch.float64, device=tdev),
+                   status=torch.zeros(max(nr, 1), dtype=torch.int32, device=tdev))
+        dr._rescale_ctx = ctx
+        return ctx
+
+    def _rescale_points(self, dr, live, edge_filter_bases):
+        """`rmr_rescale_points` for the live reads of a resident batch -> counts int32[n_reads] on the host; the points stay
+        on the device (`_rescale_context`)."""
         import torch
 
         dev = self._device_refiner(dr.engine.device)
-        out = torch.empty_like(dr.s2s)
-        status = torch.empty(max(dr.n_reads, 1), dtype=torch.int32, device=dr.s2s.device)  # written for every read
+        ctx = self._rescale_context(dr)
+        tdev = dr.s2s.device
         p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        L.check(dev._lib.rmr_refine_signal_maps(dev._h, dr.n_reads, p(dr.dacs), p(dr.d_sig_off), p(dr.s2s), p(dr.iseq),
-                                                 p(dr.d_seq_off), p(dr.shift), p(dr.scale), p(out), p(status), L.MEM_DEVICE))
-        for st in status[: dr.n_reads].cpu().numpy():
-            if st != 0:
-                raise RemoraError(dev.status_message(st))
+        d_live = torch.from_numpy(live.view(np.uint8)).to(tdev)
+        torch.cuda.current_stream(tdev).synchronize()  # the mapping and the scaling may come from torch's stream
+        L.check(dev._lib.rmr_rescale_points(dev._h, dr.n_reads, p(dr.dacs), p(dr.d_sig_off), p(dr.s2s), p(dr.d_seq_off), p(dr.shift),
+                                             p(dr.scale), p(ctx["levels"]), p(ctx["level_ok"]), p(d_live), int(edge_filter_bases),
+                                             p(ctx["count"]), p(ctx["x"]), p(ctx["y"])))
+        dr.engine.synchronize()
+        return ctx["count"][: dr.n_reads].cpu().numpy()
+
+    def _theil_sen_fit(self, dr, fit, samp, samp_off):
+        """`rmr_theil_sen_fit` through the points `_rescale_points` left, for the reads whose `fit` entry is set; `samp`: the
+        drawn index arrays (int32, 1000 each) back to back in the order of `samp_off` (int64 per read, -1: none).
+        -> (slope f64, inter f64, status i32) per read on the host."""
+        import torch
+
+        dev = self._device_refiner(dr.engine.device)
+        ctx = self._rescale_context(dr)
+        tdev = dr.s2s.device
+        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        nr = dr.n_reads
+        d_fit = torch.from_numpy(fit.view(np.uint8)).to(tdev)
+        d_samp = torch.from_numpy(np.concatenate(samp)).to(tdev) if samp else None
+        d_samp_off = torch.from_numpy(samp_off).to(tdev) if samp else None
+        torch.cuda.current_stream(tdev).synchronize()
+        L.check(dev._lib.rmr_theil_sen_fit(dev._h, nr, p(ctx["x"]), p(ctx["y"]), p(ctx["count"]), p(dr.d_seq_off),
+                                            p(d_samp) if samp else None, p(d_samp_off) if samp else None,
+                                            int(d_samp.numel()) if samp else 0, p(d_fit),
+                                            p(ctx["slope"]), p(ctx["inter"]), p(ctx["status"])))
+        dr.engine.synchronize()
+        return ctx["slope"][:nr].cpu().numpy(), ctx["inter"][:nr].cpu().numpy(), ctx["status"][:nr].cpu().numpy()
+
+    def rescale_device(self, dr, reads, live, edge_filter_bases=10, min_levels=10):
+        """One round of `rescale` for the reads of a resident `DeviceReads` batch whose `live` entry is set: the dwell
+        percentiles, the per-base mean signal and the filters in `rmr_rescale_points`, the two medians of `theil_sen` in
+        `rmr_theil_sen_fit` (csrc/k_refine.hip), bit-identical to the host method.  The host keeps what decides the
+        random stream and the last two roundings: the sub-sample of a read with more than MAX_POINTS_FOR_THEIL_SEN
+        points is drawn from numpy's global generator in read order, exactly where `refine_reads` draws it, and the new
+        (shift, scale) are formed from the medians in the expression of `theil_sen`.  Updates the reads and `dr`; -> per
+        read None or the RemoraError the host method raises for it ("Too few positions", a zero slope).  A read without a
+        pair of increasing x gets NaN scaling and no error, as on the host (np.median of nothing is NaN, which is not 0)."""
+        nr = dr.n_reads
+        errs = [None] * nr
+        live = np.ascontiguousarray(live, bool)
+        if live.shape != (nr,):
+            raise RemoraError("live must hold one entry per read of the batch")
+        if nr == 0 or not live.any():
+            return errs
+        max_points = MAX_POINTS_FOR_THEIL_SEN
+        counts = self._rescale_points(dr, live, edge_filter_bases)
+        fit = live.copy()
+        samp, samp_off = [], np.full(nr, -1, np.int64)
+        for i in np.flatnonzero(live).tolist():
+            if counts[i] < min_levels:
+                errs[i] = RemoraError("Too few positions")
+                fit[i] = False
+            elif counts[i] > max_points:
+                samp_off[i] = len(samp) * max_points
+                samp.append(np.random.choice(int(counts[i]), max_points, replace=False).astype(np.int32))
+        if not fit.any():
+            return errs
+        slope, inter, status = self._theil_sen_fit(dr, fit, samp, samp_off)
+        shifts = np.asarray([float(r.shift) for r in reads], np.float64)
+        scales = np.asarray([float(r.scale) for r in reads], np.float64)
+        for i in np.flatnonzero(fit).tolist():
+            if status[i] == 2:
+                errs[i] = RemoraError("Theil-Sen slope is zero: cannot re-scale")
+                continue
+            if status[i] == 3:
+                raise RemoraError("rmr_theil_sen_fit: inconsistent points")
+            r = reads[i]
+            sl, it, shift, scale = slope[i], inter[i], r.shift, r.scale
+            r.shift, r.scale = shift + (-it / sl) * scale, scale * (1 / sl)  # the expression of theil_sen
+            r._sig = None
+            shifts[i], scales[i] = float(r.shift), float(r.scale)
+        dr.set_scaling(shifts, scales)
+        return errs
+
+    def refine_device_reads(self, dr, reads, errors="raise"):
+        """The refinement rounds of `refine_reads` on reads that are already resident (`DeviceReads`), any `scale_iters`
+        >= 0: max(1, scale_iters) banded-DP passes, each followed - for an iterative refiner (scale_iters > 0) - by the
+        precise re-scale of `rescale_device`.  A read whose band is invalid gets that error and leaves; one whose
+        re-scale raises keeps the mapping of that round and leaves without an error; the rest go round again.  A read
+        that has left keeps its mapping through the later passes.  The refined mappings replace `dr.s2s` on the device
+        and are copied back into the read objects once, after the last round; shift and scale of `dr` and of the reads
+        follow every round.  Mappings, scalings and errors equal `refine_reads` bit for bit, the draws from numpy's
+        global generator included.
+        `errors`: "raise" raises the RemoraError of the first read (in read order) that has one - a single pass before
+        anything is written back, an iterative refiner after the last round and with numpy's global generator put back
+        to where the call found it (the caller's per-read fallback then draws what it would have drawn); "collect" returns the list of per-read
+        errors (None or RemoraError) that `refine_reads` returns."""
+        import torch
+
+        if errors not in ("raise", "collect"):
+            raise ValueError(f"errors must be 'raise' or 'collect', not {errors!r}")
+        dev = self._device_refiner(dr.engine.device)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         from .data_chunks import device_to_numpy
 
-        dr.s2s = out
-        host = device_to_numpy(out)
-        mo = dr.seq_off + np.arange(dr.n_reads + 1)
-        for i, r in enumerate(reads):
-            r.seq_to_sig_map = host[mo[i] : mo[i + 1]].astype(np.asarray(r.seq_to_sig_map).dtype, copy=False)
-            r._sig = None
+        if self.scale_iters <= 0 and errors == "raise":
+            out = torch.empty_like(dr.s2s)
+            status = torch.empty(max(dr.n_reads, 1), dtype=torch.int32, device=dr.s2s.device)  # written for every read
+            L.check(dev._lib.rmr_refine_signal_maps(dev._h, dr.n_reads, p(dr.dacs), p(dr.d_sig_off), p(dr.s2s), p(dr.iseq),
+                                                     p(dr.d_seq_off), p(dr.shift), p(dr.scale), p(out), p(status), L.MEM_DEVICE))
+            for st in status[: dr.n_reads].cpu().numpy():
+                if st != 0:
+                    raise RemoraError(dev.status_message(st))
+            dr.s2s = out
+            host = device_to_numpy(out)
+            mo = dr.seq_off + np.arange(dr.n_reads + 1)
+            for i, r in enumerate(reads):
+                r.seq_to_sig_map = host[mo[i] : mo[i + 1]].astype(np.asarray(r.seq_to_sig_map).dtype, copy=False)
+                r._sig = None
+            return None
+        nr = dr.n_reads
+        errs = [None] * nr
+        tdev = dr.s2s.device
+        live = np.ones(nr, bool)
+        moved = np.zeros(nr, bool)
+        # a caller that answers a raised error by going read by read must find the generator where this call found it
+        rng_state = np.random.get_state() if errors == "raise" and self.scale_iters > 0 else None
+        rows = np.diff(dr.seq_off) + 1  # mapping entries per read
+        for _ in range(max(1, self.scale_iters)):
+            if not live.any():
+                break
+            out = torch.empty_like(dr.s2s)
+            status = torch.empty(max(nr, 1), dtype=torch.int32, device=tdev)
+            torch.cuda.current_stream(tdev).synchronize()  # the previous round's mapping and scaling come from torch's stream
+            L.check(dev._lib.rmr_refine_signal_maps(dev._h, nr, p(dr.dacs), p(dr.d_sig_off), p(dr.s2s), p(dr.iseq), p(dr.d_seq_off),
+                                                     p(dr.shift), p(dr.scale), p(out), p(status), L.MEM_DEVICE))
+            st = status[:nr].cpu().numpy()
+            for i in np.flatnonzero(live & (st != 0)).tolist():
+                errs[i] = RemoraError(dev.status_message(st[i]))
+            live &= st == 0
+            moved |= live
+            if live.all():
+                dr.s2s = out
+            else:  # reads that have left (and those just rejected, whose rows the pass does not write) keep their mapping
+                take = torch.from_numpy(np.repeat(live, rows)).to(tdev)
+                dr.s2s = torch.where(take, out, dr.s2s)
+            if self.scale_iters > 0:
+                for i, e in enumerate(self.rescale_device(dr, reads, live)):
+                    if e is not None:
+                        live[i] = False
+        if moved.any():
+            host = device_to_numpy(dr.s2s)
+            mo = dr.seq_off + np.arange(nr + 1)
+            for i in np.flatnonzero(moved).tolist():
+                r = reads[i]
+                r.seq_to_sig_map = host[mo[i] : mo[i + 1]].astype(np.asarray(r.seq_to_sig_map).dtype, copy=False)
+                r._sig = None
+        if errors == "raise":
+            for e in errs:
+                if e is not None:
+                    if rng_state is not None:
+                        np.random.set_state(rng_state)
+                    raise e
+            return None
+        return errs
 
     # ---- (de)serialisation (:499-587) -----------------------------------------------------------
     def asdict(self):

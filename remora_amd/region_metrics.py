@@ -335,7 +335,7 @@ def _refine_resident(refiner, dr, stubs):
     loaded = refiner is not None and getattr(refiner, "is_loaded", False)
     if loaded and refiner.do_rough_rescale:
         refiner.rough_rescale_device(dr, stubs)
-    if loaded and refiner.scale_iters == 0:
+    if loaded and refiner.scale_iters >= 0:
         refiner.refine_device_reads(dr, stubs)
 
 
@@ -406,8 +406,7 @@ def _ready_from_batch(rb, records, picked, slots, signals, refiner, reverse_sign
 
     select = np.zeros(rb.n, bool)
     select[picked] = True
-    iterative = refiner is not None and getattr(refiner, "is_loaded", False) and refiner.scale_iters > 0
-    got = "slow" if (iterative or pa_scaling is not None) else rio._ingest_batch(
+    got = "slow" if pa_scaling is not None else rio._ingest_batch(
         rb, records, signals, get_ingest_engine(device), None, True, ref_anchored=True, reverse_signal=reverse_signal, select=select)
     if isinstance(got, rio.IngestBatch):
         gk = got.keep[got.good]
