@@ -164,7 +164,8 @@ static int launch_conv_s_t(rmr_engine *e, const ConvLayer &c, const float *in, i
     const int plane = ((cb * pin + 2) * SLR + 15) & ~15;  // +2 guard rows
     const int part = NPL * plane + 16;                    // + trash slot
     const size_t lds = (size_t)part * NP * 16;
-    if (lds > 160 * 1024) RMR_FAIL(RMR_ERR_INVALID, "split conv layer needs %zu B of LDS", lds);
+    if (lds > 160 * 1024)
+        RMR_FAIL(RMR_ERR_INVALID, "split conv layer %s needs %zu B of LDS for one chunk of %d rows (160 KB per block)", kernel_name(c.kid), lds, pin);
     ConvSArgs a;
     a.in = in; a.out = out; a.apack = reinterpret_cast<const uint4 *>(c.spack); a.bias = c.bias; a.n = n;
     a.in_row = in_row; a.pin = pin; a.pout = pout; a.out_row = out_row; a.out_coff = out_coff;

@@ -219,13 +219,18 @@ __global__ __launch_bounds__(4 * H) void lstm_bf16s_kernel(LstmSArgs a) {
             if (q == 0) part[w][nn][o] = p;
         }
         RMR_SYNC();
-        if (tid < 16 * a.num_out) {
-            const int ch = tid / a.num_out, o = tid - ch * a.num_out;
-            if (chunk0 + ch < a.n) {
-                float s = a.b_fc[o];
+        // 16 chunks x num_out logits, strided by the block's 4 H threads: up to 16 x 16 (desc_ok) on 256, 128 (H = 32) or 64 (H = 16)
 #pragma unroll
-                for (int ww = 0; ww < NW; ++ww) s += part[ww][ch][o];
-                a.logits[(size_t)(chunk0 + ch) * a.num_out + o] = s;
+        for (int i0 = 0; i0 < 16 * 16; i0 += 4 * H) {
+            const int i = i0 + tid;
+            if (i < 16 * a.num_out) {
+                const int ch = i / a.num_out, o = i - ch * a.num_out;
+                if (chunk0 + ch < a.n) {
+                    float s = a.b_fc[o];
+#pragma unroll
+                    for (int ww = 0; ww < NW; ++ww) s += part[ww][ch][o];
+                    a.logits[(size_t)(chunk0 + ch) * a.num_out + o] = s;
+                }
             }
         }
     }
