@@ -376,6 +376,43 @@ int rmr_modbam_site_counts(rmr_engine *e, const rmr_modbam_batch *b, int32_t *or
 int rmr_modbam_site_fill(rmr_engine *e, const rmr_modbam_batch *b, const int32_t *ords, const int64_t *cig_q, const int64_t *cig_r,
                          const int32_t *status, const int64_t *out_off, float *probs, uint8_t *label, int64_t *qpos, int64_t *rpos);
 
+/* The simplex-to-duplex alignment of duplex calling (GPU; HOST pointers, synchronous).
+ * replaces: duplex_utils.parasail_align + trim_parasail_alignment, src/remora/duplex_utils.py:22-115, i.e.
+ * parasail.sg_qx_trace_scan_32(simplex, duplex, 10, 2, dnafull) and the stripping of the gap operations at both ends, for a
+ * batch of alignments.  Semi-global affine-gap alignment, exact (unbanded): the query (simplex) has free ends, the ref (duplex)
+ * is consumed whole; H[i][0] = 0, H[0][j] = -(OPEN + EXTEND (j - 1)), the result is max_i H[i][m].  The scores are the block
+ * below (a gap of k bases costs OPEN + EXTEND (k - 1)).  Among co-optimal paths ("Duplex"): the end row is the
+ * smallest i with H[i][m] maximal; walking back, H prefers the diagonal, then the deletion state (consumes the duplex), then
+ * the insertion state (consumes the simplex); a gap state returns to H as soon as the scores allow. */
+#define RMR_DUPLEX_MATCH 5
+#define RMR_DUPLEX_MISMATCH (-4)
+#define RMR_DUPLEX_N_BASE (-2)   /* N against A / C / G / T */
+#define RMR_DUPLEX_N_N (-1)
+#define RMR_DUPLEX_GAP_OPEN 10
+#define RMR_DUPLEX_GAP_EXTEND 2
+#define RMR_DUPLEX_ROWS_PER_LANE 8
+#define RMR_DUPLEX_STRIP_ROWS 512   /* 64 lanes of RMR_DUPLEX_ROWS_PER_LANE simplex rows: the strip height of the kernel */
+#define RMR_DUPLEX_DEFAULT_TRACE_BYTES ((int64_t)1 << 34) /* 16 GiB */
+/* per-alignment status (out field 0) */
+#define RMR_DUPLEX_OK 0
+#define RMR_DUPLEX_NO_MATCH 1      /* no match operation on the path */
+#define RMR_DUPLEX_BAD_BASE 2      /* a letter other than A C G T N (upper case) */
+#define RMR_DUPLEX_OVER_BUDGET 3   /* its own trace is larger than trace_budget */
+#define RMR_DUPLEX_EMPTY 4         /* an empty sequence */
+#define RMR_DUPLEX_OUT_FIELDS 8
+/* Alignment a: query bases[q_off[a] .. + q_len[a]), ref bases[r_off[a] .. + r_len[a]) (ASCII).  The trace of an alignment takes
+ * ceil(q_len / STRIP_ROWS) * (r_len + 63) * 256 bytes (4 bits per cell).  The alignments are sorted by that size and run in as
+ * many groups as trace_budget bytes need (<= 0: RMR_DUPLEX_DEFAULT_TRACE_BYTES); one group's traces are allocated for the call
+ * and freed before it returns.  The grouping changes no result.  *n_groups (may be NULL) receives the number of groups.
+ * out i32[n][RMR_DUPLEX_OUT_FIELDS]: status, score, end row, query_start, ref_start, ref_end, number of runs, 0; everything
+ * after the status is 0 unless the status is RMR_DUPLEX_OK.  The path between (query_start, ref_start) and the end, gap runs at
+ * both ends stripped, is written as BAM CIGAR words (length << 4 | op; M = 0 with = and X folded, I = 1, D = 2) to
+ * runs[run_off[a] ..]: the caller provides run_off i64[n + 1] with room for at least 2 r_len + 2 words per alignment (the most
+ * a path can have). */
+int rmr_duplex_align(rmr_engine *e, int64_t n, const uint8_t *bases, const int64_t *q_off, const int64_t *q_len, const int64_t *r_off,
+                     const int64_t *r_len, int64_t trace_budget, int32_t *out, const int64_t *run_off, uint32_t *runs,
+                     int64_t *n_groups);
+
 /* The signal coordinate of every reference position of one alignment (host code).
  * replaces: compute_ref_to_signal = map_ref_to_signal(make_sequence_coordinate_mapping(cigar)), src/remora/data_chunks.py:60-122
  * (called from io.Read.add_alignment, src/remora/io.py:2070-2080), with np.interp's float64 arithmetic: the same integers.

@@ -307,6 +307,35 @@ def _infer(args):
     return 0
 
 
+def _infer_duplex(args):
+    """src/remora/parsers.py:1615-1662."""
+    import logging
+
+    from .inference import infer_duplex
+    from .model_util import load_torchscript_model
+
+    log = logging.getLogger("Remora")
+    log.setLevel(logging.INFO)
+    if not log.handlers:
+        log.addHandler(logging.StreamHandler(sys.stderr))
+    if args.log_filename is not None:
+        log.addHandler(logging.FileHandler(args.log_filename, mode="w"))
+    if len(args.model) > 1:  # refused before anything is loaded
+        raise NotImplementedError("Duplex infer does not currently implement running of multiple models")
+    for what, path in (("pod5", args.pod5), ("simplex bam", args.simplex_bam), ("duplex bam", args.duplex_bam),
+                       ("duplex read pairs", args.duplex_read_pairs)):
+        if not os.path.exists(path):
+            raise ValueError(f"didn't find {what} at {path}")
+    model, md = load_torchscript_model(args.model[0], device=args.device, eval_only=True, dtype=args.dtype)
+    infer_duplex(simplex_pod5_path=args.pod5, simplex_bam_path=args.simplex_bam, duplex_bam_path=args.duplex_bam,
+                 pairs_path=args.duplex_read_pairs, model=model, model_metadata=md, out_bam=args.out_bam,
+                 num_extract_alignment_threads=args.num_extract_alignment_workers, num_duplex_prep_workers=args.num_duplex_prep_workers,
+                 num_infer_threads=args.num_infer_workers, num_reads=args.num_reads, duplex_deliminator=args.duplex_delim,
+                 reads_per_batch=args.reads_per_batch, bam_level=args.bam_level)
+    log.info("Done")
+    return 0
+
+
 def _estimate_kmer_levels(args):
     """src/remora/parsers.py:2268-2333."""
     import logging
@@ -375,6 +404,26 @@ def build_parser():
     p.add_argument("--reference-anchored", action="store_true",
                    help="call at reference positions; output records become <len>M with the reference sequence")
     p.set_defaults(func=_infer)
+
+    d = infer.add_parser("duplex_from_pod5_and_bam", help="Infer modified bases on duplex reads from POD5 + simplex BAM + duplex BAM "
+                                                          "with duplex pairs (src/remora/parsers.py:1420-1535)")
+    d.add_argument("pod5", help="POD5 file matched to the simplex BAM")
+    d.add_argument("simplex_bam", help="basecalled BAM file containing mv tags")
+    d.add_argument("duplex_bam", help="BAM file with the duplex basecalls; record names are the template read id or "
+                                      "template<delim>complement")
+    d.add_argument("duplex_read_pairs", help="whitespace separated text file of template / complement read id pairs, no header")
+    d.add_argument("--duplex-delim", default=";", help="string between the template and complement read ids in the duplex BAM")
+    d.add_argument("--out-bam", required=True)
+    d.add_argument("--log-filename")
+    d.add_argument("--model", required=True, action="append", help="TorchScript model file (with meta.txt); one model only")
+    d.add_argument("--num-reads", type=int, default=None, help="number of (valid) pairs")
+    d.add_argument("--device", type=int, default=0)
+    for flag in ("--num-extract-alignment-workers", "--num-duplex-prep-workers", "--num-infer-workers"):
+        d.add_argument(flag, type=int, default=1, help="accepted and ignored: the pairs go through the GPU in batches")
+    d.add_argument("--dtype", default=None, help="as for infer from_pod5_and_bam")
+    d.add_argument("--bam-level", type=int, default=None, help="as for infer from_pod5_and_bam")
+    d.add_argument("--reads-per-batch", type=int, default=64, help="duplex pairs per batch: two alignments and two model passes each")
+    d.set_defaults(func=_infer_duplex)
 
     val = sub.add_parser("validate").add_subparsers(dest="sub", required=True)
     v = val.add_parser("from_remora_dataset", help="Validate a model on an on-disk Remora dataset (directory or config)")

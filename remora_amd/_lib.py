@@ -119,6 +119,7 @@ SIGNATURES = {
     "rmr_mod_tags_fill": (c_int, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int]),
     "rmr_modbam_site_counts": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rmr_modbam_site_fill": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rmr_duplex_align": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64)]),
     "rmr_inflate_raw": (c_int, [c_vp, c_i64, c_vp, c_i64]),
     "rmr_bgzf_huffman": (c_int, [c_vp, c_i64, c_int, c_vp, c_i64, ctypes.POINTER(c_i64)]),
     "rmr_zstd_frame_sizes": (c_int, [c_vp, c_vp, c_i64, c_vp]),

@@ -1,6 +1,7 @@
 // api_data.hip — the data entry points of the C ABI: k-mer encoding, context trimming, move tables, signal histograms, read
-// assembly, chunk extraction, label counts, the validation tally, motif scans, the VBZ decode and the site join of `validate from_modbams`.  Each RMR_MEM_HOST call
-// declares its arrays in a Stage (rmr_stage.h), uploads, launches (k_data.hip, k_vbz.hip, k_modbam.hip) and copies back.
+// assembly, chunk extraction, label counts, the validation tally, motif scans, the VBZ decode, the site join of `validate from_modbams` and the duplex alignment.  Each RMR_MEM_HOST call
+// declares its arrays in a Stage (rmr_stage.h), uploads, launches (k_data.hip, k_vbz.hip, k_modbam.hip, k_duplex.hip) and copies back.
+#include <algorithm>
 #include <cstring>
 
 #include "rmr_internal.h"
@@ -525,6 +526,108 @@ int rmr_modbam_site_fill(rmr_engine *e, const rmr_modbam_batch *b, const int32_t
     RMR_HIP(hipSetDevice(e->device));
     return launch_modbam_sites(e, *b, const_cast<int32_t *>(ords), const_cast<int64_t *>(cig_q), const_cast<int64_t *>(cig_r), nullptr,
                                const_cast<int32_t *>(status), out_off, probs, label, qpos, rpos);
+}
+
+int rmr_duplex_align(rmr_engine *e, int64_t n, const uint8_t *bases, const int64_t *q_off, const int64_t *q_len, const int64_t *r_off,
+                     const int64_t *r_len, int64_t trace_budget, int32_t *out, const int64_t *run_off, uint32_t *runs,
+                     int64_t *n_groups) {
+    if (n_groups) *n_groups = 0;
+    if (!e || n < 0) RMR_FAIL(RMR_ERR_INVALID, "bad argument");
+    if (n == 0) return 0;
+    if (!bases || !q_off || !q_len || !r_off || !r_len || !out || !run_off || !runs) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if (n > INT32_MAX) RMR_FAIL(RMR_ERR_INVALID, "too many alignments");
+    const int64_t budget = trace_budget > 0 ? trace_budget : RMR_DUPLEX_DEFAULT_TRACE_BYTES;
+    // what does not reach the GPU gets its status here; the rest is sorted by trace size, largest first
+    std::vector<int32_t> hout((size_t)n * RMR_DUPLEX_OUT_FIELDS, 0);
+    std::vector<DuplexJob> jobs;
+    std::vector<int64_t> tdw((size_t)n, 0);  // trace dwords of alignment a
+    int64_t n_bases = 0;
+    if (run_off[0] < 0) RMR_FAIL(RMR_ERR_INVALID, "run_off is negative");
+    for (int64_t a = 0; a < n; ++a) {
+        const int64_t nq = q_len[a], nr = r_len[a];
+        if (nq < 0 || nr < 0 || q_off[a] < 0 || r_off[a] < 0) RMR_FAIL(RMR_ERR_INVALID, "negative offset or length (alignment %lld)", (long long)a);
+        if (run_off[a + 1] - run_off[a] < 2 * nr + 2)
+            RMR_FAIL(RMR_ERR_INVALID, "run_off leaves alignment %lld fewer than 2 r_len + 2 words", (long long)a);
+        n_bases = std::max(n_bases, std::max(q_off[a] + nq, r_off[a] + nr));
+        int32_t *o = &hout[(size_t)a * RMR_DUPLEX_OUT_FIELDS];
+        if (nq == 0 || nr == 0) {
+            o[0] = RMR_DUPLEX_EMPTY;
+            continue;
+        }
+        bool ok = true;
+        for (int side = 0; side < 2 && ok; ++side) {
+            const uint8_t *p = bases + (side ? r_off[a] : q_off[a]);
+            for (int64_t i = 0, k = side ? nr : nq; i < k && ok; ++i)
+                ok = p[i] == 'A' || p[i] == 'C' || p[i] == 'G' || p[i] == 'T' || p[i] == 'N';
+        }
+        if (!ok) {
+            o[0] = RMR_DUPLEX_BAD_BASE;
+            continue;
+        }
+        // (lengths beyond 2^30 fit no budget; below them the product stays far inside int64)
+        const int64_t strips = (nq + RMR_DUPLEX_STRIP_ROWS - 1) / RMR_DUPLEX_STRIP_ROWS;
+        if (nq > (1 << 30) || nr > (1 << 30) || strips * (nr + 63) > budget / 256) {
+            o[0] = RMR_DUPLEX_OVER_BUDGET;
+            continue;
+        }
+        tdw[(size_t)a] = strips * (nr + 63) * 64;
+        DuplexJob j{};
+        j.q_off = q_off[a], j.r_off = r_off[a], j.run_off = run_off[a];
+        j.n = (int32_t)nq, j.m = (int32_t)nr, j.out_idx = (int32_t)a;
+        jobs.push_back(j);
+    }
+    if (jobs.empty()) {
+        memcpy(out, hout.data(), hout.size() * 4);
+        return 0;
+    }
+    std::stable_sort(jobs.begin(), jobs.end(),
+                     [&](const DuplexJob &x, const DuplexJob &y) { return tdw[(size_t)x.out_idx] > tdw[(size_t)y.out_idx]; });
+    // groups of consecutive jobs whose traces fit the budget together; a job's offset inside its group's trace
+    std::vector<size_t> group_start{0};
+    int64_t used = 0, max_used = 0, line_total = 0;
+    for (size_t k = 0; k < jobs.size(); ++k) {
+        const int64_t w = tdw[(size_t)jobs[k].out_idx];
+        if (used > 0 && (used + w) * 4 > budget) group_start.push_back(k), used = 0;
+        jobs[k].trace_off = used, jobs[k].line_off = line_total;
+        used += w, line_total += jobs[k].m;
+        max_used = std::max(max_used, used);
+    }
+    group_start.push_back(jobs.size());
+
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    Stage st;
+    uint8_t *d_bases;
+    DuplexJob *d_jobs;
+    int2 *d_line, *d_best;
+    uint32_t *d_runs;
+    int32_t *d_out;
+    st.add(&d_bases, n_bases).add(&d_jobs, jobs.size()).add(&d_line, line_total).add(&d_best, jobs.size()).add(&d_runs, run_off[n])
+        .add(&d_out, hout.size());
+    RMR_TRY(st.commit(e));
+    uint32_t *d_trace = nullptr;
+    if (hipMalloc(&d_trace, (size_t)max_used * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        RMR_FAIL(RMR_ERR_HIP, "cannot allocate %lld bytes of alignment trace (lower the trace budget)", (long long)max_used * 4);
+    }
+    auto run = [&]() -> int {
+        H2D(d_bases, bases, (size_t)n_bases);
+        H2D(d_jobs, jobs.data(), jobs.size() * sizeof(DuplexJob));
+        H2D(d_out, hout.data(), hout.size() * 4);
+        for (size_t g = 0; g + 1 < group_start.size(); ++g) {
+            const size_t k0 = group_start[g];
+            RMR_TRY(launch_duplex_group(e, d_jobs + k0, (int)(group_start[g + 1] - k0), d_bases, d_trace, d_line, d_best + k0, d_runs, d_out));
+        }
+        D2H(out, d_out, hout.size() * 4);
+        D2H(runs, d_runs, (size_t)run_off[n] * 4);
+        RMR_HIP(hipStreamSynchronize(e->stream));
+        return 0;
+    };
+    const int rc = run();
+    if (rc != 0) (void)hipStreamSynchronize(e->stream);  // nothing may still write the trace when it is freed
+    (void)hipFree(d_trace);
+    if (rc == 0 && n_groups) *n_groups = (int64_t)group_start.size() - 1;
+    return rc;
 }
 
 }  // extern "C"

@@ -25,7 +25,8 @@ static const char *k_names[K_NUM] = {
     "conv_merge1", "conv_merge2", "conv_merge3", "conv_merge4", "lstm_head", "fc_head",
     "count_labels", "motif_scan", "vbz_decode", "refine_band", "refine_dp", "refine_dp_rowwise",
     "fused_front", "rescale_quantiles", "sig3_front", "seq2_front", "probe_max_diff", "probe_nonfinite", "winograd_form",
-    "base_metrics", "region_metrics", "region_signals", "site_kmer_levels", "modbam_sites", "rescale_points", "theil_sen_fit"};
+    "base_metrics", "region_metrics", "region_signals", "site_kmer_levels", "modbam_sites", "rescale_points", "theil_sen_fit",
+    "duplex_dp", "duplex_traceback"};
 const char *kernel_name(int id) { return (id >= 0 && id < K_NUM) ? k_names[id] : "?"; }
 
 }  // namespace rmr
@@ -180,7 +181,7 @@ int rmr_engine::prof_collect() {
 extern "C" {
 
 const char *rmr_last_error(void) { return g_err.c_str(); }
-const char *rmr_version(void) { return "remora_hip 0.8 (gfx950)"; }  // 0.8: rmr_mod_tags_sizes / _fill, rmr_modbam_site_counts / _fill
+const char *rmr_version(void) { return "remora_hip 0.9 (gfx950)"; }  // 0.9: rmr_duplex_align
 
 int rmr_engine_create(int device, void *stream, int flags, rmr_engine **out) {
     if (!out) RMR_FAIL(RMR_ERR_INVALID, "out is NULL");

@@ -67,6 +67,8 @@ enum KernelId {
     K_MODBAM_SITES,
     K_RESCALE_POINTS,
     K_THEIL_SEN,
+    K_DUPLEX_DP,
+    K_DUPLEX_TRACE,
     K_NUM
 };
 const char *kernel_name(int id);
@@ -208,6 +210,14 @@ int launch_motif_focus(rmr_engine *e, const int8_t *seq, const int64_t *seq_off,
 // k_modbam.hip: the site join of `validate from_modbams` (count pass: out_off == nullptr)
 int launch_modbam_sites(rmr_engine *e, const rmr_modbam_batch &b, int32_t *ords, int64_t *cig_q, int64_t *cig_r, int64_t *counts,
                         int32_t *status, const int64_t *out_off, float *probs, uint8_t *label, int64_t *qpos, int64_t *rpos);
+// k_duplex.hip: one group of simplex-to-duplex alignments whose traces share `trace` (rmr_duplex_align).  A job's offsets: bases in
+// `bases`, dwords in `trace`, entries in `line` (m of them) and in `runs` (2 m + 2); its result goes to out[out_idx].
+struct DuplexJob {
+    int64_t q_off, r_off, trace_off, line_off, run_off;
+    int32_t n, m, out_idx, pad;
+};
+int launch_duplex_group(rmr_engine *e, const DuplexJob *jobs, int n_jobs, const uint8_t *bases, uint32_t *trace, int2 *line, int2 *best,
+                        uint32_t *runs, int32_t *out);
 int launch_motif(rmr_engine *e, const int8_t *seq, const int64_t *seq_off, int n_reads, int64_t total,
                  const rmr_motif_set &ms, uint8_t *flags);
 

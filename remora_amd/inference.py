@@ -961,3 +961,167 @@ def post_process_reads(read_mapping, models_metadata, ref_anchored=False):
         mm_tags.append(mm)
         ml_arr.extend(ml)
     return io_read, "".join(mm_tags), ml_arr
+
+
+# ---- duplex calling (src/remora/inference.py:715-1010) ----
+def _duplex_read_mod_probs(duplex_read, template_result, complement_result):
+    """The calls of a duplex read's two re-anchored reads, as (probs, labels, pos) each, in duplex coordinates
+    (src/remora/inference.py:733-770)."""
+    from .io import revcomp
+
+    t_probs, _, t_pos = template_result
+    c_probs, _, c_pos = complement_result
+    t_pos = np.asarray(t_pos, np.int64) + duplex_read.template_ref_start
+    c_pos = np.asarray(c_pos, np.int64) + duplex_read.complement_ref_start
+    seq = duplex_read.duplex_basecalled_sequence
+    read_sequence = revcomp(seq) if duplex_read.is_reverse_mapped else seq
+    if duplex_read.is_reverse_mapped:
+        (t_pos, t_probs), (c_pos, c_probs) = (c_pos, c_probs), (t_pos, t_probs)
+    return {"template_probs": t_probs, "template_positions": t_pos, "complement_probs": c_probs,
+            "complement_positions": len(read_sequence) - c_pos - 1, "read_sequence": read_sequence}
+
+
+class DuplexReadModCaller:
+    """Modified-base calls of one DuplexRead (src/remora/inference.py:715-799); infer_duplex does the same for a batch."""
+
+    def __init__(self, model, model_metadata):
+        self.model = model
+        self.model_metadata = model_metadata
+
+    def call_duplex_read_mod_probs(self, duplex_read):
+        res = [call_read_mods(read=r.into_remora_read(False), model=self.model, model_metadata=self.model_metadata, return_mod_probs=True)
+               for r in (duplex_read.template_read, duplex_read.complement_read)]
+        return _duplex_read_mod_probs(duplex_read, *res)
+
+    def call_duplex_read_mods(self, duplex_read):
+        from .io import revcomp
+
+        dat = self.call_duplex_read_mod_probs(duplex_read)
+        md = self.model_metadata
+        t_mm, t_ml = format_mm_ml_tags(seq=dat["read_sequence"], poss=dat["template_positions"], probs=dat["template_probs"],
+                                       mod_bases=md["mod_bases"], can_base=md["can_base"], strand="+")
+        c_mm, c_ml = format_mm_ml_tags(seq=dat["read_sequence"], poss=dat["complement_positions"], probs=dat["complement_probs"],
+                                       mod_bases=md["mod_bases"], can_base=revcomp(md["can_base"]), strand="-")
+        return f"MM:Z:{t_mm + c_mm}", "ML:B:C," + ",".join(str(x) for x in t_ml + c_ml)
+
+
+def check_simplex_alignments(*, simplex_index, duplex_index, pairs):
+    """The pairs that have all their parts: both ids in the simplex BAM, the template id in the duplex BAM
+    (src/remora/inference.py:802-838) -> (valid pairs, their number)."""
+    import logging
+    from itertools import chain
+
+    log = logging.getLogger("Remora")
+    if len(pairs) == 0:
+        raise ValueError("no pairs found in file")
+    simplex_read_ids, duplex_read_ids = set(simplex_index.read_ids), set(duplex_index.read_ids)
+    n_simplex = len(set(chain(*pairs)).intersection(simplex_read_ids))
+    log.debug(f"Found {n_simplex} simplex simplex alignments in a pair out of {len(simplex_read_ids)} total simplex reads.")
+    if n_simplex == 0:
+        raise ValueError("zero simplex alignments found")
+    valid = [(t, c) for t, c in pairs if t in simplex_read_ids and c in simplex_read_ids and t in duplex_read_ids]
+    log.debug(f"Found {len(valid)} valid reads out of {len(pairs)} total pairs")
+    return valid, len(valid)
+
+
+def _duplex_batch_records(pairs, builder, duplex_index, model, model_metadata, errs):
+    """One batch of pairs -> the bytes of their output records, in the order of `pairs`: both reads of every pair gathered, ONE
+    alignment call for the 2 B alignments, ONE call_reads_mods for the 2 B re-anchored reads, the tags of each strand
+    formatted for the batch, the records rewritten in one call.  Failed pairs are tallied in `errs` by reason."""
+    from . import io as rio
+    from .util import format_mm_ml_tags_batch
+
+    engine = getattr(model, "engine", None)
+    items = []
+    for (t_id, _), (reads, err) in zip(pairs, builder.make_read_pairs(pairs, engine)):
+        if err is None and t_id not in duplex_index:
+            err = "duplex BAM record not found for read_id"
+        if err is not None:
+            errs[err] += 1
+            continue
+        # (only the first duplex record of a template id is used, as in the reference)
+        items.append((reads[0], reads[1], next(duplex_index.get_alignments(t_id, want_ref=False))))
+    duplex_reads, remora_reads = [], []
+    for dr, err in rio.duplex_reads_batch(items, engine):
+        if err is None:
+            try:
+                two = [dr.template_read.into_remora_read(False), dr.complement_read.into_remora_read(False)]
+            except RemoraError as e:
+                err = str(e)
+        if err is not None:
+            errs[err] += 1
+            continue
+        duplex_reads.append(dr)
+        remora_reads.extend(two)
+    if not duplex_reads:
+        return b""
+    results = call_reads_mods(remora_reads, model, model_metadata, return_mod_probs=True)
+    dats = [_duplex_read_mod_probs(dr, results[2 * k], results[2 * k + 1]) for k, dr in enumerate(duplex_reads)]
+    n, n_mods = len(dats), len(model_metadata["mod_bases"])
+    seqs = [d["read_sequence"].encode() for d in dats]
+    seq_off = np.zeros(n + 1, np.int64)
+    np.cumsum([len(s) for s in seqs], out=seq_off[1:])
+    seq_bytes = b"".join(seqs)
+    strands = []
+    for key, can_base, strand in (("template", model_metadata["can_base"], "+"), ("complement", rio.revcomp(model_metadata["can_base"]), "-")):
+        pos = [np.asarray(d[f"{key}_positions"], np.int64) for d in dats]
+        call_off = np.zeros(n + 1, np.int64)
+        np.cumsum([p.size for p in pos], out=call_off[1:])
+        probs = [np.asarray(d[f"{key}_probs"], np.float64).reshape(-1, n_mods) for d in dats]
+        strands.append(format_mm_ml_tags_batch(seq_bytes, seq_off, np.concatenate(pos), np.concatenate(probs), call_off,
+                                               model_metadata["mod_bases"], can_base, strand=strand))
+    # per record: the template strand's tag bytes, then the complement strand's
+    joined = []
+    for col in (0, 2):
+        parts = [(np.asarray(s[col], np.uint8), np.asarray(s[col + 1], np.int64)) for s in strands]
+        off = np.zeros(n + 1, np.int64)
+        np.cumsum(sum(np.diff(o) for _, o in parts), out=off[1:])
+        buf = b"".join(b[o[k]:o[k + 1]].tobytes() for k in range(n) for b, o in parts)
+        joined += [np.frombuffer(buf + b"\0", np.uint8), off]
+    return rio.records_with_mod_tags_batch([dr.record for dr in duplex_reads], *joined, np.ones(n, np.uint8))
+
+
+def infer_duplex(*, simplex_pod5_path, simplex_bam_path, duplex_bam_path, pairs_path, model, model_metadata, out_bam,
+                 num_extract_alignment_threads=1, num_duplex_prep_workers=1, num_infer_threads=1, num_reads=None, skip_non_primary=True,
+                 duplex_deliminator=";", reads_per_batch=64, bam_level=None):
+    """`remora infer duplex_from_pod5_and_bam` (src/remora/inference.py:894-1010): for every valid pair of the pairs file the
+    first duplex record of its template id is written to `out_bam` with the MM / ML tags of both strands (existing MM* / ML* tags
+    dropped), in the order of the pairs file (the reference's order depends on its worker queues).  The three worker counts are
+    accepted and ignored: the pairs go through the GPU in batches of `reads_per_batch`.  Returns {reason: failed pairs}."""
+    import logging
+    import sys
+    from collections import defaultdict
+
+    from . import io as rio
+
+    log = logging.getLogger("Remora")
+    log.info("Indexing Duplex BAM")
+    duplex_index = rio.ReadIndexedBam(duplex_bam_path, skip_non_primary=skip_non_primary, req_tags=set(),
+                                      read_id_converter=lambda k: k.split(duplex_deliminator)[0])
+    if duplex_index.num_records == 0:
+        log.info("No records found in duplex BAM file.")
+        sys.exit()
+    log.info("Indexing Simplex BAM")
+    simplex_index = rio.ReadIndexedBam(simplex_bam_path, skip_non_primary=True, req_tags={"mv"})
+    if simplex_index.num_records == 0:
+        log.info("No records found in simplex BAM file.")
+        sys.exit()
+    with open(pairs_path, "r") as fh:
+        pairs = [tuple(line.split()) for line in fh]
+    valid_pairs, num_valid = check_simplex_alignments(simplex_index=simplex_index, duplex_index=duplex_index, pairs=pairs)
+    valid_pairs = valid_pairs[:num_valid if num_reads is None else min(num_valid, num_reads)]
+    errs = defaultdict(int)
+    step = max(int(reads_per_batch), 1)
+    try:
+        with rio.DuplexPairsBuilder(simplex_index, simplex_pod5_path) as builder, \
+                rio.BamWriter(out_bam, rio.read_bam_header_bytes(duplex_bam_path), level=bam_level) as writer:
+            for k in range(0, len(valid_pairs), step):
+                rec_bytes = _duplex_batch_records(valid_pairs[k:k + step], builder, duplex_index, model, model_metadata, errs)
+                if rec_bytes:
+                    writer.write(rec_bytes)
+    finally:
+        duplex_index.close()
+    if errs:
+        err_types = sorted([(num, err) for err, num in errs.items()])[::-1]
+        log.info("Unsuccessful read reasons:\n" + "\n".join(f"{num:>7} : {err:<80}" for num, err in err_types))
+    return dict(errs)

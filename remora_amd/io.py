@@ -1619,6 +1619,42 @@ class Read:
         """Shallow copy with its own attribute set (arrays are shared, add_alignment rebinds them)."""
         return dataclasses.replace(self)
 
+    @classmethod
+    def from_pod5_and_alignment(cls, pod5_read_record, alignment_record, reverse_signal=False, pa_scaling=None):
+        """A read from its POD5 record and its BAM record (src/remora/io.py:2086-2121)."""
+        read = cls.from_pod5(pod5_read_record, reverse_signal=reverse_signal, infer_convention=False)
+        read.add_alignment(alignment_record, reverse_signal=reverse_signal, pa_scaling=pa_scaling)
+        return read
+
+    def check_duplex_alignment(self, duplex_read_alignment):
+        """The three refusals of with_duplex_alignment (src/remora/io.py:1935-1940)."""
+        if self.query_to_signal is None:
+            raise RemoraError("requires query_to_signal")
+        if duplex_read_alignment.query_sequence is None:
+            raise RemoraError("no duplex base call sequence?")
+        if len(duplex_read_alignment.query_sequence) <= 0:
+            raise RemoraError("duplex base call sequence is empty string?")
+
+    def with_duplex_alignment(self, duplex_read_alignment, duplex_orientation, simplex_duplex_mapping=None):
+        """(copy of the read re-anchored on the duplex sequence, offset of the trimmed duplex sequence in it)
+        (src/remora/io.py:1926-1970): the simplex basecalls are aligned to the duplex record's sequence (`duplex_orientation`)
+        or to its reverse complement, the read takes the trimmed duplex sequence, and each of its bases the signal position
+        of the simplex base it aligns to.  `simplex_duplex_mapping`: the alignment's result when a batch call has made it
+        already (duplex_utils.map_simplexes_to_duplexes); otherwise the alignment runs here, as a batch of one."""
+        from . import data_chunks, duplex_utils
+
+        self.check_duplex_alignment(duplex_read_alignment)
+        read = self.copy()
+        if simplex_duplex_mapping is None:
+            seq = duplex_read_alignment.query_sequence
+            simplex_duplex_mapping = duplex_utils.map_simplex_to_duplex(
+                simplex_seq=read.seq, duplex_seq=seq if duplex_orientation else revcomp(seq))
+        read.query_to_signal = data_chunks.map_ref_to_signal(
+            query_to_signal=read.query_to_signal, ref_to_query_knots=simplex_duplex_mapping.duplex_to_simplex_mapping)
+        read.seq = simplex_duplex_mapping.trimmed_duplex_seq
+        read.ref_seq = read.ref_to_signal = read.ref_reg = None
+        return read, simplex_duplex_mapping.duplex_offset
+
     def get_filtered_focus_positions(self, select_focus_positions):
         """Read-oriented offsets into the reference sequence of this alignment for the positions of
         `select_focus_positions` (as from parse_bed) that the alignment covers (src/remora/io.py:2215-2247)."""
@@ -2568,6 +2604,125 @@ def concat_bam_parts(out_path, part_paths, remove=True):
         for p in part_paths:
             os.remove(p)
     return how
+
+
+# ---- duplex reads (src/remora/io.py:2487-2599) ----
+@dataclasses.dataclass
+class DuplexRead:
+    """The two simplex reads of a duplex pair, each re-anchored on the duplex basecalls (its own strand of them).  On a
+    reverse-mapped duplex record the stored sequence is the complement strand's: `template_read` is then the read in that
+    orientation (the pair's complement read), as in the reference."""
+
+    duplex_read_id: str
+    duplex_alignment: dict
+    is_reverse_mapped: bool
+    template_read: Read
+    complement_read: Read
+    template_ref_start: int
+    complement_ref_start: int
+    record: object = None  # the duplex BamRecord (for output)
+
+    @staticmethod
+    def alignment_pairs(*, template_read, complement_read, duplex_alignment):
+        """The two (simplex_seq, duplex_seq) alignments from_reads_and_alignment needs, in the order it takes their results."""
+        first, second = (complement_read, template_read) if duplex_alignment.is_reverse else (template_read, complement_read)
+        for r in (first, second):
+            r.check_duplex_alignment(duplex_alignment)
+        seq = duplex_alignment.query_sequence
+        return [(first.seq, seq), (second.seq, revcomp(seq))]
+
+    @classmethod
+    def from_reads_and_alignment(cls, *, template_read, complement_read, duplex_alignment, mappings=None):
+        """`mappings`: the results of alignment_pairs' two alignments where a batch call has made them."""
+        is_reverse_mapped = duplex_alignment.is_reverse
+        duplex_direction_read, reverse_complement_read = (
+            (complement_read, template_read) if is_reverse_mapped else (template_read, complement_read))
+        m0, m1 = mappings if mappings is not None else (None, None)
+        template_read, template_ref_start = duplex_direction_read.with_duplex_alignment(duplex_alignment, True, m0)
+        complement_read, complement_ref_start = reverse_complement_read.with_duplex_alignment(duplex_alignment, False, m1)
+        return cls(duplex_read_id=duplex_alignment.query_name, duplex_alignment=duplex_alignment.to_dict(),
+                   is_reverse_mapped=is_reverse_mapped, template_read=template_read, complement_read=complement_read,
+                   template_ref_start=template_ref_start, complement_ref_start=complement_ref_start, record=duplex_alignment)
+
+    @property
+    def duplex_basecalled_sequence(self):
+        return self.duplex_alignment["seq"]  # as stored: reverse-complemented on a reverse mapping
+
+
+def duplex_reads_batch(items, engine=None, trace_budget=None):
+    """DuplexRead.from_reads_and_alignment for a batch with ONE alignment call: items = [(template_read, complement_read,
+    duplex record)] -> [(DuplexRead | None, error text | None)]."""
+    from . import duplex_utils
+
+    pairs, first, errs = [], [], []
+    for t, c, rec in items:
+        try:
+            two = DuplexRead.alignment_pairs(template_read=t, complement_read=c, duplex_alignment=rec)
+            first.append(len(pairs))
+            pairs.extend(two)
+            errs.append(None)
+        except RemoraError as e:
+            first.append(-1)
+            errs.append(str(e))
+    maps = duplex_utils.map_simplexes_to_duplexes(pairs, engine, trace_budget) if pairs else []
+    out = []
+    for (t, c, rec), k, err in zip(items, first, errs):
+        if err is None:
+            err = next((m for m in maps[k:k + 2] if isinstance(m, str)), None)
+        if err is not None:
+            out.append((None, err))
+            continue
+        out.append((DuplexRead.from_reads_and_alignment(template_read=t, complement_read=c, duplex_alignment=rec,
+                                                        mappings=maps[k:k + 2]), None))
+    return out
+
+
+class DuplexPairsBuilder:
+    """Both simplex reads of a duplex pair from the POD5 file and the simplex BAM index (src/remora/io.py:2544-2599)."""
+
+    def __init__(self, simplex_index, pod5_path):
+        from collections import Counter
+
+        self.simplex_index = simplex_index
+        self.pod5_path = pod5_path
+        self.reader = Pod5File(pod5_path)
+        self._repeated = {rid for rid, k in Counter(self.reader.read_ids).items() if k > 1}
+
+    def make_read_pairs(self, read_id_pairs, engine=None):
+        """make_read_pair for several pairs with the signals decoded in one GPU call: [((template, complement) | None, error)]."""
+        out, want = [], []
+        for k, pair in enumerate(read_id_pairs):
+            err = None
+            if any(rid not in self.reader for rid in pair):
+                err = "duplex pair read id(s) missing from pod5"
+            elif any(rid in self._repeated for rid in pair):
+                err = "pod5 has multiple reads with the same id"
+            else:
+                try:
+                    aligns = [self.simplex_index.get_first_alignment(rid) for rid in pair]
+                    want.append((k, aligns))
+                except RemoraError:
+                    err = "failed to find read in simplex bam"
+            out.append((None, err))
+        signals = self.reader.get_many([rid for k, _ in want for rid in read_id_pairs[k]], engine) if want else []
+        for w, (k, aligns) in enumerate(want):
+            try:
+                out[k] = (tuple(Read.from_pod5_and_alignment(signals[2 * w + x], aligns[x]) for x in (0, 1)), None)
+            except RemoraError as e:
+                out[k] = (None, str(e))
+        return out
+
+    def make_read_pair(self, read_id_pair):
+        return self.make_read_pairs([tuple(read_id_pair)])[0]
+
+    def close(self):
+        self.simplex_index.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc_val, exc_tb):
+        self.close()
 
 
 # ---- the region API (src/remora/io.py:579-922): remora_amd/region_metrics.py, under the reference's names ----
