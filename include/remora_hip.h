@@ -133,7 +133,9 @@ int rmr_model_pad_weights(const rmr_model_desc *desc, const float *weights, size
  * if every logit of both runs is finite and the two differ by at most `tol` (default 2e-5).  Every forward entry of the
  * model (rmr_forward, rmr_infer_chunks, rmr_call_read) follows the decision; RMR_WINOGRAD=0 still selects the direct form
  * per call.  A screen on 256 chunks, not a proof.  Models without a Winograd layer (the 16-bit and split dtypes, sizes
- * other than 64) are not screened: checked = 0, winograd = 0.
+ * other than 64) are not screened: checked = 0, winograd = 0.  The probe is handed over as chunk arrays; a k-mer length
+ * above 21, which rmr_infer_chunks refuses, takes the same batch as a one-hot tensor through rmr_forward's path, and a model
+ * that neither entry runs (the one-hot tensor of one chunk beyond the LDS) is not screened.
  * replaces: nothing (torch.nn.Conv1d has one form; the layers concerned are models/ConvLSTM_w_ref.py:36-37,50 and
  *           models/Conv_w_ref.py:35-38,54-55). */
 typedef struct rmr_model_numerics {

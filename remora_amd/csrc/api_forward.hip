@@ -267,6 +267,7 @@ int pipeline_fp32(rmr_model *m, const ChunkArrays &in, int64_t n, float *logits,
 // in.enc != nullptr: dense seqs path; otherwise gather path from (seqs, maps, lens)
 int run_pipeline(rmr_model *m, const ChunkArrays &in, int64_t n, float *logits) {
     if (n <= 0) return 0;
+    if (in.enc) RMR_TRY(check_seq1_dense(m));  // before the signal branch is launched
     // the switches of every kernel choice below, read once per call
     const FwdSwitches sw{tune_int("RMR_FUSED", 1) != 0, tune_int("RMR_CONV_FRONT", 1) != 0,
                          tune_int("RMR_WINOGRAD", 1) != 0 && m->use_winograd, tune_int("RMR_SIG3_MFMA", 1) != 0};
@@ -314,6 +315,11 @@ static int model_probe_winograd(rmr_model *m, float tol) {
     const int K = m->desc.kmer_len, kb = (K - 1) / 2, ka = K - 1 - kb, L = m->L, no = m->desc.num_out;
     const int max_len = probe_max_len(L);
     if (!model_takes_winograd(m, kb, ka, max_len + kb + ka, max_len + 1, PROBE_CHUNKS)) return 0;
+    // the entry the probe goes through: the chunk arrays where launch_front takes the model's k-mer length, else the same batch
+    // as a one-hot tensor through the dense entry; a model that neither entry runs (every forward call of it is refused by name)
+    // has no form to choose and is handed out unchecked
+    const bool dense = !front_seq_supported(m, max_len + kb + ka, max_len + 1);
+    if (dense && !seq1_dense_supported(m)) return 0;
     // the batch is generated once per geometry and kept as ONE host blob in the layout of the staging slots below: one upload
     struct Packed { ProbeBatch pb; std::vector<char> blob; };
     static std::mutex cache_mu;
@@ -344,9 +350,14 @@ static int model_probe_winograd(rmr_model *m, float tol) {
     st.add(&dsig, pb.signal.size()).add(&ds, pb.seqs.size()).add(&dm, pb.maps.size()).add(&dl, pb.lens.size());
     if (st.total != pk->blob.size()) RMR_FAIL(RMR_ERR_INVALID, "internal: probe blob of %zu bytes, slots of %zu", pk->blob.size(), st.total);
     st.add(&dw, (size_t)n * no).add(&dd, (size_t)n * no).add(&dred, 2);
+    float *denc = nullptr;
+    const std::vector<float> enc = dense ? probe_one_hot(pb) : std::vector<float>();  // (alive until the stream is synchronised below)
+    st.add(&denc, enc.size());
     RMR_TRY(st.commit(e));
     H2D(dsig, pk->blob.data(), pk->blob.size());
-    const ChunkArrays in{dsig, nullptr, ds, pb.seq_w, dm, pb.map_w, dl, kb, ka};
+    H2D(denc, enc.data(), enc.size() * sizeof(float));
+    const ChunkArrays in = dense ? ChunkArrays{dsig, denc, nullptr, 0, nullptr, 0, nullptr, 0, 0}
+                                 : ChunkArrays{dsig, nullptr, ds, pb.seq_w, dm, pb.map_w, dl, kb, ka};
     const bool profiling = e->profiling;
     const int64_t subbatch = e->subbatch;
     e->profiling = false;

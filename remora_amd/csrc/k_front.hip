@@ -15,6 +15,7 @@
 // Outputs are channel-last: sig2 f32[n][P2][16], seq1 f32[n][P1][16].
 #include "rmr_internal.h"
 #include "rmr_math.h"
+#include "rmr_plan.h"
 
 namespace rmr {
 
@@ -356,6 +357,15 @@ __global__ __launch_bounds__(512, 4) void front_seq_tap_kernel(FrontSeqArgs a) {
     }
 }
 
+// whether launch_front runs seq_conv1 of this model from chunk arrays of these widths: a window's bases, three bits each, fit one
+// 64-bit word up to FRONT_MAX_KMER, and one chunk's carve fits the CU's LDS
+constexpr int FRONT_MAX_KMER = 21;
+bool front_seq_supported(const rmr_model *m, int seq_w, int map_w) {
+    const int K = m->desc.kmer_len, kw = m->front.kw1;
+    if ((kw != 5 && kw != 11) || K > FRONT_MAX_KMER || map_w < 1 || seq_w < map_w - 1 + K - 1) return false;
+    return plan_front_seq(kw, K, m->L, m->P1, seq_w, map_w).ok;
+}
+
 int launch_front(rmr_model *m, hipStream_t st, const ChunkArrays &c, int64_t n, float *sig2, float *seq1) {
     rmr_engine *e = m->eng;
     if (n <= 0) return 0;
@@ -363,6 +373,15 @@ int launch_front(rmr_model *m, hipStream_t st, const ChunkArrays &c, int64_t n, 
     const int K = m->desc.kmer_len;
     const int kw = m->front.kw1;
     if (kw != 5 && kw != 11) RMR_FAIL(RMR_ERR_INVALID, "front kernel width %d unsupported", kw);
+    // what the sequence branch refuses, it refuses before the signal branch is launched: gather table + per-chunk LDS carve (rmr_plan.h)
+    SeqFrontPlan p;
+    if (seq1) {
+        if (kb + ka + 1 != K) RMR_FAIL(RMR_ERR_INVALID, "kmer context (%d,%d) != model kmer_len %d", kb, ka, K);
+        if (K > FRONT_MAX_KMER) RMR_FAIL(RMR_ERR_INVALID, "kmer_len %d > %d not supported by the fused encode", K, FRONT_MAX_KMER);
+        if (seq_w < map_w - 1 + K - 1) RMR_FAIL(RMR_ERR_INVALID, "sequence width %d too small for mapping width %d", seq_w, map_w);
+        p = plan_front_seq(kw, K, m->L, m->P1, seq_w, map_w);
+        if (!p.ok) RMR_FAIL(RMR_ERR_INVALID, "front_seq: max_seq_len %d needs %zu B of LDS", map_w - 1, p.lds);
+    }
     if (sig2) {   // ---- signal branch (skipped when the caller folds it into sig_conv3: launch_sig3_front_mfma) ----
         FrontSigArgs a;
         a.signal = c.signal; a.w_sig1 = m->front.w_sig1; a.b_sig1 = m->front.b_sig1;
@@ -379,54 +398,28 @@ int launch_front(rmr_model *m, hipStream_t st, const ChunkArrays &c, int64_t n, 
         RMR_HIP(hipGetLastError());
     }
     if (!seq1) return 0;
-    if (kb + ka + 1 != K) RMR_FAIL(RMR_ERR_INVALID, "kmer context (%d,%d) != model kmer_len %d", kb, ka, K);
-    if (K > 21) RMR_FAIL(RMR_ERR_INVALID, "kmer_len %d > 21 not supported by the fused encode", K);
     FrontSeqArgs a;
     a.seqs = c.seqs; a.maps = c.maps; a.lens = c.lens; a.wt5 = m->front.wt5_seq1; a.b_seq1 = m->front.b_seq1;
     a.seq1 = seq1; a.n = n; a.L = m->L; a.seq_w = seq_w; a.map_w = map_w; a.K = K; a.P1 = m->P1;
     a.maxlen = map_w - 1;
-    if (seq_w < a.maxlen + K - 1) RMR_FAIL(RMR_ERR_INVALID, "sequence width %d too small for mapping width %d", seq_w, map_w);
-    // per-chunk LDS carve in 4-byte words, every region 16-byte aligned
-    auto up4 = [](int words) { return (words + 3) & ~3; };
-    int off = 0;
-    a.o_map = off; off += up4((map_w * 2 + 3) / 4);
-    a.o_seq = off; off += up4((seq_w + 3) / 4);
-    a.o_code = off; off += up4(a.maxlen * 2);
-    a.o_pidx = off; off += up4((m->L * 2 + 3) / 4);
+    a.o_map = p.o_map; a.o_seq = p.o_seq; a.o_code = p.o_code; a.o_pidx = p.o_pidx; a.o_u = p.o_u; a.per_chunk = p.per_chunk;
+    const size_t lds = p.lds;
     // Conv_w_ref's released shape (11 taps, k-mer length 9): the tap-by-tap two-level kernel, one wave per chunk
-    if (kw == 11 && K == 9 && m->P1 * 4 <= 64 * 6 && a.maxlen <= 1024) {
-        int off = 0;
-        a.o_map = off; off += up4((map_w * 2 + 3) / 4);
-        a.o_seq = off; off += up4((seq_w + 3) / 4);
-        a.o_code = off; off += up4(a.maxlen);
-        a.o_pidx = off; off += up4((m->L * 2 + 3) / 4);
-        a.o_u = off; off += (a.maxlen + 1) * 16;
-        a.per_chunk = up4(off);
+    if (p.tap) {
         a.cb = 1;
-        const int waves = 8;
-        const size_t lds = ((size_t)kw * K * 80 + (size_t)waves * a.per_chunk) * 4;
-        if (lds <= 80 * 1024) {  // two blocks (16 waves) per CU; longer rows fall through to the forms below
-            auto kern = front_seq_tap_kernel<11, 9>;
-            RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(kern)));
-            int64_t grid = (int64_t)e->num_cus * 4;
-            const int64_t need = (n + waves - 1) / waves;
-            if (grid > need) grid = need;
-            ProfScope ps(e, K_FRONT_SEQ, st, true);
-            hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * waves), lds, st, a);
-            RMR_HIP(hipGetLastError());
-            return 0;
-        }
+        const int waves = p.cb;
+        auto kern = front_seq_tap_kernel<11, 9>;
+        RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(kern)));
+        int64_t grid = (int64_t)e->num_cus * 4;
+        const int64_t need = (n + waves - 1) / waves;
+        if (grid > need) grid = need;
+        ProfScope ps(e, K_FRONT_SEQ, st, true);
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * waves), lds, st, a);
+        RMR_HIP(hipGetLastError());
+        return 0;
     }
-    const bool direct = kw == 11;
-    a.o_u = off; if (!direct) off += (a.maxlen + 1) * kw * 16;
-    a.per_chunk = up4(off);
-    const size_t fixed = (size_t)kw * K * 80 * 4;
-    int cb = 8;
-    const size_t lds_cap = (size_t)78 * 1024;
-    while (cb > 1 && fixed + (size_t)cb * a.per_chunk * 4 > lds_cap) cb >>= 1;
-    const size_t lds = fixed + (size_t)cb * a.per_chunk * 4;
-    if (lds > 160 * 1024) RMR_FAIL(RMR_ERR_INVALID, "front_seq: max_seq_len %d needs %zu B of LDS", a.maxlen, lds);
-    a.cb = cb;
+    const bool direct = p.direct;
+    const int cb = a.cb = p.cb;
     auto kern = (kw == 5) ? front_seq_kernel<5, false> : front_seq_kernel<11, true>;
     RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(kern)));
     const int64_t iters = (n + cb - 1) / cb;
@@ -479,6 +472,17 @@ __global__ __launch_bounds__(256) void seq1_dense_kernel(DenseArgs a) {
     }
 }
 
+// dynamic LDS of seq1_dense_kernel: the weights [kw][EC][16] and one chunk's tensor [EC][L]
+static size_t seq1_dense_lds(const rmr_model *m) {
+    const size_t EC = 4 * (size_t)m->desc.kmer_len;
+    return ((size_t)m->front.kw1 * EC * 16 + EC * m->L) * 4;
+}
+bool seq1_dense_supported(const rmr_model *m) { return seq1_dense_lds(m) <= 160 * 1024; }
+int check_seq1_dense(const rmr_model *m) {
+    if (!seq1_dense_supported(m)) RMR_FAIL(RMR_ERR_INVALID, "dense seq_conv1 needs %zu B LDS", seq1_dense_lds(m));
+    return 0;
+}
+
 int launch_seq1_dense(rmr_model *m, const float *enc, int64_t n, float *seq1) {
     rmr_engine *e = m->eng;
     if (n <= 0) return 0;
@@ -486,8 +490,8 @@ int launch_seq1_dense(rmr_model *m, const float *enc, int64_t n, float *seq1) {
     a.enc = enc; a.wd = m->front.wt_seq1; a.bias = m->front.b_seq1; a.seq1 = seq1; a.n = n;
     a.EC = 4 * m->desc.kmer_len; a.L = m->L; a.P1 = m->P1; a.kw = m->front.kw1;
     // wt_seq1 layout [kw][K][4][16] == [kw][EC][16] with ic = 4*kp + base: same table
-    const size_t lds = ((size_t)a.kw * a.EC * 16 + (size_t)a.EC * a.L) * 4;
-    if (lds > 160 * 1024) RMR_FAIL(RMR_ERR_INVALID, "dense seq_conv1 needs %zu B LDS", lds);
+    const size_t lds = seq1_dense_lds(m);
+    RMR_TRY(check_seq1_dense(m));
     RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(seq1_dense_kernel)));
     int64_t grid = (int64_t)e->num_cus * 2;
     if (grid > n) grid = n;

@@ -238,6 +238,10 @@ struct ChunkArrays {
 // fused pipeline stages; all tensors channel-last in device scratch
 int launch_front(rmr_model *m, hipStream_t st, const ChunkArrays &c, int64_t n, float *sig2, float *seq1 /* nullptr: skip seq path */);
 int launch_seq1_dense(rmr_model *m, const float *enc, int64_t n, float *seq1);
+// whether the two entries run seq_conv1 of this model at all (what they refuse, they refuse by name before any launch)
+bool front_seq_supported(const rmr_model *m, int seq_w, int map_w);
+bool seq1_dense_supported(const rmr_model *m);
+int check_seq1_dense(const rmr_model *m);  // the dense entry's refusal, by name
 // the kernel switches of the fp32 path: read from the environment once per forward call (run_pipeline, api_forward.hip) and passed
 // down, so that a change between two calls on the same model takes effect
 struct FwdSwitches {

@@ -231,4 +231,54 @@ inline FrontPlan plan_seq2_front(int L, int P1, int P3, int K, int seq_w, int ma
     return p;
 }
 
+// ---- seq_conv1 alone from the chunk arrays (k_front.hip, launch_front): the gather table of kw x K x 5 rows, then a private
+// carve per chunk - mapping row, sequence row, window codes, base-of-position row and (two-level forms) the per-base table U ----
+struct SeqFrontPlan {
+    bool ok = false;
+    bool tap = false;     // front_seq_tap_kernel<11, 9>: one wave per chunk, `cb` waves per block
+    bool direct = false;  // front_seq_kernel<11, true>: no U table
+    int cb = 0;           // chunks per block (32 threads each; tap: 64)
+    int o_map = 0, o_seq = 0, o_code = 0, o_pidx = 0, o_u = 0, per_chunk = 0;  // in 4-byte words, every region 16-byte aligned
+    size_t fixed = 0;     // bytes of the gather table in front of the chunks' carves
+    size_t lds = 0;       // dynamic LDS bytes
+};
+
+inline SeqFrontPlan plan_front_seq(int kw, int K, int L, int P1, int seq_w, int map_w) {
+    SeqFrontPlan p;
+    const int maxlen = map_w - 1;
+    p.fixed = (size_t)kw * K * 80 * 4;
+    // Conv_w_ref's released shape (11 taps, k-mer length 9): the tap-by-tap two-level kernel, one wave per chunk, 32-bit window
+    // codes and one tap's U rows; two blocks (16 waves) per CU, longer rows go on to the forms below
+    if (kw == 11 && K == 9 && P1 * 4 <= 64 * 6 && maxlen <= 1024) {
+        int off = 0;
+        p.o_map = off; off += up4((map_w * 2 + 3) / 4);
+        p.o_seq = off; off += up4((seq_w + 3) / 4);
+        p.o_code = off; off += up4(maxlen);
+        p.o_pidx = off; off += up4((L * 2 + 3) / 4);
+        p.o_u = off; off += (maxlen + 1) * 16;
+        p.per_chunk = up4(off);
+        p.cb = 8;
+        p.lds = p.fixed + (size_t)p.cb * p.per_chunk * 4;
+        if (p.lds <= 80 * 1024) {
+            p.tap = p.ok = true;
+            return p;
+        }
+    }
+    p.direct = kw == 11;
+    int off = 0;
+    p.o_map = off; off += up4((map_w * 2 + 3) / 4);
+    p.o_seq = off; off += up4((seq_w + 3) / 4);
+    p.o_code = off; off += up4(maxlen * 2);
+    p.o_pidx = off; off += up4((L * 2 + 3) / 4);
+    p.o_u = off; if (!p.direct) off += (maxlen + 1) * kw * 16;
+    p.per_chunk = up4(off);
+    // eight chunks per block, halved until the block fits 78 KB (two blocks per CU); one chunk may take the CU's 160 KB
+    const size_t lds_cap = (size_t)78 * 1024;
+    p.cb = 8;
+    while (p.cb > 1 && p.fixed + (size_t)p.cb * p.per_chunk * 4 > lds_cap) p.cb >>= 1;
+    p.lds = p.fixed + (size_t)p.cb * p.per_chunk * 4;
+    p.ok = p.lds <= PLAN_LDS_CU;
+    return p;
+}
+
 }  // namespace rmr

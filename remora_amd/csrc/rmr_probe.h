@@ -106,6 +106,26 @@ inline ProbeBatch make_probe_batch(int L, int kb, int ka) {
     return b;
 }
 
+// The probe batch as the one-hot tensor f32[n][4 K][L] that the dense entry takes (rmr_forward; the reference's
+// compute_encoded_kmer_batch): at every sample s of base p's [map[p], map[p + 1]) a 1.0 in row 4 kp + seqs[p + kp] for each of
+// the K = kb + ka + 1 slots kp; nothing for a base outside 0 .. 3 or a sample no base owns.
+inline std::vector<float> probe_one_hot(const ProbeBatch &b) {
+    const int K = b.kb + b.ka + 1;
+    std::vector<float> enc((size_t)b.n * 4 * K * b.L, 0.0f);
+    for (int i = 0; i < b.n; ++i) {
+        const int8_t *seq = &b.seqs[(size_t)i * b.seq_w];
+        const int16_t *map = &b.maps[(size_t)i * b.map_w];
+        float *e = &enc[(size_t)i * 4 * K * b.L];
+        for (int p = 0; p < b.lens[i]; ++p)
+            for (int kp = 0; kp < K; ++kp) {
+                const int base = seq[p + kp];
+                if (base < 0 || base > 3) continue;
+                for (int s = std::max<int>(map[p], 0); s < std::min<int>(map[p + 1], b.L); ++s) e[(size_t)(4 * kp + base) * b.L + s] = 1.0f;
+            }
+    }
+    return enc;
+}
+
 // FNV-1a over the bytes of an array (the digest tests/c/probe_batch.cpp prints)
 inline uint64_t fnv1a(const void *p, size_t bytes, uint64_t h = 0xCBF29CE484222325ull) {
     const unsigned char *c = static_cast<const unsigned char *>(p);

@@ -1,7 +1,8 @@
 // rmr_probe.h on the CPU (tests/test_host_winograd_guard.py): the probe batch of the Winograd guard at the (L, k-mer length)
 // given on the command line - every mapping row starts at 0, is non-decreasing and ends at L at index len, every length lies
 // within [1, probe_max_len(L)], every base is 0..3 in front of len + kb + ka and the padding value -1 behind it, the signal
-// stays within +-5 and the noise chunks have about unit variance.  Prints the FNV-1a digest of the four arrays.
+// stays within +-5 and the noise chunks have about unit variance; the one-hot tensor of the same batch (the probe of a k-mer
+// length the chunk-array entry refuses) is the arrays' encoding.  Prints the FNV-1a digest of the four arrays.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -47,6 +48,22 @@ int main(int argc, char **argv) {
     CHECK(shortest == 1 && longest == b.max_len);  // the two extremes of the geometry are among the structured chunks
     const double cnt = (double)PROBE_NOISE * L, mean = s1 / cnt, var = s2 / cnt - mean * mean;
     CHECK(std::fabs(mean) < 0.05 && std::fabs(var - 1.0) < 0.05);
+    // the same batch as the one-hot tensor of the dense entry (probe_one_hot, filled base by base): read sample by sample, the
+    // base p that owns sample s puts exactly one 1.0 into the four rows of every slot kp, in row seq[p + kp]
+    const std::vector<float> enc = probe_one_hot(b);
+    CHECK(enc.size() == (size_t)b.n * 4 * K * L);
+    for (int i = 0; i < b.n && enc.size() == (size_t)b.n * 4 * K * L; ++i) {
+        const int16_t *map = &b.maps[(size_t)i * b.map_w];
+        const int8_t *seq = &b.seqs[(size_t)i * b.seq_w];
+        const float *e = &enc[(size_t)i * 4 * K * L];
+        long wrong = 0;
+        for (int s = 0, p = 0; s < L; ++s) {
+            while (p < b.lens[i] && map[p + 1] <= s) ++p;
+            for (int kp = 0; kp < K; ++kp)
+                for (int base = 0; base < 4; ++base) wrong += e[(size_t)(4 * kp + base) * L + s] != (p < b.lens[i] && seq[p + kp] == base ? 1.0f : 0.0f);
+        }
+        CHECK(wrong == 0);
+    }
     uint64_t h = fnv1a(b.signal.data(), b.signal.size() * sizeof(float));
     h = fnv1a(b.seqs.data(), b.seqs.size(), h);
     h = fnv1a(b.maps.data(), b.maps.size() * sizeof(int16_t), h);

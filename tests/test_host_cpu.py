@@ -2823,7 +2823,9 @@ def test_front_plans_fit_their_budgets_and_pin_the_benchmark_shapes(tmp_path):
     """rmr_plan.h is the ONE place where the launch plans of the fp32 conv and front kernels are made (the support checks and the
     launchers of k_conv.hip / k_conv_front.hip call it).  tests/c/front_plans.cpp: over a sweep of chunk lengths, sequence
     widths, batch sizes, CU counts and register counts every plan stays within the LDS budget it was planned against and within
-    160 KB; the plans of ConvLSTM_w_ref size 64 at C100 / C200 (256 CUs, the kernels' gfx950 register counts) are pinned."""
+    160 KB; the plans of ConvLSTM_w_ref size 64 at C100 / C200 (256 CUs, the kernels' gfx950 register counts) are pinned.  The
+    11-tap signal front and launch_front's seq_conv1 carve (plan_front_seq) are checked at every chunk length Conv_w_ref admits,
+    95 ... 106: a plan exists, every LDS region starts on 16 bytes and ends inside the allocation."""
     import shutil
 
     gxx = shutil.which("g++")
@@ -2863,6 +2865,12 @@ def test_front_plans_fit_their_budgets_and_pin_the_benchmark_shapes(tmp_path):
         "C200/300 seq2_direct ok=1 wino=0 cb=1 plane=832 vplane=0 o_v=0 o_front=3344 per_chunk=3496 o_map=0 o_seq=24 o_code=36 o_pidx=116 o_u=216 lds=41760 grid=300",
         "C200/300 sig_conv3 ok=1 cb=1 nwin=1 pin=192 pout=62 plane=768 lds=12352 grid=300",
         "C200/300 seq_conv2 ok=1 cb=1 nwin=1 pin=196 pout=62 plane=832 lds=13376 grid=300",
+        # launch_front (k_front.hip) at L = 100: the first max_seq_len that runs fewer than eight chunks per block, which
+        # tests/test_gpu_kmer_lengths.py derives again in Python and runs
+        "front_seq kw=5 K=3 narrow_msl=27 cb=4 per_chunk=2372 lds=42752",
+        "front_seq kw=5 K=21 narrow_msl=16 cb=4 per_chunk=1468 lds=57088",
+        "front_seq kw=11 K=3 narrow_msl=767 cb=4 per_chunk=2168 lds=45248",
+        "front_seq kw=11 K=21 narrow_msl=45 cb=4 per_chunk=188 lds=76928",
     ]
 
 
