@@ -399,7 +399,7 @@ int rmr_modbam_site_fill(rmr_engine *e, const rmr_modbam_batch *b, const int32_t
 #define RMR_DUPLEX_OK 0
 #define RMR_DUPLEX_NO_MATCH 1      /* no match operation on the path */
 #define RMR_DUPLEX_BAD_BASE 2      /* a letter other than A C G T N (upper case) */
-#define RMR_DUPLEX_OVER_BUDGET 3   /* its own trace is larger than trace_budget */
+#define RMR_DUPLEX_OVER_BUDGET 3   /* its own trace (checkpointed: its lines and one strip of trace) is larger than trace_budget */
 #define RMR_DUPLEX_EMPTY 4         /* an empty sequence */
 #define RMR_DUPLEX_OUT_FIELDS 8
 /* Alignment a: query bases[q_off[a] .. + q_len[a]), ref bases[r_off[a] .. + r_len[a]) (ASCII).  The trace of an alignment takes
@@ -414,6 +414,26 @@ int rmr_modbam_site_fill(rmr_engine *e, const rmr_modbam_batch *b, const int32_t
 int rmr_duplex_align(rmr_engine *e, int64_t n, const uint8_t *bases, const int64_t *q_off, const int64_t *q_len, const int64_t *r_off,
                      const int64_t *r_len, int64_t trace_budget, int32_t *out, const int64_t *run_off, uint32_t *runs,
                      int64_t *n_groups);
+
+/* rmr_duplex_align with a choice of the memory the walk back is made from.  The alignments, their scores, the rule among
+ * co-optimal paths and every output are those of rmr_duplex_align in every mode, bit for bit.
+ *   RMR_DUPLEX_MODE_FULL        the 4-bit trace of every cell is stored: rmr_duplex_align itself (which is this call).
+ *   RMR_DUPLEX_MODE_CHECKPOINT  the forward pass keeps the DP line (r_len (H, F) pairs) above every strip of STRIP_ROWS query rows
+ *                               and no trace; the walk back recomputes the trace of one strip at a time, from the strip of the
+ *                               end row down, and only the columns at or left of where the walk stands.  An alignment takes
+ *                               ceil(q_len / STRIP_ROWS) * r_len * 8 + (r_len + 63) * 256 bytes (about 1/20 of its trace at 25 kb)
+ *                               and each cell is computed at most twice.  RMR_DUPLEX_OVER_BUDGET is given only to an alignment
+ *                               whose own checkpointed footprint exceeds trace_budget; the rest is sorted by footprint and
+ *                               grouped under the budget as the traces are, allocated for the call and freed before it returns.
+ *   RMR_DUPLEX_MODE_AUTO        FULL where no live alignment is over the budget with its trace and all traces fit it together
+ *                               (one group); otherwise the whole call runs CHECKPOINT.
+ * *n_checkpointed (may be NULL) receives the number of alignments that ran checkpointed (0 in FULL). */
+#define RMR_DUPLEX_MODE_FULL 0
+#define RMR_DUPLEX_MODE_CHECKPOINT 1
+#define RMR_DUPLEX_MODE_AUTO 2
+int rmr_duplex_align_mode(rmr_engine *e, int64_t n, const uint8_t *bases, const int64_t *q_off, const int64_t *q_len, const int64_t *r_off,
+                          const int64_t *r_len, int64_t trace_budget, int mode, int32_t *out, const int64_t *run_off, uint32_t *runs,
+                          int64_t *n_groups, int64_t *n_checkpointed);
 
 /* The signal coordinate of every reference position of one alignment (host code).
  * replaces: compute_ref_to_signal = map_ref_to_signal(make_sequence_coordinate_mapping(cigar)), src/remora/data_chunks.py:60-122

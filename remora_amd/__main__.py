@@ -331,7 +331,7 @@ def _infer_duplex(args):
                  pairs_path=args.duplex_read_pairs, model=model, model_metadata=md, out_bam=args.out_bam,
                  num_extract_alignment_threads=args.num_extract_alignment_workers, num_duplex_prep_workers=args.num_duplex_prep_workers,
                  num_infer_threads=args.num_infer_workers, num_reads=args.num_reads, duplex_deliminator=args.duplex_delim,
-                 reads_per_batch=args.reads_per_batch, bam_level=args.bam_level)
+                 reads_per_batch=args.reads_per_batch, bam_level=args.bam_level, trace_budget=int(args.duplex_trace_gib * (1 << 30)))
     log.info("Done")
     return 0
 
@@ -423,6 +423,9 @@ def build_parser():
     d.add_argument("--dtype", default=None, help="as for infer from_pod5_and_bam")
     d.add_argument("--bam-level", type=int, default=None, help="as for infer from_pod5_and_bam")
     d.add_argument("--reads-per-batch", type=int, default=64, help="duplex pairs per batch: two alignments and two model passes each")
+    d.add_argument("--duplex-trace-gib", type=float, default=16.0,
+                   help="GiB of GPU memory the simplex-to-duplex alignments of a batch may take at a time; a batch that does not fit "
+                        "with whole traces runs in checkpointed memory (same alignments, any read length)")
     d.set_defaults(func=_infer_duplex)
 
     val = sub.add_parser("validate").add_subparsers(dest="sub", required=True)

@@ -120,6 +120,8 @@ SIGNATURES = {
     "rmr_modbam_site_counts": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rmr_modbam_site_fill": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rmr_duplex_align": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64)]),
+    "rmr_duplex_align_mode": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64),
+                                      ctypes.POINTER(c_i64)]),
     "rmr_inflate_raw": (c_int, [c_vp, c_i64, c_vp, c_i64]),
     "rmr_bgzf_huffman": (c_int, [c_vp, c_i64, c_int, c_vp, c_i64, ctypes.POINTER(c_i64)]),
     "rmr_zstd_frame_sizes": (c_int, [c_vp, c_vp, c_i64, c_vp]),

@@ -277,6 +277,37 @@ int upload_reads(rmr_engine *e, const rmr_reads *r, int mem, bool need_dacs, con
     RMR_HIP(hipStreamSynchronize(e->stream));
     return 0;
 }
+
+// The groups of one rmr_duplex_align_mode call, in either mode: `bytes[k]` is what live[k] needs of the group's memory.  A job that
+// needs more than the budget alone is set aside (`over`); the rest is sorted, largest first, and cut into groups of consecutive jobs
+// that fit the budget together.  byte_off: a job's place in its group's memory; max_bytes: the largest group.
+struct DuplexPlan {
+    std::vector<DuplexJob> jobs;
+    std::vector<int64_t> byte_off;
+    std::vector<size_t> group_start;
+    std::vector<int32_t> over;  // out_idx
+    int64_t max_bytes = 0;
+};
+
+DuplexPlan plan_duplex_groups(const std::vector<DuplexJob> &live, const std::vector<int64_t> &bytes, int64_t budget) {
+    DuplexPlan p;
+    std::vector<size_t> order;
+    for (size_t k = 0; k < live.size(); ++k) {
+        if (bytes[k] > budget) p.over.push_back(live[k].out_idx);
+        else order.push_back(k);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return bytes[x] > bytes[y]; });
+    p.group_start.push_back(0);
+    int64_t used = 0;
+    for (size_t k : order) {
+        if (used > 0 && used + bytes[k] > budget) p.group_start.push_back(p.jobs.size()), used = 0;
+        p.jobs.push_back(live[k]), p.byte_off.push_back(used);
+        used += bytes[k];
+        p.max_bytes = std::max(p.max_bytes, used);
+    }
+    p.group_start.push_back(p.jobs.size());
+    return p;
+}
 }  // namespace
 
 extern "C" {
@@ -531,16 +562,25 @@ int rmr_modbam_site_fill(rmr_engine *e, const rmr_modbam_batch *b, const int32_t
 int rmr_duplex_align(rmr_engine *e, int64_t n, const uint8_t *bases, const int64_t *q_off, const int64_t *q_len, const int64_t *r_off,
                      const int64_t *r_len, int64_t trace_budget, int32_t *out, const int64_t *run_off, uint32_t *runs,
                      int64_t *n_groups) {
+    return rmr_duplex_align_mode(e, n, bases, q_off, q_len, r_off, r_len, trace_budget, RMR_DUPLEX_MODE_FULL, out, run_off, runs, n_groups,
+                                 nullptr);
+}
+
+int rmr_duplex_align_mode(rmr_engine *e, int64_t n, const uint8_t *bases, const int64_t *q_off, const int64_t *q_len, const int64_t *r_off,
+                          const int64_t *r_len, int64_t trace_budget, int mode, int32_t *out, const int64_t *run_off, uint32_t *runs,
+                          int64_t *n_groups, int64_t *n_checkpointed) {
     if (n_groups) *n_groups = 0;
+    if (n_checkpointed) *n_checkpointed = 0;
     if (!e || n < 0) RMR_FAIL(RMR_ERR_INVALID, "bad argument");
+    if (mode != RMR_DUPLEX_MODE_FULL && mode != RMR_DUPLEX_MODE_CHECKPOINT && mode != RMR_DUPLEX_MODE_AUTO)
+        RMR_FAIL(RMR_ERR_INVALID, "unknown duplex alignment mode %d", mode);
     if (n == 0) return 0;
     if (!bases || !q_off || !q_len || !r_off || !r_len || !out || !run_off || !runs) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
     if (n > INT32_MAX) RMR_FAIL(RMR_ERR_INVALID, "too many alignments");
     const int64_t budget = trace_budget > 0 ? trace_budget : RMR_DUPLEX_DEFAULT_TRACE_BYTES;
-    // what does not reach the GPU gets its status here; the rest is sorted by trace size, largest first
+    // what does not reach the GPU gets its status here
     std::vector<int32_t> hout((size_t)n * RMR_DUPLEX_OUT_FIELDS, 0);
-    std::vector<DuplexJob> jobs;
-    std::vector<int64_t> tdw((size_t)n, 0);  // trace dwords of alignment a
+    std::vector<DuplexJob> live;
     int64_t n_bases = 0;
     if (run_off[0] < 0) RMR_FAIL(RMR_ERR_INVALID, "run_off is negative");
     for (int64_t a = 0; a < n; ++a) {
@@ -564,35 +604,45 @@ int rmr_duplex_align(rmr_engine *e, int64_t n, const uint8_t *bases, const int64
             o[0] = RMR_DUPLEX_BAD_BASE;
             continue;
         }
-        // (lengths beyond 2^30 fit no budget; below them the product stays far inside int64)
-        const int64_t strips = (nq + RMR_DUPLEX_STRIP_ROWS - 1) / RMR_DUPLEX_STRIP_ROWS;
-        if (nq > (1 << 30) || nr > (1 << 30) || strips * (nr + 63) > budget / 256) {
+        if (nq > (1 << 30) || nr > (1 << 30)) {  // fits no budget; below 2^30 every product here stays far inside int64
             o[0] = RMR_DUPLEX_OVER_BUDGET;
             continue;
         }
-        tdw[(size_t)a] = strips * (nr + 63) * 64;
         DuplexJob j{};
         j.q_off = q_off[a], j.r_off = r_off[a], j.run_off = run_off[a];
         j.n = (int32_t)nq, j.m = (int32_t)nr, j.out_idx = (int32_t)a;
-        jobs.push_back(j);
+        live.push_back(j);
     }
+    // bytes of trace (FULL) or of lines and one strip of trace (CHECKPOINT) of a job: include/remora_hip.h
+    auto strips_of = [](const DuplexJob &j) { return ((int64_t)j.n + RMR_DUPLEX_STRIP_ROWS - 1) / RMR_DUPLEX_STRIP_ROWS; };
+    auto trace_bytes = [&](const DuplexJob &j) { return strips_of(j) * ((int64_t)j.m + 63) * 256; };
+    auto line_bytes = [&](const DuplexJob &j) { return strips_of(j) * (int64_t)j.m * 8; };
+    bool ckpt = mode == RMR_DUPLEX_MODE_CHECKPOINT;
+    if (mode == RMR_DUPLEX_MODE_AUTO) {  // FULL where that is one group with nothing over the budget
+        int64_t left = budget;
+        for (size_t k = 0; k < live.size() && !ckpt; ++k) ckpt = trace_bytes(live[k]) > left, left -= trace_bytes(live[k]);
+    }
+    std::vector<int64_t> bytes;
+    for (const DuplexJob &j : live) bytes.push_back(ckpt ? line_bytes(j) + ((int64_t)j.m + 63) * 256 : trace_bytes(j));
+    DuplexPlan plan = plan_duplex_groups(live, bytes, budget);
+    for (int32_t a : plan.over) hout[(size_t)a * RMR_DUPLEX_OUT_FIELDS] = RMR_DUPLEX_OVER_BUDGET;
+    std::vector<DuplexJob> &jobs = plan.jobs;
     if (jobs.empty()) {
         memcpy(out, hout.data(), hout.size() * 4);
         return 0;
     }
-    std::stable_sort(jobs.begin(), jobs.end(),
-                     [&](const DuplexJob &x, const DuplexJob &y) { return tdw[(size_t)x.out_idx] > tdw[(size_t)y.out_idx]; });
-    // groups of consecutive jobs whose traces fit the budget together; a job's offset inside its group's trace
-    std::vector<size_t> group_start{0};
-    int64_t used = 0, max_used = 0, line_total = 0;
+    // FULL: the group's memory is trace, the one line of every job lies in the staging arena.  CHECKPOINT: a job's share of the
+    // group's memory is its lines, then its strip of trace
+    int64_t line_total = 0;
     for (size_t k = 0; k < jobs.size(); ++k) {
-        const int64_t w = tdw[(size_t)jobs[k].out_idx];
-        if (used > 0 && (used + w) * 4 > budget) group_start.push_back(k), used = 0;
-        jobs[k].trace_off = used, jobs[k].line_off = line_total;
-        used += w, line_total += jobs[k].m;
-        max_used = std::max(max_used, used);
+        if (ckpt) {
+            jobs[k].line_off = plan.byte_off[k] / 8, jobs[k].trace_off = (plan.byte_off[k] + line_bytes(jobs[k])) / 4;
+        } else {
+            jobs[k].trace_off = plan.byte_off[k] / 4, jobs[k].line_off = line_total;
+            line_total += jobs[k].m;
+        }
     }
-    group_start.push_back(jobs.size());
+    const std::vector<size_t> &group_start = plan.group_start;
 
     std::lock_guard<std::mutex> lk(e->mu);
     RMR_HIP(hipSetDevice(e->device));
@@ -606,9 +656,9 @@ int rmr_duplex_align(rmr_engine *e, int64_t n, const uint8_t *bases, const int64
         .add(&d_out, hout.size());
     RMR_TRY(st.commit(e));
     uint32_t *d_trace = nullptr;
-    if (hipMalloc(&d_trace, (size_t)max_used * 4) != hipSuccess) {
+    if (hipMalloc(&d_trace, (size_t)plan.max_bytes) != hipSuccess) {
         (void)hipGetLastError();
-        RMR_FAIL(RMR_ERR_HIP, "cannot allocate %lld bytes of alignment trace (lower the trace budget)", (long long)max_used * 4);
+        RMR_FAIL(RMR_ERR_HIP, "cannot allocate %lld bytes of alignment trace (lower the trace budget)", (long long)plan.max_bytes);
     }
     auto run = [&]() -> int {
         H2D(d_bases, bases, (size_t)n_bases);
@@ -616,7 +666,9 @@ int rmr_duplex_align(rmr_engine *e, int64_t n, const uint8_t *bases, const int64
         H2D(d_out, hout.data(), hout.size() * 4);
         for (size_t g = 0; g + 1 < group_start.size(); ++g) {
             const size_t k0 = group_start[g];
-            RMR_TRY(launch_duplex_group(e, d_jobs + k0, (int)(group_start[g + 1] - k0), d_bases, d_trace, d_line, d_best + k0, d_runs, d_out));
+            const int cnt = (int)(group_start[g + 1] - k0);
+            if (ckpt) RMR_TRY(launch_duplex_group_checkpoint(e, d_jobs + k0, cnt, d_bases, d_trace, (int2 *)d_trace, d_best + k0, d_runs, d_out));
+            else RMR_TRY(launch_duplex_group(e, d_jobs + k0, cnt, d_bases, d_trace, d_line, d_best + k0, d_runs, d_out));
         }
         D2H(out, d_out, hout.size() * 4);
         D2H(runs, d_runs, (size_t)run_off[n] * 4);
@@ -627,6 +679,7 @@ int rmr_duplex_align(rmr_engine *e, int64_t n, const uint8_t *bases, const int64
     if (rc != 0) (void)hipStreamSynchronize(e->stream);  // nothing may still write the trace when it is freed
     (void)hipFree(d_trace);
     if (rc == 0 && n_groups) *n_groups = (int64_t)group_start.size() - 1;
+    if (rc == 0 && n_checkpointed) *n_checkpointed = ckpt ? (int64_t)jobs.size() : 0;
     return rc;
 }
 

@@ -26,7 +26,7 @@ static const char *k_names[K_NUM] = {
     "count_labels", "motif_scan", "vbz_decode", "refine_band", "refine_dp", "refine_dp_rowwise",
     "fused_front", "rescale_quantiles", "sig3_front", "seq2_front", "probe_max_diff", "probe_nonfinite", "winograd_form",
     "base_metrics", "region_metrics", "region_signals", "site_kmer_levels", "modbam_sites", "rescale_points", "theil_sen_fit",
-    "duplex_dp", "duplex_traceback"};
+    "duplex_dp", "duplex_traceback", "duplex_lines", "duplex_backtrack"};
 const char *kernel_name(int id) { return (id >= 0 && id < K_NUM) ? k_names[id] : "?"; }
 
 }  // namespace rmr
@@ -181,7 +181,7 @@ int rmr_engine::prof_collect() {
 extern "C" {
 
 const char *rmr_last_error(void) { return g_err.c_str(); }
-const char *rmr_version(void) { return "remora_hip 0.9 (gfx950)"; }  // 0.9: rmr_duplex_align
+const char *rmr_version(void) { return "remora_hip 0.10 (gfx950)"; }  // 0.10: rmr_duplex_align_mode
 
 int rmr_engine_create(int device, void *stream, int flags, rmr_engine **out) {
     if (!out) RMR_FAIL(RMR_ERR_INVALID, "out is NULL");

@@ -69,6 +69,8 @@ enum KernelId {
     K_THEIL_SEN,
     K_DUPLEX_DP,
     K_DUPLEX_TRACE,
+    K_DUPLEX_LINES,      // the forward pass that keeps one line per strip instead of the trace
+    K_DUPLEX_BACKTRACK,  // the walk back that recomputes the trace one strip at a time
     K_NUM
 };
 const char *kernel_name(int id);
@@ -218,6 +220,10 @@ struct DuplexJob {
 };
 int launch_duplex_group(rmr_engine *e, const DuplexJob *jobs, int n_jobs, const uint8_t *bases, uint32_t *trace, int2 *line, int2 *best,
                         uint32_t *runs, int32_t *out);
+// The same group in checkpointed memory (rmr_duplex_align_mode): a job's `line` entries are one line of m per strip
+// (ceil(n / STRIP_ROWS) * m of them) and its `trace` dwords the trace of ONE strip ((m + 63) * 64).
+int launch_duplex_group_checkpoint(rmr_engine *e, const DuplexJob *jobs, int n_jobs, const uint8_t *bases, uint32_t *trace, int2 *line,
+                                   int2 *best, uint32_t *runs, int32_t *out);
 int launch_motif(rmr_engine *e, const int8_t *seq, const int64_t *seq_off, int n_reads, int64_t total,
                  const rmr_motif_set &ms, uint8_t *flags);
 

@@ -1,5 +1,5 @@
 """Simplex-to-duplex alignment (src/remora/duplex_utils.py): where the reference calls parasail on the CPU for one pair
-at a time, a batch of alignments runs on the GPU (rmr_duplex_align, csrc/k_duplex.hip).  The alignment, its scores and the
+at a time, a batch of alignments runs on the GPU (rmr_duplex_align_mode, csrc/k_duplex.hip).  The alignment, its scores and the
 rule among co-optimal paths: include/remora_hip.h and DESIGN.md, "Duplex"."""
 import ctypes
 from dataclasses import dataclass
@@ -29,9 +29,20 @@ STATUS_MESSAGE = {
 }
 
 
+# how the walk back gets its trace (rmr_duplex_align_mode): stored for every cell, recomputed strip by strip from one kept DP line
+# per strip, or the first where the whole call fits the budget as one group and the second otherwise.  Same results in all three.
+MODE_FULL, MODE_CHECKPOINT, MODE_AUTO = range(3)
+MODES = {"full": MODE_FULL, "checkpoint": MODE_CHECKPOINT, "auto": MODE_AUTO}
+
+
 def trace_bytes(simplex_len, duplex_len):
     """Bytes of trace one alignment takes (include/remora_hip.h)."""
     return -(-simplex_len // STRIP_ROWS) * (duplex_len + 63) * 256
+
+
+def checkpoint_bytes(simplex_len, duplex_len):
+    """Bytes one alignment takes in checkpointed memory: a line of duplex_len (H, F) pairs per strip and one strip of trace."""
+    return -(-simplex_len // STRIP_ROWS) * duplex_len * 8 + (duplex_len + 63) * 256
 
 
 @dataclass
@@ -54,7 +65,7 @@ class SimplexDuplexMapping:
 class AlignmentBatch:
     """What rmr_duplex_align returns for a batch: per alignment its status, score, end row (simplex bases consumed),
     query_start, ref_start, ref_end, and its runs (ops, lengths) with M = 0, I = 1, D = 2; the number of groups the trace
-    budget made."""
+    budget made and the number of alignments that ran in checkpointed memory."""
     status: np.ndarray
     score: np.ndarray
     end_row: np.ndarray
@@ -65,6 +76,7 @@ class AlignmentBatch:
     n_runs: np.ndarray
     words: np.ndarray
     n_groups: int
+    n_checkpointed: int = 0
 
     def runs(self, a):
         w = self.words[self.run_off[a]:self.run_off[a] + self.n_runs[a]]
@@ -77,8 +89,9 @@ class AlignmentBatch:
                                  query_end=int(self.query_start[a]) + qlen, cigar=list(zip(ops.tolist(), lens.tolist())))
 
 
-def align_batch(pairs, engine=None, trace_budget=None):
-    """Align every (simplex_seq, duplex_seq) of `pairs` in one call (upper-cased here).  No status raises: the caller decides."""
+def align_batch(pairs, engine=None, trace_budget=None, mode="full"):
+    """Align every (simplex_seq, duplex_seq) of `pairs` in one call (upper-cased here).  No status raises: the caller decides.
+    `mode`: "full", "checkpoint" or "auto" (MODES); it changes the memory the call takes, never a result."""
     from .engine import get_engine
 
     n = len(pairs)
@@ -94,14 +107,16 @@ def align_batch(pairs, engine=None, trace_budget=None):
     np.cumsum(2 * r_len + 2, out=run_off[1:])
     out = np.zeros((n, OUT_FIELDS), np.int32)
     words = np.zeros(int(run_off[-1]), np.uint32)
-    groups = ctypes.c_int64(0)
+    if mode not in MODES:
+        raise RemoraError(f"unknown duplex alignment mode {mode!r} (one of {', '.join(MODES)})")
+    groups, checkpointed = ctypes.c_int64(0), ctypes.c_int64(0)
     if n:
-        L.check(L.lib().rmr_duplex_align(eng.handle, n, bases.ctypes.data, q_off.ctypes.data, q_len.ctypes.data, r_off.ctypes.data,
-                                         r_len.ctypes.data, int(trace_budget or 0), out.ctypes.data, run_off.ctypes.data,
-                                         words.ctypes.data, ctypes.byref(groups)))
+        L.check(L.lib().rmr_duplex_align_mode(eng.handle, n, bases.ctypes.data, q_off.ctypes.data, q_len.ctypes.data, r_off.ctypes.data,
+                                              r_len.ctypes.data, int(trace_budget or 0), MODES[mode], out.ctypes.data,
+                                              run_off.ctypes.data, words.ctypes.data, ctypes.byref(groups), ctypes.byref(checkpointed)))
     return AlignmentBatch(status=out[:, 0].copy(), score=out[:, 1].copy(), end_row=out[:, 2].copy(), query_start=out[:, 3].copy(),
                           ref_start=out[:, 4].copy(), ref_end=out[:, 5].copy(), run_off=run_off, n_runs=out[:, 6].astype(np.int64),
-                          words=words, n_groups=int(groups.value))
+                          words=words, n_groups=int(groups.value), n_checkpointed=int(checkpointed.value))
 
 
 def mapping_from_alignment(pairwise_alignment, duplex_seq):
@@ -116,10 +131,10 @@ def mapping_from_alignment(pairwise_alignment, duplex_seq):
                                 duplex_offset=pa.ref_start)
 
 
-def map_simplexes_to_duplexes(pairs, engine=None, trace_budget=None):
-    """The batch form of map_simplex_to_duplex: one rmr_duplex_align call for every (simplex_seq, duplex_seq) of `pairs`.
+def map_simplexes_to_duplexes(pairs, engine=None, trace_budget=None, mode="full"):
+    """The batch form of map_simplex_to_duplex: one rmr_duplex_align_mode call for every (simplex_seq, duplex_seq) of `pairs`.
     Returns a list with a SimplexDuplexMapping per pair, or the error text (str) of a pair that has none."""
-    res = align_batch(pairs, engine, trace_budget)
+    res = align_batch(pairs, engine, trace_budget, mode)
     out = []
     for a, (_, duplex_seq) in enumerate(pairs):
         st = int(res.status[a])

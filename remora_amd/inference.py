@@ -1024,10 +1024,12 @@ def check_simplex_alignments(*, simplex_index, duplex_index, pairs):
     return valid, len(valid)
 
 
-def _duplex_batch_records(pairs, builder, duplex_index, model, model_metadata, errs):
+def _duplex_batch_records(pairs, builder, duplex_index, model, model_metadata, errs, trace_budget=None):
     """One batch of pairs -> the bytes of their output records, in the order of `pairs`: both reads of every pair gathered, ONE
     alignment call for the 2 B alignments, ONE call_reads_mods for the 2 B re-anchored reads, the tags of each strand
-    formatted for the batch, the records rewritten in one call.  Failed pairs are tallied in `errs` by reason."""
+    formatted for the batch, the records rewritten in one call.  Failed pairs are tallied in `errs` by reason.  `trace_budget`:
+    bytes of alignment memory the call may take at a time (None: duplex_utils.DEFAULT_TRACE_BYTES); a batch that does not fit it
+    whole with stored traces is aligned in checkpointed memory."""
     from . import io as rio
     from .util import format_mm_ml_tags_batch
 
@@ -1042,7 +1044,7 @@ def _duplex_batch_records(pairs, builder, duplex_index, model, model_metadata, e
         # (only the first duplex record of a template id is used, as in the reference)
         items.append((reads[0], reads[1], next(duplex_index.get_alignments(t_id, want_ref=False))))
     duplex_reads, remora_reads = [], []
-    for dr, err in rio.duplex_reads_batch(items, engine):
+    for dr, err in rio.duplex_reads_batch(items, engine, trace_budget, mode="auto"):
         if err is None:
             try:
                 two = [dr.template_read.into_remora_read(False), dr.complement_read.into_remora_read(False)]
@@ -1083,11 +1085,12 @@ def _duplex_batch_records(pairs, builder, duplex_index, model, model_metadata, e
 
 def infer_duplex(*, simplex_pod5_path, simplex_bam_path, duplex_bam_path, pairs_path, model, model_metadata, out_bam,
                  num_extract_alignment_threads=1, num_duplex_prep_workers=1, num_infer_threads=1, num_reads=None, skip_non_primary=True,
-                 duplex_deliminator=";", reads_per_batch=64, bam_level=None):
+                 duplex_deliminator=";", reads_per_batch=64, bam_level=None, trace_budget=None):
     """`remora infer duplex_from_pod5_and_bam` (src/remora/inference.py:894-1010): for every valid pair of the pairs file the
     first duplex record of its template id is written to `out_bam` with the MM / ML tags of both strands (existing MM* / ML* tags
     dropped), in the order of the pairs file (the reference's order depends on its worker queues).  The three worker counts are
-    accepted and ignored: the pairs go through the GPU in batches of `reads_per_batch`.  Returns {reason: failed pairs}."""
+    accepted and ignored: the pairs go through the GPU in batches of `reads_per_batch`, each batch's alignments in at most
+    `trace_budget` bytes at a time (_duplex_batch_records).  Returns {reason: failed pairs}."""
     import logging
     import sys
     from collections import defaultdict
@@ -1116,7 +1119,7 @@ def infer_duplex(*, simplex_pod5_path, simplex_bam_path, duplex_bam_path, pairs_
         with rio.DuplexPairsBuilder(simplex_index, simplex_pod5_path) as builder, \
                 rio.BamWriter(out_bam, rio.read_bam_header_bytes(duplex_bam_path), level=bam_level) as writer:
             for k in range(0, len(valid_pairs), step):
-                rec_bytes = _duplex_batch_records(valid_pairs[k:k + step], builder, duplex_index, model, model_metadata, errs)
+                rec_bytes = _duplex_batch_records(valid_pairs[k:k + step], builder, duplex_index, model, model_metadata, errs, trace_budget)
                 if rec_bytes:
                     writer.write(rec_bytes)
     finally:

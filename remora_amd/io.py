@@ -2649,9 +2649,10 @@ class DuplexRead:
         return self.duplex_alignment["seq"]  # as stored: reverse-complemented on a reverse mapping
 
 
-def duplex_reads_batch(items, engine=None, trace_budget=None):
+def duplex_reads_batch(items, engine=None, trace_budget=None, mode="auto"):
     """DuplexRead.from_reads_and_alignment for a batch with ONE alignment call: items = [(template_read, complement_read,
-    duplex record)] -> [(DuplexRead | None, error text | None)]."""
+    duplex record)] -> [(DuplexRead | None, error text | None)].  `mode`: duplex_utils.MODES; "auto" stores the whole trace where
+    the batch fits `trace_budget` at once and runs in checkpointed memory (any length, same alignments) where it does not."""
     from . import duplex_utils
 
     pairs, first, errs = [], [], []
@@ -2664,7 +2665,7 @@ def duplex_reads_batch(items, engine=None, trace_budget=None):
         except RemoraError as e:
             first.append(-1)
             errs.append(str(e))
-    maps = duplex_utils.map_simplexes_to_duplexes(pairs, engine, trace_budget) if pairs else []
+    maps = duplex_utils.map_simplexes_to_duplexes(pairs, engine, trace_budget, mode) if pairs else []
     out = []
     for (t, c, rec), k, err in zip(items, first, errs):
         if err is None:
