@@ -824,6 +824,59 @@ int rmr_site_kmer_levels(rmr_engine *e, int64_t n_reads, const int64_t *seq_off,
                          const double *trimmean, const int8_t *int_seq, int kmer_before, int kmer_after, int64_t min_cov,
                          double *levels, int64_t *kmer_sites, int32_t *site_kmer, double *site_level, int64_t *n_sites);
 
+/* ---- training (L5: `remora model train`) ------------------------------------------------------------------------------
+ * One fp32 training step of ConvLSTM_w_ref (models/ConvLSTM_w_ref.py:11-58) on the device: the forward pass with BatchNorm
+ * in train mode (batch mean and biased variance over (N, L), eps 1e-5; running statistics moved with momentum 0.1 and the
+ * unbiased variance), mean cross-entropy over the rows a byte mask keeps, the backward pass and AdamW.  size a multiple of 16
+ * from 16 to 256, k-mer length 1..21, chunk length >= 29, num_out 2..16, batch 2..max_batch; Conv_w_ref, the 16-bit dtypes
+ * and every other size are refused by name (zero-weight channel padding is no identity under train-mode BatchNorm).
+ * The trainer's state is ONE flat fp32 buffer in the order of rmr_model_create's blob (parameters and running statistics),
+ * so what rmr_trainer_read returns can be handed to rmr_model_create unchanged; gradients and the two Adam moments are
+ * buffers of the same layout (zeros in the running statistics' places).  The same inputs and state give the same bits on
+ * every run: every sum over rows is per-block partials plus a second pass in fixed order, no float atomics. */
+typedef struct rmr_trainer rmr_trainer;
+enum rmr_train_buffer {
+    RMR_TRAIN_PARAMS = 0,  /* parameters + running statistics */
+    RMR_TRAIN_GRADS = 1,
+    RMR_TRAIN_ADAM_M = 2,  /* exp_avg */
+    RMR_TRAIN_ADAM_V = 3,  /* exp_avg_sq */
+    RMR_TRAIN_COUNTERS = 4 /* 3 floats: optimiser steps taken, num_batches_tracked, workspace bytes per chunk (read only) */
+};
+#define RMR_TRAIN_NAME_LEN 32
+/* `blob`: the initial state, host, rmr_model_weight_count(desc) floats; desc->dtype must be 0.  The workspace is allocated
+ * here, once, for max_batch chunks.
+ * replaces: model construction and `.to(device)`, src/remora/train_model.py:333-352; torch.optim.AdamW's state, :354-360. */
+int rmr_trainer_create(rmr_engine *e, const rmr_model_desc *desc, const float *blob, size_t n_floats, int64_t max_batch,
+                       rmr_trainer **out);
+void rmr_trainer_destroy(rmr_trainer *t);
+/* sigs f32[n][1][L], seqs f32[n][4 kmer_len][L] (dense one-hot, as rmr_forward takes them), labels i64[n], mask u8[n] or
+ * NULL (rows with 0 leave the loss and still take part in BatchNorm: --high-conf-incorrect-thr-frac); all four in `mem`.
+ * Fills the gradient buffer, moves the running statistics, *loss (HOST) = mean cross-entropy; logits f32[n][num_out] (in
+ * `mem`) or NULL.  Synchronous.
+ * replaces: model.train(); outputs = model(sigs, seqs); loss = criterion(outputs, labels); loss.backward(),
+ *           src/remora/train_model.py:470-499. */
+int rmr_trainer_forward_backward(rmr_trainer *t, const float *sigs, const float *seqs, const int64_t *labels,
+                                 const uint8_t *mask, int64_t n, float *loss, float *logits, int mem);
+/* out (HOST) f32[parameter tensors]: max |grad| of each, named_parameters order.
+ * replaces: apply_clipping's grad_maxs, src/remora/train_model.py:118-123. */
+int rmr_trainer_grad_absmax(rmr_trainer *t, float *out);
+/* One torch.optim.AdamW step over the whole buffer in one launch: decoupled decay p -= lr wd p, bias-corrected moments,
+ * p -= lr mhat / (sqrt(vhat) + eps).  clip (HOST, f32[parameter tensors]) or NULL: gradients of tensor i are clamped to
+ * [-clip[i], clip[i]] first (a negative entry: not clamped).  The scalars are doubles so that 1 - beta is formed before the
+ * rounding to fp32, as torch forms it (1 - (float)0.999 is off by 1.3e-5 of itself).
+ * replaces: apply_clipping's clamp_ and opt.step(), src/remora/train_model.py:124-131, :500-503. */
+int rmr_trainer_adamw_step(rmr_trainer *t, double lr, double beta1, double beta2, double eps, double weight_decay, const float *clip);
+/* copy one buffer (rmr_train_buffer) to / from HOST memory; n_floats must be the buffer's size
+ * replaces: model.state_dict() / load_state_dict(), opt.state_dict(), src/remora/train_model.py:134-161. */
+int rmr_trainer_read(rmr_trainer *t, int which, float *out, size_t n_floats);
+int rmr_trainer_write(rmr_trainer *t, int which, const float *in, size_t n_floats);
+/* The tensors of the flat buffer in order: names (cap x RMR_TRAIN_NAME_LEN bytes, NUL-terminated torch names), offsets and
+ * sizes in floats, is_param (0: a running statistic).  The entries with is_param = 1 are named_parameters, in its order.
+ * Every array may be NULL; *n_out = number of tensors.
+ * replaces: model.named_parameters() / named_buffers(). */
+int rmr_trainer_tensor_layout(const rmr_trainer *t, int cap, char *names, int64_t *offsets, int64_t *sizes, int32_t *is_param,
+                              int *n_out);
+
 /* ---- measurement: HIP-event timing of every kernel launch on the engine stream ----------- */
 int rmr_profile_enable(rmr_engine *e, int on);
 int rmr_profile_reset(rmr_engine *e);

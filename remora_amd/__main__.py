@@ -5,7 +5,8 @@
 the stored chunks of an on-disk dataset (directory or config) through the model with the model's chunk /
 k-mer contexts, the reference's validation summary line against the stored labels; and `python -m remora_amd dataset prepare`
 (:64-337), the ETL into the on-disk chunk format, with the bookkeeping verbs around that format (`dataset inspect |
-make_config | merge | head | copy`, :359-727: host code over `CoreRemoraDataset` / `RemoraDataset`, no kernel involved)."""
+make_config | merge | head | copy`, :359-727: host code over `CoreRemoraDataset` / `RemoraDataset`, no kernel involved);
+`python -m remora_amd model train DATASET --model ARCH.py` (:753-1024): ConvLSTM_w_ref in fp32, the training step in HIP."""
 import argparse
 import os
 import sys
@@ -379,9 +380,100 @@ def _estimate_kmer_levels(args):
     return 0
 
 
+def _model_train(args):
+    """src/remora/parsers.py:977-1024."""
+    import logging
+
+    from .model_util import TrainOpts
+    from .train_model import train_model
+    from .util import prepare_out_dir
+
+    log = logging.getLogger("Remora")
+    log.setLevel(logging.INFO)
+    if not log.handlers:
+        log.addHandler(logging.StreamHandler(sys.stderr))
+    # what is refused is refused before the output directory is touched
+    if args.optimizer != "AdamW":
+        raise RemoraError(f"--optimizer {args.optimizer}: the HIP trainer implements AdamW only")
+    if args.finetune_path is not None or args.freeze_num_layers:
+        raise RemoraError("--finetune-path / --freeze-num-layers: fine-tuning is not built for the HIP trainer")
+    from .model_util import scan_model_file
+
+    if scan_model_file(args.model) != "conv_lstm":
+        raise RemoraError(f"--model {args.model} assigns the layers of Conv_w_ref: the HIP trainer trains ConvLSTM_w_ref only")
+    device = args.device
+    if device is not None:
+        device = int(device) if str(device).isdigit() else device
+    # argparse appends to the default list in the reference: what is given is added to (and overrides) the defaults
+    opt_kwargs = list(constants.DEFAULT_OPT_VALUES) + [tuple(x) for x in (args.optimizer_kwargs or [])]
+    sch_kwargs = list(constants.DEFAULT_SCH_VALUES) + [tuple(x) for x in (args.lr_scheduler_kwargs or [])]
+    prepare_out_dir(args.output_path, args.overwrite)
+    train_opts = TrainOpts(epochs=args.epochs, early_stopping=args.early_stopping, optimizer_str=args.optimizer,
+                           opt_kwargs=opt_kwargs, learning_rate=args.lr, lr_scheduler_str=args.lr_scheduler,
+                           lr_scheduler_kwargs=sch_kwargs, lr_cool_down_epochs=args.lr_cool_down_epochs,
+                           lr_cool_down_lr=args.lr_cool_down_learning_rate)
+    train_model(args.seed, device, args.output_path, args.remora_dataset_path, args.chunk_context, args.kmer_context_bases,
+                args.batch_size, args.model, args.size, train_opts, args.chunks_per_epoch, args.num_test_chunks, args.save_freq,
+                args.filter_fraction, args.ext_val, args.ext_val_names, args.high_conf_incorrect_thr_frac, args.finetune_path,
+                args.freeze_num_layers, args.super_batch_size, args.super_batch_sample_fraction, args.read_batches_from_disk,
+                args.gradient_clip_num_mads)
+    log.info("Done")
+    return 0
+
+
+def _add_model_train(sub):
+    """The reference's arguments (src/remora/parsers.py:753-975)."""
+    t = sub.add_parser("model").add_subparsers(dest="sub", required=True).add_parser(
+        "train", help="Train a ConvLSTM_w_ref model on an MI355X (fp32; forward, backward and AdamW in HIP)")
+    t.add_argument("remora_dataset_path", help="Remora training dataset (directory or config)")
+    g = t.add_argument_group("Data Arguments")
+    g.add_argument("--batch-size", default=constants.DEFAULT_BATCH_SIZE, type=int)
+    g.add_argument("--chunk-context", type=int, nargs=2, metavar=("NUM_BEFORE", "NUM_AFTER"), help="override the chunk context of data prep")
+    g.add_argument("--kmer-context-bases", type=int, nargs=2, metavar=("BASES_BEFORE", "BASES_AFTER"),
+                   help="override the k-mer context bases of data prep")
+    g.add_argument("--ext-val", nargs="+", help="external validation datasets")
+    g.add_argument("--ext-val-names", nargs="+", help="names of the external datasets (as many as --ext-val)")
+    g.add_argument("--chunks-per-epoch", default=constants.DEFAULT_CHUNKS_PER_EPOCH, type=int)
+    g.add_argument("--num-test-chunks", default=constants.DEFAULT_NUM_TEST_CHUNKS, type=int)
+    g.add_argument("--filter-fraction", default=constants.DEFAULT_FILT_FRAC, type=float)
+    g.add_argument("--read-batches-from-disk", action="store_true", help="accepted and ignored: validation batches are always read from disk")
+    g = t.add_argument_group("Output Arguments")
+    g.add_argument("--output-path", default="remora_train_results")
+    g.add_argument("--save-freq", default=10, type=int, help="save the model every this many epochs")
+    g.add_argument("--overwrite", action="store_true")
+    g = t.add_argument_group("Model Arguments")
+    g.add_argument("--model", required=True, help="model architecture file: copied to the output, scanned for its layer names, never executed")
+    g.add_argument("--finetune-path", help="refused: fine-tuning is not built")
+    g.add_argument("--freeze-num-layers", default=0, type=int, help="refused unless 0")
+    g.add_argument("--size", type=int, default=constants.DEFAULT_NN_SIZE, help="layer size: a multiple of 16 from 16 to 256")
+    g = t.add_argument_group("Training Arguments")
+    g.add_argument("--epochs", default=constants.DEFAULT_EPOCHS, type=int)
+    g.add_argument("--optimizer", default=constants.DEFAULT_OPTIMIZER, help="AdamW (anything else is refused)")
+    g.add_argument("--optimizer-kwargs", nargs=3, action="append", default=None, metavar=("NAME", "VALUE", "TYPE"),
+                   help="lr / weight_decay / eps of AdamW; TYPE is str, int or float (default: weight_decay 1e-4 float)")
+    g.add_argument("--lr", default=constants.DEFAULT_LR, type=float,
+                   help="as in the reference this value does not reach the optimiser: give `--optimizer-kwargs lr VALUE float`")
+    g.add_argument("--lr-scheduler", default=constants.DEFAULT_SCHEDULER, help="a torch.optim.lr_scheduler class")
+    g.add_argument("--lr-scheduler-kwargs", nargs=3, action="append", default=None, metavar=("NAME", "VALUE", "TYPE"))
+    g.add_argument("--lr-cool-down-epochs", type=int, default=constants.DEFAULT_SCH_COOL_DOWN_EPOCHS)
+    g.add_argument("--lr-cool-down-learning-rate", type=float, default=constants.DEFAULT_SCH_COOL_DOWN_LR)
+    g.add_argument("--early-stopping", default=constants.DEFAULT_EARLY_STOPPING, type=int, help="0: never stop early")
+    g.add_argument("--seed", type=int)
+    g.add_argument("--high-conf-incorrect-thr-frac", nargs=2, type=float, metavar=("THRESHOLD", "FRACTION"),
+                   help="leave confidently wrong chunks out of each iteration's loss (they still take part in BatchNorm)")
+    g.add_argument("--gradient-clip-num-mads", default=0, type=lambda x: None if x == "None" else float(x),
+                   help="clip gradients by value at this many MADs above the median of the last 1000 maxima; None: no clipping")
+    g = t.add_argument_group("Compute Arguments")
+    g.add_argument("--device", default=None, help="GPU index or torch device string")
+    g.add_argument("--super-batch-size", default=constants.DEFAULT_SUPER_BATCH_SIZE, type=int)
+    g.add_argument("--super-batch-sample-fraction", default=constants.DEFAULT_SUPER_BATCH_SAMPLE_FRAC, type=float)
+    t.set_defaults(func=_model_train)
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog="remora_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
+    _add_model_train(sub)
     infer = sub.add_parser("infer").add_subparsers(dest="sub", required=True)
     p = infer.add_parser("from_pod5_and_bam", help="Infer modified bases from POD5 + BAM on an MI355X")
     p.add_argument("pod5")

@@ -14,6 +14,8 @@ MEM_HOST, MEM_DEVICE = 0, 1
 ARCH_CONV_LSTM, ARCH_CONV_ONLY = 0, 1
 ENGINE_OWN_STREAM, ENGINE_USE_STREAM = 0, 1
 ERR_DISCORDANT_SEQ, ERR_DISCORDANT_SIG = -4, -5
+TRAIN_PARAMS, TRAIN_GRADS, TRAIN_ADAM_M, TRAIN_ADAM_V, TRAIN_COUNTERS = range(5)
+TRAIN_NAME_LEN = 32
 
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
@@ -163,6 +165,14 @@ SIGNATURES = {
                                    c_vp, c_vp]),
     "rmr_site_kmer_levels": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_vp,
                                      ctypes.POINTER(c_i64)]),
+    "rmr_trainer_create": (c_int, [c_vp, ctypes.POINTER(ModelDesc), c_vp, ctypes.c_size_t, c_i64, ctypes.POINTER(c_vp)]),
+    "rmr_trainer_destroy": (None, [c_vp]),
+    "rmr_trainer_forward_backward": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(ctypes.c_float), c_vp, c_int]),
+    "rmr_trainer_grad_absmax": (c_int, [c_vp, c_vp]),
+    "rmr_trainer_adamw_step": (c_int, [c_vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_vp]),
+    "rmr_trainer_read": (c_int, [c_vp, c_int, c_vp, ctypes.c_size_t]),
+    "rmr_trainer_write": (c_int, [c_vp, c_int, c_vp, ctypes.c_size_t]),
+    "rmr_trainer_tensor_layout": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_int)]),
     "rmr_profile_enable": (c_int, [c_vp, c_int]),
     "rmr_profile_reset": (c_int, [c_vp]),
     "rmr_profile_num_kernels": (c_int, []),

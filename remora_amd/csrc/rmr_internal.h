@@ -71,6 +71,15 @@ enum KernelId {
     K_DUPLEX_TRACE,
     K_DUPLEX_LINES,      // the forward pass that keeps one line per strip instead of the trace
     K_DUPLEX_BACKTRACK,  // the walk back that recomputes the trace one strip at a time
+    // the training step (k_train.hip)
+    K_TRAIN_GEMM,    // forward, data-gradient and LSTM products on the fp32 matrix cores
+    K_TRAIN_WGRAD,   // weight-gradient products (per-slice partials)
+    K_TRAIN_REDUCE,  // the fixed-order second passes of the weight gradients and column sums
+    K_TRAIN_BN,      // BatchNorm column sums, normalise + swish, backward apply
+    K_TRAIN_LSTM,    // the LSTM steps (recurrent product + cell), forward and backward
+    K_TRAIN_LOSS,    // fc, cross-entropy and its gradient
+    K_TRAIN_ADAMW,   // the optimiser and max |grad|
+    K_TRAIN_AUX,     // weight repacks, sig_conv1, the k-mer transpose, fills
     K_NUM
 };
 const char *kernel_name(int id);
@@ -294,6 +303,39 @@ int launch_fused_front(rmr_model *m, const ChunkArrays &c, int64_t n, uint16_t *
 bool lstm_x16s_supported(const rmr_model *m);
 int launch_lstm_head_x16s(rmr_model *m, const float *x, int64_t n, float *logits);
 int launch_lstm_head_x16(rmr_model *m, const uint16_t *x, int64_t n, float *logits);
+
+// k_train.hip: the training step (api_train.hip).  Row r of a product is `rs`-spaced inside chunk r / rpc: its first float is
+// (r / rpc) * cs + (r % rpc) * rs + off of the buffer, and floats outside [0, valid) of the chunk read as zero / are not written
+struct TrainSpan {
+    int rpc;
+    long long cs;
+    int rs, off;
+    long long valid;
+};
+int train_gemm(rmr_engine *e, const float *A, const TrainSpan &sa, const float *B, int ldb, int K, float *C, const TrainSpan &sc, int NC,
+               long long R, const float *bias);
+int train_wgrad(rmr_engine *e, const float *A, const TrainSpan &sa, const float *D, const TrainSpan &sd, int K, int NC, long long R, int IC,
+                int KW, float *part, size_t part_floats, float *grad);
+int train_repack(rmr_engine *e, const float *W, int OC, int IC, int KW, int P, int J, int mode, float *out);
+int train_colsum_blocks(long long R);
+int train_bn_forward(rmr_engine *e, const float *Y, int C, long long R, float *stat, const float *gamma, const float *beta, float *run_mean,
+                     float *run_var, float *part, float *out, int aw, int coff);
+int train_bn_backward(rmr_engine *e, const float *Y, int C, long long R, float *stat, const float *gamma, const float *beta, const float *dA, int aw,
+                      int coff, float *part, float *dgamma, float *dbeta, float *dY, float *dbias);
+int train_bias_grad(rmr_engine *e, const float *D, int C, long long R, float *part, float *out, float *out2);
+int train_sig1(rmr_engine *e, const float *sig, int L, int Lout, int OC, int KW, const float *w, const float *b, long long n, float *y);
+int train_seq_transpose(rmr_engine *e, const float *in, int EC, int L, long long n, float *out);
+int train_fill(rmr_engine *e, float *p, long long n, float v);
+int train_lstm_step(rmr_engine *e, float *G, float *Cs, float *H, float *Z, const float *WhhT, int S, int T, int t, long long n);
+int train_lstm_step_bwd(rmr_engine *e, float *G, const float *Cs, const float *H, const float *Whh, const float *dz1, float *dc, int S, int T, int t,
+                        long long n);
+int train_lstm2(rmr_engine *e, float *G2, float *C2, float *H2, float *Z2, int S, long long n);
+int train_lstm2_bwd(rmr_engine *e, float *G2, const float *C2, const float *H2, const float *dlog, const float *fcw, int num_out, int S, long long n);
+int train_fc_loss(rmr_engine *e, const float *Z2, const float *fcw, const float *fcb, int S, int num_out, const int64_t *labels, const uint8_t *mask,
+                  int *count, long long n, float *logits, float *dlog, float *loss_part, float *logits_out, float *loss);
+int train_adamw(rmr_engine *e, float *p, float *g, float *m, float *v, const uint8_t *tensor_of, long long n, float lr_wd, float omb1, float b2,
+                float omb2, float eps, float step_size, float bc2_sqrt, const float *clip);
+int train_absmax(rmr_engine *e, const float *g, const long long *off, const long long *size, int n_tensors, float *out);
 
 // integer switch from the environment (DESIGN.md has the table of every name the product reads)
 inline int tune_int(const char *name, int dflt) {

@@ -6,7 +6,14 @@ The model file format is unchanged: a TorchScript archive whose extra file `meta
 JSON dict (:115-176).  torch.jit.load is used only to read the file; the weights go to the
 HIP engine (BatchNorm folding and MFMA packing happen inside rmr_model_create) and what is
 returned in place of the ScriptModule is a `HipModel`.
+
+The training side of the same module: TrainOpts :77-107, CustomPlusCoolDownScheduler :34-74 and
+export_model_torchscript :115-176, for remora_amd.train_model; `scan_model_file` stands in for
+_load_python_model (:451-465): the architecture file of `--model` is read, never executed.
 """
+import ast
+import dataclasses
+import datetime
 import json
 import logging
 import os
@@ -14,8 +21,8 @@ from os.path import isfile
 
 import numpy as np
 
-from . import RemoraError
-from .engine import HipModel, _torch
+from . import RemoraError, constants
+from .engine import HipModel, _torch, detect_arch
 from .refine_signal_map import SigMapRefiner
 
 LOGGER = logging.getLogger("Remora")
@@ -135,3 +142,149 @@ def model_from_state(state, model_metadata, device=None, engine=None, dtype="fp3
     model = HipModel(st, int(sum(model_metadata["chunk_context"])), device=device, engine=engine, dtype=dtype)
     _record_winograd(model, model_metadata, f"{model.arch} size {model.size} (from state)")
     return model
+
+
+# ---- training options (src/remora/model_util.py:34-107) ----------------------------------------------------------------------
+TYPE_CONVERTERS = {"str": str, "int": int, "float": float}
+
+
+def _typed_kwargs(triples):
+    """((name, value, type name), ...) of --optimizer-kwargs / --lr-scheduler-kwargs -> {name: converted value}."""
+    out = {}
+    for name, value, type_name in triples:
+        if type_name not in TYPE_CONVERTERS:
+            raise RemoraError(f"argument type must be one of {sorted(TYPE_CONVERTERS)}, got {type_name!r} for {name}")
+        out[name] = TYPE_CONVERTERS[type_name](value)
+    return out
+
+
+class CustomPlusCoolDownScheduler:
+    """Any torch.optim.lr_scheduler class for the first `epochs` - 1 steps, a constant cool-down rate afterwards.  `opt` is a
+    torch optimiser; here it is a dummy over one parameter whose only job is to carry the learning rate, read once per epoch
+    (the AdamW arithmetic runs in rmr_trainer_adamw_step)."""
+
+    def __init__(self, opt, initial_lr, lr_scheduler_str, lr_scheduler_kwargs, epochs, cool_down_epochs, cool_down_lr):
+        torch = _torch()
+        self.opt, self.initial_lr = opt, initial_lr
+        self.num_epochs, self.num_cool_down_epochs, self.cool_down_lr = epochs, cool_down_epochs, cool_down_lr
+        self.total_epochs = epochs + cool_down_epochs
+        self.last_epoch = -1
+        if not hasattr(torch.optim.lr_scheduler, lr_scheduler_str):
+            raise RemoraError(f"torch.optim.lr_scheduler has no {lr_scheduler_str}")
+        self.custom_scheduler = getattr(torch.optim.lr_scheduler, lr_scheduler_str)(opt, **_typed_kwargs(lr_scheduler_kwargs))
+
+    def _cooling(self):
+        return self.last_epoch >= self.num_epochs - 1
+
+    def get_last_lr(self):
+        return [self.cool_down_lr for _ in self.opt.param_groups] if self._cooling() else self.custom_scheduler.get_last_lr()
+
+    def step(self):
+        self.last_epoch += 1
+        if not self._cooling():
+            import warnings
+
+            with warnings.catch_warnings():  # the dummy optimiser never steps: torch's order-of-calls advice does not apply
+                warnings.filterwarnings("ignore", message="Detected call of `lr_scheduler.step\\(\\)` before")
+                return self.custom_scheduler.step()
+        for group in self.opt.param_groups:
+            group["lr"] = self.cool_down_lr
+
+    @property
+    def lr(self):
+        """The rate the next epoch's steps run at: what the optimiser's (only) parameter group holds."""
+        return float(self.opt.param_groups[0]["lr"])
+
+
+@dataclasses.dataclass
+class TrainOpts:
+    epochs: int = constants.DEFAULT_EPOCHS
+    early_stopping: int = constants.DEFAULT_EARLY_STOPPING
+    optimizer_str: str = constants.DEFAULT_OPTIMIZER
+    opt_kwargs: tuple = constants.DEFAULT_OPT_VALUES
+    learning_rate: float = constants.DEFAULT_LR
+    lr_scheduler_str: str = constants.DEFAULT_SCHEDULER
+    lr_scheduler_kwargs: tuple = constants.DEFAULT_SCH_VALUES
+    lr_cool_down_epochs: int = constants.DEFAULT_SCH_COOL_DOWN_EPOCHS
+    lr_cool_down_lr: float = constants.DEFAULT_SCH_COOL_DOWN_LR
+
+    ADAMW_KWARGS = ("lr", "weight_decay", "eps")
+
+    def optimizer_kwargs(self):
+        """The AdamW arguments of --optimizer-kwargs.  As in the reference (:89-96) --lr is NOT among them: the rate is
+        AdamW's default 1e-3 unless `--optimizer-kwargs lr VALUE float` is given."""
+        if self.optimizer_str != "AdamW":
+            raise RemoraError(f"--optimizer {self.optimizer_str}: the HIP trainer implements AdamW only")
+        kw = _typed_kwargs(self.opt_kwargs)
+        unknown = sorted(set(kw) - set(self.ADAMW_KWARGS))
+        if unknown:
+            raise RemoraError(f"--optimizer-kwargs {unknown}: the HIP trainer takes {list(self.ADAMW_KWARGS)}")
+        return kw
+
+    def load_optimizer(self, model=None):
+        """A torch AdamW over one dummy parameter with the run's arguments: the scheduler's handle on the learning rate."""
+        torch = _torch()
+        return torch.optim.AdamW([torch.zeros(1, requires_grad=True)], **self.optimizer_kwargs())
+
+    def load_scheduler(self, opt):
+        return CustomPlusCoolDownScheduler(opt, self.learning_rate, self.lr_scheduler_str, self.lr_scheduler_kwargs, epochs=self.epochs,
+                                           cool_down_epochs=self.lr_cool_down_epochs, cool_down_lr=self.lr_cool_down_lr)
+
+
+def scan_model_file(model_path):
+    """The architecture of a `--model` file ("conv_lstm" / "conv_only") from the layer names its classes assign to `self`
+    (detect_arch's rule).  The file is parsed, never imported or executed."""
+    with open(model_path) as fh:
+        try:
+            tree = ast.parse(fh.read(), filename=str(model_path))
+        except SyntaxError as e:
+            raise RemoraError(f"cannot parse model file {model_path}: {e}")
+    names = set()
+    for node in ast.walk(tree):
+        targets = node.targets if isinstance(node, ast.Assign) else [node.target] if isinstance(node, (ast.AnnAssign, ast.AugAssign)) else []
+        for tgt in targets:
+            for t in (tgt.elts if isinstance(tgt, (ast.Tuple, ast.List)) else [tgt]):
+                if isinstance(t, ast.Attribute) and isinstance(t.value, ast.Name) and t.value.id == "self":
+                    names.add(t.attr)
+    return detect_arch(names)
+
+
+# ---- export (src/remora/model_util.py:115-176) ---------------------------------------------------------------------------------
+_META_KEYS = ("kmer_context_bases", "chunk_context", "modified_base_labels", "mod_bases", "reverse_signal", "refine_kmer_center_idx",
+              "refine_do_rough_rescale", "refine_scale_iters", "refine_algo", "refine_half_bandwidth", "base_start_justify", "offset",
+              "pa_scaling", "model_params")
+
+
+def export_model_torchscript(ckpt, state, save_filename):
+    """The model file of the reference: a TorchScript archive of the network (remora_amd.nets, eval mode) holding `state`
+    (a state_dict; default: ckpt["state_dict"]) with the extra file meta.txt built from the checkpoint's entries.  Loads through
+    `load_model` here and through torch.jit.load anywhere."""
+    torch = _torch()
+    from . import nets
+
+    def plain(v):  # JSON has no numpy scalars or arrays
+        if isinstance(v, np.ndarray):
+            return v.tolist()
+        if isinstance(v, np.generic):
+            return v.item()
+        if isinstance(v, (list, tuple)):
+            return [plain(x) for x in v]
+        if isinstance(v, dict):
+            return {k: plain(x) for k, x in v.items()}
+        return v
+
+    script = torch.jit.script(nets.from_state(ckpt["state_dict"] if state is None else state))
+    meta = {"creation_date": datetime.datetime.now().strftime("%m/%d/%Y, %H:%M:%S")}
+    for key in _META_KEYS:
+        meta[key] = plain(ckpt[key])
+    if ckpt["mod_bases"] is not None:
+        for i, name in enumerate(ckpt["mod_long_names"]):
+            meta[f"mod_long_names_{i}"] = str(name)
+    for i, (motif, offset) in enumerate(ckpt["motifs"]):
+        meta[f"motif_{i}"], meta[f"motif_offset_{i}"] = str(motif), str(offset)
+    meta["num_motifs"] = str(len(ckpt["motifs"]))
+    for key in ("refine_kmer_levels", "refine_sd_arr"):  # float32 bytes carried as cp437 text
+        meta[key] = None if ckpt[key] is None else np.asarray(ckpt[key]).astype(np.float32).tobytes().decode("cp437")
+    meta["doc_string"] = "Nanopore Remora model"
+    meta["model_version"] = ckpt.get("model_version", 0)
+    torch.jit.save(script, save_filename, _extra_files={"meta.txt": json.dumps(meta, indent=4)})
