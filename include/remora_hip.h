@@ -823,6 +823,29 @@ int rmr_region_signals(rmr_engine *e, int64_t n_reads, const int16_t *dacs, cons
 int rmr_site_kmer_levels(rmr_engine *e, int64_t n_reads, const int64_t *seq_off, const int64_t *site0, int64_t n_bases,
                          const double *trimmean, const int8_t *int_seq, int kmer_before, int kmer_after, int64_t min_cov,
                          double *levels, int64_t *kmer_sites, int32_t *site_kmer, double *site_level, int64_t *n_sites);
+/* The two stages of rmr_site_kmer_levels as calls of their own, for an input that is aggregated one range of site keys after the
+ * other in bounded device memory (remora_amd.metrics.plan_level_ranges cuts the ranges).  The results are those of one
+ * rmr_site_kmer_levels call over all observations, bit for bit, however the keys are cut and the k-mers grouped.
+ * rmr_site_medians: stage 1 for the range [key_lo, key_hi).  The observations are given as to rmr_site_kmer_levels and must hold
+ * every observation of the input with a key in [key_lo - kmer_before, key_hi + kmer_after) (reads clipped to that interval; more
+ * does no harm): only sites inside [key_lo, key_hi) are reported, the margins supply their neighbours' bases.  Every reported site
+ * is appended as (k-mer index, median) to list_kmer i32 / list_level f64, which hold list_len entries and have room for
+ * list_capacity (a range reports at most min(n_bases, key_hi - key_lo) sites; a call that would overrun fails and leaves
+ * list_len entries valid), in no particular order; *n_appended (host): how many; site_counts i64[4^k] (zeroed by the caller before
+ * the first range) gains the number of appended sites of every k-mer.  32 bytes of scratch per observation, as the one-shot call.
+ * rmr_kmer_levels_from_sites: stage 2 over the n_sites accumulated entries and their site_counts.  levels, kmer_sites (nullable),
+ * site_kmer / site_level (nullable, both or none, capacity n_sites) as rmr_site_kmer_levels writes them.  max_bytes > 0 bounds the
+ * sort buffers (32 bytes per site): consecutive k-mers whose sites fit are sorted together, one group after the other, each group
+ * gathered from the lists (*n_groups, host, nullable: how many); a single k-mer whose sites alone exceed it is refused by name.
+ * 0: everything in one group.  Slots are handed out with one integer atomic per wave, counts are integer atomics; no float atomics.
+ * All array pointers are DEVICE memory.  Synchronous. */
+int rmr_site_medians(rmr_engine *e, int64_t n_reads, const int64_t *seq_off, const int64_t *site0, int64_t n_bases, const double *trimmean,
+                     const int8_t *int_seq, int kmer_before, int kmer_after, int64_t min_cov, int64_t key_lo, int64_t key_hi,
+                     int32_t *list_kmer, double *list_level, int64_t list_len, int64_t list_capacity, int64_t *site_counts,
+                     int64_t *n_appended);
+int rmr_kmer_levels_from_sites(rmr_engine *e, int64_t n_sites, const int32_t *list_kmer, const double *list_level, int kmer_len,
+                               const int64_t *site_counts, int64_t max_bytes, double *levels, int64_t *kmer_sites, int32_t *site_kmer,
+                               double *site_level, int64_t *n_groups);
 
 /* ---- training (L5: `remora model train`) ------------------------------------------------------------------------------
  * One fp32 training step of ConvLSTM_w_ref (models/ConvLSTM_w_ref.py:11-58) on the device: the forward pass with BatchNorm

@@ -344,8 +344,8 @@ def _estimate_kmer_levels(args):
     import numpy as np
 
     from .engine import get_engine
-    from .io import add_site_levels, read_bam_header_bytes
-    from .metrics import SiteLevels, kmer_strings
+    from .io import read_bam_header_bytes, run_site_level_ranges
+    from .metrics import LEVEL_BYTES_PER_BASE, SiteLevels, kmer_strings
     from .refine_signal_map import SigMapRefiner
 
     log = logging.getLogger("Remora")
@@ -359,7 +359,18 @@ def _estimate_kmer_levels(args):
     if not refiner.is_loaded or refiner.scale_iters < 0:
         log.warning("It is highly recommended to apply signal mapping refinement in order to output a valid kmer level table.")
     log.info("--chunk-width, --max-chunk-coverage and --num-workers are ignored: the BAM is streamed once and every read is used")
-    acc = SiteLevels(get_engine(args.device), args.kmer_context_bases, args.min_coverage)
+    import torch
+
+    eng = get_engine(args.device)
+    if not args.levels_device_gib > 0:
+        raise RemoraError("--levels-device-gib must be positive")
+    free = torch.cuda.mem_get_info(eng.torch_device)[0]
+    gib = min(float(args.levels_device_gib), free / 2 / 2**30)
+    max_resident = int(gib * 2**30 // LEVEL_BYTES_PER_BASE)
+    log.info(f"k-mer levels aggregate in {gib:.3g} GiB of device memory ({max_resident} bases at a time; --levels-device-gib "
+             f"{args.levels_device_gib:g}, {free / 2**30:.1f} GiB free)")
+    acc = SiteLevels(eng, args.kmer_context_bases, args.min_coverage, max_resident)
+    pairs = []
     for sample, (pod5_path, bam_path) in enumerate(args.pod5_and_bam):
         hdr = read_bam_header_bytes(bam_path)
         l_text = int.from_bytes(hdr[4:8], "little")
@@ -367,8 +378,10 @@ def _estimate_kmer_levels(args):
             log.warning("Cannot estimate levels from BAM file without mappings or index")
             continue
         log.info(f"Extracting levels from {pod5_path} and {bam_path}")
-        add_site_levels(acc, pod5_path, bam_path, refiner, sample=sample, reads_per_batch=args.reads_per_batch, device=args.device,
-                        reverse_signal=args.reverse_signal)
+        pairs.append((sample, pod5_path, bam_path))
+    n_ranges, _ = run_site_level_ranges(acc, pairs, refiner, reads_per_batch=args.reads_per_batch, device=args.device,
+                                        reverse_signal=args.reverse_signal, log=log.info)
+    log.info(f"Aggregated in {n_ranges} ranges")
     log.info("Aggregating and outputting levels")
     levels, _ = acc.levels()
     if np.isnan(levels).any():
@@ -641,6 +654,10 @@ def build_parser():
                    help="the signal was recorded 3'->5' (direct RNA): build the reads as models with reverse_signal read them. "
                         "The reference's get_site_kmer_levels takes this argument, its command line does not expose it")
     k.add_argument("--reads-per-batch", type=int, default=256)
+    k.add_argument("--levels-device-gib", type=float, default=64.0,
+                   help="GiB of GPU memory the bases aggregated at a time may take (capped at half of what is free): an input that "
+                        "needs more is aggregated one range of reference sites after the other, each with a pass of its own over "
+                        "the input (same table, any input size)")
     k.add_argument("--device", type=int, default=0)
     k.set_defaults(func=_estimate_kmer_levels)
     return ap

@@ -165,6 +165,9 @@ SIGNATURES = {
                                    c_vp, c_vp]),
     "rmr_site_kmer_levels": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_vp,
                                      ctypes.POINTER(c_i64)]),
+    "rmr_site_medians": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp,
+                                 ctypes.POINTER(c_i64)]),
+    "rmr_kmer_levels_from_sites": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64)]),
     "rmr_trainer_create": (c_int, [c_vp, ctypes.POINTER(ModelDesc), c_vp, ctypes.c_size_t, c_i64, ctypes.POINTER(c_vp)]),
     "rmr_trainer_destroy": (None, [c_vp]),
     "rmr_trainer_forward_backward": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(ctypes.c_float), c_vp, c_int]),

@@ -361,13 +361,14 @@ __device__ __forceinline__ int64_t lb_u64(const uint64_t *a, int64_t n, uint64_t
 // skey / idx: the observations ordered by (site, value).  The first observation of every site writes the site's k-mer and the
 // key of its median; every other position (and a site that is not reported) writes NOT_A_SITE.
 __global__ void site_median_kernel(const uint64_t *__restrict__ skey, const uint64_t *__restrict__ idx, int64_t n, const double *__restrict__ vals,
-                                   const int8_t *__restrict__ int_seq, int kb, int ka, int64_t min_cov, uint64_t *__restrict__ kkey,
-                                   uint64_t *__restrict__ mkey) {
+                                   const int8_t *__restrict__ int_seq, int kb, int ka, int64_t min_cov, uint64_t key_lo, uint64_t key_hi,
+                                   uint64_t *__restrict__ kkey, uint64_t *__restrict__ mkey) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     uint64_t kk = NOT_A_SITE, mk = NOT_A_SITE;
     const uint64_t key = skey[p];
-    if (p == 0 || skey[p - 1] != key) {
+    // a site outside [key_lo, key_hi) is a margin of a range: its observations serve the k-mers of its neighbours only
+    if ((p == 0 || skey[p - 1] != key) && key >= key_lo && key < key_hi) {
         const int64_t end = lb_u64(skey, n, key + 1);
         int64_t lo = p, hi = end;  // the finite values stand in front: first position of the site whose value is not finite
         while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (sortable_f64(vals[idx[mid]]) != ~0ULL) lo = mid + 1; else hi = mid; }
@@ -394,11 +395,11 @@ __global__ void site_median_kernel(const uint64_t *__restrict__ skey, const uint
     mkey[p] = mk;
 }
 
-// kkey / mkey ordered by (k-mer, site median): a thread per k-mer
-__global__ void kmer_median_kernel(const uint64_t *__restrict__ kkey, const uint64_t *__restrict__ mkey, int64_t n, int64_t n_kmers,
+// kkey / mkey ordered by (k-mer, site median), holding every site of the k-mers [m0, m1): a thread per k-mer of them
+__global__ void kmer_median_kernel(const uint64_t *__restrict__ kkey, const uint64_t *__restrict__ mkey, int64_t n, int64_t m0, int64_t m1,
                                    double *__restrict__ levels, int64_t *__restrict__ counts) {
-    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= n_kmers) return;
+    const int64_t m = m0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= m1) return;
     const int64_t lo = lb_u64(kkey, n, (uint64_t)m), hi = lb_u64(kkey, n, (uint64_t)m + 1);
     const int64_t c = hi - lo;
     double lv = __longlong_as_double(0x7ff8000000000000LL);
@@ -419,9 +420,68 @@ __global__ void site_list_kernel(const uint64_t *__restrict__ kkey, const uint64
     site_level[p] = unsortable_f64(mkey[p]);
 }
 
-// keys / vals sorted by `keys` (stable) into keys_out / vals_out
-static int sort_pairs(rmr_engine *e, void *tmp, size_t tmp_bytes, uint64_t *keys, uint64_t *keys_out, uint64_t *vals, uint64_t *vals_out, int64_t n) {
-    RMR_HIP(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys_out, vals, vals_out, (size_t)n, 0, 64, e->stream));
+// A slot of an output list for every lane with `mine`, drawn from one cursor with one integer atomic per wave.  The order of the
+// list is whatever the waves' arrival makes it; what is made of the list is sorted by the whole entry, so no result depends on it.
+// Every lane of the wave has to get here.
+__device__ __forceinline__ int64_t wave_slot(bool mine, unsigned long long *cursor) {
+    const unsigned long long mask = __ballot(mine);
+    if (!mask) return -1;
+    const int lane = (int)(threadIdx.x & 63), leader = __ffsll((long long)mask) - 1;
+    unsigned long long base = 0;
+    if (lane == leader) base = atomicAdd(cursor, (unsigned long long)__popcll(mask));
+    base = __shfl(base, leader);
+    return mine ? (int64_t)(base + (unsigned long long)__popcll(mask & ((1ULL << lane) - 1))) : -1;
+}
+
+// the reported sites among kkey / mkey [n] (site_median_kernel) appended to list_kmer / list_level; a slot beyond `capacity` is
+// counted by the cursor and not written
+__global__ void site_append_kernel(const uint64_t *__restrict__ kkey, const uint64_t *__restrict__ mkey, int64_t n, unsigned long long *cursor,
+                                   int64_t capacity, int32_t *__restrict__ list_kmer, double *__restrict__ list_level) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t kk = p < n ? kkey[p] : NOT_A_SITE;
+    const int64_t slot = wave_slot(kk != NOT_A_SITE, cursor);
+    if (slot < 0 || slot >= capacity) return;
+    list_kmer[slot] = (int32_t)kk;
+    list_level[slot] = unsortable_f64(mkey[p]);
+}
+
+// counts[m] += the entries of kmer[n] equal to m (all in [0, n_kmers)): integer atomics, per block in LDS while the table fits
+constexpr int KMER_COUNT_LDS = 4096, KMER_COUNT_BLOCKS = 1024;
+__global__ void kmer_count_kernel(const int32_t *__restrict__ kmer, int64_t n, int64_t n_kmers, unsigned long long *__restrict__ counts) {
+    __shared__ unsigned int h[KMER_COUNT_LDS];
+    const bool in_lds = n_kmers <= KMER_COUNT_LDS;  // a block sees n / gridDim.x < 2^32 entries (n <= 2^39, KMER_COUNT_BLOCKS blocks)
+    if (in_lds) {
+        for (int64_t m = threadIdx.x; m < n_kmers; m += blockDim.x) h[m] = 0;
+        __syncthreads();
+    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t m = kmer[i];
+        if (m < 0 || m >= n_kmers) continue;
+        if (in_lds) atomicAdd(&h[m], 1u);
+        else atomicAdd(&counts[m], 1ULL);
+    }
+    if (in_lds) {
+        __syncthreads();
+        for (int64_t m = threadIdx.x; m < n_kmers; m += blockDim.x)
+            if (h[m]) atomicAdd(&counts[m], (unsigned long long)h[m]);
+    }
+}
+
+// the sites of the k-mers [m0, m1) out of the lists, as sort keys: kkey / mkey [capacity]
+__global__ void kmer_group_gather_kernel(const int32_t *__restrict__ list_kmer, const double *__restrict__ list_level, int64_t n, int64_t m0, int64_t m1,
+                                         unsigned long long *cursor, int64_t capacity, uint64_t *__restrict__ kkey, uint64_t *__restrict__ mkey) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t m = p < n ? (int64_t)list_kmer[p] : -1;
+    const int64_t slot = wave_slot(m >= m0 && m < m1, cursor);
+    if (slot < 0 || slot >= capacity) return;
+    kkey[slot] = (uint64_t)m;
+    mkey[slot] = sortable_f64(list_level[p]);
+}
+
+// keys / vals sorted by bits [0, end_bit) of `keys` (stable) into keys_out / vals_out
+static int sort_pairs(rmr_engine *e, void *tmp, size_t tmp_bytes, uint64_t *keys, uint64_t *keys_out, uint64_t *vals, uint64_t *vals_out, int64_t n,
+                      unsigned end_bit = 64) {
+    RMR_HIP(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys_out, vals, vals_out, (size_t)n, 0, end_bit, e->stream));
     return 0;
 }
 
@@ -435,35 +495,53 @@ struct DevFree {  // the temporaries of one call
     }
 };
 
-int run_site_kmer_levels(rmr_engine *e, int64_t n_reads, const int64_t *seq_off, const int64_t *site0, int64_t n, const double *vals,
-                         const int8_t *int_seq, int kb, int ka, int64_t min_cov, double *levels, int64_t *counts, int32_t *site_kmer,
-                         double *site_level, int64_t *n_sites) {
-    const int64_t n_kmers = (int64_t)1 << (2 * (kb + ka + 1));
-    const unsigned T = 256;
+struct SortBufs {  // four key / payload arrays of `n` 8-byte items and the radix sort's own scratch
     uint64_t *A = nullptr, *B = nullptr, *C = nullptr, *D = nullptr;
     void *tmp = nullptr;
     size_t tmp_bytes = 0;
-    DevFree pool;
-    int64_t sites = 0;
-    if (n > 0) {
+    int get(rmr_engine *e, DevFree &pool, int64_t n) {
         RMR_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, A, B, C, D, (size_t)n, 0, 64, e->stream));
         RMR_TRY(pool.get((void **)&A, n * 8));
         RMR_TRY(pool.get((void **)&B, n * 8));
         RMR_TRY(pool.get((void **)&C, n * 8));
         RMR_TRY(pool.get((void **)&D, n * 8));
         RMR_TRY(pool.get(&tmp, tmp_bytes));
-        const dim3 grid((unsigned)((n + T - 1) / T));
+        return 0;
+    }
+};
+
+// Stage 1, n > 0 observations: the median of every site with a key in [key_lo, key_hi).  -> s.A[p]: the k-mer of the site whose
+// first observation stands at p of the (site, value) order, s.D[p]: the key of its median; NOT_A_SITE everywhere else.
+static int site_stage(rmr_engine *e, SortBufs &s, int64_t n_reads, const int64_t *seq_off, const int64_t *site0, int64_t n, const double *vals,
+                      const int8_t *int_seq, int kb, int ka, int64_t min_cov, uint64_t key_lo, uint64_t key_hi) {
+    const unsigned T = 256;
+    const dim3 grid((unsigned)((n + T - 1) / T));
+    // by value (A: value keys, C: indices -> B, D), then by site (A: site keys of D -> C keys, B indices)
+    hipLaunchKernelGGL(obs_value_keys_kernel, grid, dim3(T), 0, e->stream, vals, n, s.A, s.C);
+    RMR_TRY(sort_pairs(e, s.tmp, s.tmp_bytes, s.A, s.B, s.C, s.D, n));
+    hipLaunchKernelGGL(obs_site_keys_kernel, grid, dim3(T), 0, e->stream, s.D, n, seq_off, n_reads, site0, s.A);
+    RMR_TRY(sort_pairs(e, s.tmp, s.tmp_bytes, s.A, s.C, s.D, s.B, n));
+    // C: sites, B: indices, ordered by (site, value) -> A: k-mer of every site, D: key of its median
+    hipLaunchKernelGGL(site_median_kernel, grid, dim3(T), 0, e->stream, s.C, s.B, n, vals, int_seq, kb, ka, min_cov, key_lo, key_hi, s.A, s.D);
+    RMR_HIP(hipGetLastError());
+    return 0;
+}
+
+int run_site_kmer_levels(rmr_engine *e, int64_t n_reads, const int64_t *seq_off, const int64_t *site0, int64_t n, const double *vals,
+                         const int8_t *int_seq, int kb, int ka, int64_t min_cov, double *levels, int64_t *counts, int32_t *site_kmer,
+                         double *site_level, int64_t *n_sites) {
+    const int64_t n_kmers = (int64_t)1 << (2 * (kb + ka + 1));
+    const unsigned T = 256;
+    SortBufs s;
+    DevFree pool;
+    int64_t sites = 0;
+    if (n > 0) {
+        RMR_TRY(s.get(e, pool, n));
         ProfScope ps(e, K_SITE_KMER_LEVELS);
-        // by value (A: value keys, C: indices -> B, D), then by site (A: site keys of D -> C keys, B indices)
-        hipLaunchKernelGGL(obs_value_keys_kernel, grid, dim3(T), 0, e->stream, vals, n, A, C);
-        RMR_TRY(sort_pairs(e, tmp, tmp_bytes, A, B, C, D, n));
-        hipLaunchKernelGGL(obs_site_keys_kernel, grid, dim3(T), 0, e->stream, D, n, seq_off, n_reads, site0, A);
-        RMR_TRY(sort_pairs(e, tmp, tmp_bytes, A, C, D, B, n));
-        // C: sites, B: indices, ordered by (site, value) -> A: k-mer of every site, D: key of its median
-        hipLaunchKernelGGL(site_median_kernel, grid, dim3(T), 0, e->stream, C, B, n, vals, int_seq, kb, ka, min_cov, A, D);
+        RMR_TRY(site_stage(e, s, n_reads, seq_off, site0, n, vals, int_seq, kb, ka, min_cov, 0, NOT_A_SITE));
         // by median (D keys, A payload -> B, C), then by k-mer (C keys, B payload -> A, D)
-        RMR_TRY(sort_pairs(e, tmp, tmp_bytes, D, B, A, C, n));
-        RMR_TRY(sort_pairs(e, tmp, tmp_bytes, C, A, B, D, n));
+        RMR_TRY(sort_pairs(e, s.tmp, s.tmp_bytes, s.D, s.B, s.A, s.C, n));
+        RMR_TRY(sort_pairs(e, s.tmp, s.tmp_bytes, s.C, s.A, s.B, s.D, n));
         RMR_HIP(hipGetLastError());
     }
     // A: k-mers ascending (NOT_A_SITE last), D: their sites' medians ascending inside each k-mer
@@ -471,7 +549,8 @@ int run_site_kmer_levels(rmr_engine *e, int64_t n_reads, const int64_t *seq_off,
     if (!cnt) RMR_TRY(pool.get((void **)&cnt, n_kmers * 8));
     {
         ProfScope ps(e, K_SITE_KMER_LEVELS);
-        hipLaunchKernelGGL(kmer_median_kernel, dim3((unsigned)((n_kmers + T - 1) / T)), dim3(T), 0, e->stream, A, D, n, n_kmers, levels, cnt);
+        hipLaunchKernelGGL(kmer_median_kernel, dim3((unsigned)((n_kmers + T - 1) / T)), dim3(T), 0, e->stream, s.A, s.D, n, (int64_t)0, n_kmers, levels,
+                           cnt);
         RMR_HIP(hipGetLastError());
     }
     if (n > 0 && (site_kmer || n_sites)) {  // the reported sites stand in front of A / D: as many as the k-mers count together
@@ -480,11 +559,127 @@ int run_site_kmer_levels(rmr_engine *e, int64_t n_reads, const int64_t *seq_off,
         RMR_HIP(hipStreamSynchronize(e->stream));
         for (int64_t c : h) sites += c;
         if (site_kmer && sites > 0) {
-            hipLaunchKernelGGL(site_list_kernel, dim3((unsigned)((sites + T - 1) / T)), dim3(T), 0, e->stream, A, D, sites, site_kmer, site_level);
+            hipLaunchKernelGGL(site_list_kernel, dim3((unsigned)((sites + T - 1) / T)), dim3(T), 0, e->stream, s.A, s.D, sites, site_kmer, site_level);
             RMR_HIP(hipGetLastError());
         }
     }
     if (n_sites) *n_sites = sites;
+    RMR_HIP(hipStreamSynchronize(e->stream));  // the temporaries are freed on return
+    return 0;
+}
+
+// Stage 1 alone, for one range of the key space: the sites of [key_lo, key_hi) join the caller's lists and its counts per k-mer
+int run_site_medians(rmr_engine *e, int64_t n_reads, const int64_t *seq_off, const int64_t *site0, int64_t n, const double *vals,
+                     const int8_t *int_seq, int kb, int ka, int64_t min_cov, uint64_t key_lo, uint64_t key_hi, int32_t *list_kmer,
+                     double *list_level, int64_t list_len, int64_t capacity, int64_t *site_counts, int64_t *n_appended) {
+    const int64_t n_kmers = (int64_t)1 << (2 * (kb + ka + 1));
+    const unsigned T = 256;
+    *n_appended = 0;
+    if (n == 0) return 0;
+    SortBufs s;
+    DevFree pool;
+    unsigned long long *cursor = nullptr, took = 0;
+    RMR_TRY(s.get(e, pool, n));
+    RMR_TRY(pool.get((void **)&cursor, 8));
+    {
+        ProfScope ps(e, K_SITE_KMER_LEVELS);
+        RMR_HIP(hipMemsetAsync(cursor, 0, 8, e->stream));
+        RMR_TRY(site_stage(e, s, n_reads, seq_off, site0, n, vals, int_seq, kb, ka, min_cov, key_lo, key_hi));
+        hipLaunchKernelGGL(site_append_kernel, dim3((unsigned)((n + T - 1) / T)), dim3(T), 0, e->stream, s.A, s.D, n, cursor, capacity - list_len,
+                           list_kmer + list_len, list_level + list_len);
+        RMR_HIP(hipGetLastError());
+    }
+    RMR_HIP(hipMemcpyAsync(&took, cursor, 8, hipMemcpyDeviceToHost, e->stream));
+    RMR_HIP(hipStreamSynchronize(e->stream));
+    if ((int64_t)took > capacity - list_len)
+        RMR_FAIL(RMR_ERR_INVALID, "rmr_site_medians: the range reports %lld sites, the lists have room for %lld", (long long)took,
+                 (long long)(capacity - list_len));
+    if (took) {
+        ProfScope ps(e, K_SITE_KMER_LEVELS);
+        const int64_t blocks = std::min<int64_t>(((int64_t)took + T - 1) / T, KMER_COUNT_BLOCKS);
+        hipLaunchKernelGGL(kmer_count_kernel, dim3((unsigned)blocks), dim3(T), 0, e->stream, list_kmer + list_len, (int64_t)took, n_kmers,
+                           (unsigned long long *)site_counts);
+        RMR_HIP(hipGetLastError());
+    }
+    *n_appended = (int64_t)took;
+    RMR_HIP(hipStreamSynchronize(e->stream));  // the temporaries are freed on return
+    return 0;
+}
+
+static void kmer_letters(int64_t m, int k, char *out) {
+    for (int j = k - 1; j >= 0; --j, m >>= 2) out[j] = "ACGT"[m & 3];
+    out[k] = 0;
+}
+
+// Stage 2: the lists of every range -> the table, group by group of consecutive k-mers whose sites fit `max_bytes` of sort buffers
+int run_kmer_levels_from_sites(rmr_engine *e, int64_t n_sites, const int32_t *list_kmer, const double *list_level, int k, const int64_t *site_counts,
+                               int64_t max_bytes, double *levels, int64_t *kmer_sites, int32_t *site_kmer, double *site_level, int64_t *n_groups) {
+    const int64_t n_kmers = (int64_t)1 << (2 * k), BYTES_PER_SITE = 32;
+    const unsigned T = 256;
+    std::vector<int64_t> h((size_t)n_kmers);
+    RMR_HIP(hipMemcpyAsync(h.data(), site_counts, n_kmers * 8, hipMemcpyDeviceToHost, e->stream));
+    RMR_HIP(hipStreamSynchronize(e->stream));
+    int64_t total = 0;
+    for (int64_t c : h) {
+        if (c < 0 || c > n_sites) RMR_FAIL(RMR_ERR_INVALID, "rmr_kmer_levels_from_sites: a site count of %lld among %lld sites", (long long)c, (long long)n_sites);
+        total += c;
+    }
+    if (total != n_sites)
+        RMR_FAIL(RMR_ERR_INVALID, "rmr_kmer_levels_from_sites: the counts hold %lld sites, the lists %lld", (long long)total, (long long)n_sites);
+    const int64_t room = max_bytes > 0 ? max_bytes / BYTES_PER_SITE : n_sites;
+    std::vector<int64_t> cut{0};  // k-mers [cut[g], cut[g + 1]) are sorted together
+    int64_t most = 0;
+    for (int64_t m0 = 0; m0 < n_kmers;) {
+        int64_t m1 = m0, g = 0;
+        while (m1 < n_kmers && g + h[m1] <= room) g += h[m1++];
+        if (m1 == m0) {
+            char name[RMR_MAX_LEVEL_KMER + 1];
+            kmer_letters(m0, k, name);
+            RMR_FAIL(RMR_ERR_INVALID, "k-mer levels: the %lld sites of k-mer %s (index %lld) need %lld bytes of sort buffers, the budget is %lld",
+                     (long long)h[m0], name, (long long)m0, (long long)(h[m0] * BYTES_PER_SITE), (long long)max_bytes);
+        }
+        most = std::max(most, g);
+        cut.push_back(m1);
+        m0 = m1;
+    }
+    if (n_groups) *n_groups = (int64_t)cut.size() - 1;
+    SortBufs s;
+    DevFree pool;
+    unsigned long long *cursor = nullptr;
+    if (most > 0) RMR_TRY(s.get(e, pool, most));
+    RMR_TRY(pool.get((void **)&cursor, 8));
+    int64_t base = 0;
+    for (size_t gi = 0; gi + 1 < cut.size(); ++gi) {
+        const int64_t m0 = cut[gi], m1 = cut[gi + 1];
+        int64_t g = 0;
+        for (int64_t m = m0; m < m1; ++m) g += h[m];
+        if (g > 0) {
+            unsigned long long took = 0;
+            {
+                ProfScope ps(e, K_SITE_KMER_LEVELS);
+                RMR_HIP(hipMemsetAsync(cursor, 0, 8, e->stream));
+                hipLaunchKernelGGL(kmer_group_gather_kernel, dim3((unsigned)((n_sites + T - 1) / T)), dim3(T), 0, e->stream, list_kmer, list_level, n_sites,
+                                   m0, m1, cursor, g, s.A, s.C);
+                RMR_HIP(hipGetLastError());
+            }
+            RMR_HIP(hipMemcpyAsync(&took, cursor, 8, hipMemcpyDeviceToHost, e->stream));
+            RMR_HIP(hipStreamSynchronize(e->stream));
+            if ((int64_t)took != g)
+                RMR_FAIL(RMR_ERR_INVALID, "rmr_kmer_levels_from_sites: the lists hold %lld sites of k-mers %lld..%lld, the counts %lld", (long long)took,
+                         (long long)m0, (long long)m1 - 1, (long long)g);
+        }
+        ProfScope ps(e, K_SITE_KMER_LEVELS);
+        if (g > 0) {
+            // A: k-mers, C: keys of the medians.  By median (C keys, A payload -> B, D), then by k-mer (D keys, B payload -> A, C)
+            RMR_TRY(sort_pairs(e, s.tmp, s.tmp_bytes, s.C, s.B, s.A, s.D, g));
+            RMR_TRY(sort_pairs(e, s.tmp, s.tmp_bytes, s.D, s.A, s.B, s.C, g, (unsigned)(2 * k)));
+        }
+        hipLaunchKernelGGL(kmer_median_kernel, dim3((unsigned)((m1 - m0 + T - 1) / T)), dim3(T), 0, e->stream, s.A, s.C, g, m0, m1, levels, kmer_sites);
+        if (site_kmer && g > 0)
+            hipLaunchKernelGGL(site_list_kernel, dim3((unsigned)((g + T - 1) / T)), dim3(T), 0, e->stream, s.A, s.C, g, site_kmer + base, site_level + base);
+        RMR_HIP(hipGetLastError());
+        base += g;
+    }
     RMR_HIP(hipStreamSynchronize(e->stream));  // the temporaries are freed on return
     return 0;
 }
@@ -567,6 +762,38 @@ int rmr_site_kmer_levels(rmr_engine *e, int64_t n_reads, const int64_t *seq_off,
     RMR_HIP(hipSetDevice(e->device));
     return run_site_kmer_levels(e, n_reads, seq_off, site0, n_bases, trimmean, int_seq, kmer_before, kmer_after, min_cov, levels, kmer_sites,
                                 site_kmer, site_level, n_sites);
+}
+
+int rmr_site_medians(rmr_engine *e, int64_t n_reads, const int64_t *seq_off, const int64_t *site0, int64_t n_bases, const double *trimmean,
+                     const int8_t *int_seq, int kmer_before, int kmer_after, int64_t min_cov, int64_t key_lo, int64_t key_hi,
+                     int32_t *list_kmer, double *list_level, int64_t list_len, int64_t list_capacity, int64_t *site_counts,
+                     int64_t *n_appended) {
+    if (!e || !site_counts || !n_appended) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if (kmer_before < 0 || kmer_after < 0 || kmer_before + kmer_after + 1 > RMR_MAX_LEVEL_KMER)
+        RMR_FAIL(RMR_ERR_INVALID, "k-mers of 1 to %d bases are supported, got %d + 1 + %d", RMR_MAX_LEVEL_KMER, kmer_before, kmer_after);
+    if (n_reads < 0 || n_bases < 0 || n_bases > 0x7fffffffLL * 256) RMR_FAIL(RMR_ERR_INVALID, "bad n_reads / n_bases");
+    if (n_bases > 0 && (!seq_off || !site0 || !trimmean || !int_seq || n_reads == 0)) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if (key_lo < 0 || key_hi < key_lo) RMR_FAIL(RMR_ERR_INVALID, "bad key range [%lld, %lld)", (long long)key_lo, (long long)key_hi);
+    if (list_len < 0 || list_capacity < list_len) RMR_FAIL(RMR_ERR_INVALID, "bad list_len / list_capacity");
+    if (list_capacity > list_len && (!list_kmer || !list_level)) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    return run_site_medians(e, n_reads, seq_off, site0, n_bases, trimmean, int_seq, kmer_before, kmer_after, min_cov, (uint64_t)key_lo,
+                            (uint64_t)key_hi, list_kmer, list_level, list_len, list_capacity, site_counts, n_appended);
+}
+
+int rmr_kmer_levels_from_sites(rmr_engine *e, int64_t n_sites, const int32_t *list_kmer, const double *list_level, int kmer_len,
+                               const int64_t *site_counts, int64_t max_bytes, double *levels, int64_t *kmer_sites, int32_t *site_kmer,
+                               double *site_level, int64_t *n_groups) {
+    if (!e || !levels || !site_counts) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if (kmer_len < 1 || kmer_len > RMR_MAX_LEVEL_KMER) RMR_FAIL(RMR_ERR_INVALID, "k-mers of 1 to %d bases are supported, got %d", RMR_MAX_LEVEL_KMER, kmer_len);
+    if (n_sites < 0 || n_sites > 0x7fffffffLL * 256 || max_bytes < 0) RMR_FAIL(RMR_ERR_INVALID, "bad n_sites / max_bytes");
+    if (n_sites > 0 && (!list_kmer || !list_level)) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if ((site_kmer == nullptr) != (site_level == nullptr)) RMR_FAIL(RMR_ERR_INVALID, "site_kmer and site_level go together");
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    return run_kmer_levels_from_sites(e, n_sites, list_kmer, list_level, kmer_len, site_counts, max_bytes, levels, kmer_sites, site_kmer, site_level,
+                                      n_groups);
 }
 
 }  // extern "C"

@@ -2203,11 +2203,13 @@ def _readahead(gen, depth=2):
 
 
 def iter_ingest_batches(pod5_path, bam_path, pa_scaling=None, skip_non_primary=True, batch=256, shard=None, device=None,
-                        ref_anchored=False, reverse_signal=False):
+                        ref_anchored=False, reverse_signal=False, select=None):
     """The batch form of iter_reads_from_pod5_and_bam for calling of forward or (`reverse_signal`) reversed signal, anchored on
     the basecalls or (`ref_anchored`) on the reference bases of the alignments: IngestBatch objects
     (arrays on the GPU) instead of (io.Read, error) pairs; a batch the array form does not cover comes as the list of
-    (io.Read, error) pairs the per-read path yields for its records."""
+    (io.Read, error) pairs the per-read path yields for its records.  `select(rb)` -> bool per record of a raw batch: only
+    these records are ingested (_ingest_batch), a batch with none is passed over; the per-read form of a batch still holds
+    all of its records."""
     from .engine import get_ingest_engine
 
     signals = Pod5File(pod5_path)
@@ -2215,8 +2217,11 @@ def iter_ingest_batches(pod5_path, bam_path, pa_scaling=None, skip_non_primary=T
     raw_batches = iter_bam_raw_batches(bam_path, want_ref=bool(ref_anchored), batch=batch, shard=shard)
     raw_batches = _readahead(raw_batches, 2)  # the native parser releases the GIL: BAM batches are read one ahead
     for rb, records in raw_batches:
+        picked = None if select is None else select(rb)
+        if picked is not None and not picked.any():
+            continue
         got = _ingest_batch(rb, records, signals, eng, pa_scaling, skip_non_primary, ref_anchored=ref_anchored,
-                            reverse_signal=reverse_signal)
+                            reverse_signal=reverse_signal, select=picked)
         if got is None:
             continue
         per_read = lambda rb=rb: list(_reads_of_records(records(rb), signals, eng, bool(reverse_signal), pa_scaling, skip_non_primary,  # noqa: E731
@@ -2228,23 +2233,69 @@ def iter_ingest_batches(pod5_path, bam_path, pa_scaling=None, skip_non_primary=T
         yield got
 
 
+def _level_records_of_batch(rb, sample):
+    """(eligible bool[rb.n], key0 int64[rb.n], span int64[rb.n]) of a raw BAM batch read with its CIGARs: the records the levels
+    pass would try - primary, mapped, on a contig, spanning reference - with the key of their first base and the reference
+    positions they span (0 / 0 for the others)."""
+    from .metrics import site_key0
+    from .region_metrics import _ref_lens_of_batch
+
+    span = _ref_lens_of_batch(rb)
+    ok = ((rb.flag & 0x904) == 0) & (rb.ref_id >= 0) & (rb.pos >= 0) & (span > 0)
+    key0, span = np.zeros(rb.n, np.int64), np.where(ok, span, 0)
+    key0[ok] = site_key0(sample, rb.ref_id[ok], (rb.flag[ok] & 16) != 0, rb.pos[ok], span[ok])
+    return ok, key0, span
+
+
+def count_site_level_reads(bam_path, sample=0, reads_per_batch=4096):
+    """The counting pass of k-mer levels in ranges: one stream over `bam_path` that decodes no signal.  -> (key0, span) int64
+    arrays, one entry per record the levels pass would try (_level_records_of_batch).  A record that drops out there (no
+    signal, no move table or MD tag, rejected by the refiner) only makes the plan made from these an upper bound."""
+    keys, spans = [], []
+    for rb, _ in iter_bam_raw_batches(bam_path, want_ref=False, batch=reads_per_batch):
+        ok, key0, span = _level_records_of_batch(rb, sample)
+        keys.append(key0[ok])
+        spans.append(span[ok])
+    cat = lambda xs: np.concatenate(xs) if xs else np.zeros(0, np.int64)  # noqa: E731
+    return cat(keys), cat(spans)
+
+
 def add_site_levels(acc, pod5_path, bam_path, sig_map_refiner, start_trim=1, end_trim=1, sample=0, reads_per_batch=256, device=None,
-                    reverse_signal=False):
+                    reverse_signal=False, key_range=None):
     """One streaming pass over `bam_path`: every primary, mapped read with a move table and an MD tag is anchored on its
     reference bases (iter_ingest_batches, ref_anchored), its signal mapping refined as Read.set_refine_signal_mapping(..,
     ref_mapping=True) does (src/remora/io.py:861-863), and the trimmed mean of every base joins `acc` (metrics.SiteLevels) on
     the device.  A batch the array ingest or the resident refinement does not cover (a read whose band
     the refiner rejects) goes read by read through the same kernels; a read that cannot be anchored or refined is left out,
     as `missing_ok` / the reference's per-read errors leave it out.  `reverse_signal`: the reads are built as
-    io.Read.from_pod5 / add_alignment build them with reverse_signal=True (signal recorded 3'->5').  -> number of reads used."""
+    io.Read.from_pod5 / add_alignment build them with reverse_signal=True (signal recorded 3'->5').
+    `key_range` (a, b): the pass of one range of site keys (`acc` made with max_resident_bases, between its begin_range(a, b)
+    and end_range()): only records whose bases meet [a - kb, b + ka) are ingested - the signals of the others are never
+    decoded -, acc.add keeps the part of every read that lies there (metrics.clip_to_key_range, on either path), and a read
+    whose base count is not the reference span the counting pass saw (count_site_level_reads) is an error.
+    -> number of reads used."""
     from .data_chunks import DeviceReads
     from .metrics import site_key0
 
     refiner = sig_map_refiner
     loaded = refiner is not None and getattr(refiner, "is_loaded", False)
     used = 0
+    select = None
+    if key_range is not None:
+        lo, hi = int(key_range[0]) - acc.kb, int(key_range[1]) + acc.ka
+
+        def select(rb):
+            ok, key0, span = _level_records_of_batch(rb, sample)
+            return ok & (key0 < hi) & (key0 + span > lo)
+
+    def planned(lens, spans):
+        if key_range is not None and not np.array_equal(lens, spans):
+            at = int(np.nonzero(np.asarray(lens) != np.asarray(spans))[0][0])
+            raise RemoraError(f"k-mer levels in ranges: a read of {bam_path} has {int(lens[at])} reference bases where its CIGAR spans "
+                              f"{int(spans[at])}: the ranges were planned from the spans")
+
     for item in iter_ingest_batches(pod5_path, bam_path, batch=reads_per_batch, device=device, ref_anchored=True,
-                                    reverse_signal=reverse_signal):
+                                    reverse_signal=reverse_signal, select=select):
         if isinstance(item, IngestBatch):
             if not item.good.size:
                 continue
@@ -2258,6 +2309,8 @@ def add_site_levels(acc, pod5_path, bam_path, sig_map_refiner, start_trim=1, end
                 pairs = item.per_read()
             else:
                 rb, gk, lens = item.rb, item.keep[item.good], np.diff(item.seq_off)
+                if key_range is not None:
+                    planned(lens, _level_records_of_batch(rb, sample)[2][gk])
                 acc.add(dr.per_base_metrics("dwell_trimmean", start_trim, end_trim)["trimmean"], dr.iseq,
                         site_key0(sample, rb.ref_id[gk], (rb.flag[gk] & 16) != 0, rb.pos[gk], lens), lens)
                 used += int(lens.size)
@@ -2280,25 +2333,60 @@ def add_site_levels(acc, pod5_path, bam_path, sig_map_refiner, start_trim=1, end
             continue
         dr = DeviceReads(rrs, get_engine(device))
         lens = np.diff(dr.seq_off)
+        planned(lens, [(c.reference_end or c.reference_start) - c.reference_start for c in recs])
         acc.add(dr.per_base_metrics("dwell_trimmean", start_trim, end_trim)["trimmean"], dr.iseq,
                 site_key0(sample, [c.reference_id for c in recs], [c.is_reverse for c in recs], [c.reference_start for c in recs], lens), lens)
         used += int(lens.size)
     return used
 
 
+def run_site_level_ranges(acc, pairs, sig_map_refiner, start_trim=1, end_trim=1, reads_per_batch=256, device=None, reverse_signal=False,
+                          log=None):
+    """k-mer levels of the (sample, pod5, bam) triples `pairs` in bounded device memory: the counting pass over every BAM, the
+    ranges (metrics.plan_level_ranges with acc.max_resident_bases), then one add_site_levels pass per range and pair whose
+    sample has reads on the range's keys.  `acc`: a SiteLevels made with max_resident_bases; acc.levels() afterwards.
+    -> (number of ranges, reads used, counted over the ranges a read lies on)."""
+    from .metrics import plan_level_ranges
+
+    counted = {sample: count_site_level_reads(bam, sample) for sample, _, bam in pairs}
+    key0 = np.concatenate([k for k, _ in counted.values()]) if counted else np.zeros(0, np.int64)
+    span = np.concatenate([s for _, s in counted.values()]) if counted else np.zeros(0, np.int64)
+    cuts = plan_level_ranges(key0, span, acc.max_resident_bases, acc.kb, acc.ka)
+    n_ranges = int(cuts.size) - 1
+    if log is not None:
+        log(f"k-mer levels: {int(span.sum())} bases of {int(span.size)} alignments in {n_ranges} ranges of at most {acc.max_resident_bases} "
+            f"resident bases")
+    used = 0
+    for a, b in zip(cuts[:-1].tolist(), cuts[1:].tolist()):
+        acc.begin_range(a, b)
+        for sample, pod5, bam in pairs:
+            k, s = counted[sample]
+            if not ((k < b + acc.ka) & (k + s > a - acc.kb)).any():
+                continue
+            used += add_site_levels(acc, pod5, bam, sig_map_refiner, start_trim, end_trim, sample=sample, reads_per_batch=reads_per_batch,
+                                    device=device, reverse_signal=reverse_signal, key_range=(a, b))
+        acc.end_range()
+    return n_ranges, used
+
+
 def get_site_kmer_levels(pod5_path, bam_path, sig_map_refiner, kmer_context_bases, min_cov=10, chunk_len=None, max_chunk_cov=None,
-                         start_trim=1, end_trim=1, num_workers=1, reverse_signal=False, device=None):
+                         start_trim=1, end_trim=1, num_workers=1, reverse_signal=False, device=None, max_resident_bases=None):
     """{k-mer: float64 array of the levels of its reference sites, ascending} for every k-mer over ACGT
     (src/remora/io.py:991-1044).  A site's level is the median over the reads of the trimmed mean of the base on it; sites with
     fewer than `min_cov` finite values are left out.  Computed on the GPU in one streaming pass over the BAM (add_site_levels,
     metrics.SiteLevels), every read used: where the reference walks an indexed BAM in regions of `chunk_len` bases and
     sub-samples a region whose mean coverage exceeds `max_chunk_cov`, both arguments are accepted and ignored here (no index is
     needed; the results are the reference's whenever no region exceeds that coverage); `num_workers` likewise.
-    `reverse_signal` (src/remora/io.py:1002): the levels of reads built with reverse_signal=True - direct RNA."""
+    `reverse_signal` (src/remora/io.py:1002): the levels of reads built with reverse_signal=True - direct RNA.
+    `max_resident_bases`: at most that many bases of the input on the device at a time (run_site_level_ranges: a counting pass,
+    then one pass per range of site keys); the same arrays, to the bit, for an input of any size."""
     from .metrics import SiteLevels, kmer_strings
 
-    acc = SiteLevels(get_engine(device), kmer_context_bases, min_cov)
-    add_site_levels(acc, pod5_path, bam_path, sig_map_refiner, start_trim, end_trim, device=device, reverse_signal=reverse_signal)
+    acc = SiteLevels(get_engine(device), kmer_context_bases, min_cov, max_resident_bases)
+    if max_resident_bases is None:
+        add_site_levels(acc, pod5_path, bam_path, sig_map_refiner, start_trim, end_trim, device=device, reverse_signal=reverse_signal)
+    else:
+        run_site_level_ranges(acc, [(0, pod5_path, bam_path)], sig_map_refiner, start_trim, end_trim, device=device, reverse_signal=reverse_signal)
     _, counts, _, site_level = acc.levels(want_sites=True)
     bounds = np.concatenate([[0], np.cumsum(counts)])
     return {kmer: site_level[bounds[i] : bounds[i + 1]] for i, kmer in enumerate(kmer_strings(acc.kmer_len))}
