@@ -144,6 +144,10 @@ int pipeline_stream16(rmr_model *m, const ChunkArrays &in, int64_t n, float *log
     const int sz = m->desc.size, L = m->L, EC = 4 * m->desc.kmer_len;
     const size_t front_fl = (size_t)(m->P1 + m->P2) * 16;
     const size_t cat_el = (size_t)m->P3 * 2 * sz, x_el = (size_t)m->T * sz;
+    // a chunk length one of the three convolutions refuses is refused here, before the front kernels are queued
+    RMR_TRY(check_conv_stream16(m->sig3, m->P2));
+    RMR_TRY(check_conv_stream16(m->seq2, m->P1));
+    RMR_TRY(check_conv_stream16(m->merge1, m->P3));
     return for_subbatches(e, 131072, n, front_fl * sizeof(float) + (cat_el + x_el) * sizeof(uint16_t) + 64, [&](int64_t c0, int64_t nb, int64_t sb) -> int {
         float *seq1 = reinterpret_cast<float *>(e->act.ptr);
         float *sig2 = seq1 + (size_t)nb * m->P1 * 16;

@@ -135,6 +135,18 @@ __global__ __launch_bounds__(512) void conv_stream16_kernel(ConvS16Args a) {
     }
 }
 
+// LDS bytes of an iteration of cb chunks: their rows + the rows a padded k-step and a clamped column may touch
+size_t conv16_lds(const ConvLayer &c, int pin, int cb) { return ((size_t)cb * pin + c.kw + 2) * (c.ic * 2 + 16); }
+
+// (cb > 1 always fits: launch_conv16_t only takes several chunks where their rows stay within 64 KiB)
+int conv16_fits(const ConvLayer &c, int pin, int cb) {
+    const size_t lds = conv16_lds(c, pin, cb);
+    if (lds > 160 * 1024 - 256)
+        RMR_FAIL(RMR_ERR_INVALID, "conv layer %d -> %d channels: one chunk of %d positions needs %zu B of LDS (chunk contexts this long run in "
+                                  "fp32 for networks of more than 64 channels)", c.ic, c.oc, pin, lds);
+    return 0;
+}
+
 template <int STRIDE, bool F16, bool IN16>
 int launch_conv16_t(rmr_engine *e, const ConvLayer &c, const void *in, int pin, uint16_t *out, int out_row, int out_coff, int pout, int64_t n) {
     const int OT = c.oc / 16;
@@ -158,10 +170,8 @@ int launch_conv16_t(rmr_engine *e, const ConvLayer &c, const void *in, int pin, 
         if (eff > best + 1e-9) { best = eff; cb = k; }
     }
     while (cb > 1 && (n + cb - 1) / cb < e->num_cus) cb = (cb + 1) / 2;  // a small batch spread over the CUs
-    const size_t lds = ((size_t)cb * pin + c.kw + 2) * rb;  // + the rows a padded k-step and a clamped column may touch
-    if (lds > 160 * 1024 - 256)
-        RMR_FAIL(RMR_ERR_INVALID, "conv layer %d -> %d channels: one chunk of %d positions needs %zu B of LDS (chunk contexts this long run in "
-                                  "fp32 for networks of more than 64 channels)", c.ic, c.oc, pin, lds);
+    const size_t lds = conv16_lds(c, pin, cb);
+    RMR_TRY(conv16_fits(c, pin, cb));
     ConvS16Args a;
     a.in = in; a.out = out; a.apack = reinterpret_cast<const uint4 *>(c.apack16); a.bias = c.bias; a.n = n;
     a.ic = c.ic; a.oc = c.oc; a.ks = (c.kw * c.ic + 31) / 32;
@@ -180,6 +190,10 @@ int launch_conv16_t(rmr_engine *e, const ConvLayer &c, const void *in, int pin, 
 }
 
 }  // namespace
+
+// launch_conv16_t's refusal of a chunk too long for a block's LDS, asked before anything is launched: pipeline_stream16 would
+// otherwise have queued the front kernels and two convolutions of a batch whose merge_conv1 it then refuses
+int check_conv_stream16(const ConvLayer &c, int pin) { return conv16_fits(c, pin, 1); }
 
 // `in16`: the input rows are 16-bit (cat); otherwise fp32 (the front kernels' sig2 / seq1, 16 channels)
 int launch_conv_stream16(rmr_model *m, const ConvLayer &c, const void *in, bool in16, int pin, uint16_t *out, int out_row, int out_coff, int pout,

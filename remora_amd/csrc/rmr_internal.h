@@ -292,6 +292,7 @@ int launch_lstm_stream(rmr_model *m, const float *x, int64_t n, float *logits);
 // k_stream16.hip: the same network in the 16-bit dtypes (activations 16-bit in HBM between the launches)
 int launch_conv_stream16(rmr_model *m, const ConvLayer &c, const void *in, bool in16, int pin, uint16_t *out, int out_row, int out_coff, int pout,
                          int64_t n);
+int check_conv_stream16(const ConvLayer &c, int pin);  // whether one chunk of `pin` input rows fits a block's LDS (else the refusal by name)
 int launch_lstm_stream16(rmr_model *m, const uint16_t *x, int64_t n, float *logits);
 int launch_lstm_head_split(rmr_model *m, const float *x, int64_t n, float *logits);
 int launch_conv_split(rmr_engine *e, const ConvLayer &c, int np, const float *in, int in_row, int pin,

@@ -61,15 +61,16 @@ def float64_logits(state, sig, enc):
         return frozen(torch_ref.from_state(state).double()(torch.tensor(sig).double(), torch.tensor(enc).double()).numpy())
 
 
-def bf16_emulated_errors(state, sig, enc, exact, sites=STREAM16_SITES):
-    """|emulated bf16 logits - float64| for the four `prescale` draws of oracle.lowp_emulation (one array per draw)."""
+def bf16_emulated_errors(state, sig, enc, exact, sites=STREAM16_SITES, fmt="bf16"):
+    """|emulated 16-bit logits - float64| for the four `prescale` draws of oracle.lowp_emulation (one array per draw); `fmt`: "bf16"
+    or "f16"."""
     import torch
 
     from oracle import lowp_emulation, torch_ref
 
     net = torch_ref.from_state(state)
     with torch.no_grad():
-        return [frozen(np.abs(lowp_emulation.forward(net, torch.tensor(sig), torch.tensor(enc), sites=sites, fmt="bf16", prescale=ps).numpy() - exact))
+        return [frozen(np.abs(lowp_emulation.forward(net, torch.tensor(sig), torch.tensor(enc), sites=sites, fmt=fmt, prescale=ps).numpy() - exact))
                 for ps in PRESCALES]
 
 

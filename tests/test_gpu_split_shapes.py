@@ -9,6 +9,7 @@ tests/test_gpu_lstm_heads.py (GATE, assert_bf16_statistics), whose helpers are u
 import numpy as np
 import pytest
 
+from stream_cases import layer_rows
 from test_gpu_lstm_heads import (GATE, KCB, assert_bf16_statistics, assert_gate, bf16_emulated_errors, bits, chunk_case, float64_logits,
                                  infer, make_model)
 
@@ -20,15 +21,6 @@ SPLIT_DTYPES = ("bf16x6", "bf16x3", "f16x3")
 # chunks per convolution iteration and the LSTM's groups of sixteen
 SUB_BATCHES = ((0, 1), (5, 3), (7, 15), (100, 16), (300, 17), (700, 257))
 _cases = {}
-
-
-def layer_rows(L):
-    """Rows of sig_conv1 / seq_conv1 (P1), sig_conv2 (P2), sig_conv3 / seq_conv2 (P3) and merge_conv1 = LSTM steps (T)."""
-    P1 = L - 4
-    P2 = P1 - 4
-    P3 = (P2 - 9) // 3 + 1
-    assert (P1 - 13) // 3 + 1 == P3
-    return P1, P2, P3, P3 - 4
 
 
 def conv_split_plan(ic, pin, nparts):
