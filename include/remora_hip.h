@@ -876,6 +876,12 @@ void rmr_trainer_destroy(rmr_trainer *t);
  * NULL (rows with 0 leave the loss and still take part in BatchNorm: --high-conf-incorrect-thr-frac); all four in `mem`.
  * Fills the gradient buffer, moves the running statistics, *loss (HOST) = mean cross-entropy; logits f32[n][num_out] (in
  * `mem`) or NULL.  Synchronous.
+ * A label outside 0..num_out-1 in a row of the loss (torch raises there) is refused by name, RMR_ERR_INVALID "label ... of chunk
+ * ... is outside 0..num_out-1", with the gradients, the running statistics, the batch counter and *loss left as they were;
+ * rows the mask drops may hold any label.  HOST labels are checked before anything is staged or launched.  DEVICE labels are
+ * checked by the step's first kernel, which leaves the first such row beside the row count; the kernels that write a gradient
+ * or a running statistic read that record and hold their stores, and the host reads it with the loss on the one
+ * synchronisation the call always had - the step's other launches still run, and a DEVICE `logits` is written.
  * replaces: model.train(); outputs = model(sigs, seqs); loss = criterion(outputs, labels); loss.backward(),
  *           src/remora/train_model.py:470-499. */
 int rmr_trainer_forward_backward(rmr_trainer *t, const float *sigs, const float *seqs, const int64_t *labels,

@@ -95,16 +95,17 @@ int conv_forward(rmr_trainer *t, Layer &l, int64_t n) {
     rmr_engine *e = t->eng;
     const long long R = n * l.Lout;
     RMR_TRY(train_gemm(e, l.in, l.span_in(), l.Bf, l.OC, l.KW * l.IC, l.ypre, plain(l.OC), l.OC, R, t->params + l.b));
-    return train_bn_forward(e, l.ypre, l.OC, R, l.stat, t->params + l.g, t->params + l.be, t->params + l.rm, t->params + l.rv, t->part_c, l.out, l.aw,
-                            l.coff);
+    return train_bn_forward(e, l.ypre, l.OC, R, l.stat, t->params + l.g, t->params + l.be, t->params + l.rm, t->params + l.rv, t->part_c,
+                            t->count + 1, l.out, l.aw, l.coff);
 }
 
 int conv_backward(rmr_trainer *t, Layer &l, int64_t n) {
     rmr_engine *e = t->eng;
     const long long R = n * l.Lout;
-    RMR_TRY(train_bn_backward(e, l.ypre, l.OC, R, l.stat, t->params + l.g, t->params + l.be, l.d_out, l.aw, l.coff, t->part_c, t->grads + l.g,
-                              t->grads + l.be, t->dY, t->grads + l.b));
-    RMR_TRY(train_wgrad(e, l.in, l.span_in(), t->dY, plain(l.OC), l.KW * l.IC, l.OC, R, l.IC, l.KW, t->part_w, t->part_w_floats, t->grads + l.w));
+    RMR_TRY(train_bn_backward(e, l.ypre, l.OC, R, l.stat, t->params + l.g, t->params + l.be, l.d_out, l.aw, l.coff, t->part_c, t->count + 1,
+                              t->grads + l.g, t->grads + l.be, t->dY, t->grads + l.b));
+    RMR_TRY(train_wgrad(e, l.in, l.span_in(), t->dY, plain(l.OC), l.KW * l.IC, l.OC, R, l.IC, l.KW, t->part_w, t->part_w_floats, t->count + 1,
+                        t->grads + l.w));
     if (!l.d_in) return 0;
     // the data gradient: rows q of P * IC columns, dX[P q + p][ic] = sum_j sum_oc dY[q - j][oc] W[oc][ic][p + P j]
     const int rows = l.rows_in();
@@ -117,6 +118,10 @@ int forward_backward(rmr_trainer *t, const float *sig, const float *seq, const i
     rmr_engine *e = t->eng;
     const int S = t->S, T = t->T, NO = t->NO;
     float *P = t->params, *Gr = t->grads;
+    // count[0]: the rows in the loss; count[1] (`refused`): the first of them whose label is out of range, or -1.  Every later store
+    // to a gradient or a running statistic is held when it is set, and the caller refuses the call once it has read the record
+    const int *refused = t->count + 1;
+    RMR_TRY(train_count_rows(e, mask, labels, NO, n, t->count));
     // ---- the weights in product order ----
     for (Layer *l : {&t->sig2, &t->sig3, &t->seq1, &t->seq2, &t->merge}) RMR_TRY(train_repack(e, P + l->w, l->OC, l->IC, l->KW, 1, 1, 0, l->Bf));
     for (Layer *l : {&t->sig2, &t->sig3, &t->seq2, &t->merge}) RMR_TRY(train_repack(e, P + l->w, l->OC, l->IC, l->KW, l->P(), l->J(), 1, l->Bd));
@@ -135,7 +140,7 @@ int forward_backward(rmr_trainer *t, const float *sig, const float *seq, const i
         Layer &l = t->sig1;
         l.in = sig;
         RMR_TRY(train_sig1(e, sig, l.Lin, l.Lout, l.OC, l.KW, P + l.w, P + l.b, n, l.ypre));
-        RMR_TRY(train_bn_forward(e, l.ypre, l.OC, n * l.Lout, l.stat, P + l.g, P + l.be, P + l.rm, P + l.rv, t->part_c, l.out, l.aw, l.coff));
+        RMR_TRY(train_bn_forward(e, l.ypre, l.OC, n * l.Lout, l.stat, P + l.g, P + l.be, P + l.rm, P + l.rv, t->part_c, refused, l.out, l.aw, l.coff));
     }
     RMR_TRY(conv_forward(t, t->sig2, n));
     RMR_TRY(conv_forward(t, t->sig3, n));
@@ -153,31 +158,29 @@ int forward_backward(rmr_trainer *t, const float *sig, const float *seq, const i
     RMR_TRY(train_fc_loss(e, t->Z2, P + t->fc_w, P + t->fc_b, S, NO, labels, mask, t->count, n, t->logits, t->dlog, t->loss_part, logits_dev, t->loss));
 
     // ---- backward ----
-    RMR_TRY(train_wgrad(e, t->Z2, plain(S), t->dlog, plain(NO), S, NO, n, S, 1, t->part_w, t->part_w_floats, Gr + t->fc_w));
-    RMR_TRY(train_bias_grad(e, t->dlog, NO, n, t->part_c, Gr + t->fc_b, nullptr));
+    RMR_TRY(train_wgrad(e, t->Z2, plain(S), t->dlog, plain(NO), S, NO, n, S, 1, t->part_w, t->part_w_floats, refused, Gr + t->fc_w));
+    RMR_TRY(train_bias_grad(e, t->dlog, NO, n, t->part_c, refused, Gr + t->fc_b, nullptr));
     RMR_TRY(train_lstm2_bwd(e, t->G2, t->C2, t->H2, t->dlog, P + t->fc_w, NO, S, n));
-    RMR_TRY(train_wgrad(e, t->Z1, last, t->G2, plain(4 * S), S, 4 * S, n, S, 1, t->part_w, t->part_w_floats, Gr + t->l2_wih));
-    RMR_TRY(train_fill(e, Gr + t->l2_whh, (long long)4 * S * S, 0.f));  // h_0 = 0: exactly zero
-    RMR_TRY(train_bias_grad(e, t->G2, 4 * S, n, t->part_c, Gr + t->l2_bih, Gr + t->l2_bhh));
+    RMR_TRY(train_wgrad(e, t->Z1, last, t->G2, plain(4 * S), S, 4 * S, n, S, 1, t->part_w, t->part_w_floats, refused, Gr + t->l2_wih));
+    RMR_TRY(train_fill(e, Gr + t->l2_whh, (long long)4 * S * S, 0.f, refused));  // h_0 = 0: exactly zero
+    RMR_TRY(train_bias_grad(e, t->G2, 4 * S, n, t->part_c, refused, Gr + t->l2_bih, Gr + t->l2_bhh));
     RMR_TRY(train_gemm(e, t->G2, plain(4 * S), P + t->l2_wih, S, 4 * S, t->dz1, plain(S), S, n, nullptr));
     // lstm1: the gradient enters at step T - 1 only; dh_{t-1} = dgates_t W_hh is the sequential part
     for (int s = T - 1; s >= 0; --s) RMR_TRY(train_lstm_step_bwd(e, t->G, t->Cs, t->H, P + t->l1_whh, t->dz1, t->dc, S, T, s, n));
     RMR_TRY(train_gemm(e, t->G, plain(4 * S), P + t->l1_wih, S, 4 * S, t->dx, plain(S), S, n * T, nullptr));
-    RMR_TRY(train_wgrad(e, t->x, plain(S), t->G, plain(4 * S), S, 4 * S, n * T, S, 1, t->part_w, t->part_w_floats, Gr + t->l1_wih));
+    RMR_TRY(train_wgrad(e, t->x, plain(S), t->G, plain(4 * S), S, 4 * S, n * T, S, 1, t->part_w, t->part_w_floats, refused, Gr + t->l1_wih));
     {
         const TrainSpan sa{T - 1, (long long)T * S, S, 0, (long long)T * S};
         const TrainSpan sd{T - 1, (long long)T * 4 * S, 4 * S, 4 * S, (long long)T * 4 * S};
-        RMR_TRY(train_wgrad(e, t->H, sa, t->G, sd, S, 4 * S, n * (T - 1), S, 1, t->part_w, t->part_w_floats, Gr + t->l1_whh));
+        RMR_TRY(train_wgrad(e, t->H, sa, t->G, sd, S, 4 * S, n * (T - 1), S, 1, t->part_w, t->part_w_floats, refused, Gr + t->l1_whh));
     }
-    RMR_TRY(train_bias_grad(e, t->G, 4 * S, n * T, t->part_c, Gr + t->l1_bih, Gr + t->l1_bhh));
+    RMR_TRY(train_bias_grad(e, t->G, 4 * S, n * T, t->part_c, refused, Gr + t->l1_bih, Gr + t->l1_bhh));
     RMR_TRY(conv_backward(t, t->merge, n));
     RMR_TRY(conv_backward(t, t->sig3, n));
     RMR_TRY(conv_backward(t, t->sig2, n));
     RMR_TRY(conv_backward(t, t->sig1, n));
     RMR_TRY(conv_backward(t, t->seq2, n));
-    RMR_TRY(conv_backward(t, t->seq1, n));
-    t->batches_tracked += 1;
-    return 0;
+    return conv_backward(t, t->seq1, n);
 }
 
 float *which_buffer(rmr_trainer *t, int which) {
@@ -308,7 +311,7 @@ int rmr_trainer_create(rmr_engine *e, const rmr_model_desc *desc, const float *b
         t->in_sig = take(N * L), t->in_seq = take(N * EC * L), t->seqT = take(N * L * EC);
         t->in_labels = reinterpret_cast<int64_t *>(take(N * 2));
         t->in_mask = reinterpret_cast<uint8_t *>(take((N + 3) / 4));
-        t->count = reinterpret_cast<int *>(take(1));
+        t->count = reinterpret_cast<int *>(take(2));  // rows in the loss; the first row with a label out of range or -1
         for (Layer *l : layers) {
             l->ypre = take(N * l->Lout * l->OC);
             l->stat = take(4 * (size_t)l->OC);
@@ -322,7 +325,7 @@ int rmr_trainer_create(rmr_engine *e, const rmr_model_desc *desc, const float *b
         t->da1 = take(N * t->sig1.Lout * 4), t->daq1 = take(N * t->seq1.Lout * 16);
         t->G = take(N * T * 4 * S), t->Cs = take(N * T * S), t->H = take(N * T * S), t->Z1 = take(N * T * S);
         t->G2 = take(N * 4 * S), t->C2 = take(N * S), t->H2 = take(N * S), t->Z2 = take(N * S);
-        t->logits = take(N * NO), t->dlog = take(N * NO), t->loss_part = take(N), t->loss = take(1);
+        t->logits = take(N * NO), t->dlog = take(N * NO), t->loss_part = take(N), t->loss = take(2);  // the loss; count[1]'s bits
         t->dz1 = take(N * S), t->dc = take(N * S);
         t->dY = take(dY_floats), t->part_w = take(part_w), t->part_c = take(part_c);
         t->WihT1 = take((size_t)4 * S * S), t->WhhT1 = take((size_t)4 * S * S), t->WihT2 = take((size_t)4 * S * S);
@@ -357,7 +360,12 @@ int rmr_trainer_forward_backward(rmr_trainer *t, const float *sigs, const float 
     std::lock_guard<std::mutex> lk(e->mu);
     RMR_HIP(hipSetDevice(e->device));
     float *logits_dev = nullptr;
+    const int64_t *labels_in = labels;
     if (mem == RMR_MEM_HOST) {
+        // host labels are checked before anything is staged; device labels by the step's first kernel (below)
+        for (int64_t i = 0; i < n; ++i)
+            if ((!mask || mask[i]) && (labels[i] < 0 || labels[i] >= t->NO))
+                RMR_FAIL(RMR_ERR_INVALID, "label %lld of chunk %lld is outside 0..num_out-1 (num_out %d)", (long long)labels[i], (long long)i, t->NO);
         RMR_HIP(hipMemcpyAsync(t->in_sig, sigs, (size_t)n * t->L * sizeof(float), hipMemcpyHostToDevice, e->stream));
         RMR_HIP(hipMemcpyAsync(t->in_seq, seqs, (size_t)n * t->EC * t->L * sizeof(float), hipMemcpyHostToDevice, e->stream));
         RMR_HIP(hipMemcpyAsync(t->in_labels, labels, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, e->stream));
@@ -368,10 +376,20 @@ int rmr_trainer_forward_backward(rmr_trainer *t, const float *sigs, const float 
         logits_dev = logits;
     }
     RMR_TRY(forward_backward(t, sigs, seqs, labels, mask, n, logits_dev));
-    RMR_HIP(hipMemcpyAsync(loss, t->loss, sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    float got[2] = {0.f, 0.f};  // the loss and, as bits, the first chunk in the loss with a label out of range or -1
+    RMR_HIP(hipMemcpyAsync(got, t->loss, sizeof(got), hipMemcpyDeviceToHost, e->stream));
     if (mem == RMR_MEM_HOST && logits)
         RMR_HIP(hipMemcpyAsync(logits, t->logits, (size_t)n * t->NO * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     RMR_HIP(hipStreamSynchronize(e->stream));
+    int32_t row;
+    std::memcpy(&row, &got[1], sizeof(row));
+    if (row >= 0) {  // device labels: the kernels held every store to a gradient or a running statistic
+        int64_t lab = 0;
+        RMR_HIP(hipMemcpy(&lab, labels_in + row, sizeof(lab), hipMemcpyDeviceToHost));
+        RMR_FAIL(RMR_ERR_INVALID, "label %lld of chunk %d is outside 0..num_out-1 (num_out %d)", (long long)lab, (int)row, t->NO);
+    }
+    *loss = got[0];
+    t->batches_tracked += 1;
     return 0;
 }
 

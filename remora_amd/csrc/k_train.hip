@@ -12,6 +12,8 @@
 //                       the slices in fixed order (double) and writes the gradient in the parameter's own layout
 // Every sum over rows (weight gradients, BatchNorm statistics, bias gradients, loss) is per-block partials plus a
 // second pass in fixed order: no float atomics, the same bits on every run.
+#include <climits>
+
 #include "rmr_mma.h"
 
 namespace rmr {
@@ -113,9 +115,10 @@ __global__ __launch_bounds__(256) void train_wgrad_kernel(const float *__restric
 }
 
 // grad[c][ic][kw] = sum over slices of P[slice][kw * IC + ic][c] (a linear layer: KW = 1); slices == 0 writes zeros.  One
-// block of 64 lanes per element: lane i adds slices i, i + 64, ... in order, lane 0 then adds the 64 lane sums in order
+// block of 64 lanes per element: lane i adds slices i, i + 64, ... in order, lane 0 then adds the 64 lane sums in order.
+// refused[0] >= 0 (train_mask_count_kernel found a label out of range): the gradient is left as it was
 __global__ __launch_bounds__(64) void train_wgrad_reduce_kernel(const float *__restrict__ P, const int slices, const int K, const int NC, const int IC,
-                                                                const int KW, float *__restrict__ grad) {
+                                                                const int KW, const int *__restrict__ refused, float *__restrict__ grad) {
     __shared__ double red[64];
     const int e = blockIdx.x;
     const int k = e / NC, c = e - k * NC;
@@ -123,7 +126,7 @@ __global__ __launch_bounds__(64) void train_wgrad_reduce_kernel(const float *__r
     for (int z = threadIdx.x; z < slices; z += 64) s += (double)P[((size_t)z * K + k) * NC + c];
     red[threadIdx.x] = s;
     __syncthreads();
-    if (threadIdx.x) return;
+    if (threadIdx.x || refused[0] >= 0) return;
     s = 0.0;
     for (int i = 0; i < 64; ++i) s += red[i];
     const int kw = k / IC, ic = k - kw * IC;
@@ -208,10 +211,11 @@ __global__ __launch_bounds__(256) void train_colsum_kernel(const float *__restri
 // second pass, one block of 64 lanes per column: lane i adds the partials of blocks i, i + 64, ... in order, lane 0 then adds
 // the 64 lane sums in order.  what: 0 out[c] = sum (plain column sum, e.g. a bias gradient; out2 gets the same value when
 // given: lstm bias_hh), 1 stat[c] = mean, 2 stat[C + c] = rstd and the running statistics move (momentum 0.1, unbiased
-// variance), 3 out[c] = dgamma, out2[c] = dbeta and stat[2C + c], stat[3C + c] keep them over R for the apply pass
+// variance), 3 out[c] = dgamma, out2[c] = dbeta and stat[2C + c], stat[3C + c] keep them over R for the apply pass.
+// refused[0] >= 0 (a label out of range): `stat` is still written, the gradients and the running statistics stay as they were
 __global__ __launch_bounds__(64) void train_colsum_final_kernel(const float *__restrict__ part, const int nblk, const int C, const int what,
-                                                                const long long R, float *__restrict__ stat, float *__restrict__ out,
-                                                                float *__restrict__ out2, float *__restrict__ run_mean,
+                                                                const long long R, const int *__restrict__ refused, float *__restrict__ stat,
+                                                                float *__restrict__ out, float *__restrict__ out2, float *__restrict__ run_mean,
                                                                 float *__restrict__ run_var) {
     __shared__ double red[2][64];
     const int c = blockIdx.x;
@@ -226,7 +230,9 @@ __global__ __launch_bounds__(64) void train_colsum_final_kernel(const float *__r
     if (threadIdx.x) return;
     s0 = s1 = 0.0;
     for (int i = 0; i < 64; ++i) s0 += red[0][i], s1 += red[1][i];
+    const bool keep = refused[0] >= 0;
     if (what == 0) {
+        if (keep) return;
         out[c] = (float)s0;
         if (out2) out2[c] = (float)s0;
     } else if (what == 1) {
@@ -234,13 +240,15 @@ __global__ __launch_bounds__(64) void train_colsum_final_kernel(const float *__r
     } else if (what == 2) {
         const double var = s0 / (double)R;
         stat[C + c] = (float)(1.0 / sqrt(var + 1e-5));
+        if (keep) return;
         run_mean[c] = 0.9f * run_mean[c] + 0.1f * stat[c];
         run_var[c] = 0.9f * run_var[c] + 0.1f * (float)(var * (double)R / (double)(R - 1));
     } else {
-        out[c] = (float)s1;   // bn.weight gradient
-        out2[c] = (float)s0;  // bn.bias gradient
         stat[2 * C + c] = (float)(s0 / (double)R);
         stat[3 * C + c] = (float)(s1 / (double)R);
+        if (keep) return;
+        out[c] = (float)s1;   // bn.weight gradient
+        out2[c] = (float)s0;  // bn.bias gradient
     }
 }
 
@@ -296,9 +304,9 @@ __global__ void train_seq_transpose_kernel(const float *__restrict__ in, const i
     out[e] = in[(n * EC + c) * L + l];
 }
 
-__global__ void train_fill_kernel(float *__restrict__ p, const long long n, const float v) {
+__global__ void train_fill_kernel(float *__restrict__ p, const long long n, const float v, const int *__restrict__ refused) {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < n) p[e] = v;
+    if (e < n && refused[0] < 0) p[e] = v;
 }
 
 // ---- LSTM ------------------------------------------------------------------------------------------------------------------
@@ -462,21 +470,34 @@ __global__ void train_fc_loss_kernel(const float *__restrict__ Z2, const float *
     loss_part[n] = on ? l : 0.f;
 }
 
-// one block: count of the rows the mask keeps (no mask: n)
-__global__ __launch_bounds__(256) void train_mask_count_kernel(const uint8_t *__restrict__ mask, const long long n, int *__restrict__ count) {
-    __shared__ int red[256];
-    int s = 0;
-    for (long long i = threadIdx.x; i < n; i += 256) s += mask ? (mask[i] != 0) : 1;
-    red[threadIdx.x] = s;
+// one block, the first launch of a step: count[0] = the rows the mask keeps (no mask: n); count[1] = the first such row whose
+// label is outside 0 .. num_out - 1, or -1.  What writes a gradient or a running statistic later in the step reads count[1]
+// (`refused`) and holds its store when a row was found, so that the host, which sees the record with the loss, can refuse the
+// call with nothing moved
+__global__ __launch_bounds__(256) void train_mask_count_kernel(const uint8_t *__restrict__ mask, const int64_t *__restrict__ labels,
+                                                               const int num_out, const long long n, int *__restrict__ count) {
+    __shared__ int red[256], first[256];
+    int s = 0, bad = INT_MAX;
+    for (long long i = threadIdx.x; i < n; i += 256) {
+        if (mask && !mask[i]) continue;
+        s += 1;
+        const int64_t lab = labels[i];
+        if ((lab < 0 || lab >= num_out) && bad == INT_MAX) bad = (int)i;
+    }
+    red[threadIdx.x] = s, first[threadIdx.x] = bad;
     __syncthreads();
     for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        if ((int)threadIdx.x < w) {
+            red[threadIdx.x] += red[threadIdx.x + w];
+            first[threadIdx.x] = min(first[threadIdx.x], first[threadIdx.x + w]);
+        }
         __syncthreads();
     }
-    if (threadIdx.x == 0) count[0] = red[0];
+    if (threadIdx.x == 0) count[0] = red[0], count[1] = first[0] == INT_MAX ? -1 : first[0];
 }
 
-// one block, fixed order: loss = sum of the chunks' terms / count
+// one block, fixed order: loss[0] = sum of the chunks' terms / count; loss[1] = count[1] (the refused row or -1) as bits, so that one
+// copy brings both to the host
 __global__ __launch_bounds__(256) void train_loss_reduce_kernel(const float *__restrict__ loss_part, const long long n, const int *__restrict__ count,
                                                                 float *__restrict__ loss) {
     __shared__ double red[256];
@@ -488,7 +509,7 @@ __global__ __launch_bounds__(256) void train_loss_reduce_kernel(const float *__r
         if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
         __syncthreads();
     }
-    if (threadIdx.x == 0) loss[0] = (float)(red[0] / (double)count[0]);
+    if (threadIdx.x == 0) loss[0] = (float)(red[0] / (double)count[0]), loss[1] = __int_as_float(count[1]);
 }
 
 // ---- optimiser --------------------------------------------------------------------------------------------------------------
@@ -547,7 +568,7 @@ int train_gemm(rmr_engine *e, const float *A, const TrainSpan &sa, const float *
 }
 
 int train_wgrad(rmr_engine *e, const float *A, const TrainSpan &sa, const float *D, const TrainSpan &sd, int K, int NC, long long R, int IC,
-                int KW, float *part, size_t part_floats, float *grad) {
+                int KW, float *part, size_t part_floats, const int *refused, float *grad) {
     int slices = 0;
     long long rows_per = 0;
     if (R > 0) {
@@ -565,7 +586,7 @@ int train_wgrad(rmr_engine *e, const float *A, const TrainSpan &sa, const float 
         RMR_HIP(hipGetLastError());
     }
     ProfScope ps(e, K_TRAIN_REDUCE);
-    hipLaunchKernelGGL(train_wgrad_reduce_kernel, dim3((unsigned)(K * NC)), dim3(64), 0, e->stream, part, slices, K, NC, IC, KW, grad);
+    hipLaunchKernelGGL(train_wgrad_reduce_kernel, dim3((unsigned)(K * NC)), dim3(64), 0, e->stream, part, slices, K, NC, IC, KW, refused, grad);
     RMR_HIP(hipGetLastError());
     return 0;
 }
@@ -585,7 +606,7 @@ int train_colsum_blocks(long long R) {
 }
 
 int train_colsum(rmr_engine *e, int mode, const float *X, int C, long long R, float *stat, const float *gamma, const float *beta, const float *dA,
-                 int aw, int coff, float *part, int what, float *out, float *out2, float *run_mean, float *run_var) {
+                 int aw, int coff, float *part, int what, const int *refused, float *out, float *out2, float *run_mean, float *run_var) {
     const int nblk = train_colsum_blocks(R);
     const long long rows_per = (R + nblk - 1) / nblk;
     const dim3 grid(nblk, blocks_for(C, 16));
@@ -597,15 +618,15 @@ int train_colsum(rmr_engine *e, int mode, const float *X, int C, long long R, fl
         RMR_HIP(hipGetLastError());
     }
     ProfScope ps(e, K_TRAIN_REDUCE);
-    hipLaunchKernelGGL(train_colsum_final_kernel, dim3((unsigned)C), dim3(64), 0, e->stream, part, nblk, C, what, R, stat, out, out2, run_mean, run_var);
+    hipLaunchKernelGGL(train_colsum_final_kernel, dim3((unsigned)C), dim3(64), 0, e->stream, part, nblk, C, what, R, refused, stat, out, out2, run_mean, run_var);
     RMR_HIP(hipGetLastError());
     return 0;
 }
 
 int train_bn_forward(rmr_engine *e, const float *Y, int C, long long R, float *stat, const float *gamma, const float *beta, float *run_mean,
-                     float *run_var, float *part, float *out, int aw, int coff) {
-    RMR_TRY(train_colsum(e, COL_SUM, Y, C, R, stat, nullptr, nullptr, nullptr, 0, 0, part, 1, nullptr, nullptr, nullptr, nullptr));
-    RMR_TRY(train_colsum(e, COL_VAR, Y, C, R, stat, nullptr, nullptr, nullptr, 0, 0, part, 2, nullptr, nullptr, run_mean, run_var));
+                     float *run_var, float *part, const int *refused, float *out, int aw, int coff) {
+    RMR_TRY(train_colsum(e, COL_SUM, Y, C, R, stat, nullptr, nullptr, nullptr, 0, 0, part, 1, refused, nullptr, nullptr, nullptr, nullptr));
+    RMR_TRY(train_colsum(e, COL_VAR, Y, C, R, stat, nullptr, nullptr, nullptr, 0, 0, part, 2, refused, nullptr, nullptr, run_mean, run_var));
     ProfScope ps(e, K_TRAIN_BN);
     hipLaunchKernelGGL(train_bn_swish_kernel, dim3(blocks_for(R * C)), dim3(256), 0, e->stream, Y, C, R * C, stat, gamma, beta, out, aw, coff);
     RMR_HIP(hipGetLastError());
@@ -613,19 +634,19 @@ int train_bn_forward(rmr_engine *e, const float *Y, int C, long long R, float *s
 }
 
 int train_bn_backward(rmr_engine *e, const float *Y, int C, long long R, float *stat, const float *gamma, const float *beta, const float *dA, int aw,
-                      int coff, float *part, float *dgamma, float *dbeta, float *dY, float *dbias) {
-    RMR_TRY(train_colsum(e, COL_BNBWD, Y, C, R, stat, gamma, beta, dA, aw, coff, part, 3, dgamma, dbeta, nullptr, nullptr));
+                      int coff, float *part, const int *refused, float *dgamma, float *dbeta, float *dY, float *dbias) {
+    RMR_TRY(train_colsum(e, COL_BNBWD, Y, C, R, stat, gamma, beta, dA, aw, coff, part, 3, refused, dgamma, dbeta, nullptr, nullptr));
     {
         ProfScope ps(e, K_TRAIN_BN);
         hipLaunchKernelGGL(train_bn_bwd_kernel, dim3(blocks_for(R * C)), dim3(256), 0, e->stream, Y, C, R * C, stat, gamma, beta, dA, aw, coff, dY);
         RMR_HIP(hipGetLastError());
     }
     // the convolution's bias gradient: the column sum of dY, zero up to rounding (train-mode BatchNorm removes the channel mean)
-    return train_colsum(e, COL_SUM, dY, C, R, stat, nullptr, nullptr, nullptr, 0, 0, part, 0, dbias, nullptr, nullptr, nullptr);
+    return train_colsum(e, COL_SUM, dY, C, R, stat, nullptr, nullptr, nullptr, 0, 0, part, 0, refused, dbias, nullptr, nullptr, nullptr);
 }
 
-int train_bias_grad(rmr_engine *e, const float *D, int C, long long R, float *part, float *out, float *out2) {
-    return train_colsum(e, COL_SUM, D, C, R, nullptr, nullptr, nullptr, nullptr, 0, 0, part, 0, out, out2, nullptr, nullptr);
+int train_bias_grad(rmr_engine *e, const float *D, int C, long long R, float *part, const int *refused, float *out, float *out2) {
+    return train_colsum(e, COL_SUM, D, C, R, nullptr, nullptr, nullptr, nullptr, 0, 0, part, 0, refused, out, out2, nullptr, nullptr);
 }
 
 int train_sig1(rmr_engine *e, const float *sig, int L, int Lout, int OC, int KW, const float *w, const float *b, long long n, float *y) {
@@ -644,10 +665,10 @@ int train_seq_transpose(rmr_engine *e, const float *in, int EC, int L, long long
     return 0;
 }
 
-int train_fill(rmr_engine *e, float *p, long long n, float v) {
+int train_fill(rmr_engine *e, float *p, long long n, float v, const int *refused) {
     if (n <= 0) return 0;
     ProfScope ps(e, K_TRAIN_AUX);
-    hipLaunchKernelGGL(train_fill_kernel, dim3(blocks_for(n)), dim3(256), 0, e->stream, p, n, v);
+    hipLaunchKernelGGL(train_fill_kernel, dim3(blocks_for(n)), dim3(256), 0, e->stream, p, n, v, refused);
     RMR_HIP(hipGetLastError());
     return 0;
 }
@@ -681,10 +702,18 @@ int train_lstm2_bwd(rmr_engine *e, float *G2, const float *C2, const float *H2, 
     return 0;
 }
 
-int train_fc_loss(rmr_engine *e, const float *Z2, const float *fcw, const float *fcb, int S, int num_out, const int64_t *labels, const uint8_t *mask,
-                  int *count, long long n, float *logits, float *dlog, float *loss_part, float *logits_out, float *loss) {
+// the first launch of a step: count[0] = rows in the loss, count[1] = the first of them with a label outside 0 .. num_out - 1 or -1
+int train_count_rows(rmr_engine *e, const uint8_t *mask, const int64_t *labels, int num_out, long long n, int *count) {
     ProfScope ps(e, K_TRAIN_LOSS);
-    hipLaunchKernelGGL(train_mask_count_kernel, dim3(1), dim3(256), 0, e->stream, mask, n, count);
+    hipLaunchKernelGGL(train_mask_count_kernel, dim3(1), dim3(256), 0, e->stream, mask, labels, num_out, n, count);
+    RMR_HIP(hipGetLastError());
+    return 0;
+}
+
+// count: what train_count_rows left; loss[0] the mean cross-entropy, loss[1] the bits of count[1]
+int train_fc_loss(rmr_engine *e, const float *Z2, const float *fcw, const float *fcb, int S, int num_out, const int64_t *labels, const uint8_t *mask,
+                  const int *count, long long n, float *logits, float *dlog, float *loss_part, float *logits_out, float *loss) {
+    ProfScope ps(e, K_TRAIN_LOSS);
     hipLaunchKernelGGL(train_fc_loss_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, e->stream, Z2, fcw, fcb, S, num_out, labels, mask, count, n, logits,
                        dlog, loss_part, logits_out);
     hipLaunchKernelGGL(train_loss_reduce_kernel, dim3(1), dim3(256), 0, e->stream, loss_part, n, count, loss);

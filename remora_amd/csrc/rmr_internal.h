@@ -316,24 +316,25 @@ struct TrainSpan {
 int train_gemm(rmr_engine *e, const float *A, const TrainSpan &sa, const float *B, int ldb, int K, float *C, const TrainSpan &sc, int NC,
                long long R, const float *bias);
 int train_wgrad(rmr_engine *e, const float *A, const TrainSpan &sa, const float *D, const TrainSpan &sd, int K, int NC, long long R, int IC,
-                int KW, float *part, size_t part_floats, float *grad);
+                int KW, float *part, size_t part_floats, const int *refused, float *grad);
 int train_repack(rmr_engine *e, const float *W, int OC, int IC, int KW, int P, int J, int mode, float *out);
 int train_colsum_blocks(long long R);
 int train_bn_forward(rmr_engine *e, const float *Y, int C, long long R, float *stat, const float *gamma, const float *beta, float *run_mean,
-                     float *run_var, float *part, float *out, int aw, int coff);
+                     float *run_var, float *part, const int *refused, float *out, int aw, int coff);
 int train_bn_backward(rmr_engine *e, const float *Y, int C, long long R, float *stat, const float *gamma, const float *beta, const float *dA, int aw,
-                      int coff, float *part, float *dgamma, float *dbeta, float *dY, float *dbias);
-int train_bias_grad(rmr_engine *e, const float *D, int C, long long R, float *part, float *out, float *out2);
+                      int coff, float *part, const int *refused, float *dgamma, float *dbeta, float *dY, float *dbias);
+int train_bias_grad(rmr_engine *e, const float *D, int C, long long R, float *part, const int *refused, float *out, float *out2);
 int train_sig1(rmr_engine *e, const float *sig, int L, int Lout, int OC, int KW, const float *w, const float *b, long long n, float *y);
 int train_seq_transpose(rmr_engine *e, const float *in, int EC, int L, long long n, float *out);
-int train_fill(rmr_engine *e, float *p, long long n, float v);
+int train_fill(rmr_engine *e, float *p, long long n, float v, const int *refused);
 int train_lstm_step(rmr_engine *e, float *G, float *Cs, float *H, float *Z, const float *WhhT, int S, int T, int t, long long n);
 int train_lstm_step_bwd(rmr_engine *e, float *G, const float *Cs, const float *H, const float *Whh, const float *dz1, float *dc, int S, int T, int t,
                         long long n);
 int train_lstm2(rmr_engine *e, float *G2, float *C2, float *H2, float *Z2, int S, long long n);
 int train_lstm2_bwd(rmr_engine *e, float *G2, const float *C2, const float *H2, const float *dlog, const float *fcw, int num_out, int S, long long n);
+int train_count_rows(rmr_engine *e, const uint8_t *mask, const int64_t *labels, int num_out, long long n, int *count);
 int train_fc_loss(rmr_engine *e, const float *Z2, const float *fcw, const float *fcb, int S, int num_out, const int64_t *labels, const uint8_t *mask,
-                  int *count, long long n, float *logits, float *dlog, float *loss_part, float *logits_out, float *loss);
+                  const int *count, long long n, float *logits, float *dlog, float *loss_part, float *logits_out, float *loss);
 int train_adamw(rmr_engine *e, float *p, float *g, float *m, float *v, const uint8_t *tensor_of, long long n, float lr_wd, float omb1, float b2,
                 float omb2, float eps, float step_size, float bc2_sqrt, const float *clip);
 int train_absmax(rmr_engine *e, const float *g, const long long *off, const long long *size, int n_tensors, float *out);

@@ -129,7 +129,13 @@ class Trainer:
     def forward_backward(self, sigs, enc_kmers, labels, mask=None, return_logits=False):
         """sigs f32[n,1,L], enc_kmers f32[n,4K,L], labels i64[n], mask bool[n] or None (rows with False leave the loss but
         still take part in BatchNorm): fills the gradients, moves the running statistics, returns the mean cross-entropy
-        (and the logits).  numpy / CPU tensors are staged; CUDA tensors are read in place."""
+        (and the logits).  numpy / CPU tensors are staged; CUDA tensors are read in place.
+
+        A label outside 0..num_out-1 in a row of the loss raises RemoraError ("label ... outside 0..num_out-1") and leaves the
+        gradients, the running statistics and num_batches_tracked as they were.  Host labels are checked before any launch.
+        Device labels are checked by the step's first kernel, before the BatchNorm launches: those kernels hold their stores to
+        the running statistics and the gradients, and the error is raised once the loss has been read - no synchronisation is
+        added for it."""
         torch = _torch()
         on_dev = isinstance(sigs, torch.Tensor) and sigs.is_cuda
         want = [(sigs, np.float32, torch.float32), (enc_kmers, np.float32, torch.float32), (labels, np.int64, torch.int64)]
