@@ -16,6 +16,7 @@
 #include "rmr_internal.h"
 #include "rmr_math.h"
 #include "rmr_mma.h"
+#include "rmr_plan.h"
 
 namespace rmr {
 
@@ -152,32 +153,18 @@ __global__ __launch_bounds__(256) void conv_bf16s_kernel(ConvSArgs a) {
 template <int IC, int KW, int STRIDE, int NP, bool F16 = false>
 static int launch_conv_s_t(rmr_engine *e, const ConvLayer &c, const float *in, int in_row, int pin, float *out,
                            int out_row, int out_coff, int pout, int64_t n) {
-    constexpr bool PAIR = (IC == 16);
-    constexpr int KS = PAIR ? 1 : IC / 32;
-    constexpr int SLR = (KS % 2 == 0) ? KS + 1 : KS;
-    constexpr int NPL = PAIR ? 2 : 4;
-    const size_t chunk_bytes = (size_t)pin * SLR * 16 * NPL * NP;
-    int cb = (int)((size_t)(112 * 1024) / chunk_bytes);
-    if (cb < 1) cb = 1;
-    if (cb > 8) cb = 8;
-    if (cb >= 4) cb &= ~3;
-    const int plane = ((cb * pin + 2) * SLR + 15) & ~15;  // +2 guard rows
-    const int part = NPL * plane + 16;                    // + trash slot
-    const size_t lds = (size_t)part * NP * 16;
-    if (lds > 160 * 1024)
-        RMR_FAIL(RMR_ERR_INVALID, "split conv layer %s needs %zu B of LDS for one chunk of %d rows (160 KB per block)", kernel_name(c.kid), lds, pin);
+    const SplitPlan p = plan_conv_split(IC, pin, NP, n, e->num_cus);  // rmr_plan.h
+    if (!p.ok)
+        RMR_FAIL(RMR_ERR_INVALID, "split conv layer %s needs %zu B of LDS for one chunk of %d rows (160 KB per block)", kernel_name(c.kid), p.lds, pin);
     ConvSArgs a;
     a.in = in; a.out = out; a.apack = reinterpret_cast<const uint4 *>(c.spack); a.bias = c.bias; a.n = n;
     a.in_row = in_row; a.pin = pin; a.pout = pout; a.out_row = out_row; a.out_coff = out_coff;
-    a.cb = cb; a.plane = plane; a.part = part; a.div_pout = make_fastdiv(pout);
-    const int64_t iters = (n + cb - 1) / cb;
-    int64_t grid = (int64_t)e->num_cus * 2;
-    if (grid > iters) grid = iters;
-    if (grid < 1) return 0;
+    a.cb = p.cb; a.plane = p.plane; a.part = p.part; a.div_pout = make_fastdiv(pout);
+    if (p.grid < 1) return 0;
     auto kern = conv_bf16s_kernel<IC, KW, STRIDE, NP, F16>;
     RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(kern)));
     ProfScope ps(e, c.kid);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * (c.oc / 16)), lds, e->stream, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(64 * (c.oc / 16)), p.lds, e->stream, a);
     RMR_HIP(hipGetLastError());
     return 0;
 }

@@ -16,6 +16,7 @@
 #include "rmr_internal.h"
 #include "rmr_math.h"
 #include "rmr_mma.h"
+#include "rmr_plan.h"
 
 namespace rmr {
 
@@ -160,57 +161,20 @@ __global__ __launch_bounds__(512) void conv_stream_kernel(ConvStreamArgs a) {
 template <int KW, int STRIDE>
 static int launch_conv_stream_t(rmr_engine *e, const ConvLayer &c, const float *in, int pin, float *out, int out_row, int out_coff,
                                 int pout, int64_t n) {
-    const int G = c.ic / 16;
-    const int RS = (G % 2 == 0) ? c.ic / 4 + 4 : c.ic / 4;
-    const int OT = c.oc / 16;
-    // waves per block: one output-channel tile each where that is at most 8, else a divisor of the tile count (equal work)
-    int nw = OT;
-    if (nw > 8) {
-        nw = 8;
-        for (int d = 8; d >= 4; --d)
-            if (OT % d == 0) { nw = d; break; }
-    }
-    const size_t row_bytes = (size_t)pin * RS * 4 * sizeof(float);  // all four planes
-    const size_t budget = (size_t)65536;  // two blocks per CU
-    int cb_max = (int)(budget / row_bytes);
-    if (cb_max < 1) cb_max = 1;
-    if (cb_max > 8) cb_max = 8;
-    int cb = cb_max;
-    double best = -1.0;
-    for (int k = cb_max; k >= (cb_max + 1) / 2; --k) {  // the chunk count whose columns fill their 16-column tiles best
-        const int cols = k * pout;
-        const double eff = (double)cols / (16.0 * ((cols + 15) / 16));
-        if (eff > best + 1e-9) { best = eff; cb = k; }
-    }
-    // a chunk whose rows do not fit one block's LDS at all goes through position windows: the most output positions whose input
-    // rows ((win - 1) * STRIDE + KW of them) fit the two-blocks-per-CU share, one window of one chunk per iteration
-    int nwin = 1, pin_w = pin, pout_w = pout;
-    if (row_bytes + 64 > 150 * 1024) {
-        const int rows_fit = (int)(budget / ((size_t)RS * 4 * sizeof(float)));
-        pout_w = (rows_fit - KW) / STRIDE + 1;
-        if (pout_w < 16) RMR_FAIL(RMR_ERR_INVALID, "conv layer %d -> %d channels: not even a 16-column window fits %zu B of LDS", c.ic, c.oc, budget);
-        pout_w &= ~15;  // whole column tiles
-        nwin = (pout + pout_w - 1) / pout_w;
-        pin_w = (pout_w - 1) * STRIDE + KW;
-        cb = 1;
-    }
-    const int plane = ((cb * pin_w * RS) + 63) & ~63;
-    const size_t lds = (size_t)plane * 4 * sizeof(float) + 64;  // + trash slot for masked staging writes
-    if (lds > 160 * 1024 - 256) RMR_FAIL(RMR_ERR_INVALID, "conv layer %d -> %d channels needs %zu B of LDS", c.ic, c.oc, lds);
+    const ConvPlan p = plan_conv_stream(c.ic, c.oc, KW, STRIDE, pin, pout, n, e->num_cus);  // rmr_plan.h
+    if (!p.lds) RMR_FAIL(RMR_ERR_INVALID, "conv layer %d -> %d channels: not even a 16-column window fits %zu B of LDS", c.ic, c.oc, p.budget);
+    if (!p.ok) RMR_FAIL(RMR_ERR_INVALID, "conv layer %d -> %d channels needs %zu B of LDS", c.ic, c.oc, p.lds);
     ConvStreamArgs a;
     a.in = in; a.out = out; a.apack4 = c.apack4; a.bias = c.bias; a.n = n;
-    a.ic = c.ic; a.oc = c.oc; a.pin = pin_w; a.pout = pout_w; a.out_row = out_row; a.out_coff = out_coff;
-    a.cb = cb; a.plane = plane; a.rs = RS;
-    a.div_pout = make_fastdiv(pout_w); a.div_r4 = make_fastdiv(c.ic / 4); a.div_g = make_fastdiv(G);
-    a.nwin = nwin; a.pin_total = pin; a.pout_total = pout;
-    const int64_t iters = nwin > 1 ? n * nwin : (n + cb - 1) / cb;
-    int64_t grid = (int64_t)e->num_cus * 4;
-    if (grid > iters) grid = iters;
-    if (grid < 1) return 0;
+    a.ic = c.ic; a.oc = c.oc; a.pin = p.pin; a.pout = p.pout; a.out_row = out_row; a.out_coff = out_coff;
+    a.cb = p.cb; a.plane = p.plane; a.rs = p.rs;
+    a.div_pout = make_fastdiv(p.pout); a.div_r4 = make_fastdiv(c.ic / 4); a.div_g = make_fastdiv(c.ic / 16);
+    a.nwin = p.nwin; a.pin_total = pin; a.pout_total = pout;
+    if (p.grid < 1) return 0;
     auto kern = conv_stream_kernel<KW, STRIDE>;
     RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(kern)));
     ProfScope ps(e, c.kid);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * nw), lds, e->stream, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(64 * p.nw), p.lds, e->stream, a);
     RMR_HIP(hipGetLastError());
     return 0;
 }
@@ -391,37 +355,24 @@ __global__ __launch_bounds__(MAXT) void lstm_stream_kernel(LstmStreamArgs a) {
     }
 }
 
-template <int NT, int MAXT>
-static int launch_lstm_stream_t(rmr_model *m, const LstmStreamArgs &a, int64_t n) {
-    rmr_engine *e = m->eng;
-    const int H = a.H;
-    const size_t lds = (size_t)4 * 4 * 16 * NT * a.rs * sizeof(float);
-    if (lds > 160 * 1024 - 256) RMR_FAIL(RMR_ERR_INVALID, "streamed LSTM: %zu B of LDS for %d hidden units", lds, H);
-    const int64_t groups = (n + 16 * NT - 1) / (16 * NT);
-    int64_t grid = (int64_t)e->num_cus * 4;
-    if (grid > groups) grid = groups;
-    if (grid < 1) return 0;
-    auto kern = lstm_stream_kernel<NT, MAXT>;
-    RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(kern)));
-    ProfScope ps(e, K_LSTM_HEAD);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(4 * H), lds, e->stream, a);
-    RMR_HIP(hipGetLastError());
-    return 0;
-}
-
 int launch_lstm_stream(rmr_model *m, const float *x, int64_t n, float *logits) {
     const int H = m->desc.size;
     if (H % 16 || H > 256 || !m->lstm.t_ih1) RMR_FAIL(RMR_ERR_INVALID, "internal: LSTM of %d units not packed for the streamed kernel", H);
-    const int G = H / 16;
+    const LstmStreamPlan p = plan_lstm_stream(H, n, m->eng->num_cus);  // rmr_plan.h
+    if (!p.ok) RMR_FAIL(RMR_ERR_INVALID, "streamed LSTM: %zu B of LDS for %d hidden units", p.lds, H);
+    if (p.grid < 1) return 0;
     LstmStreamArgs a;
     a.x = x; a.logits = logits; a.n = n; a.T = m->T; a.num_out = m->desc.num_out; a.H = H;
-    a.rs = (G % 2 == 0) ? H / 4 + 4 : H / 4;
-    a.div_r4 = make_fastdiv(H / 4);
+    a.rs = p.rs; a.div_r4 = make_fastdiv(H / 4);
     a.a_ih1 = m->lstm.t_ih1; a.a_hh1 = m->lstm.t_hh1; a.b1 = m->lstm.b1;
     a.a_ih2 = m->lstm.t_ih2; a.b2 = m->lstm.b2; a.w_fc = m->lstm.w_fc; a.b_fc = m->lstm.b_fc;
-    // column tiles per wave: four halve the weight traffic of two, and fit (registers: 512 threads; LDS) up to 128 units
-    if (H <= 128) return launch_lstm_stream_t<4, 512>(m, a, n);
-    return launch_lstm_stream_t<2, 1024>(m, a, n);
+    rmr_engine *e = m->eng;
+    auto kern = p.nt == 4 ? lstm_stream_kernel<4, 512> : lstm_stream_kernel<2, 1024>;
+    RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(kern)));
+    ProfScope ps(e, K_LSTM_HEAD);
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(p.threads), p.lds, e->stream, a);
+    RMR_HIP(hipGetLastError());
+    return 0;
 }
 
 }  // namespace rmr

@@ -19,6 +19,7 @@
 #include "rmr_internal.h"
 #include "rmr_math.h"
 #include "rmr_mma.h"
+#include "rmr_plan.h"
 
 namespace rmr {
 
@@ -135,56 +136,26 @@ __global__ __launch_bounds__(512) void conv_stream16_kernel(ConvS16Args a) {
     }
 }
 
-// LDS bytes of an iteration of cb chunks: their rows + the rows a padded k-step and a clamped column may touch
-size_t conv16_lds(const ConvLayer &c, int pin, int cb) { return ((size_t)cb * pin + c.kw + 2) * (c.ic * 2 + 16); }
-
-// (cb > 1 always fits: launch_conv16_t only takes several chunks where their rows stay within 64 KiB)
-int conv16_fits(const ConvLayer &c, int pin, int cb) {
-    const size_t lds = conv16_lds(c, pin, cb);
-    if (lds > 160 * 1024 - 256)
-        RMR_FAIL(RMR_ERR_INVALID, "conv layer %d -> %d channels: one chunk of %d positions needs %zu B of LDS (chunk contexts this long run in "
-                                  "fp32 for networks of more than 64 channels)", c.ic, c.oc, pin, lds);
-    return 0;
+// the refusal of a chunk too long for a block's LDS (no windows here), by name
+int conv16_refuse(const ConvLayer &c, int pin, size_t lds) {
+    RMR_FAIL(RMR_ERR_INVALID, "conv layer %d -> %d channels: one chunk of %d positions needs %zu B of LDS (chunk contexts this long run in "
+                              "fp32 for networks of more than 64 channels)", c.ic, c.oc, pin, lds);
 }
 
 template <int STRIDE, bool F16, bool IN16>
 int launch_conv16_t(rmr_engine *e, const ConvLayer &c, const void *in, int pin, uint16_t *out, int out_row, int out_coff, int pout, int64_t n) {
-    const int OT = c.oc / 16;
-    int nw = OT;
-    if (nw > 8) {
-        nw = 8;
-        for (int d = 8; d >= 4; --d)
-            if (OT % d == 0) { nw = d; break; }
-    }
-    const int rb = c.ic * 2 + 16;
-    const size_t row_bytes = (size_t)pin * rb;
-    const size_t budget = 65536;  // two blocks per CU
-    int cb_max = (int)(budget / row_bytes);
-    if (cb_max < 1) cb_max = 1;
-    if (cb_max > 8) cb_max = 8;
-    int cb = cb_max;
-    double best = -1.0;
-    for (int k = cb_max; k >= (cb_max + 1) / 2; --k) {  // the chunk count whose columns fill their 16-column tiles best
-        const int cols = k * pout;
-        const double eff = (double)cols / (16.0 * ((cols + 15) / 16));
-        if (eff > best + 1e-9) { best = eff; cb = k; }
-    }
-    while (cb > 1 && (n + cb - 1) / cb < e->num_cus) cb = (cb + 1) / 2;  // a small batch spread over the CUs
-    const size_t lds = conv16_lds(c, pin, cb);
-    RMR_TRY(conv16_fits(c, pin, cb));
+    const Conv16Plan p = plan_conv_stream16(c.ic, c.oc, c.kw, pin, pout, n, e->num_cus);  // rmr_plan.h
+    if (!p.ok) return conv16_refuse(c, pin, p.lds);
     ConvS16Args a;
     a.in = in; a.out = out; a.apack = reinterpret_cast<const uint4 *>(c.apack16); a.bias = c.bias; a.n = n;
-    a.ic = c.ic; a.oc = c.oc; a.ks = (c.kw * c.ic + 31) / 32;
-    a.pin = pin; a.pout = pout; a.out_row = out_row; a.out_coff = out_coff; a.cb = cb; a.rb = rb; a.lds_bytes = (int)((lds + 15) & ~(size_t)15);
+    a.ic = c.ic; a.oc = c.oc; a.ks = p.ks;
+    a.pin = pin; a.pout = pout; a.out_row = out_row; a.out_coff = out_coff; a.cb = p.cb; a.rb = p.rb; a.lds_bytes = (int)p.lds;
     a.div_pout = make_fastdiv(pout); a.div_c8 = make_fastdiv(c.ic / 8); a.div_ic = make_fastdiv(c.ic);
-    const int64_t iters = (n + cb - 1) / cb;
-    int64_t grid = (int64_t)e->num_cus * 4;
-    if (grid > iters) grid = iters;
-    if (grid < 1) return 0;
+    if (p.grid < 1) return 0;
     auto kern = conv_stream16_kernel<STRIDE, F16, IN16>;
     RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(kern)));
     ProfScope ps(e, c.kid);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * nw), (size_t)a.lds_bytes, e->stream, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(64 * p.nw), p.lds, e->stream, a);
     RMR_HIP(hipGetLastError());
     return 0;
 }
@@ -193,7 +164,10 @@ int launch_conv16_t(rmr_engine *e, const ConvLayer &c, const void *in, int pin, 
 
 // launch_conv16_t's refusal of a chunk too long for a block's LDS, asked before anything is launched: pipeline_stream16 would
 // otherwise have queued the front kernels and two convolutions of a batch whose merge_conv1 it then refuses
-int check_conv_stream16(const ConvLayer &c, int pin) { return conv16_fits(c, pin, 1); }
+int check_conv_stream16(const ConvLayer &c, int pin) {
+    const size_t lds = plan_conv_stream16_lds(c.ic, c.kw, pin, 1);
+    return lds > STREAM_MAX_LDS ? conv16_refuse(c, pin, lds) : 0;
+}
 
 // `in16`: the input rows are 16-bit (cat); otherwise fp32 (the front kernels' sig2 / seq1, 16 channels)
 int launch_conv_stream16(rmr_model *m, const ConvLayer &c, const void *in, bool in16, int pin, uint16_t *out, int out_row, int out_coff, int pout,
@@ -367,38 +341,29 @@ __global__ __launch_bounds__(MAXT) void lstm_stream16_kernel(LstmS16Args a) {
     }
 }
 
-template <int NT, bool F16, int MAXT>
-int launch_lstm16_t(rmr_model *m, LstmS16Args &a, int64_t n) {
-    rmr_engine *e = m->eng;
-    const size_t lds = (size_t)4 * 16 * NT * a.rb;
-    if (lds > 160 * 1024 - 256) RMR_FAIL(RMR_ERR_INVALID, "streamed 16-bit LSTM: %zu B of LDS for %d hidden units", lds, a.H);
-    if ((size_t)a.H * 16 * NT * 4 > lds / 2) RMR_FAIL(RMR_ERR_INVALID, "internal: fc partial sums do not fit the h images");
-    a.lds_bytes = (int)lds;
-    const int64_t groups = (n + 16 * NT - 1) / (16 * NT);
-    int64_t grid = (int64_t)e->num_cus * 4;
-    if (grid > groups) grid = groups;
-    if (grid < 1) return 0;
-    auto kern = lstm_stream16_kernel<NT, F16, MAXT>;
-    RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(kern)));
-    ProfScope ps(e, K_LSTM_HEAD);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(4 * a.H), lds, e->stream, a);
-    RMR_HIP(hipGetLastError());
-    return 0;
-}
-
 }  // namespace
 
 int launch_lstm_stream16(rmr_model *m, const uint16_t *x, int64_t n, float *logits) {
     const int H = m->desc.size;
     if (H % 32 || H > 256 || !m->lstm.s16_ih) RMR_FAIL(RMR_ERR_INVALID, "internal: LSTM of %d units not packed for the streamed 16-bit kernel", H);
+    const LstmStreamPlan p = plan_lstm_stream16(H, n, m->eng->num_cus);  // rmr_plan.h
+    if (p.lds > STREAM_MAX_LDS) RMR_FAIL(RMR_ERR_INVALID, "streamed 16-bit LSTM: %zu B of LDS for %d hidden units", p.lds, H);
+    if (!p.ok) RMR_FAIL(RMR_ERR_INVALID, "internal: fc partial sums do not fit the h images");
+    if (p.grid < 1) return 0;
     LstmS16Args a;
     a.x = x; a.logits = logits; a.n = n; a.T = m->T; a.num_out = m->desc.num_out; a.H = H;
-    a.ksh = H / 32; a.rb = H * 2 + 16; a.div_c8 = make_fastdiv(H / 8);
+    a.ksh = p.ksh; a.rb = p.rb; a.lds_bytes = (int)p.lds; a.div_c8 = make_fastdiv(H / 8);
     a.a_ih = reinterpret_cast<const uint4 *>(m->lstm.s16_ih); a.a_hh = reinterpret_cast<const uint4 *>(m->lstm.s16_hh);
     a.a_ih2 = reinterpret_cast<const uint4 *>(m->lstm.s16_ih2);
     a.b1 = m->lstm.s16_b1; a.b2 = m->lstm.s16_b2; a.w_fc = m->lstm.w_fc; a.b_fc = m->lstm.b_fc;
-    if (H <= 128) return m->f16 ? launch_lstm16_t<4, true, 512>(m, a, n) : launch_lstm16_t<4, false, 512>(m, a, n);
-    return m->f16 ? launch_lstm16_t<2, true, 1024>(m, a, n) : launch_lstm16_t<2, false, 1024>(m, a, n);
+    rmr_engine *e = m->eng;
+    auto kern = p.nt == 4 ? (m->f16 ? lstm_stream16_kernel<4, true, 512> : lstm_stream16_kernel<4, false, 512>)
+                          : (m->f16 ? lstm_stream16_kernel<2, true, 1024> : lstm_stream16_kernel<2, false, 1024>);
+    RMR_TRY(e->allow_big_lds(reinterpret_cast<const void *>(kern)));
+    ProfScope ps(e, K_LSTM_HEAD);
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(p.threads), p.lds, e->stream, a);
+    RMR_HIP(hipGetLastError());
+    return 0;
 }
 
 }  // namespace rmr

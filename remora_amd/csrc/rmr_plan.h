@@ -1,11 +1,17 @@
-// Launch plans of the fp32 convolutions: conv_mfma_kernel (k_conv.hip) and the folded fronts sig3_front_* / seq2_front_*
-// (k_conv_front.hip) - chunks per block iteration, LDS layout, dynamic LDS bytes and grid, from the model geometry, the batch
-// size, the CU count and the kernel's registers.  Plain integers in, a plain struct out, no HIP: the support checks and the
-// launchers call the same function (tests/c/front_plans.cpp calls it on the CPU).
+// Launch plans of the model kernels whose chunk count, LDS image and grid depend on the shape: the fp32 convolutions
+// conv_mfma_kernel (k_conv.hip) and the folded fronts sig3_front_* / seq2_front_* (k_conv_front.hip), seq_conv1's carve
+// (k_front.hip), the streamed-weight kernels of the networks of more than 64 channels (k_stream.hip, k_stream16.hip) and the
+// split-operand convolution (k_conv_bf16s.hip) - chunks per block iteration, LDS layout, dynamic LDS bytes, block size and
+// grid, from the model geometry, the batch size, the CU count and (fp32 conv, fronts) the kernel's registers.  Plain integers
+// in, a plain struct out, no HIP: the support checks and the launchers call the same function, and so do tests/c/front_plans.cpp
+// and tests/c/stream_plans.cpp on the CPU.  A launcher calls its plan, refuses what is not `ok`, fills its argument struct and
+// launches.  (Not here: fused_front_plan of k_fused.hip, which writes a device argument struct; kernels with static LDS.)
 //
-// The common recipe: blocks per CU from the kernel's registers (512 per SIMD lane, granule 8), the LDS budget of a block =
-// its share of the CU's 160 KB at that occupancy, capped at 72 KB (two blocks per CU); the chunk count per iteration that
-// fits the budget (and fills its 16-column tiles best); fewer chunks for a small batch; persistent blocks, 8 per CU.
+// The common recipe of the fp32 conv and the fronts: blocks per CU from the kernel's registers (512 per SIMD lane, granule 8),
+// the LDS budget of a block = its share of the CU's 160 KB at that occupancy, capped at 72 KB (two blocks per CU); the chunk
+// count per iteration that fits the budget (and fills its 16-column tiles best); fewer chunks for a small batch; persistent
+// blocks, 8 per CU.  The streamed and split kernels plan against fixed budgets; their recipes differ from this one and from
+// each other in the ways their sections name.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -44,53 +50,164 @@ inline int64_t plan_grid(int64_t iters, int num_cus, int per_cu) {
 inline int plan_plane(int k, int pin) { return ((k * pin * 4) + 63) & ~63; }
 inline int plan_vplane(int k, int ngrp) { return ((k * ngrp + 15) & ~15) * 4; }
 inline int up4(int words) { return (words + 3) & ~3; }
-
-// ---- conv_mfma_kernel<IC, KW, STRIDE> of `oc` output channels (k_conv.hip) ----
-struct ConvPlan {
-    bool ok = false;
-    int cb = 0;                  // chunks per iteration (1 with windows)
-    int nwin = 1, pin = 0, pout = 0;  // position windows: rows staged / columns computed per window (the chunk's when nwin == 1)
-    int plane = 0;               // LDS plane stride in floats
-    size_t budget = 0, lds = 0;  // the block's LDS share; dynamic LDS bytes
-    int64_t grid = 0;
-};
-
-inline ConvPlan plan_conv_mfma(int ic, int kw, int stride, int oc, int pin, int pout, int64_t n, int num_cus, int regs) {
-    ConvPlan p;
-    const int RS = (ic / 16) % 2 == 0 ? ic / 4 + 4 : ic / 4;  // floats per row per plane (conv_mfma_kernel)
-    p.budget = plan_budget(plan_resident(regs, oc / 16, 8));
-    // among the chunk counts that fit, the one whose columns fill their 16-column tiles best wins (Conv_w_ref's merge_conv1:
-    // 4 x 20 columns = 5 tiles exactly, where 5 chunks would pad the 7th tile to 25 %); ties go to the larger count
-    const size_t row_bytes = (size_t)pin * RS * 4 * sizeof(float);  // all four planes
-    int cb_max = (int)(p.budget / row_bytes);
-    cb_max = cb_max < 1 ? 1 : (cb_max > 8 ? 8 : cb_max);
+// floats per row and plane of the four-plane fp32 images (conv_mfma_kernel, k_stream.hip, k_lstm.hip): a quarter of the
+// channels, + 4 where that makes row stride / 4 odd (every 16-lane ds_read_b128 group on 16 distinct bank slots)
+constexpr int plan_row_stride(int channels) { return (channels / 16) % 2 == 0 ? channels / 4 + 4 : channels / 4; }
+// chunks per iteration whose rows of `row_bytes` fit `budget`, 1 .. 8
+inline int plan_cb_max(size_t budget, size_t row_bytes) { return budget < row_bytes ? 1 : (budget / row_bytes > 8 ? 8 : (int)(budget / row_bytes)); }
+// among the chunk counts cb_max .. (cb_max + 1) / 2, the one whose columns fill their 16-column tiles best (Conv_w_ref's
+// merge_conv1: 4 x 20 columns = 5 tiles exactly, where 5 chunks would pad the 7th tile to 25 %); ties go to the larger count
+inline int plan_best_cb(int cb_max, int pout) {
     int cb = cb_max;
     double best = -1.0;
     for (int k = cb_max; k >= (cb_max + 1) / 2; --k) {
         const double eff = plan_tile_fill(k * pout);
         if (eff > best + 1e-9) { best = eff; cb = k; }
     }
-    cb = plan_spread(cb, n, num_cus);
-    // a chunk whose rows do not fit the share goes through position windows: the most output positions whose input rows
-    // ((win - 1) * stride + kw of them) fit, whole column tiles, one window of one chunk per iteration
-    p.pin = pin;
-    p.pout = pout;
-    if (row_bytes > p.budget) {
-        const int rows_fit = (int)(p.budget / ((size_t)RS * 4 * sizeof(float)));
-        p.pout = (rows_fit - kw) / stride + 1;
-        if (p.pout < 16) return p;
-        p.pout &= ~15;
-        p.nwin = (pout + p.pout - 1) / p.pout;
-        p.pin = (p.pout - 1) * stride + kw;
-        cb = 1;
-    }
-    p.cb = cb;
-    p.plane = ((cb * p.pin * RS) + 63) & ~63;
-    p.lds = (size_t)p.plane * 4 * sizeof(float) + 64;  // + trash slot for masked staging writes
-    if (p.lds > PLAN_LDS_CU) return p;
-    const int64_t iters = p.nwin > 1 ? n * p.nwin : (n + cb - 1) / cb;
-    p.grid = plan_grid(iters, num_cus, 8 * (oc >= 64 ? 1 : 64 / oc));
-    p.ok = true;
+    return cb;
+}
+
+// ---- conv_mfma_kernel<IC, KW, STRIDE> of `oc` output channels (k_conv.hip); conv_stream_kernel<KW, STRIDE> (k_stream.hip) ----
+struct ConvPlan {
+    bool ok = false;
+    int nw = 0, cb = 0;          // waves per block (conv_stream_kernel); chunks per iteration (1 with windows)
+    int nwin = 1, pin = 0, pout = 0;  // position windows: rows staged / columns computed per window (the chunk's when nwin == 1)
+    int rs = 0, plane = 0;       // floats per row and plane; LDS plane stride in floats
+    size_t budget = 0, lds = 0;  // the block's LDS share; dynamic LDS bytes (0: not even one window fits the share)
+    int64_t grid = 0;
+};
+
+// a chunk whose rows do not fit goes through position windows: the most output positions whose input rows ((win - 1) * stride
+// + kw of them) fit `budget`, whole column tiles, one window of one chunk per iteration.  false: fewer than 16 columns fit
+inline bool plan_windows(ConvPlan &p, int kw, int stride, int pout) {
+    const int rows_fit = (int)(p.budget / ((size_t)p.rs * 4 * sizeof(float)));
+    p.pout = (rows_fit - kw) / stride + 1;
+    if (p.pout < 16) return false;
+    p.pout &= ~15;
+    p.nwin = (pout + p.pout - 1) / p.pout;
+    p.pin = (p.pout - 1) * stride + kw;
+    p.cb = 1;
+    return true;
+}
+// the image of p.cb x p.pin rows: four planes + the trash slot for masked staging writes; the grid over its iterations
+inline void plan_conv_image(ConvPlan &p, int64_t n, int num_cus, int per_cu) {
+    p.plane = ((p.cb * p.pin * p.rs) + 63) & ~63;
+    p.lds = (size_t)p.plane * 4 * sizeof(float) + 64;
+    p.grid = plan_grid(p.nwin > 1 ? n * p.nwin : (n + p.cb - 1) / p.cb, num_cus, per_cu);
+}
+
+inline ConvPlan plan_conv_mfma(int ic, int kw, int stride, int oc, int pin, int pout, int64_t n, int num_cus, int regs) {
+    ConvPlan p;
+    p.rs = plan_row_stride(ic);
+    p.budget = plan_budget(plan_resident(regs, oc / 16, 8));
+    const size_t row_bytes = (size_t)pin * p.rs * 4 * sizeof(float);  // all four planes
+    p.cb = plan_spread(plan_best_cb(plan_cb_max(p.budget, row_bytes), pout), n, num_cus);
+    p.pin = pin; p.pout = pout;
+    if (row_bytes > p.budget && !plan_windows(p, kw, stride, pout)) return p;
+    plan_conv_image(p, n, num_cus, 8 * (oc >= 64 ? 1 : 64 / oc));
+    p.ok = p.lds <= PLAN_LDS_CU;
+    return p;
+}
+
+// ---- the streamed-weight kernels (k_stream.hip fp32, k_stream16.hip bf16 / f16): channel counts are runtime values ----
+constexpr size_t STREAM_BUDGET = 65536;                // rows of several chunks: two blocks per CU
+constexpr size_t STREAM_MAX_LDS = 160 * 1024 - 256;    // what one block may take
+constexpr size_t STREAM_WINDOW_ABOVE = 150 * 1024;     // fp32 conv: a chunk of more staged bytes (+ trash slot) goes through windows
+constexpr int STREAM_GRID_PER_CU = 4;
+
+// waves per block of both streamed convolutions: one output-channel tile each where that is at most 8, else the largest divisor
+// of the tile count in 8 .. 4 (equal work), else 8
+inline int plan_stream_waves(int oc) {
+    const int ot = oc / 16;
+    for (int d = 8; ot > 8 && d >= 4; --d)
+        if (ot % d == 0) return d;
+    return ot < 8 ? ot : 8;
+}
+
+// conv_stream_kernel: no spreading of a small batch; ONE chunk may take up to STREAM_WINDOW_ABOVE, a longer one goes through
+// windows sized against STREAM_BUDGET
+inline ConvPlan plan_conv_stream(int ic, int oc, int kw, int stride, int pin, int pout, int64_t n, int num_cus) {
+    ConvPlan p;
+    p.nw = plan_stream_waves(oc);
+    p.rs = plan_row_stride(ic);
+    p.budget = STREAM_BUDGET;
+    const size_t row_bytes = (size_t)pin * p.rs * 4 * sizeof(float);  // all four planes
+    p.cb = plan_best_cb(plan_cb_max(p.budget, row_bytes), pout);
+    p.pin = pin; p.pout = pout;
+    if (row_bytes + 64 > STREAM_WINDOW_ABOVE && !plan_windows(p, kw, stride, pout)) return p;
+    plan_conv_image(p, n, num_cus, STREAM_GRID_PER_CU);
+    p.ok = p.lds <= STREAM_MAX_LDS;
+    return p;
+}
+
+// conv_stream16_kernel: flat rows of 16-bit channels + 16 bytes (row bytes / 16 odd); an iteration's image is its chunks' rows
+// + the rows a padded k-step and a clamped column may touch.  No windows: a chunk that does not fit is refused
+struct Conv16Plan {
+    bool ok = false;
+    int nw = 0, cb = 0, rb = 0, ks = 0;  // waves per block; chunks per iteration; LDS row bytes; k-steps of 32
+    size_t lds = 0;                      // dynamic LDS bytes, whole 16-byte pieces (the kernel zero-fills them)
+    int64_t grid = 0;
+};
+inline int plan_row_bytes16(int channels) { return channels * 2 + 16; }
+inline size_t plan_conv_stream16_lds(int ic, int kw, int pin, int cb) { return ((size_t)cb * pin + kw + 2) * plan_row_bytes16(ic); }
+
+inline Conv16Plan plan_conv_stream16(int ic, int oc, int kw, int pin, int pout, int64_t n, int num_cus) {
+    Conv16Plan p;
+    p.nw = plan_stream_waves(oc);
+    p.rb = plan_row_bytes16(ic);
+    p.ks = (kw * ic + 31) / 32;
+    p.cb = plan_spread(plan_best_cb(plan_cb_max(STREAM_BUDGET, (size_t)pin * p.rb), pout), n, num_cus);
+    p.lds = (plan_conv_stream16_lds(ic, kw, pin, p.cb) + 15) & ~(size_t)15;
+    p.grid = plan_grid((n + p.cb - 1) / p.cb, num_cus, STREAM_GRID_PER_CU);
+    p.ok = p.lds <= STREAM_MAX_LDS;  // (cb > 1 always fits: several chunks' rows stay within STREAM_BUDGET)
+    return p;
+}
+
+// lstm_stream_kernel / lstm_stream16_kernel: H / 16 waves x 16 nt chunks per group, two x and two h images.  Four column tiles
+// per wave halve the weight traffic of two, and fit (registers: 512 threads; LDS) up to 128 units
+struct LstmStreamPlan {
+    bool ok = false;
+    int nt = 0, threads = 0, bound = 0;  // column tiles per wave; block size 4 H; the instantiation's launch bound
+    int rs = 0, rb = 0, ksh = 0;         // fp32: floats per row and plane;  16-bit: row bytes, k-steps of 32
+    size_t lds = 0;
+    int64_t grid = 0;
+};
+inline LstmStreamPlan plan_lstm_streamed(int H, int64_t n, int num_cus, bool half) {
+    LstmStreamPlan p;
+    p.nt = H <= 128 ? 4 : 2;
+    p.bound = H <= 128 ? 512 : 1024;
+    p.threads = 4 * H;
+    p.rs = plan_row_stride(H);
+    p.rb = plan_row_bytes16(H);
+    p.ksh = H / 32;
+    p.lds = (size_t)4 * 16 * p.nt * (half ? p.rb : 4 * p.rs * sizeof(float));  // 4 images of 16 nt rows (fp32: in 4 planes)
+    p.grid = plan_grid((n + 16 * p.nt - 1) / (16 * p.nt), num_cus, STREAM_GRID_PER_CU);
+    // 16-bit: the fc partial sums [H / 16][16 nt][16] floats take the place of the two h images
+    p.ok = p.lds <= STREAM_MAX_LDS && (!half || (size_t)H * 16 * p.nt * 4 <= p.lds / 2);
+    return p;
+}
+inline LstmStreamPlan plan_lstm_stream(int H, int64_t n, int num_cus) { return plan_lstm_streamed(H, n, num_cus, false); }
+inline LstmStreamPlan plan_lstm_stream16(int H, int64_t n, int num_cus) { return plan_lstm_streamed(H, n, num_cus, true); }
+
+// ---- conv_bf16s_kernel<IC, ..., NP> (k_conv_bf16s.hip): `nparts` images of 16-byte slots (8 channels), 2 planes (ic 16: two
+// taps per k-step) or 4; whole groups of four chunks from 4 up; no spreading; 2 blocks per CU ----
+constexpr size_t SPLIT_BUDGET = 112 * 1024;
+struct SplitPlan {
+    bool ok = false;
+    int cb = 0, plane = 0, part = 0;  // chunks per iteration; plane / part stride in slots
+    size_t lds = 0;
+    int64_t grid = 0;
+};
+inline SplitPlan plan_conv_split(int ic, int pin, int nparts, int64_t n, int num_cus) {
+    SplitPlan p;
+    const int ks = ic == 16 ? 1 : ic / 32, slr = ks % 2 == 0 ? ks + 1 : ks, planes = ic == 16 ? 2 : 4;  // slr: odd row stride in slots
+    p.cb = plan_cb_max(SPLIT_BUDGET, (size_t)pin * slr * 16 * planes * nparts);
+    if (p.cb >= 4) p.cb &= ~3;
+    p.plane = ((p.cb * pin + 2) * slr + 15) & ~15;  // + 2 guard rows
+    p.part = planes * p.plane + 16;                 // + trash slot
+    p.lds = (size_t)p.part * nparts * 16;
+    p.grid = plan_grid((n + p.cb - 1) / p.cb, num_cus, 2);
+    p.ok = p.lds <= PLAN_LDS_CU;
     return p;
 }
 

@@ -3,10 +3,14 @@
 Networks of more than 64 channels run on conv_stream_kernel / lstm_stream_kernel (k_stream.hip, fp32) and conv_stream16_kernel /
 lstm_stream16_kernel (k_stream16.hip, bf16 and f16).  Which form of those kernels a launch takes - waves per block, chunks per
 block iteration (cb), position windows, the column tiles of a work item (NTV), LDS bytes - is decided on the host by
-launch_conv_stream_t, launch_lstm_stream, launch_conv16_t and launch_lstm_stream16.  The functions below restate that arithmetic
-in the way conv_split_plan (tests/test_gpu_split_shapes.py) restates launch_conv_s_t, so that tests/test_host_stream_cases.py can
-assert without a GPU that every case takes the path it is there for.  THE RESTATEMENT HAS TO FOLLOW THE KERNELS: when the launch
-code changes, change it here, and look at the case table again - a case may no longer reach its path.
+plan_conv_stream, plan_lstm_stream, plan_conv_stream16 and plan_lstm_stream16 (remora_amd/csrc/rmr_plan.h), which the launchers
+call.  The functions below restate that arithmetic in the way conv_split_plan (tests/test_gpu_split_shapes.py) restates
+plan_conv_split, so that tests/test_host_stream_cases.py can assert without a GPU, and the GPU tests use where nothing is
+compiled, that every case takes the path it is there for.  The restatement is held to the launch code by
+test_stream_plans_keep_their_invariants_and_the_restatement_follows_them (tests/test_host_stream_cases.py): it runs the header's
+plans on the CPU over every size, chunk length and batch of the case tables and compares every number with the functions here.
+When it fails after a change of the plans, change them here, and look at the case table again - a case may no longer reach its
+path.
 
 A plain module (no tests in it), like duplex_fixture.py."""
 from collections import namedtuple

@@ -24,8 +24,8 @@ _cases = {}
 
 
 def conv_split_plan(ic, pin, nparts):
-    """launch_conv_s_t's arithmetic (k_conv_bf16s.hip): (chunks per block iteration, LDS bytes) of a split convolution of `ic`
-    input channels whose chunks have `pin` input rows."""
+    """plan_conv_split's arithmetic (rmr_plan.h, for k_conv_bf16s.hip): (chunks per block iteration, LDS bytes) of a split
+    convolution of `ic` input channels whose chunks have `pin` input rows.  tests/test_host_stream_cases.py holds it to the header."""
     pair = ic == 16                      # two taps per k-step, two planes
     ks = 1 if pair else ic // 32
     slr = ks + 1 if ks % 2 == 0 else ks  # odd row stride in 16-byte slots

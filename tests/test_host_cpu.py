@@ -2820,8 +2820,9 @@ def test_staging_layouts_are_aligned_disjoint_and_within_the_committed_total(tmp
 
 
 def test_front_plans_fit_their_budgets_and_pin_the_benchmark_shapes(tmp_path):
-    """rmr_plan.h is the ONE place where the launch plans of the fp32 conv and front kernels are made (the support checks and the
-    launchers of k_conv.hip / k_conv_front.hip call it).  tests/c/front_plans.cpp: over a sweep of chunk lengths, sequence
+    """rmr_plan.h is the ONE place where launch plans are made; this test is about those of the fp32 conv and front kernels (the
+    support checks and the launchers of k_conv.hip / k_conv_front.hip call it), tests/test_host_stream_cases.py about those of
+    the streamed-weight and split kernels.  tests/c/front_plans.cpp: over a sweep of chunk lengths, sequence
     widths, batch sizes, CU counts and register counts every plan stays within the LDS budget it was planned against and within
     160 KB; the plans of ConvLSTM_w_ref size 64 at C100 / C200 (256 CUs, the kernels' gfx950 register counts) are pinned.  The
     11-tap signal front and launch_front's seq_conv1 carve (plan_front_seq) are checked at every chunk length Conv_w_ref admits,

@@ -126,6 +126,78 @@ def test_16bit_cases(cus):
         assert pin == (150 if ok else 151)
 
 
+# ---- the restatement is the launch code's ------------------------------------------------------------------------------------------
+def test_stream_plans_keep_their_invariants_and_the_restatement_follows_them(tmp_path):
+    """rmr_plan.h makes the launch plans of the streamed-weight kernels and of the split convolution; their launchers only fill
+    the argument structs from them.  tests/c/stream_plans.cpp (plain g++, no HIP) sweeps ConvLSTM_w_ref at every size 80 .. 256,
+    chunk length 29 .. 470, batch 1 .. 8 CUs + 37 and 256 / 304 / 80 CUs: every plan that is ok stays within its kernel's LDS limit
+    and its chunk budget, windows tile the chunk, the wave count divides the output tiles or is 8, the LSTM block is 4 H threads
+    within its launch bound and the fc partial sums fit (the count's floor: what the program makes, so that the sweep cannot
+    shrink unseen).  Then one line per plan, and the plans restated in Python - stream_cases.conv_stream_plan, conv16_plan, waves,
+    lstm_stream_plan, lstm_stream16_plan and test_gpu_split_shapes.conv_split_plan, which the GPU tests and the case checks above
+    rely on - give the same numbers on every line, the shapes of the case tables among them.  (n and the CU count reach the fp32
+    convolutions, the LSTMs and the split convolution through the grid alone, which the restatement does not have: one line per
+    shape; the 16-bit convolutions' lines carry both.)"""
+    import os
+    import shutil
+    import subprocess
+
+    import test_gpu_split_shapes as P
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is part of the image"
+    (tmp_path / "hip").mkdir()
+    (tmp_path / "hip" / "hip_runtime.h").write_text("#pragma once\n#define __host__\n#define __device__\n")
+    exe = str(tmp_path / "plans")
+    cc = subprocess.run([gxx, "-O2", "-std=c++17", "-Wall", "-I", str(tmp_path), "-I", os.path.join(root, "remora_amd", "csrc"),
+                         os.path.join(root, "tests", "c", "stream_plans.cpp"), "-o", exe], capture_output=True, text=True)
+    assert cc.returncode == 0 and not cc.stderr, cc.stderr
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, run.stdout[:4000] + run.stderr
+    out = run.stdout.splitlines()
+    assert out[0].endswith(" 0 violations") and int(out[0].split()[0]) > 6_000_000, out[0]
+
+    specs, seen32, seen16, count = {}, set(), set(), dict.fromkeys(("conv32", "conv16", "lstm32", "lstm16", "split"), 0)
+    for line in out[1:]:
+        kind, *f = line.split()
+        count[kind] += 1
+        if kind in ("conv32", "conv16"):
+            size, L, layer = int(f[0]), int(f[1]), f[4 if kind == "conv16" else 2]
+            if (size, L) not in specs:
+                specs = {(size, L): S.conv_layers(size, L)}  # (the lines of a shape follow each other)
+            ic, oc, kw, stride, pin, pout = specs[size, L][layer]
+        if kind == "conv32":
+            ok, nw, cb, nwin, pin_w, pout_w, rs, lds = map(int, f[3:])
+            p = S.conv_stream_plan(ic, oc, kw, stride, pin, pout)
+            assert (p.nw, p.cb, p.nwin, p.pin_w, p.pout_w, p.rs, p.lds) == (nw, cb, nwin, pin_w, pout_w, rs, lds) and nw == S.waves(oc), line
+            assert ok == (lds <= S.LDS_LIMIT) == 1, line
+            seen32.add((size, L))
+        elif kind == "conv16":
+            n, cus, (ok, nw, cb, lds) = int(f[2]), int(f[3]), map(int, f[5:])
+            assert S.conv16_plan(ic, oc, kw, pin, pout, n, cus) == (nw, cb, lds) and ok == (lds <= S.LDS_LIMIT), line
+            seen16.add((size, L, n, cus))
+        elif kind in ("lstm32", "lstm16"):
+            size, ok, nt, threads, lds = map(int, f)
+            assert (S.lstm_stream_plan if kind == "lstm32" else S.lstm_stream16_plan)(size) == (nt, threads, lds) and ok == 1, line
+        else:
+            ic, pin, parts, ok, cb, lds = map(int, f)
+            assert P.conv_split_plan(ic, pin, parts) == (cb, lds) and ok == (lds <= 160 * 1024), line
+    sweep = len(S.SIZES) * len(range(29, 471))
+    assert count == {"conv32": 3 * sweep, "conv16": 3 * sweep * 27, "lstm32": 12, "lstm16": 6, "split": 3 * 591 * 3}, count
+    # every shape of the case tables was compared: the fp32 cases by (size, L), the 16-bit ones with their batch and both CU counts
+    for c in S.FP32_CASES:
+        assert (c.size, c.L) in seen32, c
+    for size, L, _ in S.WINDOW_SWITCH:
+        assert (size, L) in seen32, (size, L)
+    for cus in (256, 304):
+        for c in S.CASES16:
+            for n in (c.n if c.n is not None else 8 * cus + 37, 64, 300):  # the case's batch; what test_16bit_cases asks besides
+                assert (c.size, c.L, n, cus) in seen16, (c, n, cus)
+        for L in S.LDS_EDGE16[1:]:
+            assert (S.LDS_EDGE16[0], L, 3, cus) in seen16, (L, cus)
+
+
 # ---- the fp32 gate has teeth on the long-chunk cases ------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", S.LONG_CASES, ids=lambda c: f"{c.size}-{c.L}")
 def test_one_wrong_tile_of_merge_conv1_moves_the_logits_by_three_gates(case):
