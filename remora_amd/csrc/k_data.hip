@@ -194,13 +194,18 @@ int launch_encode(rmr_engine *e, int kb, int ka, const int8_t *seqs, int seq_w,
     const size_t mapb = pf ? (((size_t)map_w * 2 + 15) & ~(size_t)15) : 0;
     const size_t per_wave = ((size_t)Lp * 4 + ((seq_w + 15) & ~15) + mapb + 15) & ~(size_t)15;
     const size_t lds = per_wave * 4;
+    // (the kernel is launched with the default dynamic-LDS limit: a longer chunk or wider rows would fail at the launch)
+    if (lds > 64 * 1024)
+        RMR_FAIL(RMR_ERR_INVALID, "encode: chunk length %d with rows of %d and %d elements needs %zu bytes of LDS (limit %d)", sig_len, seq_w,
+                 map_w, lds, 64 * 1024);
     int64_t grid = (int64_t)e->num_cus * 8;
     if (grid > (n + 3) / 4) grid = (n + 3) / 4;
     ProfScope ps(e, K_ENCODE);
-    // the shapes of the shipped models' chunk contexts get an unrolled store loop; anything else the plain one
+    // the shapes of the shipped models' chunk contexts get an unrolled store loop; anything else the plain one.  NST > 0 runs
+    // the code form whatever the shape, so the store count alone does not choose it: 6 x 150 or 12 x 75 have nst 15 as well
     const int nst = (a.K * sig_len + 63) / 64;
     void (*kern)(EncodeArgs) = pf == 1 ? encode_kernel<1, 0> : pf == 2 ? encode_kernel<2, 0> : pf == 4 ? encode_kernel<4, 0> : encode_kernel<0, 0>;
-    if (pf == 1 && form >= 2) {
+    if (pf == 1 && form >= 2 && (sig_len & 3) == 0 && a.K <= 10) {
         if (nst == 15) kern = encode_kernel<1, 15>;       // 9-mer, 100 samples
         else if (nst == 29) kern = encode_kernel<1, 29>;  // 9-mer, 200 samples
         else if (nst == 10) kern = encode_kernel<1, 10>;  // 6-mer, 100 samples
@@ -735,7 +740,7 @@ __global__ __launch_bounds__(256) void count_kernel(const float *logits, int64_t
         float bv = p[0];
         for (int o = 1; o < num_out; ++o) {
             const float v = p[o];
-            if (v > bv) { bv = v; best = o; }
+            if (v > bv || (v != v && bv == bv)) { bv = v; best = o; }  // np.argmax: the first NaN is the maximum
         }
         atomicAdd(&bins[best], 1u);
     }
@@ -879,13 +884,14 @@ __global__ __launch_bounds__(256) void validation_tally_kernel(TallyArgs a) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
         const float *p = a.logits + i * a.km;
         float v[16];
-        float mx = -3.0e38f;
+        float mx = 0.0f;
         int best = 0;
 #pragma unroll
         for (int c = 0; c < 16; ++c) {
             if (c < a.kf) {
                 v[c] = a.colmap[c] >= 0 ? p[a.colmap[c]] : -1000.0f;
-                if (v[c] > mx) { mx = v[c]; best = c; }
+                // np.argmax / np.max: the first maximum, and the first NaN is one (the row's probabilities are NaN then)
+                if (c == 0 || v[c] > mx || (v[c] != v[c] && mx == mx)) { mx = v[c]; best = c; }
             }
         }
         float s = 0.0f, eb = 0.0f;
