@@ -6,7 +6,8 @@ the stored chunks of an on-disk dataset (directory or config) through the model 
 k-mer contexts, the reference's validation summary line against the stored labels; and `python -m remora_amd dataset prepare`
 (:64-337), the ETL into the on-disk chunk format, with the bookkeeping verbs around that format (`dataset inspect |
 make_config | merge | head | copy`, :359-727: host code over `CoreRemoraDataset` / `RemoraDataset`, no kernel involved);
-`python -m remora_amd model train DATASET --model ARCH.py` (:753-1024): ConvLSTM_w_ref in fp32, the training step in HIP."""
+`python -m remora_amd model train DATASET --model ARCH.py` (:753-1024): ConvLSTM_w_ref in fp32, the training step in HIP;
+`model export CHECKPOINT OUT [--format dorado|torchscript]` and `model inspect CHECKPOINT` (:1036-1162): host code, no GPU."""
 import argparse
 import os
 import sys
@@ -434,9 +435,97 @@ def _model_train(args):
     return 0
 
 
-def _add_model_train(sub):
+def _load_for_export(args, log):
+    """(checkpoint-like dict, state, came from a checkpoint) of `model export` / `model inspect`: the input as a TorchScript
+    model first (its metadata as load_model returns it, without an engine), failing that as a training checkpoint
+    (src/remora/parsers.py:1063-1070)."""
+    from .model_util import _raw_load_torchscript_model, add_derived_metadata, load_checkpoint
+
+    log.info("Loading model")
+    try:
+        if not os.path.isfile(args.checkpoint_path):
+            raise RuntimeError("not a file")
+        state, md = _raw_load_torchscript_model(args.checkpoint_path)
+    except RuntimeError:  # what torch.jit.load says to a file that is no TorchScript archive
+        ckpt = load_checkpoint(args.checkpoint_path, args.model_path)
+        log.info("Loaded model from checkpoint")
+        return ckpt, ckpt["state_dict"], True
+    add_derived_metadata(md)
+    if args.model_path is not None:
+        from .engine import detect_arch
+        from .model_util import scan_model_file
+
+        arch, scanned = detect_arch({k.split(".")[0] for k in state}), scan_model_file(args.model_path)
+        if scanned != arch:
+            raise RemoraError(f"--model-path {args.model_path} assigns the layers of a {scanned} network, the model's state is "
+                              f"that of a {arch} network")
+    log.info("Loaded a torchscript model")
+    return md, state, False
+
+
+def _model_log():
+    import logging
+
+    log = logging.getLogger("Remora")
+    log.setLevel(logging.INFO)
+    if not log.handlers:
+        log.addHandler(logging.StreamHandler(sys.stderr))
+    return log
+
+
+def _model_inspect(args):
+    """src/remora/parsers.py:1055-1104.  No engine, no GPU."""
+    from .model_util import refiner_from_checkpoint, repr_model_metadata
+
+    log = _model_log()
+    md, _, from_ckpt = _load_for_export(args, log)
+    if from_ckpt:
+        md = dict(md)
+        md["sig_map_refiner"] = refiner_from_checkpoint(md)
+        if md.get("refine_kmer_levels") is None:  # models from before the refiner
+            md["base_start_justify"], md["offset"] = False, 0
+        for key in [k for k in md if k.startswith("refine_")] + ["state_dict", "opt"]:
+            md.pop(key, None)
+    log.info(f"Loaded Remora model attrs\n{repr_model_metadata(md)}\n")
+    log.info("Done")
+    return 0
+
+
+def _model_export(args):
+    """src/remora/parsers.py:1136-1162.  No engine, no GPU."""
+    from .model_util import export_model_dorado, export_model_torchscript
+
+    log = _model_log()
+    ckpt, state, from_ckpt = _load_for_export(args, log)
+    if args.format == "dorado":
+        log.info("Exporting model to dorado format")
+        export_model_dorado(ckpt, state, args.output_path)
+    else:
+        log.info("Exporting model to TorchScript format")
+        if not from_ckpt:  # the refiner's entries, which add_derived_metadata folded into sig_map_refiner
+            ckpt = {**ckpt["sig_map_refiner"].asdict(), **ckpt}
+        export_model_torchscript(ckpt, state, args.output_path)
+    log.info("Done")
+    return 0
+
+
+def _add_model_export_inspect(model):
+    """The reference's arguments (src/remora/parsers.py:1036-1052, :1107-1133)."""
+    e = model.add_parser("export", help="Export a trained model for deployment: a dorado-format directory or a TorchScript file")
+    e.add_argument("checkpoint_path", help="a training checkpoint, or a TorchScript model file")
+    e.add_argument("output_path", help="directory (dorado) or file (torchscript) to save the model to")
+    e.add_argument("--model-path", help="model architecture file: scanned for its layer names, never executed (default: the checkpoint's)")
+    e.add_argument("--format", default="dorado", choices=["dorado", "torchscript"], help="export format")
+    e.set_defaults(func=_model_export)
+    i = model.add_parser("inspect", help="Print the attributes of a training checkpoint or a TorchScript model file")
+    i.add_argument("checkpoint_path", help="a training checkpoint, or a TorchScript model file")
+    i.add_argument("--model-path", help="model architecture file: scanned for its layer names, never executed (default: the checkpoint's)")
+    i.set_defaults(func=_model_inspect)
+
+
+def _add_model_train(model):
     """The reference's arguments (src/remora/parsers.py:753-975)."""
-    t = sub.add_parser("model").add_subparsers(dest="sub", required=True).add_parser(
+    t = model.add_parser(
         "train", help="Train a ConvLSTM_w_ref model on an MI355X (fp32; forward, backward and AdamW in HIP)")
     t.add_argument("remora_dataset_path", help="Remora training dataset (directory or config)")
     g = t.add_argument_group("Data Arguments")
@@ -486,13 +575,15 @@ def _add_model_train(sub):
 def build_parser():
     ap = argparse.ArgumentParser(prog="remora_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
-    _add_model_train(sub)
+    model = sub.add_parser("model").add_subparsers(dest="sub", required=True)
+    _add_model_train(model)
+    _add_model_export_inspect(model)
     infer = sub.add_parser("infer").add_subparsers(dest="sub", required=True)
     p = infer.add_parser("from_pod5_and_bam", help="Infer modified bases from POD5 + BAM on an MI355X")
     p.add_argument("pod5")
     p.add_argument("in_bam")
     p.add_argument("--model", required=True, action="append",
-                   help="TorchScript model file (with meta.txt); repeat for one model per canonical base")
+                   help="TorchScript model file (with meta.txt) or dorado-format model directory; repeat for one model per canonical base")
     p.add_argument("--out-bam", required=True)
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--gpus", type=int, default=1,
@@ -520,7 +611,7 @@ def build_parser():
     d.add_argument("--duplex-delim", default=";", help="string between the template and complement read ids in the duplex BAM")
     d.add_argument("--out-bam", required=True)
     d.add_argument("--log-filename")
-    d.add_argument("--model", required=True, action="append", help="TorchScript model file (with meta.txt); one model only")
+    d.add_argument("--model", required=True, action="append", help="TorchScript model file (with meta.txt) or dorado-format model directory; one model only")
     d.add_argument("--num-reads", type=int, default=None, help="number of (valid) pairs")
     d.add_argument("--device", type=int, default=0)
     for flag in ("--num-extract-alignment-workers", "--num-duplex-prep-workers", "--num-infer-workers"):
@@ -536,7 +627,7 @@ def build_parser():
     val = sub.add_parser("validate").add_subparsers(dest="sub", required=True)
     v = val.add_parser("from_remora_dataset", help="Validate a model on an on-disk Remora dataset (directory or config)")
     v.add_argument("remora_dataset_path")
-    v.add_argument("--model", required=True)
+    v.add_argument("--model", required=True, help="TorchScript model file (with meta.txt) or dorado-format model directory")
     v.add_argument("--out-file", help="validation summary (default stdout)")
     v.add_argument("--full-results-filename", help="per-chunk label, call and probabilities (TSV)")
     v.add_argument("--pct-filt", type=float, default=10.0)

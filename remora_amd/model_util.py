@@ -7,9 +7,12 @@ JSON dict (:115-176).  torch.jit.load is used only to read the file; the weights
 HIP engine (BatchNorm folding and MFMA packing happen inside rmr_model_create) and what is
 returned in place of the ScriptModule is a `HipModel`.
 
+A dorado-format model directory (`config.toml` plus one `*.tensor` file per parameter, the form export_model_dorado :179-309
+writes) is the second model format: `load_model` takes the directory, `export_model_dorado` writes it.
+
 The training side of the same module: TrainOpts :77-107, CustomPlusCoolDownScheduler :34-74 and
 export_model_torchscript :115-176, for remora_amd.train_model; `scan_model_file` stands in for
-_load_python_model (:451-465): the architecture file of `--model` is read, never executed.
+_load_python_model (:317-324): the architecture file of `--model` is read, never executed.
 """
 import ast
 import dataclasses
@@ -21,8 +24,8 @@ from os.path import isfile
 
 import numpy as np
 
-from . import RemoraError, constants
-from .engine import HipModel, _torch, detect_arch
+from . import RemoraError, constants, toml_lite
+from .engine import _CONV_ORDER, HipModel, _torch, detect_arch
 from .refine_signal_map import SigMapRefiner
 
 LOGGER = logging.getLogger("Remora")
@@ -96,26 +99,206 @@ def _raw_load_torchscript_model(model_filename, device=None):
 
 
 def load_torchscript_model(model_filename, device=None, quiet=False, eval_only=False, dtype=None):
-    state, md = _raw_load_torchscript_model(model_filename, device)
-    add_derived_metadata(md)
+    """A model file - or a dorado-format model directory (`read_dorado_model`) - onto the engine."""
+    if os.path.isdir(model_filename):
+        state, md = read_dorado_model(model_filename)
+    else:
+        state, md = _raw_load_torchscript_model(model_filename, device)
+        add_derived_metadata(md)
     # arithmetic of the GEMM stages: "fp32" (default, exact fp32 MFMA) or a bf16-MFMA mode
     # ("bf16x6" fp32-class split, "bf16x3", "bf16"); REMORA_HIP_DTYPE overrides the default
     dtype = dtype or os.environ.get("REMORA_HIP_DTYPE", "fp32")
     model = HipModel(state, md["chunk_len"], device=device, dtype=dtype)
     if model.kmer_len != md["kmer_len"]:
         raise RemoraError(f"model weights expect kmer_len {model.kmer_len}, metadata says {md['kmer_len']}")
-    _record_winograd(model, md, os.path.basename(str(model_filename)))
+    _record_winograd(model, md, os.path.basename(os.path.normpath(str(model_filename))))
     return model.eval(), md
+
+
+# ---- dorado-format model directories ------------------------------------------------------------------------------------------
+DORADO_CONFIG = "config.toml"
+DORADO_MODELS = ("conv_lstm", "conv_only")
+_LSTM_KEYS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+_LEVELS_TENSOR = "refine_kmer_levels"
+
+
+def _lost_field_defaults():
+    """What the directory format does not carry, and the value `read_dorado_model` assumes for each."""
+    dflt = SigMapRefiner()
+    return {"base_start_justify": False, "modified_base_labels": True, "refine_scale_iters": dflt.scale_iters,
+            "refine_algo": dflt.algo, "refine_half_bandwidth": dflt.half_bandwidth, "refine_sd_arr": dflt.sd_arr,
+            "model_version": constants.MODEL_VERSION}
+
+
+def ordered_layers(arch):
+    """The layers with weights, BatchNorms aside, in `named_modules` order: creation order in the networks of nets.py."""
+    convs = [c for c, _ in _CONV_ORDER[arch]]
+    return convs + (["lstm1", "lstm2"] if arch == "conv_lstm" else []) + ["fc"]
+
+
+def dorado_tensor_names(arch):
+    """The `<layer>.<key>` names of the tensor files of an architecture, in the exporter's order."""
+    return [f"{layer}.{key}" for layer in ordered_layers(arch)
+            for key in (_LSTM_KEYS if layer.startswith("lstm") else ("weight", "bias"))]
+
+
+def save_tensor_file(path, array):
+    """One `.tensor` file: the TorchScript archive of an empty module with the single parameter "0" (:188-194)."""
+    torch = _torch()
+    m = torch.nn.Module()
+    x = array.detach() if hasattr(array, "detach") else torch.from_numpy(np.ascontiguousarray(array))
+    m.register_parameter("0", torch.nn.Parameter(x, requires_grad=False))
+    torch.jit.script(m).save(str(path))
+
+
+def load_tensor_file(path):
+    """The single parameter or buffer of a `.tensor` file, whatever its name, as a numpy array."""
+    torch = _torch()
+    try:
+        m = torch.jit.load(str(path), map_location="cpu")
+    except RuntimeError as e:
+        raise RemoraError(f"{path}: not a TorchScript tensor file ({str(e).splitlines()[0]})")
+    vals = list(m.parameters()) + list(m.buffers())
+    if len(vals) != 1:
+        raise RemoraError(f"{path}: expected one tensor, found {len(vals)}")
+    return vals[0].detach().cpu().numpy()
+
+
+def read_dorado_model(model_dir):
+    """`config.toml` and the tensor files of a dorado-format directory -> (state, metadata): the state in torch's names
+    with identity BatchNorm statistics beside every (already folded) convolution, the metadata as `add_derived_metadata`
+    leaves that of a model file.  No engine and no GPU is touched."""
+    model_dir = str(model_dir)
+    cfg_path = os.path.join(model_dir, DORADO_CONFIG)
+    if not isfile(cfg_path):
+        raise RemoraError(f"Remora model directory ({model_dir}) holds no {DORADO_CONFIG}.")
+    cfg = toml_lite.load(cfg_path)
+    for table in ("general", "modbases"):
+        if not isinstance(cfg.get(table), dict):
+            raise RemoraError(f"{cfg_path}: no [{table}] table")
+    kind = cfg["general"].get("model")
+    if kind not in DORADO_MODELS:
+        raise RemoraError(f"{cfg_path}: general.model = {kind!r} is not a model type of this engine; supported: "
+                          f"{DORADO_MODELS[0]!r} and {DORADO_MODELS[1]!r}")
+    names = sorted(f[: -len(".tensor")] for f in os.listdir(model_dir) if f.endswith(".tensor"))
+    layers = {n.split(".")[0] for n in names} - {_LEVELS_TENSOR}
+    want = dorado_tensor_names(kind)
+    try:
+        arch = detect_arch(layers)
+    except RemoraError:
+        missing = [n for n in want if n not in names]
+        if missing:
+            raise RemoraError(f"{model_dir}: tensor file {missing[0]}.tensor of a {kind} model is missing"
+                              + (f" (and {len(missing) - 1} more)" if len(missing) > 1 else ""))
+        raise
+    if arch != kind:
+        raise RemoraError(f"{model_dir}: the tensor files are those of a {arch} model, {DORADO_CONFIG} says general.model = {kind!r}")
+    for n in want:
+        if n not in names:
+            raise RemoraError(f"{model_dir}: tensor file {n}.tensor of a {kind} model is missing")
+    state = {n: load_tensor_file(os.path.join(model_dir, n + ".tensor")).astype(np.float32, copy=False) for n in want}
+    # the convolutions are folded already and rmr_model_create folds once more: statistics under which its fold returns
+    # every weight and bias bit for bit (scale 1 / sqrt(float32(1 - 1e-5) + 1e-5) = 1 + 6.8e-9, under fp32's half ulp)
+    for conv, bn in _CONV_ORDER[arch]:
+        oc = state[f"{conv}.weight"].shape[0]
+        state[f"{bn}.weight"] = np.ones(oc, np.float32)
+        state[f"{bn}.bias"] = np.zeros(oc, np.float32)
+        state[f"{bn}.running_mean"] = np.zeros(oc, np.float32)
+        state[f"{bn}.running_var"] = np.full(oc, np.float32(1 - 1e-5), np.float32)
+
+    mb, refinement = cfg["modbases"], cfg.get("refinement", {})
+    lost = _lost_field_defaults()
+    try:
+        md = {"creation_date": cfg["general"].get("creation_date"),
+              "kmer_context_bases": [int(mb["kmer_context_bases_0"]), int(mb["kmer_context_bases_1"])],
+              "chunk_context": [int(mb["chunk_context_0"]), int(mb["chunk_context_1"])],
+              "modified_base_labels": lost["modified_base_labels"], "mod_bases": mb.get("mod_bases", "None"),
+              "reverse_signal": bool(mb.get("reverse_signal", False)), "base_start_justify": lost["base_start_justify"],
+              "offset": int(mb.get("offset", 0)), "pa_scaling": mb.get("pa_scaling"),
+              "model_params": dict(cfg.get("model_params", {})),
+              "motif_0": str(mb["motif"]), "motif_offset_0": str(int(mb["motif_offset"])), "num_motifs": "1",
+              "doc_string": "Nanopore Remora model", "model_version": lost["model_version"]}
+        if md["mod_bases"] != "None":
+            for i in range(len(md["mod_bases"])):
+                md[f"mod_long_names_{i}"] = str(mb[f"mod_long_names_{i}"])
+    except KeyError as e:
+        raise RemoraError(f"{cfg_path}: [modbases] has no {e.args[0]}")
+    offset = md["offset"]
+    add_derived_metadata(md)  # no level table in `md`: the default refiner, and the offset taken for 0
+    md["offset"] = offset
+    if refinement.get("refine_do_rough_rescale"):
+        if _LEVELS_TENSOR not in names:
+            raise RemoraError(f"{model_dir}: refine_do_rough_rescale is set and {_LEVELS_TENSOR}.tensor is missing")
+        if "refine_kmer_center_idx" not in refinement:
+            raise RemoraError(f"{cfg_path}: refine_do_rough_rescale is set and refine_kmer_center_idx is missing")
+        levels = load_tensor_file(os.path.join(model_dir, _LEVELS_TENSOR + ".tensor")).astype(np.float32, copy=False)
+        md["sig_map_refiner"] = SigMapRefiner(_levels_array=levels, center_idx=int(refinement["refine_kmer_center_idx"]),
+                                              do_rough_rescale=True)
+    LOGGER.info(f"model directory {model_dir}: the format does not carry {', '.join(lost)}; defaults assumed")
+    return state, md
+
+
+def refiner_from_checkpoint(ckpt):
+    """The SigMapRefiner of a checkpoint: `sig_map_refiner` where metadata of a loaded model file is passed, otherwise built
+    from the `refine_*` entries of a training checkpoint (src/remora/parsers.py:1073-1091)."""
+    if ckpt.get("sig_map_refiner") is not None:
+        return ckpt["sig_map_refiner"]
+    if ckpt.get("refine_kmer_levels") is None:
+        return SigMapRefiner()
+    return SigMapRefiner(_levels_array=np.asarray(ckpt["refine_kmer_levels"]), center_idx=int(ckpt["refine_kmer_center_idx"]),
+                         do_rough_rescale=ckpt["refine_do_rough_rescale"], scale_iters=int(ckpt["refine_scale_iters"]),
+                         algo=ckpt["refine_algo"], half_bandwidth=int(ckpt["refine_half_bandwidth"]),
+                         sd_arr=np.asarray(ckpt["refine_sd_arr"]))
+
+
+def repr_model_metadata(metadata):
+    """One line per attribute, the per-index entries of parsed values left out (:451-465)."""
+    skip = ("mod_long_names_", "kmer_context_bases_", "chunk_context_", "motif_")
+    return "\n".join(f"  {k: >20} : {v}" for k, v in metadata.items() if not any(k.startswith(p) for p in skip))
+
+
+def load_checkpoint(ckpt_path, model_path=None):
+    """A training checkpoint as `train_model.save_model` writes it (continue_from_checkpoint :327-338).  `model_path` (default:
+    the checkpoint's own, where that file still exists) is scanned for its layer names and never executed; it has to name
+    the architecture the checkpoint's state holds."""
+    torch = _torch()
+    if not isfile(ckpt_path):
+        raise RemoraError(f"Checkpoint path is not a file ({ckpt_path})")
+    import pickle
+
+    try:
+        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=False)
+    except (pickle.UnpicklingError, RuntimeError, EOFError, ValueError) as e:
+        raise RemoraError(f"{ckpt_path} is neither a TorchScript model nor a training checkpoint ({str(e).splitlines()[0]})")
+    if not isinstance(ckpt, dict) or "state_dict" not in ckpt:
+        raise RemoraError(f"{ckpt_path} is no training checkpoint: no state_dict entry")
+    if ckpt["state_dict"] is None:
+        raise RemoraError("Model state not saved in checkpoint.")
+    arch = detect_arch({k.split(".")[0] for k in ckpt["state_dict"]})
+    if model_path is None and ckpt.get("model_path") is not None and isfile(ckpt["model_path"]):
+        model_path = ckpt["model_path"]
+    if model_path is not None:
+        if not isfile(model_path):
+            raise RemoraError(f"--model-path {model_path} is not a file")
+        scanned = scan_model_file(model_path)
+        if scanned != arch:
+            raise RemoraError(f"--model-path {model_path} assigns the layers of a {scanned} network, the checkpoint's state is "
+                              f"that of a {arch} network")
+    return ckpt
 
 
 def load_model(model_filename=None, *, pore=None, basecall_model_type=None, basecall_model_version=None,
                modified_bases=None, remora_model_type=None, remora_model_version=None, device=None,
                quiet=True, eval_only=False):
     """Same signature as remora.model_util.load_model (:566-578).  Returns
-    (HipModel, model_metadata).  Pretrained-model lookup by pore/basecaller needs a network
+    (HipModel, model_metadata).  `model_filename` is a TorchScript model file or a dorado-format model directory.
+    Pretrained-model lookup by pore/basecaller needs a network
     download in the reference (:684-695); here it raises RemoraError unless a file is given."""
     if model_filename is not None:
-        if not isfile(model_filename):
+        if os.path.isdir(model_filename):  # a dorado-format model directory
+            if not isfile(os.path.join(model_filename, DORADO_CONFIG)):
+                raise RemoraError(f"Remora model directory ({model_filename}) holds no {DORADO_CONFIG}.")
+        elif not isfile(model_filename):
             raise RemoraError(f"Remora model file ({model_filename}) not found.")
         try:
             return load_torchscript_model(model_filename, device, quiet=quiet, eval_only=eval_only)
@@ -288,3 +471,69 @@ def export_model_torchscript(ckpt, state, save_filename):
     meta["doc_string"] = "Nanopore Remora model"
     meta["model_version"] = ckpt.get("model_version", 0)
     torch.jit.save(script, save_filename, _extra_files={"meta.txt": json.dumps(meta, indent=4)})
+
+
+def export_model_dorado(ckpt, state, save_dir):
+    """The dorado-format directory of the reference (:179-309): every convolution folded with its BatchNorm by torch's
+    fuse_conv_bn_eval in fp32, one `<layer>.<key>.tensor` file per entry of each layer's state_dict, `config.toml` with the
+    tables general, model_params, modbases and refinement.  `state` as in export_model_torchscript.  The refiner comes from
+    `refiner_from_checkpoint`, so a training checkpoint exports as a loaded model file does."""
+    torch = _torch()
+    from torch.nn.utils.fusion import fuse_conv_bn_eval
+
+    from . import nets
+
+    if len(ckpt["motifs"]) > 1:  # before anything is written
+        raise RemoraError("Dorado only supports models with a single motif")
+    save_dir = os.path.expanduser(str(save_dir))
+    if os.path.exists(save_dir):
+        LOGGER.info(f'Directory "{save_dir}" already exists. Exported files will be overwritten.')
+    os.makedirs(save_dir, exist_ok=True)
+
+    net = nets.from_state(ckpt["state_dict"] if state is None else state)  # eval mode
+    arch = detect_arch({name for name, _ in net.named_children()})
+    conv_to_bn = dict(_CONV_ORDER[arch])
+    layer_names = []
+    for name, module in net.named_modules():
+        if name == "" or "bn" in name or "drop" in name:
+            continue
+        if name in conv_to_bn:
+            fused = fuse_conv_bn_eval(module, getattr(net, conv_to_bn[name]))
+            module.weight, module.bias = fused.weight, fused.bias
+        for k, v in module.state_dict().items():
+            save_tensor_file(os.path.join(save_dir, f"{name}.{k}.tensor"), v)
+        layer_names.append(name)
+    if layer_names != ordered_layers(arch):
+        raise RemoraError(f"export walked the layers {layer_names}, expected {ordered_layers(arch)}")
+
+    general = {"creation_date": datetime.datetime.now().strftime("%m/%d/%Y, %H:%M:%S"), "model": arch}
+    refiner = refiner_from_checkpoint(ckpt)
+    refinement = {"refine_do_rough_rescale": int(refiner.do_rough_rescale)}  # dorado reads an int here
+    if refiner.do_rough_rescale:
+        refinement["refine_kmer_center_idx"] = int(refiner.center_idx)
+        save_tensor_file(os.path.join(save_dir, _LEVELS_TENSOR + ".tensor"), np.asarray(refiner._levels_array).astype(np.float32))
+    modbases = {key: ckpt[key] for key in ("mod_bases", "offset", "reverse_signal", "pa_scaling")}
+    if ckpt["mod_bases"] is not None:
+        for i in range(len(ckpt["mod_bases"])):
+            modbases[f"mod_long_names_{i}"] = str(ckpt["mod_long_names"][i])
+    for key in ("chunk_context", "kmer_context_bases"):
+        for i in range(2):
+            modbases[f"{key}_{i}"] = int(ckpt[key][i])
+    motif, motif_offset = ckpt["motifs"][0]
+    modbases["motif"], modbases["motif_offset"] = str(motif), int(motif_offset)
+    toml_lite.dump({"general": general, "model_params": dict(ckpt["model_params"]), "modbases": modbases, "refinement": refinement},
+                   os.path.join(save_dir, DORADO_CONFIG))
+
+    # what the directory does not carry: said once per field whose value the loader's default would change
+    held = {"refine_scale_iters": refiner.scale_iters, "refine_algo": refiner.algo, "refine_half_bandwidth": refiner.half_bandwidth,
+            "refine_sd_arr": refiner.sd_arr}
+    for field, default in _lost_field_defaults().items():
+        if field in held:
+            value = held[field]
+        elif field in ckpt:
+            value = ckpt[field]
+        else:
+            continue
+        same = np.array_equal(np.asarray(value), np.asarray(default)) if field == "refine_sd_arr" else value == default
+        if not same:
+            LOGGER.warning(f"dorado format does not carry {field} ({value!r}): a model loaded from {save_dir} takes {default!r}")

@@ -1,15 +1,14 @@
 """torch.nn statement of the network `remora model train` trains (models/ConvLSTM_w_ref.py:11-58): the same layers under
 the same names, created in the same order, so that `torch.manual_seed(seed)` draws the reference's initial weights, a
 reference state_dict loads with strict=True, and `torch.jit.script` of it is the model file the reference's exporter
-writes (src/remora/model_util.py:115-176).
+writes (src/remora/model_util.py:115-176).  `ConvOnly` states the second architecture (models/Conv_w_ref.py:8-62) the same
+way, for the exporters: it is not trained here.
 
 torch runs none of the training arithmetic here: the module is where the initial state is drawn (on the CPU), the layout
 of `state_dict()`, and what `export_model_torchscript` serialises.  The arithmetic is rmr_trainer_* (remora_amd/train_model.py).
 """
 import torch
 from torch import nn
-
-from . import RemoraError
 
 
 def swish(x):
@@ -52,6 +51,51 @@ class ConvLSTM(nn.Module):
         return self.fc(z[-1])
 
 
+class ConvOnly(nn.Module):
+    """Conv_w_ref: three-layer signal and k-mer stacks, four merge convolutions (the last two with stride 2) and a linear
+    head on the flattened three positions that are left of a 100-sample chunk."""
+
+    def __init__(self, size=64, kmer_len=9, num_out=2):
+        super().__init__()
+        self.sig_conv1 = nn.Conv1d(1, 4, 11)
+        self.sig_bn1 = nn.BatchNorm1d(4)
+        self.sig_conv2 = nn.Conv1d(4, 16, 11)
+        self.sig_bn2 = nn.BatchNorm1d(16)
+        self.sig_conv3 = nn.Conv1d(16, size, 9, 3)
+        self.sig_bn3 = nn.BatchNorm1d(size)
+        self.seq_conv1 = nn.Conv1d(kmer_len * 4, 16, 11)
+        self.seq_bn1 = nn.BatchNorm1d(16)
+        self.seq_conv2 = nn.Conv1d(16, 32, 11)
+        self.seq_bn2 = nn.BatchNorm1d(32)
+        self.seq_conv3 = nn.Conv1d(32, size, 9, 3)
+        self.seq_bn3 = nn.BatchNorm1d(size)
+        self.merge_conv1 = nn.Conv1d(size * 2, size, 5)
+        self.merge_bn1 = nn.BatchNorm1d(size)
+        self.merge_conv2 = nn.Conv1d(size, size, 5)
+        self.merge_bn2 = nn.BatchNorm1d(size)
+        self.merge_conv3 = nn.Conv1d(size, size, 3, stride=2)
+        self.merge_bn3 = nn.BatchNorm1d(size)
+        self.merge_conv4 = nn.Conv1d(size, size, 3, stride=2)
+        self.merge_bn4 = nn.BatchNorm1d(size)
+        self.fc = nn.Linear(size * 3, num_out)
+
+    def forward(self, sigs, seqs):
+        s = swish(self.sig_bn1(self.sig_conv1(sigs)))
+        s = swish(self.sig_bn2(self.sig_conv2(s)))
+        s = swish(self.sig_bn3(self.sig_conv3(s)))
+        q = swish(self.seq_bn1(self.seq_conv1(seqs)))
+        q = swish(self.seq_bn2(self.seq_conv2(q)))
+        q = swish(self.seq_bn3(self.seq_conv3(q)))
+        z = swish(self.merge_bn1(self.merge_conv1(torch.cat((s, q), 1))))
+        z = swish(self.merge_bn2(self.merge_conv2(z)))
+        z = swish(self.merge_bn3(self.merge_conv3(z)))
+        z = swish(self.merge_bn4(self.merge_conv4(z)))
+        return self.fc(torch.flatten(z, start_dim=1))
+
+
+ARCHS = {"conv_lstm": ConvLSTM, "conv_only": ConvOnly}
+
+
 def build(size, kmer_len, num_out, seed=None):
     """The network with the initial weights the reference draws for `seed` (torch's CPU generator; None: not reseeded)."""
     if seed is not None:
@@ -61,10 +105,11 @@ def build(size, kmer_len, num_out, seed=None):
 
 def from_state(state):
     """{torch name: array or tensor} -> module in eval mode (strict load; num_batches_tracked optional)."""
-    if "lstm1.weight_ih_l0" not in state or "merge_conv2.weight" in state:
-        raise RemoraError("remora_amd.nets states ConvLSTM_w_ref only")
+    from .engine import detect_arch
+
+    arch = detect_arch({k.split(".")[0] for k in state})  # RemoraError on any other layer set
     st = {k: torch.as_tensor(v) for k, v in state.items()}
-    net = ConvLSTM(size=st["sig_conv3.weight"].shape[0], kmer_len=st["seq_conv1.weight"].shape[1] // 4,
+    net = ARCHS[arch](size=st["sig_conv3.weight"].shape[0], kmer_len=st["seq_conv1.weight"].shape[1] // 4,
                    num_out=st["fc.weight"].shape[0])
     for name, buf in net.named_buffers():
         if name.endswith("num_batches_tracked") and name not in st:

@@ -1702,6 +1702,76 @@ def gen_regions(R, out):
     print("regions:", n_cases, "metric cases,", os.path.getsize(os.path.join(out, "region_metrics.npz")), "bytes")
 
 
+def gen_dorado_export(R, out):
+    """model_util.export_model_dorado (src/remora/model_util.py:179-309) on two small models: ConvLSTM_w_ref size 16 with a
+    rough-rescale refiner over tests/golden/data/levels_4mer.txt, and Conv_w_ref size 24 with three outputs and no rough
+    rescale.  The `toml` stub is replaced by one whose `dump` captures the dict; the `.tensor` files are read back into
+    arrays.  Per model: the input state, the checkpoint's metadata (JSON; level and short-dwell arrays beside it), every
+    exported tensor under its file name, the captured config (JSON), 24 chunks and the network's logits on them (taken before
+    the export, which overwrites the convolutions of the network it is handed with the folded ones).
+
+    The reference's exporter looks every BatchNorm up under the name its table gives, and the table says `merge_bn` for
+    merge_conv1 - ConvLSTM_w_ref's name; Conv_w_ref calls that layer `merge_bn1` and the export stops with an AttributeError.
+    The Conv_w_ref network is therefore handed over with `merge_bn` as a second name of its `merge_bn1` (named_modules lists a
+    module once, and the exporter skips every name with "bn" in it): the pairing the table means, nothing else changed."""
+    import tempfile
+
+    import torch
+
+    levels_path = os.path.join(out, "data", "levels_4mer.txt")
+    captured = {}
+    real_toml = R.model_util.toml
+    R.model_util.toml = types.SimpleNamespace(dump=lambda doc, fh: captured.update(doc=doc))
+    rng = np.random.default_rng(41)
+    kb, ka, L, n = 4, 4, 100, 24
+    K = kb + ka + 1
+    specs = [
+        # tag, arch, size, num_out, mod_bases, long names, motif, rough rescale
+        ("convlstm_s16", "ConvLSTM_w_ref", 16, 2, "m", ["5mC"], ("CG", 0), True),
+        ("conv_s24", "Conv_w_ref", 24, 3, "hm", ["5hmC", "5mC"], ("C", 0), False),
+    ]
+    d = {"tags": np.asarray([s[0] for s in specs])}
+    try:
+        for si, (tag, arch, size, num_out, mod_bases, long_names, motif, rough) in enumerate(specs):
+            net = make_net(R, arch, size, K, num_out, seed=900 + si)
+            for k, v in net.state_dict().items():
+                if not k.endswith("num_batches_tracked"):
+                    d[f"{tag}__state__{k}"] = v.detach().cpu().numpy().copy()
+            seqs, maps, lens = synth_chunks(rng, n, L, L // 5, kb, ka, 0.03, False)
+            sigs = rng.standard_normal((n, 1, L)).astype(np.float32)
+            enc = R.encoded_kmers.compute_encoded_kmer_batch(kb, ka, seqs, maps, lens)
+            with torch.no_grad():
+                logits = net(torch.from_numpy(sigs), torch.from_numpy(enc)).numpy().copy()
+            refiner = (R.refine_signal_map.SigMapRefiner(kmer_model_filename=levels_path, do_rough_rescale=True, do_fix_guage=True)
+                       if rough else R.refine_signal_map.SigMapRefiner())
+            ckpt = _ckpt((kb, ka), (L // 2, L - L // 2), mod_bases, long_names, [motif], size, K, num_out)
+            ckpt.update(refiner.asdict())
+            ckpt["sig_map_refiner"] = refiner
+            if arch == "Conv_w_ref":
+                net.merge_bn = net.merge_bn1
+            captured.clear()
+            with tempfile.TemporaryDirectory() as td:
+                R.model_util.export_model_dorado(ckpt, net, td)
+                files = sorted(f for f in os.listdir(td) if f.endswith(".tensor"))
+                for f in files:
+                    (par,) = list(torch.jit.load(os.path.join(td, f), map_location="cpu").parameters())
+                    d[f"{tag}__tensor__{f}"] = par.detach().numpy().copy()
+            d[f"{tag}__files"] = np.asarray(files + ["config.toml"])
+            d[f"{tag}__config"] = np.asarray(json.dumps(captured["doc"], default=lambda o: o.item()))
+            meta = {k: v for k, v in ckpt.items() if k not in ("sig_map_refiner", "refine_kmer_levels", "refine_sd_arr")}
+            d[f"{tag}__meta"] = np.asarray(json.dumps(meta, default=lambda o: o.item()))
+            if ckpt["refine_kmer_levels"] is not None:
+                d[f"{tag}__refine_kmer_levels"] = np.asarray(ckpt["refine_kmer_levels"])
+            d[f"{tag}__refine_sd_arr"] = np.asarray(ckpt["refine_sd_arr"])
+            d.update({f"{tag}__sigs": sigs, f"{tag}__seqs": seqs, f"{tag}__maps": maps, f"{tag}__lens": lens, f"{tag}__logits": logits})
+            print("dorado_export", tag, len(files), "tensors, logit range", float(logits.min()), float(logits.max()))
+    finally:
+        R.model_util.toml = real_toml
+    path = os.path.join(out, "dorado_export.npz")
+    np.savez_compressed(path, **d)
+    print("dorado_export:", os.path.getsize(path), "bytes")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(__file__), "..", "tests", "golden"))
@@ -1732,6 +1802,7 @@ def main():
         batch_params=gen_batch_params,
         modbams=gen_modbams,
         regions=gen_regions,
+        dorado_export=gen_dorado_export,
     )
     for name, fn in gens.items():
         if args.only and name not in args.only.split(","):
