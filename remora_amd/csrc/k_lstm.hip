@@ -73,8 +73,8 @@ __device__ __forceinline__ void gates(const f32x4 (&acc)[4], f32x4 &c, f32x4 &h)
 // kept minimal: the i/f/o rows of W and b are pre-scaled by -log2(e) and the g rows by
 // 2 log2(e) on the host (rmr_pack.cpp), making sigmoid = rcp(1 + exp2(a)) and
 // tanh = 1 - 2 rcp(1 + exp2(a)) three/four instructions each.  The projection MFMAs of step
-// t+1 are sliced between the gate slices so that MFMA issue never waits for a long
-// dependent VALU chain.
+// t+1 do not depend on the gates: the first four are issued in front of the gate math, the
+// rest behind it, and the other wave of the SIMD fills the matrix pipe meanwhile.
 template <int H, bool HAS_H, bool HAS_X, int ABL>
 __device__ __forceinline__ void lstm_step(const float (&xb_img)[4][16][(H / 16 % 2 == 0) ? H / 4 + 4 : H / 4],
                                           const float (&hb_img)[4][16][(H / 16 % 2 == 0) ? H / 4 + 4 : H / 4],
@@ -100,8 +100,10 @@ __device__ __forceinline__ void lstm_step(const float (&xb_img)[4][16][(H / 16 %
             for (int gt = 0; gt < 4; ++gt)
                 accN[gt] = __builtin_amdgcn_mfma_f32_16x16x4f32(Aih[gt][s], bx[s >> 2][s & 3], accN[gt], 0, 0, 0);
         }
-        // gate work: 16 pieces (r = 0..3 x {i, f, g + c, o + h}) spread over the KS slices
-        for (int piece = s * 16 / KS; piece < (s + 1) * 16 / KS; ++piece) {
+        // gate work: 16 pieces (r = 0..3 x {i, f, g + c, o + h}), all of them in ONE run behind the first slice.  Spread over
+        // the KS slices, one piece per four MFMAs, they cost 3 % of the kernel more: VALU and transcendental work between fp32
+        // MFMAs is paid per switch between the two, not per operation (profiles/NOTES_r15.md)
+        for (int piece = (s == 0 ? 0 : 16); piece < 16; ++piece) {
             const int r = piece >> 2, st = piece & 3;
             if (ABL & 1) {  // timing ablation: no transcendental work
                 if (st == 3) { c[r] += acc[0][r] * acc[1][r]; h[r] = acc[2][r] + acc[3][r] * c[r]; }
