@@ -435,6 +435,29 @@ int rmr_duplex_align_mode(rmr_engine *e, int64_t n, const uint8_t *bases, const 
                           const int64_t *r_len, int64_t trace_budget, int mode, int32_t *out, const int64_t *run_off, uint32_t *runs,
                           int64_t *n_groups, int64_t *n_checkpointed);
 
+/* ---- the read-id index of a POD5 dataset (GPU; HOST pointers, synchronous) ---------------------------------------------- */
+/* replaces: the read-id lookup of pod5.DatasetReader, which the reference opens every POD5 argument with - a file or a
+ * directory of files: src/remora/io.py:427 (iter_signal), src/remora/inference.py:481, src/remora/prepare_train_data.py:153,
+ * src/remora/parsers.py:2109 and src/remora/io.py:2554 (duplex).  The ids of all files of a run are one table on the device.
+ * keys u8[n][16]: the read ids as the POD5 reads table stores them (fixed-size binary, the bytes of the UUID in text order);
+ * values i64[n]: what an id resolves to (io.Pod5Dataset: the global row of the read).  The pairs are sorted by key on the
+ * device (two stable 64-bit radix sorts) and every entry whose key equals its predecessor's is dropped: of equal ids the one
+ * given FIRST stays.  *n_distinct (may be NULL) receives the size of the table, which stays resident at 24 bytes per distinct
+ * id until rmr_read_index_destroy; the build takes about 80 n bytes more, freed before the call returns.  n = 0 is a valid,
+ * empty index.  n > 2^31 - 1, or device memory that cannot be had, is RMR_ERR_INVALID / RMR_ERR_NOMEM with a message that names
+ * the bytes needed.  The index belongs to `e` (its device, its stream, its mutex) and must be destroyed before it. */
+typedef struct rmr_read_index rmr_read_index;
+int rmr_read_index_create(rmr_engine *e, const uint8_t *keys, const int64_t *values, int64_t n, rmr_read_index **out,
+                          int64_t *n_distinct);
+/* replaces: DatasetReader.get_read / `read_id in ...` for a batch of BAM records (src/remora/io.py:427-441,
+ * src/remora/inference.py:481-519).  Name i is the text names[name_off[i] .. name_off[i+1]) (name_off i64[m+1], ascending; no
+ * terminators); values_out[i] receives the value of its id, or -1.  A name is an id only as the canonical 36-character
+ * 8-4-4-4-12 hexadecimal text, in either letter case; anything else (another length, another character, a hyphen elsewhere,
+ * the empty name) gives -1 and is never an error.  One launch, one thread per name; m = 0 launches nothing. */
+int rmr_read_index_lookup(rmr_read_index *index, const char *names, const int64_t *name_off, int64_t m, int64_t *values_out);
+/* replaces: DatasetReader.close (src/remora/io.py:441). */
+void rmr_read_index_destroy(rmr_read_index *index);
+
 /* The signal coordinate of every reference position of one alignment (host code).
  * replaces: compute_ref_to_signal = map_ref_to_signal(make_sequence_coordinate_mapping(cigar)), src/remora/data_chunks.py:60-122
  * (called from io.Read.add_alignment, src/remora/io.py:2070-2080), with np.interp's float64 arithmetic: the same integers.

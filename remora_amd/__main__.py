@@ -572,6 +572,11 @@ def _add_model_train(model):
     t.set_defaults(func=_model_train)
 
 
+POD5_HELP = ("POD5 file, or a run's directory of POD5 files: the files named *.pod5 directly in it (sub-directories are not walked), "
+             "in sorted order; a read id that several files hold is taken from the first and the repeats are counted in one warning.  "
+             "The ids of a directory are an index on the GPU; every process (--gpus / --procs-per-gpu rank) builds its own")
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog="remora_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -580,7 +585,7 @@ def build_parser():
     _add_model_export_inspect(model)
     infer = sub.add_parser("infer").add_subparsers(dest="sub", required=True)
     p = infer.add_parser("from_pod5_and_bam", help="Infer modified bases from POD5 + BAM on an MI355X")
-    p.add_argument("pod5")
+    p.add_argument("pod5", help=POD5_HELP)
     p.add_argument("in_bam")
     p.add_argument("--model", required=True, action="append",
                    help="TorchScript model file (with meta.txt) or dorado-format model directory; repeat for one model per canonical base")
@@ -591,7 +596,8 @@ def build_parser():
                         "already under torchrun); the parts are joined into --out-bam in input order")
     p.add_argument("--procs-per-gpu", type=int, default=1,
                    help="processes per GPU: the host side (BAM / POD5 parsing, per-read arithmetic, MM/ML formatting, BGZF) is "
-                        "Python and scales with processes; each takes its own contiguous share of the alignments")
+                        "Python and scales with processes; each takes its own contiguous share of the alignments (and, for a "
+                        "directory of POD5 files, builds its own read-id index)")
     p.add_argument("--bam-level", type=int, default=None, help="zlib level of the output BAM (default 6, as htslib; 1 = fast: Huffman coding only, about a fifth larger, half the CPU time of zlib's level 1)")
     p.add_argument("--num-reads", type=int, default=None)
     p.add_argument("--reads-per-batch", type=int, default=512)
@@ -603,7 +609,7 @@ def build_parser():
 
     d = infer.add_parser("duplex_from_pod5_and_bam", help="Infer modified bases on duplex reads from POD5 + simplex BAM + duplex BAM "
                                                           "with duplex pairs (src/remora/parsers.py:1420-1535)")
-    d.add_argument("pod5", help="POD5 file matched to the simplex BAM")
+    d.add_argument("pod5", help="matched to the simplex BAM: " + POD5_HELP)
     d.add_argument("simplex_bam", help="basecalled BAM file containing mv tags")
     d.add_argument("duplex_bam", help="BAM file with the duplex basecalls; record names are the template read id or "
                                       "template<delim>complement")
@@ -663,7 +669,7 @@ def build_parser():
 
     dset = sub.add_parser("dataset").add_subparsers(dest="sub", required=True)
     d = dset.add_parser("prepare", help="POD5 + BAM -> labelled chunk dataset directory")
-    d.add_argument("pod5")
+    d.add_argument("pod5", help=POD5_HELP)
     d.add_argument("bam")
     d.add_argument("--output-path", default="remora_training_dataset")
     d.add_argument("--overwrite", action="store_true")
@@ -693,7 +699,8 @@ def build_parser():
     d.add_argument("--device", type=int, default=0)
     d.add_argument("--gpus", type=int, default=1,
                    help="one process per GPU, each extracts the chunks of its own share of the BAM; the parts become one dataset")
-    d.add_argument("--procs-per-gpu", type=int, default=1)
+    d.add_argument("--procs-per-gpu", type=int, default=1, help="processes per GPU, each with its own share of the BAM (and, for a directory "
+                                                                 "of POD5 files, its own read-id index)")
     d.set_defaults(func=_dataset_prepare)
     di = dset.add_parser("inspect", help="Summary of a dataset directory or config")
     di.add_argument("remora_dataset_path")
@@ -726,7 +733,7 @@ def build_parser():
     ana = sub.add_parser("analyze").add_subparsers(dest="sub", required=True)
     k = ana.add_parser("estimate_kmer_levels", help="Estimate k-mer level table (per-base trimmed means and both medians on the GPU)")
     k.add_argument("--pod5-and-bam", required=True, nargs=2, metavar=("POD5", "BAM"), action="append",
-                   help="POD5 signal path and BAM path; the BAM holds mapped reads with move tables and MD tags (no index needed); "
+                   help="POD5 signal path (a file, or a run's directory of *.pod5 files as for infer from_pod5_and_bam) and BAM path; the BAM holds mapped reads with move tables and MD tags (no index needed); "
                         "repeat for several samples, which are aggregated after the site level")
     k.add_argument("--refine-kmer-level-table")
     k.add_argument("--refine-rough-rescale", action="store_true")

@@ -124,6 +124,9 @@ SIGNATURES = {
     "rmr_duplex_align": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64)]),
     "rmr_duplex_align_mode": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64),
                                       ctypes.POINTER(c_i64)]),
+    "rmr_read_index_create": (c_int, [c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(c_vp), ctypes.POINTER(c_i64)]),
+    "rmr_read_index_lookup": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "rmr_read_index_destroy": (None, [c_vp]),
     "rmr_inflate_raw": (c_int, [c_vp, c_i64, c_vp, c_i64]),
     "rmr_bgzf_huffman": (c_int, [c_vp, c_i64, c_int, c_vp, c_i64, ctypes.POINTER(c_i64)]),
     "rmr_zstd_frame_sizes": (c_int, [c_vp, c_vp, c_i64, c_vp]),

@@ -1,8 +1,9 @@
 // api_data.hip — the data entry points of the C ABI: k-mer encoding, context trimming, move tables, signal histograms, read
-// assembly, chunk extraction, label counts, the validation tally, motif scans, the VBZ decode, the site join of `validate from_modbams` and the duplex alignment.  Each RMR_MEM_HOST call
-// declares its arrays in a Stage (rmr_stage.h), uploads, launches (k_data.hip, k_vbz.hip, k_modbam.hip, k_duplex.hip) and copies back.
+// assembly, chunk extraction, label counts, the validation tally, motif scans, the VBZ decode, the site join of `validate from_modbams`, the duplex alignment and the read-id index of a POD5 dataset.  Each RMR_MEM_HOST call
+// declares its arrays in a Stage (rmr_stage.h), uploads, launches (k_data.hip, k_vbz.hip, k_modbam.hip, k_duplex.hip, k_read_index.hip) and copies back.
 #include <algorithm>
 #include <cstring>
+#include <new>
 
 #include "rmr_internal.h"
 #include "rmr_stage.h"
@@ -681,6 +682,71 @@ int rmr_duplex_align_mode(rmr_engine *e, int64_t n, const uint8_t *bases, const 
     if (rc == 0 && n_groups) *n_groups = (int64_t)group_start.size() - 1;
     if (rc == 0 && n_checkpointed) *n_checkpointed = ckpt ? (int64_t)jobs.size() : 0;
     return rc;
+}
+
+int rmr_read_index_create(rmr_engine *e, const uint8_t *keys, const int64_t *values, int64_t n, rmr_read_index **out, int64_t *n_distinct) {
+    if (out) *out = nullptr;
+    if (n_distinct) *n_distinct = 0;
+    if (!e || !out || n < 0 || (n > 0 && (!keys || !values))) RMR_FAIL(RMR_ERR_INVALID, "bad argument");
+    if (n > (int64_t)INT32_MAX)  // the permutation the sorts carry is 32 bits wide
+        RMR_FAIL(RMR_ERR_INVALID, "a read-id index holds up to %lld reads, got %lld (which would need about %lld bytes of device memory to build)",
+                 (long long)INT32_MAX, (long long)n, (long long)n * 80);
+    rmr_read_index *ix = new (std::nothrow) rmr_read_index();
+    if (!ix) RMR_FAIL(RMR_ERR_NOMEM, "out of host memory");
+    ix->eng = e;
+    if (n > 0) {
+        std::lock_guard<std::mutex> lk(e->mu);
+        int rc = hipSetDevice(e->device) == hipSuccess ? 0 : RMR_ERR_HIP;
+        if (rc != 0) set_error("hipSetDevice(%d) failed", e->device);
+        if (rc == 0) rc = read_index_build(e, keys, values, n, ix);
+        if (rc != 0) {
+            (void)hipStreamSynchronize(e->stream);  // nothing may still write the temporaries or the table when they are freed
+            if (ix->mem) (void)hipFree(ix->mem);
+            delete ix;
+            return rc;
+        }
+    }
+    *out = ix;
+    if (n_distinct) *n_distinct = ix->n;
+    return 0;
+}
+
+int rmr_read_index_lookup(rmr_read_index *ix, const char *names, const int64_t *name_off, int64_t m, int64_t *values_out) {
+    if (!ix || !ix->eng || m < 0) RMR_FAIL(RMR_ERR_INVALID, "bad argument");
+    if (m == 0) return 0;
+    if (!name_off || !values_out) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if (m > (int64_t)1 << 30) RMR_FAIL(RMR_ERR_INVALID, "bad m");
+    const int64_t base = name_off[0], total = name_off[m] - base;
+    for (int64_t i = 0; i < m; ++i)
+        if (name_off[i + 1] < name_off[i]) RMR_FAIL(RMR_ERR_INVALID, "name_off is not ascending (name %lld)", (long long)i);
+    if (total > 0 && !names) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if (ix->n == 0 || total == 0) {  // nothing can be found: no launch
+        std::fill(values_out, values_out + m, (int64_t)-1);
+        return 0;
+    }
+    rmr_engine *e = ix->eng;
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    Stage st;
+    char *d_names;
+    int64_t *d_off, *d_out;
+    st.add(&d_names, total).add(&d_off, m + 1).add(&d_out, m);
+    RMR_TRY(st.commit(e));
+    H2D(d_names, names + base, (size_t)total);
+    H2D(d_off, name_off, (size_t)(m + 1) * 8);
+    RMR_TRY(launch_read_index_lookup(e, ix, d_names, d_off, base, m, d_out));
+    D2H(values_out, d_out, (size_t)m * 8);
+    RMR_HIP(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+void rmr_read_index_destroy(rmr_read_index *ix) {
+    if (!ix) return;
+    if (ix->mem) {
+        (void)hipSetDevice(ix->eng->device);
+        (void)hipFree(ix->mem);
+    }
+    delete ix;
 }
 
 }  // extern "C"

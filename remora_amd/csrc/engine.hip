@@ -27,7 +27,7 @@ static const char *k_names[K_NUM] = {
     "fused_front", "rescale_quantiles", "sig3_front", "seq2_front", "probe_max_diff", "probe_nonfinite", "winograd_form",
     "base_metrics", "region_metrics", "region_signals", "site_kmer_levels", "modbam_sites", "rescale_points", "theil_sen_fit",
     "duplex_dp", "duplex_traceback", "duplex_lines", "duplex_backtrack", "train_gemm", "train_wgrad", "train_reduce", "train_bn", "train_lstm",
-    "train_loss", "train_adamw", "train_aux"};
+    "train_loss", "train_adamw", "train_aux", "read_index_build", "read_index_lookup"};
 const char *kernel_name(int id) { return (id >= 0 && id < K_NUM) ? k_names[id] : "?"; }
 
 }  // namespace rmr
@@ -182,7 +182,7 @@ int rmr_engine::prof_collect() {
 extern "C" {
 
 const char *rmr_last_error(void) { return g_err.c_str(); }
-const char *rmr_version(void) { return "remora_hip 0.11 (gfx950)"; }  // 0.11: rmr_trainer_*
+const char *rmr_version(void) { return "remora_hip 0.12 (gfx950)"; }  // 0.12: rmr_read_index_*
 
 int rmr_engine_create(int device, void *stream, int flags, rmr_engine **out) {
     if (!out) RMR_FAIL(RMR_ERR_INVALID, "out is NULL");

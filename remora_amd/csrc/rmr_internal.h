@@ -80,6 +80,9 @@ enum KernelId {
     K_TRAIN_LOSS,    // fc, cross-entropy and its gradient
     K_TRAIN_ADAMW,   // the optimiser and max |grad|
     K_TRAIN_AUX,     // weight repacks, sig_conv1, the k-mer transpose, fills
+    // the read-id index of a POD5 dataset (k_read_index.hip)
+    K_READ_INDEX_BUILD,   // its kernels, the two radix sorts and the scan between them, bracketed in two pieces
+    K_READ_INDEX_LOOKUP,
     K_NUM
 };
 const char *kernel_name(int id);
@@ -182,8 +185,24 @@ struct rmr_model : rmr::ModelWeights {
     rmr_model_numerics numerics{};
 };
 
+// ---- read-id index (k_read_index.hip) ------------------------------------------------------
+// the table of rmr_read_index_create: n distinct ids in ascending (hi, lo) order, one device allocation of 24 n bytes
+struct rmr_read_index {
+    rmr_engine *eng = nullptr;
+    int64_t n = 0;
+    void *mem = nullptr;
+    uint64_t *hi = nullptr, *lo = nullptr;  // an id's bytes 0-7 and 8-15 as big-endian words
+    int64_t *val = nullptr;
+};
+
 // ---- kernel launchers (defined in k_*.hip) ------------------------------------------------
 namespace rmr {
+
+// k_read_index.hip: keys u8[n][16], values i64[n] on the host (n >= 1) -> the table of `ix`;  names / name_off / out on the
+// device, the text of name i at names[name_off[i] - base ...]
+int read_index_build(rmr_engine *e, const uint8_t *keys, const int64_t *values, int64_t n, rmr_read_index *ix);
+int launch_read_index_lookup(rmr_engine *e, const rmr_read_index *ix, const char *names, const int64_t *name_off, int64_t base, int64_t m,
+                             int64_t *out);
 
 int launch_encode(rmr_engine *e, int kb, int ka, const int8_t *seqs, int seq_w,
                   const int16_t *maps, int map_w, const int16_t *lens, int64_t n, int sig_len,

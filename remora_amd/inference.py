@@ -1116,7 +1116,7 @@ def infer_duplex(*, simplex_pod5_path, simplex_bam_path, duplex_bam_path, pairs_
     errs = defaultdict(int)
     step = max(int(reads_per_batch), 1)
     try:
-        with rio.DuplexPairsBuilder(simplex_index, simplex_pod5_path) as builder, \
+        with rio.DuplexPairsBuilder(simplex_index, simplex_pod5_path, device=getattr(getattr(model, "engine", None), "device", None)) as builder, \
                 rio.BamWriter(out_bam, rio.read_bam_header_bytes(duplex_bam_path), level=bam_level) as writer:
             for k in range(0, len(valid_pairs), step):
                 rec_bytes = _duplex_batch_records(valid_pairs[k:k + step], builder, duplex_index, model, model_metadata, errs, trace_budget)

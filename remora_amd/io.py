@@ -1066,24 +1066,61 @@ def _pod5_embedded_files(buf):
     return files
 
 
+def _map_without_descriptor(path):
+    """The file mapped read-only with no descriptor left open: (buffer, find).  mmap.mmap keeps a duplicate of the descriptor
+    for as long as the mapping lives, one per file of a run; mmap(2) itself needs it only for the call.  The buffer is a ctypes
+    array over the mapping; the pages are unmapped when the last object that exports it (the Arrow tables opened in place
+    included) has gone."""
+    import mmap
+    import weakref
+
+    libc = ctypes.CDLL(None, use_errno=True)
+    libc.mmap.restype = ctypes.c_void_p
+    libc.mmap.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long]
+    libc.munmap.restype = ctypes.c_int
+    libc.munmap.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
+    fd = os.open(path, os.O_RDONLY)
+    try:
+        size = os.fstat(fd).st_size
+        if size == 0:
+            raise RemoraError(f"{path} is not a POD5 file")
+        addr = libc.mmap(None, size, mmap.PROT_READ, mmap.MAP_SHARED, fd, 0)
+        if addr is None or addr == ctypes.c_void_p(-1).value:
+            raise OSError(ctypes.get_errno(), f"cannot map {path}")
+    finally:
+        os.close(fd)
+    buf = (ctypes.c_char * size).from_address(addr)
+    weakref.finalize(buf, libc.munmap, addr, size)
+    return buf, lambda pat, start=0: bytes(buf).find(pat, start)  # (find: the damaged-footer path only)
+
+
 class Pod5File:
     """Random access to the reads of a POD5 file without the pod5 package: the file is memory mapped, the
     embedded Arrow IPC tables (signal rows, reads) are opened in place, a read's signal rows are VBZ-decoded
-    (zstd on the host, the streamvbyte / zigzag / running-sum layer on the GPU) only when the read is asked for."""
+    (zstd on the host, the streamvbyte / zigzag / running-sum layer on the GPU) only when the read is asked for.
+    `_member`: the file is one of a Pod5Dataset - no descriptor stays open and no per-read Python object is made (no
+    `read_ids`, no `_row`: the dataset resolves ids for all of its files and addresses this one by row)."""
 
-    def __init__(self, pod5_path):
+    def __init__(self, pod5_path, _member=False):
         import mmap
         import uuid
 
         import pyarrow as pa
         import pyarrow.ipc as ipc
 
-        self._fh = open(pod5_path, "rb")
-        self._mm = mmap.mmap(self._fh.fileno(), 0, access=mmap.ACCESS_READ)
-        mm = self._mm
+        if _member:
+            mm, find = _map_without_descriptor(pod5_path)
+            self._mm = mm
+            view = memoryview(mm).cast("B")
+        else:
+            self._fh = open(pod5_path, "rb")
+            self._mm = mmap.mmap(self._fh.fileno(), 0, access=mmap.ACCESS_READ)
+            mm = self._mm
+            find = mm.find
         if mm[:8] != b"\x8bPOD\r\n\x1a\n":
             raise RemoraError(f"{pod5_path} is not a POD5 file")
-        view = memoryview(mm)
+        if not _member:
+            view = memoryview(mm)
         tables = {}
 
         def classify(t):
@@ -1101,10 +1138,10 @@ class Pod5File:
         if "signal" not in tables or "reads" not in tables:  # damaged / missing footer: look for the Arrow magic
             tables = {}
             marks = []
-            i = mm.find(b"ARROW1")
+            i = find(b"ARROW1")
             while i >= 0:
                 marks.append(i)
-                i = mm.find(b"ARROW1", i + 1)
+                i = find(b"ARROW1", i + 1)
             k = 0
             while k + 1 < len(marks):  # embedded files are [ARROW1\0\0 ... ARROW1] pairs
                 st = marks[k]
@@ -1123,8 +1160,9 @@ class Pod5File:
         if "signal" not in tables or "reads" not in tables:
             raise RemoraError(f"could not locate the signal / reads tables in {pod5_path}")
         self._sig, self._reads = tables["signal"], tables["reads"]
-        self.read_ids = [str(uuid.UUID(bytes=b)) for b in self._reads.column("read_id").to_pylist()]
-        self._row = {rid: r for r, rid in enumerate(self.read_ids)}
+        if not _member:
+            self.read_ids = [str(uuid.UUID(bytes=b)) for b in self._reads.column("read_id").to_pylist()]
+            self._row = {rid: r for r, rid in enumerate(self.read_ids)}
         # per-read columns once (small), per-row access into the big signal table by (chunk, index): indexing a
         # chunked column by a global row number walks its chunks every time
         self._cal_off = self._reads.column("calibration_offset").to_numpy()
@@ -1183,12 +1221,27 @@ class Pod5File:
         return read_id in self._row
 
     def __len__(self):
-        return len(self.read_ids)
+        return self._reads.num_rows
 
     def signal_rows(self, read_id):
         """[(zstd-compressed VBZ bytes, number of samples)] of a read's signal rows, in order (table access only)."""
+        return self._signal_rows_at(self._row[read_id])
+
+    def _signal_rows_at(self, row):
+        """signal_rows of the read at `row` of the reads table."""
         return [(self._cell(self._sig_chunks, self._sig_starts, i), self._cell(self._n_chunks, self._n_starts, i))
-                for i in self._rows_of(read_id)]
+                for i in self._cell(self._read_rows.chunks, self._read_rows_starts, row)]
+
+    def _read_id_bytes(self):
+        """The read_id column as uint8[n][16] views of the mapped file, one per Arrow chunk (no copy, no Python object per read)."""
+        out = []
+        for c in self._reads.column("read_id").chunks:
+            c = getattr(c, "storage", c)  # (an extension type over fixed-size binary, where one is registered)
+            if c.type.byte_width != 16:
+                raise RemoraError("POD5 read ids are not 16 bytes wide")
+            data = c.buffers()[1]
+            out.append(np.frombuffer(data, np.uint8, count=16 * len(c), offset=16 * c.offset).reshape(-1, 16))
+        return out
 
     def calibration(self, read_id):
         r = self._row[read_id]
@@ -1220,9 +1273,268 @@ class Pod5File:
             yield self.get(rid)
 
 
+def list_pod5_files(directory):
+    """The POD5 files of a run's directory: the files named `*.pod5` directly in it (no walk into sub-directories), in sorted
+    path order.  (This project's rule; pod5.DatasetReader's default was not available to compare with.)"""
+    directory = os.fspath(directory)
+    return sorted(os.path.join(directory, name) for name in os.listdir(directory)
+                  if name.endswith(".pod5") and os.path.isfile(os.path.join(directory, name)))
+
+
+class Pod5Dataset:
+    """The reads of several POD5 files - a sequencing run's directory - behind the interface of Pod5File, as
+    pod5.DatasetReader stands behind every POD5 argument of the reference (src/remora/io.py:427, src/remora/inference.py:481,
+    src/remora/prepare_train_data.py:153, src/remora/parsers.py:2109, src/remora/io.py:2554).
+    Every file is a Pod5File opened as a member: mapped, its Arrow tables in place, no descriptor kept (thousands of files open
+    under `ulimit -n 1024`).  A read is addressed by its GLOBAL ROW: the first row of its file (`_first`) + its row there.  The
+    ids are an index on the GPU (rmr_read_index_create, csrc/k_read_index.hip): the 16-byte read_id columns of the files,
+    concatenated, against the global rows; sorted once, 24 bytes per distinct id resident, searched by the names of a batch
+    of BAM records in one launch (rows_of_names).  Nothing on this path makes a Python object per read; `read_ids` (strings,
+    file order) is built when somebody asks for it.  An id that several files hold resolves to the first file in the order
+    given (a directory: sorted path order) and one warning counts the entries dropped.
+    The index lives on one engine: every process (every rank of `--gpus` / `--procs-per-gpu`) builds its own, when an id is
+    first asked for (or the number of distinct reads: len); addressing by row needs no GPU."""
+
+    def __init__(self, paths, device=None, engine=None):
+        self.paths = [os.fspath(p) for p in paths]
+        if not self.paths:
+            raise RemoraError("a POD5 dataset needs at least one file")
+        self.files = [Pod5File(p, _member=True) for p in self.paths]
+        counts = np.asarray([len(f) for f in self.files], np.int64)
+        self._first = np.zeros(len(self.files) + 1, np.int64)
+        np.cumsum(counts, out=self._first[1:])
+        n = int(self._first[-1])
+        self._cal_off = np.concatenate([f._cal_off for f in self.files])
+        self._cal_scale = np.concatenate([f._cal_scale for f in self.files])
+        self.n_rows = n
+        self._device, self._engine = device, engine
+        self._index, self._index_lock, self._ids = None, threading.Lock(), None
+
+    def _built(self):
+        """The index handle, built on first use (see the class): keys = the read_id columns as they lie in the mapped files,
+        values = the global rows."""
+        with self._index_lock:
+            if self._index is None:
+                from .engine import get_ingest_engine
+
+                if self._engine is None:
+                    self._engine = get_ingest_engine(self._device)
+                self._lib = L.lib()
+                views = [v for f in self.files for v in f._read_id_bytes()]
+                keys = np.ascontiguousarray(np.concatenate(views)) if views else np.zeros((0, 16), np.uint8)
+                values = np.arange(self.n_rows, dtype=np.int64)
+                index, distinct = ctypes.c_void_p(), ctypes.c_int64(0)
+                L.check(self._lib.rmr_read_index_create(self._engine.handle, keys.ctypes.data_as(ctypes.c_void_p),
+                                                        values.ctypes.data_as(ctypes.c_void_p), self.n_rows, ctypes.byref(index),
+                                                        ctypes.byref(distinct)))
+                self._n_reads = int(distinct.value)
+                if self.n_rows > self._n_reads:
+                    import logging
+
+                    logging.getLogger("Remora").warning(
+                        f"{self.n_rows - self._n_reads} POD5 reads repeat the id of an earlier read of the dataset and are ignored "
+                        f"({self._n_reads} distinct ids in {len(self.files)} files; of equal ids the first file's is used)")
+                self._index = index
+            return self._index
+
+    @property
+    def n_reads(self):
+        """Distinct read ids."""
+        self._built()
+        return self._n_reads
+
+    @property
+    def n_dropped(self):
+        """Rows whose id an earlier row has."""
+        return self.n_rows - self.n_reads
+
+    def __del__(self):
+        ix, self._index = getattr(self, "_index", None), None
+        if ix:
+            try:
+                self._lib.rmr_read_index_destroy(ix)
+            except Exception:
+                pass
+
+    # ---- ids ----
+    def rows_of_names(self, buf, off):
+        """Global row per name, -1 where the name is no id of the dataset: name k is the text buf[off[k]:off[k + 1]] (bytes,
+        int64 offsets) - the canonical 8-4-4-4-12 hexadecimal form, either letter case.  One launch (rmr_read_index_lookup)."""
+        off = np.ascontiguousarray(off, np.int64)
+        m = off.size - 1
+        out = np.empty(max(m, 0), np.int64)
+        if m > 0:
+            if isinstance(buf, np.ndarray):
+                hold = np.ascontiguousarray(buf)
+                ptr = hold.ctypes.data_as(ctypes.c_void_p)
+            else:
+                hold = bytes(buf) if not isinstance(buf, bytes) else buf
+                ptr = ctypes.cast(ctypes.c_char_p(hold), ctypes.c_void_p)
+            index = self._built()
+            L.check(self._lib.rmr_read_index_lookup(index, ptr, off.ctypes.data_as(ctypes.c_void_p), m, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def _rows_of_ids(self, read_ids):
+        """rows_of_names for Python strings (anything that is not a str: -1)."""
+        texts = [rid.encode("latin-1", "replace") if isinstance(rid, str) else b"" for rid in read_ids]
+        off = np.zeros(len(texts) + 1, np.int64)
+        np.cumsum([len(t) for t in texts], out=off[1:])
+        return self.rows_of_names(b"".join(texts), off)
+
+    def _row_of(self, read_id):
+        r = int(self._rows_of_ids([read_id])[0])
+        if r < 0:
+            raise KeyError(read_id)
+        return r
+
+    def __contains__(self, read_id):
+        return isinstance(read_id, str) and int(self._rows_of_ids([read_id])[0]) >= 0
+
+    def __len__(self):
+        return self.n_reads
+
+    @property
+    def read_ids(self):
+        """The ids as strings, every row of every file in file order (an id that repeats appears as often as it is stored)."""
+        if self._ids is None:
+            import uuid
+
+            self._ids = [str(uuid.UUID(bytes=v.tobytes())) for f in self.files for view in f._read_id_bytes() for v in view]
+        return self._ids
+
+    def repeated_ids(self):
+        """The ids stored more than once (set of strings); without any - the usual case - no string is made."""
+        if not self.n_dropped:
+            return set()
+        from collections import Counter
+
+        return {rid for rid, k in Counter(self.read_ids).items() if k > 1}
+
+    # ---- rows ----
+    def _split(self, global_rows):
+        """(file number, row in the file) per global row."""
+        rows = np.asarray(global_rows, np.int64)
+        if rows.size and (rows.min() < 0 or rows.max() >= self.n_rows):
+            raise RemoraError("POD5 dataset row out of range")
+        fi = np.searchsorted(self._first, rows, side="right") - 1
+        return fi, rows - self._first[fi]
+
+    def rows_of_reads(self, global_rows):
+        """Pod5File.rows_of_reads for reads given by global row, in the caller's order: the reads are split by file, every file
+        lists its own, and the pieces are put back where the caller asked for them.  The addresses are absolute (into the
+        files' mappings)."""
+        fi, local = self._split(global_rows)
+        n = fi.size
+        cnt = np.zeros(n, np.int64)
+        pieces = []
+        for f in np.unique(fi).tolist():
+            at = np.nonzero(fi == f)[0]
+            first, addr, size, samples = self.files[f].rows_of_reads(local[at])
+            cnt[at] = np.diff(first)
+            pieces.append((at, first, addr, size, samples))
+        first_all = np.zeros(n + 1, np.int64)
+        np.cumsum(cnt, out=first_all[1:])
+        total = int(first_all[-1])
+        addr_all, size_all, samples_all = np.zeros(total, np.uint64), np.zeros(total, np.int64), np.zeros(total, np.int64)
+        for at, first, addr, size, samples in pieces:
+            # entry j of the file's k-th read goes to first_all[at[k]] + j
+            dst = np.repeat(first_all[at] - first[:-1], np.diff(first)) + np.arange(int(first[-1]), dtype=np.int64)
+            addr_all[dst], size_all[dst], samples_all[dst] = addr, size, samples
+        return first_all, addr_all, size_all, samples_all
+
+    def signal_rows(self, read_id):
+        fi, local = self._split([self._row_of(read_id)])
+        return self.files[int(fi[0])]._signal_rows_at(int(local[0]))
+
+    def calibration(self, read_id):
+        r = self._row_of(read_id)
+        return float(self._cal_off[r]), float(self._cal_scale[r])
+
+    def get(self, read_id, engine=None):
+        return self.get_many([read_id], engine)[0]
+
+    def get_many(self, read_ids, engine=None):
+        """Pod5File.get_many: the ids resolved in one lookup, the signals decoded in one GPU call."""
+        read_ids = list(read_ids)
+        rows = self._rows_of_ids(read_ids)
+        for rid, r in zip(read_ids, rows.tolist()):
+            if r < 0:
+                raise KeyError(rid)
+        fi, local = self._split(rows)
+        rows_of, blobs, ns = [], [], []
+        for f, r in zip(fi.tolist(), local.tolist()):
+            got = self.files[f]._signal_rows_at(r)
+            rows_of.append(len(got))
+            for blob, n in got:
+                blobs.append(blob)
+                ns.append(n)
+        flat, off = vbz_decode_batch(blobs, ns, engine)
+        out, k = [], 0
+        for rid, r, nrows in zip(read_ids, rows.tolist(), rows_of):
+            out.append(Pod5Read(rid, flat[off[k] : off[k + nrows]], float(self._cal_off[r]), float(self._cal_scale[r])))
+            k += nrows
+        return out
+
+    def __iter__(self):
+        for rid in dict.fromkeys(self.read_ids):
+            yield self.get(rid)
+
+
+def open_pod5(pod5_path, device=None):
+    """What a POD5 argument names (pod5.DatasetReader(Path(pod5_path)) in the reference, src/remora/io.py:427): a file -> the
+    Pod5File it always was; a directory -> a Pod5Dataset of its `*.pod5` files (list_pod5_files); a list or tuple of paths
+    (files or directories, in the order given) -> a Pod5Dataset; an open Pod5File / Pod5Dataset -> itself.  `device`: the GPU
+    whose ingest engine holds a dataset's read-id index (None: the current one)."""
+    if isinstance(pod5_path, (Pod5File, Pod5Dataset)):
+        return pod5_path
+
+    def files_of(directory):
+        files = list_pod5_files(directory)
+        if not files:
+            raise RemoraError(f"no *.pod5 files in directory {directory}")
+        return files
+
+    if isinstance(pod5_path, (list, tuple)):
+        paths = []
+        for p in pod5_path:
+            paths.extend(files_of(p) if os.path.isdir(p) else [os.fspath(p)])
+        return Pod5Dataset(paths, device=device)
+    if os.path.isdir(pod5_path):
+        return Pod5Dataset(files_of(os.fspath(pod5_path)), device=device)
+    return Pod5File(pod5_path)
+
+
+def rows_of_batch_names(signals, rb, idx):
+    """For the records `idx` (ascending indices) of a raw BAM batch: (kept, rows) - those whose signal `signals` holds and the
+    rows of their reads there (a Pod5File's row, a Pod5Dataset's global row).  The read a record's signal belongs to is the
+    parent (pi) of a split read, else the record's name.  A dataset searches its index with the batch's names as they stand
+    in the batch (rows_of_names: no Python object per record); a single file keeps its dictionary."""
+    has_pi = (rb.has & 64) != 0
+    if hasattr(signals, "rows_of_names"):
+        idx = np.asarray(idx, np.int64)
+        if not idx.size:
+            return [], []
+        rows = signals.rows_of_names(rb.names, rb.name_off)
+        if has_pi[idx].any():
+            rows = np.where(has_pi, signals.rows_of_names(rb.pi, rb.pi_off), rows)
+        rows = rows[idx]
+        found = rows >= 0
+        return idx[found].tolist(), rows[found].tolist()
+    names, pi = rb.names, rb.pi
+    row_of, kept, rows = signals._row, [], []
+    no, po = rb.name_off.tolist(), rb.pi_off.tolist()
+    for i in np.asarray(idx).tolist():
+        rid = (pi[po[i] : po[i + 1]] if has_pi[i] else names[no[i] : no[i + 1]]).decode("latin-1")
+        r = row_of.get(rid)
+        if r is not None:
+            kept.append(i)
+            rows.append(r)
+    return kept, rows
+
+
 def iter_pod5_reads(pod5_path, read_ids=None):
-    """Yield Pod5Read for every (requested) read of a POD5 file."""
-    f = Pod5File(pod5_path)
+    """Yield Pod5Read for every (requested) read of a POD5 file or dataset (open_pod5)."""
+    f = open_pod5(pod5_path)
     want = None if read_ids is None else set(read_ids)
     for rid in f.read_ids:
         if want is None or rid in want:
@@ -1730,7 +2042,7 @@ def iter_reads_from_pod5_and_bam(pod5_path, bam_path, reverse_signal=False, pa_s
     reference side of the alignment (MD reconstruction, ref_to_signal) when only basecall-anchored reads are needed.
     `device`: the GPU that decodes (the model's): the generator usually runs in a producer THREAD, and a new thread's
     current device is 0 whatever the rank's device is - every rank of a `--gpus N` run would otherwise decode on GPU 0."""
-    signals = Pod5File(pod5_path)
+    signals = open_pod5(pod5_path, device=device)
     from .engine import get_ingest_engine
 
     ingest_eng = get_ingest_engine(device) if decode_batch > 1 else None  # own stream: not behind the model's kernels
@@ -1962,17 +2274,7 @@ def _ingest_batch(rb, records, signals, eng, pa_scaling, skip_non_primary, ref_a
     if select is not None:
         keep_mask = keep_mask & np.asarray(select, bool)
     # the read a record's signal belongs to: the parent (pi) of a split read, else the record's name
-    names, pi = rb.names, rb.pi
-    row_of, kept = signals._row, []
-    rows = []
-    has_pi = (rb.has & 64) != 0
-    no, po = rb.name_off.tolist(), rb.pi_off.tolist()
-    for i in np.nonzero(keep_mask)[0].tolist():
-        rid = (pi[po[i] : po[i + 1]] if has_pi[i] else names[no[i] : no[i + 1]]).decode("latin-1")
-        r = row_of.get(rid)
-        if r is not None:
-            kept.append(i)
-            rows.append(r)
+    kept, rows = rows_of_batch_names(signals, rb, np.nonzero(keep_mask)[0])
     clock("ids")
     if not kept:
         return None
@@ -2212,7 +2514,7 @@ def iter_ingest_batches(pod5_path, bam_path, pa_scaling=None, skip_non_primary=T
     all of its records."""
     from .engine import get_ingest_engine
 
-    signals = Pod5File(pod5_path)
+    signals = open_pod5(pod5_path, device=device)
     eng = get_ingest_engine(device)
     raw_batches = iter_bam_raw_batches(bam_path, want_ref=bool(ref_anchored), batch=batch, shard=shard)
     raw_batches = _readahead(raw_batches, 2)  # the native parser releases the GIL: BAM batches are read one ahead
@@ -2767,15 +3069,19 @@ def duplex_reads_batch(items, engine=None, trace_budget=None, mode="auto"):
 
 
 class DuplexPairsBuilder:
-    """Both simplex reads of a duplex pair from the POD5 file and the simplex BAM index (src/remora/io.py:2544-2599)."""
+    """Both simplex reads of a duplex pair from the POD5 file - or a run's directory of files, open_pod5 - and the simplex BAM
+    index (src/remora/io.py:2544-2599).  `device`: the GPU of a dataset's read-id index."""
 
-    def __init__(self, simplex_index, pod5_path):
+    def __init__(self, simplex_index, pod5_path, device=None):
         from collections import Counter
 
         self.simplex_index = simplex_index
         self.pod5_path = pod5_path
-        self.reader = Pod5File(pod5_path)
-        self._repeated = {rid for rid, k in Counter(self.reader.read_ids).items() if k > 1}
+        self.reader = open_pod5(pod5_path, device=device)
+        if hasattr(self.reader, "repeated_ids"):  # a dataset counted them when it built its index
+            self._repeated = self.reader.repeated_ids()
+        else:
+            self._repeated = {rid for rid, k in Counter(self.reader.read_ids).items() if k > 1}
 
     def make_read_pairs(self, read_id_pairs, engine=None):
         """make_read_pair for several pairs with the signals decoded in one GPU call: [((template, complement) | None, error)]."""

@@ -283,11 +283,11 @@ def extract_chunks(read_errs, int_label, motifs, focus_ref_pos, sig_map_refiner,
     return out
 
 
-def count_reads(pod5_path, bam_path, skip_non_primary=True, shard=None):
-    """Number of BAM records (after the primary filter) whose parent read has signal in the POD5 file, and the
-    total record count - the quantities of get_read_ids (src/remora/io.py:362-391).  `shard=(rank, world)`: of that
-    rank's share of the BAM only."""
-    signals = rio.Pod5File(pod5_path)
+def count_reads(pod5_path, bam_path, skip_non_primary=True, shard=None, device=None):
+    """Number of BAM records (after the primary filter) whose parent read has signal in the POD5 file (or dataset:
+    io.open_pod5, `device`: the GPU of a dataset's index), and the total record count - the quantities of get_read_ids
+    (src/remora/io.py:362-391).  `shard=(rank, world)`: of that rank's share of the BAM only."""
+    signals = rio.open_pod5(pod5_path, device=device)
     total = both = 0
     # the pass is bound by the inflate of the file: nothing else runs in this process yet, so the cores this RANK was given
     # inflate (dist.bind_rank's plan when there is one; RMR_BAM_INFLATE_THREADS, read by the reader itself, when the user set it)
@@ -306,11 +306,7 @@ def count_reads(pod5_path, bam_path, skip_non_primary=True, shard=None):
     for rb, _ in itertools.chain([first] if first is not None else [], batches):
         keep = np.nonzero((rb.flag & 0x900) == 0)[0] if skip_non_primary else np.arange(rb.n)
         total += int(keep.size)
-        has_pi = (rb.has & 64) != 0
-        no, po = rb.name_off.tolist(), rb.pi_off.tolist()
-        for i in keep.tolist():
-            rid = (rb.pi[po[i] : po[i + 1]] if has_pi[i] else rb.names[no[i] : no[i + 1]]).decode("latin-1")
-            both += rid in signals
+        both += len(rio.rows_of_batch_names(signals, rb, keep)[0])
     return both, total
 
 
@@ -340,6 +336,9 @@ def extract_chunk_dataset(bam_path, pod5_path, out_path, mod_base, mod_base_cont
     import time as _time
 
     t_start = _time.perf_counter()
+    # a run's directory is opened once (its read-id index is built once per rank) and handed to the passes below
+    if not isinstance(pod5_path, (str, os.PathLike)) or os.path.isdir(pod5_path):
+        pod5_path = rio.open_pod5(pod5_path, device=engine.device if engine is not None else None)
     num_both, num_records = count_reads(pod5_path, bam_path, skip_non_primary, shard=shard)
     t_counted = _time.perf_counter()
     if world > 1:

@@ -478,7 +478,7 @@ def _region_pass(ref_regs, pod5_bam_pairs, extract, sig_map_refiner, skip_sig_ma
     # 1. every BAM once: the records that cover some region, from the raw batches' fixed fields; no signal is touched
     samples = []
     for pod5, bam_path in pod5_bam_pairs:
-        signals = pod5 if isinstance(pod5, rio.Pod5File) else rio.Pod5File(pod5)
+        signals = rio.open_pod5(pod5, device=device)
         names = rio.bam_reference_names(bam_path)
         held, cands = [], [[] for _ in range(n_reg)]
         for rb, records in rio.iter_bam_raw_batches(bam_path, want_ref=True, batch=reads_per_batch):
@@ -597,7 +597,7 @@ def get_ref_reg_samples_metrics(ref_reg, pod5_bam_pairs, sig_map_refiner=None, s
                                 reverse_signal=False, metric="dwell_trimmean", missing_ok=False, **kwargs):
     """(samples_metrics, all_bam_reads), src/remora/io.py:889-922: per (POD5, BAM) pair the named metric of every read that covers
     `ref_reg`, {key: array [reads, region length]} with NaN where a read does not cover, and the BamRecords of the rows.
-    `pod5_bam_pairs`: (POD5 path or io.Pod5File, BAM path) where the reference takes open handles; no index is needed: the BAM is
+    `pod5_bam_pairs`: (POD5 path - a file or a run's directory, io.open_pod5 - or open io.Pod5File / io.Pod5Dataset, BAM path) where the reference takes open handles; no index is needed: the BAM is
     streamed once.  Rows are in file order - fetch order for the coordinate-sorted BAMs the reference requires; an unsorted BAM
     gives its own order - or, with `max_reads`, in the order random.sample draws them, from the same random numbers as the
     reference.  kwargs: ref_orient, signal_type, pa_scaling, start_trim, end_trim as get_ref_reg_sample_metrics takes them, and
@@ -612,14 +612,14 @@ def get_ref_reg_samples_metrics(ref_reg, pod5_bam_pairs, sig_map_refiner=None, s
 def get_ref_reg_sample_metrics(ref_reg, pod5, bam_reads, metric, sig_map_refiner, skip_sig_map_refine=False, reverse_signal=False,
                                ref_orient=True, missing_ok=False, pa_scaling=None, signal_type="norm", device=None, **kwargs):
     """The named metric of records the caller chose (src/remora/io.py:840-886): {key: array [reads, region length]}, None without
-    reads.  `pod5`: path or io.Pod5File.  The reads are built and refined one by one and measured in one launch."""
+    reads.  `pod5`: path (a file, or a run's directory of files: io.open_pod5), io.Pod5File or io.Pod5Dataset.  The reads are built and refined one by one and measured in one launch."""
     from . import io as rio
     from .metrics import DEFAULT_END_TRIM, DEFAULT_START_TRIM, METRIC_KEYS
 
     if metric not in METRIC_KEYS:
         raise RemoraError(f"Unknown per-base metric: {metric}")
     bam_reads = list(bam_reads)
-    signals = pod5 if isinstance(pod5, rio.Pod5File) else rio.Pod5File(pod5)
+    signals = rio.open_pod5(pod5, device=device)
     io_reads, where = _io_reads_of_records(bam_reads, signals, reverse_signal, pa_scaling, missing_ok, device)
     for io_read in io_reads:  # the reference's errors, before anything runs (:2438-2447)
         mine = io_read.ref_reg
