@@ -378,6 +378,54 @@ int rmr_modbam_site_counts(rmr_engine *e, const rmr_modbam_batch *b, int32_t *or
 int rmr_modbam_site_fill(rmr_engine *e, const rmr_modbam_batch *b, const int32_t *ords, const int64_t *cig_q, const int64_t *cig_r,
                          const int32_t *status, const int64_t *out_off, float *probs, uint8_t *label, int64_t *qpos, int64_t *rpos);
 
+/* ---- `analyze pileup_modbams`: the modified-base calls of BAM records counted per reference site ----------------------- */
+/* The reference's command line has no such step; its users build this table (bedMethyl) from the output BAM with a CPU
+ * pileup over a sorted, indexed file.  Here the calls are keyed by site, sorted and counted on the device.
+ * A site word:  ref_id << 36 | pos << 5 | strand << 4 | code  (24 + 31 + 1 + 4 bits; strand 0 '+', 1 '-'; code = the call's
+ * class 0 .. n_mods, or n_mods + 1 = `fail`).  A site key is word >> 4. */
+#define RMR_PILEUP_BINS 513                          /* 512 x the winning probability of a call: 0 .. 512 */
+#define RMR_PILEUP_MAX_CONTIGS ((int64_t)1 << 24)
+#define RMR_PILEUP_MAX_POS ((int64_t)1 << 31)       /* positions lie below it */
+/* The emit (GPU; DEVICE pointers only, asynchronous on the engine's stream): the walk of rmr_modbam_site_counts / _fill
+ * with another end.  The batch is the same struct; n_refs is the header's contig count and truth_off / truth_pos /
+ * truth_label are not read.  Differences to the site join:
+ *   - a record is skipped whole with status 3 when ref_id < 0 or flag & 0x4, 6 when flag & 0x900 (secondary, supplementary),
+ *     2 when ref_id >= n_refs; an MD tag is not asked for (no status 4); statuses 1, 2 and 5 as there;
+ *   - every called base inside M / = / X is kept - when region_ref >= 0, only on that contig at region_lo <= pos < region_hi;
+ *   - the call is classified in integers: k_j = 2 ML + 1 for a listed code (the later entry wins), 0 for the other modified
+ *     bases, column 0 = 512 - sum; class = the first largest column, kmax = its value.
+ * rmr_modbam_call_counts: counts / status / workspaces as rmr_modbam_site_counts; hist (nullable, u64[RMR_PILEUP_BINS],
+ * zeroed by the caller once) gets +1 at kmax for every kept call of every record that ends with status 0.
+ * rmr_modbam_call_fill: one site word per kept call into words[out_off[r] .. out_off[r+1]) (a record's calls in the order
+ * of the walk along the original sequence), its code `fail` where kmax < k_t. */
+int rmr_modbam_call_counts(rmr_engine *e, const rmr_modbam_batch *b, int32_t region_ref, int64_t region_lo, int64_t region_hi,
+                           int32_t *ords, int64_t *cig_q, int64_t *cig_r, int64_t *counts, int32_t *status, uint64_t *hist);
+int rmr_modbam_call_fill(rmr_engine *e, const rmr_modbam_batch *b, int32_t region_ref, int64_t region_lo, int64_t region_hi, int32_t k_t,
+                         const int32_t *ords, const int64_t *cig_q, const int64_t *cig_r, const int32_t *status, const int64_t *out_off,
+                         uint64_t *words);
+/* The per-site table (GPU).  rmr_pileup_create: a table for n_contigs contigs, the longest of max_contig_len bases, with
+ * n_alpha classes (the canonical base and 1 .. 7 modified ones; a row has n_alpha + 1 u32 counts, the last is `fail`) and a
+ * call buffer of buffer_calls words (below 2^31).  Refused before anything is allocated or launched: n_contigs outside 1 ..
+ * RMR_PILEUP_MAX_CONTIGS, max_contig_len above RMR_PILEUP_MAX_POS.  Device memory: about 52 + 4 (n_alpha + 1) bytes per word
+ * of the buffer plus rocPRIM's scratch, allocated here, and 8 + 4 (n_alpha + 1) bytes per distinct site (twice that while
+ * a merge copies the table).
+ * rmr_pileup_add: n site words (DEVICE pointer; read before the call returns or in stream order before anything the caller
+ * issues on the engine's stream afterwards) are appended to the buffer; whenever it is full it is flushed - one radix sort
+ * over the used bits, one count per (site, code) run by binary search, rows merged into the resident table of ascending
+ * unique site keys.  The table does not depend on how the words were cut into calls or flushes.
+ * rmr_pileup_finish: flushes what the buffer holds and reports the distinct sites, the words added, the flushes so far and
+ * the peak of the device memory held; RMR_ERR_INVALID naming the site if a count would have passed 2^32 - 1.  Words may be
+ * added again afterwards.
+ * rmr_pileup_read: after rmr_pileup_finish, the table to HOST arrays keys u64[n_sites] (ascending) and counts
+ * u32[n_sites][n_alpha + 1].  Synchronous.
+ * rmr_pileup_destroy: waits for the engine's stream, then frees the buffer and the table. */
+typedef struct rmr_pileup rmr_pileup;
+int rmr_pileup_create(rmr_engine *e, int64_t n_contigs, int64_t max_contig_len, int n_alpha, int64_t buffer_calls, rmr_pileup **out);
+int rmr_pileup_add(rmr_pileup *p, const uint64_t *words, int64_t n);
+int rmr_pileup_finish(rmr_pileup *p, int64_t *n_sites, int64_t *n_calls, int64_t *n_flushes, int64_t *peak_device_bytes);
+int rmr_pileup_read(rmr_pileup *p, uint64_t *keys, uint32_t *counts);
+void rmr_pileup_destroy(rmr_pileup *p);
+
 /* The simplex-to-duplex alignment of duplex calling (GPU; HOST pointers, synchronous).
  * replaces: duplex_utils.parasail_align + trim_parasail_alignment, src/remora/duplex_utils.py:22-115, i.e.
  * parasail.sg_qx_trace_scan_32(simplex, duplex, 10, 2, dnafull) and the stripping of the gap operations at both ends, for a

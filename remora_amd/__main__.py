@@ -394,6 +394,32 @@ def _estimate_kmer_levels(args):
     return 0
 
 
+def _pileup_modbams(args):
+    """`analyze pileup_modbams` (no counterpart in the reference's command line): per-site modified-base counts, bedMethyl."""
+    import logging
+
+    from .pileup import pileup_modbams, write_bedmethyl, write_counts
+
+    log = logging.getLogger("Remora")
+    log.setLevel(logging.INFO)
+    if not log.handlers:
+        log.addHandler(logging.StreamHandler(sys.stderr))
+    if args.log_filename is not None:
+        log.addHandler(logging.FileHandler(args.log_filename, mode="w"))
+    if args.min_coverage < 1:
+        raise RemoraError("--min-coverage is at least 1")
+    table = pileup_modbams(args.bam, [args.canonical_base] + list(args.mod_bases), filter_threshold=args.filter_threshold,
+                           pct_filt=args.pct_filt, region=args.region, device=args.device, batch=args.reads_per_batch,
+                           device_gib=args.pileup_device_gib)
+    # the files are written only now: a run that keeps no call leaves none behind
+    n_rows = write_bedmethyl(table, args.out_bed, min_coverage=args.min_coverage)
+    if args.counts_filename is not None:
+        write_counts(table, args.counts_filename)
+    log.info(f"{n_rows} bedMethyl rows of {table.pos.size} sites -> {args.out_bed}")
+    log.info("Done")
+    return 0
+
+
 def _model_train(args):
     """src/remora/parsers.py:977-1024."""
     import logging
@@ -758,6 +784,29 @@ def build_parser():
                         "the input (same table, any input size)")
     k.add_argument("--device", type=int, default=0)
     k.set_defaults(func=_estimate_kmer_levels)
+
+    pm = ana.add_parser("pileup_modbams", help="Per-site modified-base counts (bedMethyl) from the MM/ML calls of mapped BAM files: tags "
+                                               "tokenised on native threads; calls aligned, classified, sorted and counted per site on the GPU")
+    pm.add_argument("--bam", required=True, action="append",
+                    help="mapped BAM file with modified base tags; no index, sort order or MD tag needed; repeat to pile several files "
+                         "(mapped to one reference) into one table")
+    pm.add_argument("--out-bed", required=True, help="bedMethyl output: the eleven ENCODE columns, no header")
+    pm.add_argument("--canonical-base", required=True, choices=list("ACGTU"), help="the canonical base of the modified bases counted")
+    pm.add_argument("--mod-bases", required=True, nargs="+", metavar="CODE", help="one to seven single-letter modified-base codes, e.g. m h")
+    pm.add_argument("--filter-threshold", type=float, help="a call passes when its winning probability is at least this (0 to 1)")
+    pm.add_argument("--pct-filt", type=float,
+                    help="filter this percentage (or less given ties) of the calls, the least confident ones, found in a first pass "
+                         "over the input (default 10 when --filter-threshold is not given)")
+    pm.add_argument("--min-coverage", type=int, default=1, help="write a site when at least this many of its calls pass")
+    pm.add_argument("--counts-filename", help="TSV of the per-site counts of every class and of the failing calls")
+    pm.add_argument("--region", help="ctg or ctg:start-end (0-based, half-open): only calls on these reference positions")
+    pm.add_argument("--pileup-device-gib", type=float, default=8.0,
+                    help="GiB of GPU memory for the call buffer and its sort (capped at half of what is free); the per-site table "
+                         "comes on top, 8 + 4 (classes + 1) bytes per distinct site")
+    pm.add_argument("--reads-per-batch", type=int, default=512)
+    pm.add_argument("--device", type=int, default=0)
+    pm.add_argument("--log-filename")
+    pm.set_defaults(func=_pileup_modbams)
     return ap
 
 

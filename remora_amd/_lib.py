@@ -121,6 +121,14 @@ SIGNATURES = {
     "rmr_mod_tags_fill": (c_int, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int]),
     "rmr_modbam_site_counts": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rmr_modbam_site_fill": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rmr_modbam_call_counts": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), ctypes.c_int32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rmr_modbam_call_fill": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), ctypes.c_int32, c_i64, c_i64, ctypes.c_int32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                     c_vp]),
+    "rmr_pileup_create": (c_int, [c_vp, c_i64, c_i64, c_int, c_i64, ctypes.POINTER(c_vp)]),
+    "rmr_pileup_add": (c_int, [c_vp, c_vp, c_i64]),
+    "rmr_pileup_finish": (c_int, [c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    "rmr_pileup_read": (c_int, [c_vp, c_vp, c_vp]),
+    "rmr_pileup_destroy": (None, [c_vp]),
     "rmr_duplex_align": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64)]),
     "rmr_duplex_align_mode": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64),
                                       ctypes.POINTER(c_i64)]),

@@ -1,6 +1,6 @@
 // api_data.hip — the data entry points of the C ABI: k-mer encoding, context trimming, move tables, signal histograms, read
-// assembly, chunk extraction, label counts, the validation tally, motif scans, the VBZ decode, the site join of `validate from_modbams`, the duplex alignment and the read-id index of a POD5 dataset.  Each RMR_MEM_HOST call
-// declares its arrays in a Stage (rmr_stage.h), uploads, launches (k_data.hip, k_vbz.hip, k_modbam.hip, k_duplex.hip, k_read_index.hip) and copies back.
+// assembly, chunk extraction, label counts, the validation tally, motif scans, the VBZ decode, the site join of `validate from_modbams`, the per-site pileup of `analyze pileup_modbams`, the duplex alignment and the read-id index of a POD5 dataset.  Each RMR_MEM_HOST call
+// declares its arrays in a Stage (rmr_stage.h), uploads, launches (k_data.hip, k_vbz.hip, k_modbam.hip, k_pileup.hip, k_duplex.hip, k_read_index.hip) and copies back.
 #include <algorithm>
 #include <cstring>
 #include <new>
@@ -558,6 +558,127 @@ int rmr_modbam_site_fill(rmr_engine *e, const rmr_modbam_batch *b, const int32_t
     RMR_HIP(hipSetDevice(e->device));
     return launch_modbam_sites(e, *b, const_cast<int32_t *>(ords), const_cast<int64_t *>(cig_q), const_cast<int64_t *>(cig_r), nullptr,
                                const_cast<int32_t *>(status), out_off, probs, label, qpos, rpos);
+}
+
+static int check_call_batch(const rmr_modbam_batch *b, int32_t region_ref, int64_t region_lo, int64_t region_hi) {
+    if (b->n_records < 0 || b->n_records > (int64_t)1 << 30) RMR_FAIL(RMR_ERR_INVALID, "bad n_records");
+    if (b->n_mods < 1 || b->n_mods > 7) RMR_FAIL(RMR_ERR_INVALID, "1..7 modified-base codes supported, got %d", b->n_mods);
+    if (b->n_deltas < 0 || b->n_ml < 0) RMR_FAIL(RMR_ERR_INVALID, "bad sizes");
+    if (b->n_refs < 1 || b->n_refs > RMR_PILEUP_MAX_CONTIGS)
+        RMR_FAIL(RMR_ERR_INVALID, "a site word holds up to %lld contigs, got %lld", (long long)RMR_PILEUP_MAX_CONTIGS, (long long)b->n_refs);
+    if (b->n_records > 0 && (!b->seq_off || !b->cigar_off || !b->flag || !b->ref_id || !b->pos || !b->tok_status || !b->ent_off))
+        RMR_FAIL(RMR_ERR_INVALID, "NULL array in the batch");
+    if (region_ref >= 0 && (region_ref >= b->n_refs || region_lo < 0 || region_hi < region_lo)) RMR_FAIL(RMR_ERR_INVALID, "bad region");
+    return 0;
+}
+
+int rmr_modbam_call_counts(rmr_engine *e, const rmr_modbam_batch *b, int32_t region_ref, int64_t region_lo, int64_t region_hi,
+                           int32_t *ords, int64_t *cig_q, int64_t *cig_r, int64_t *counts, int32_t *status, uint64_t *hist) {
+    if (!e || !b || !counts || !status) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    RMR_TRY(check_call_batch(b, region_ref, region_lo, region_hi));
+    if ((b->n_deltas > 0 && !ords) || !cig_q || !cig_r) RMR_FAIL(RMR_ERR_INVALID, "NULL workspace");
+    if (b->n_records == 0) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    const PileupEmit pe{region_ref, region_lo, region_hi, 0, reinterpret_cast<unsigned long long *>(hist), nullptr};
+    return launch_modbam_calls(e, *b, pe, ords, cig_q, cig_r, counts, status, nullptr);
+}
+
+int rmr_modbam_call_fill(rmr_engine *e, const rmr_modbam_batch *b, int32_t region_ref, int64_t region_lo, int64_t region_hi, int32_t k_t,
+                         const int32_t *ords, const int64_t *cig_q, const int64_t *cig_r, const int32_t *status, const int64_t *out_off,
+                         uint64_t *words) {
+    if (!e || !b || !status || !out_off || !words) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    RMR_TRY(check_call_batch(b, region_ref, region_lo, region_hi));
+    if ((b->n_deltas > 0 && !ords) || !cig_q || !cig_r) RMR_FAIL(RMR_ERR_INVALID, "NULL workspace");
+    if (k_t < 0 || k_t > RMR_PILEUP_BINS) RMR_FAIL(RMR_ERR_INVALID, "the threshold is 0 .. %d in units of 1/512, got %d", RMR_PILEUP_BINS, k_t);
+    if (b->n_records == 0) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    const PileupEmit pe{region_ref, region_lo, region_hi, k_t, nullptr, words};
+    return launch_modbam_calls(e, *b, pe, const_cast<int32_t *>(ords), const_cast<int64_t *>(cig_q), const_cast<int64_t *>(cig_r), nullptr,
+                               const_cast<int32_t *>(status), out_off);
+}
+
+int rmr_pileup_create(rmr_engine *e, int64_t n_contigs, int64_t max_contig_len, int n_alpha, int64_t buffer_calls, rmr_pileup **out) {
+    if (out) *out = nullptr;
+    if (!e || !out) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if (n_contigs < 1 || n_contigs > RMR_PILEUP_MAX_CONTIGS)
+        RMR_FAIL(RMR_ERR_INVALID, "a pileup holds 1 to %lld contigs (24 bits of a site word), got %lld", (long long)RMR_PILEUP_MAX_CONTIGS,
+                 (long long)n_contigs);
+    if (max_contig_len < 0 || max_contig_len > RMR_PILEUP_MAX_POS)
+        RMR_FAIL(RMR_ERR_INVALID, "a pileup holds positions below %lld (31 bits of a site word), the longest contig has %lld bases",
+                 (long long)RMR_PILEUP_MAX_POS, (long long)max_contig_len);
+    if (n_alpha < 2 || n_alpha > 8) RMR_FAIL(RMR_ERR_INVALID, "a pileup counts the canonical base and 1 to 7 modified bases, got %d classes", n_alpha);
+    if (buffer_calls < 1 || buffer_calls > (int64_t)INT32_MAX) RMR_FAIL(RMR_ERR_INVALID, "the call buffer holds 1 to 2^31 - 1 words, got %lld", (long long)buffer_calls);
+    rmr_pileup *p = new (std::nothrow) rmr_pileup();
+    if (!p) RMR_FAIL(RMR_ERR_NOMEM, "out of host memory");
+    p->eng = e, p->ncol = n_alpha + 1, p->cap = buffer_calls;
+    p->end_bit = 36;
+    while (p->end_bit < 60 && ((int64_t)1 << (p->end_bit - 36)) < n_contigs) p->end_bit += 1;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int rc = hipSetDevice(e->device) == hipSuccess ? 0 : RMR_ERR_HIP;
+    if (rc != 0) set_error("hipSetDevice(%d) failed", e->device);
+    if (rc == 0) rc = pileup_alloc(p);
+    if (rc != 0) {
+        if (p->work) (void)hipFree(p->work);
+        delete p;
+        return rc;
+    }
+    *out = p;
+    return 0;
+}
+
+int rmr_pileup_add(rmr_pileup *p, const uint64_t *words, int64_t n) {
+    if (!p || !p->eng || n < 0 || (n > 0 && !words)) RMR_FAIL(RMR_ERR_INVALID, "bad argument");
+    if (n == 0) return 0;
+    rmr_engine *e = p->eng;
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    return pileup_append(p, words, n);
+}
+
+int rmr_pileup_finish(rmr_pileup *p, int64_t *n_sites, int64_t *n_calls, int64_t *n_flushes, int64_t *peak_device_bytes) {
+    if (!p || !p->eng) RMR_FAIL(RMR_ERR_INVALID, "bad argument");
+    rmr_engine *e = p->eng;
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    RMR_TRY(pileup_flush(p));
+    unsigned long long over = 0;
+    D2H(&over, p->overflow, 8);
+    RMR_HIP(hipStreamSynchronize(e->stream));
+    if (over) {
+        const uint64_t key = over - 1;
+        RMR_FAIL(RMR_ERR_INVALID, "the count of a site would pass 2^32 - 1: contig #%lld, position %lld, strand %c", (long long)(key >> 32),
+                 (long long)((key >> 1) & 0x7fffffffull), (key & 1) ? '-' : '+');
+    }
+    if (n_sites) *n_sites = p->nt;
+    if (n_calls) *n_calls = p->n_calls;
+    if (n_flushes) *n_flushes = p->n_flushes;
+    if (peak_device_bytes) *peak_device_bytes = (int64_t)p->peak_bytes;
+    return 0;
+}
+
+int rmr_pileup_read(rmr_pileup *p, uint64_t *keys, uint32_t *counts) {
+    if (!p || !p->eng) RMR_FAIL(RMR_ERR_INVALID, "bad argument");
+    if (p->used != 0) RMR_FAIL(RMR_ERR_INVALID, "rmr_pileup_read before rmr_pileup_finish: %lld words are still in the buffer", (long long)p->used);
+    if (p->nt == 0) return 0;
+    if (!keys || !counts) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    rmr_engine *e = p->eng;
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    D2H(keys, p->t_keys, (size_t)p->nt * 8);
+    D2H(counts, p->t_counts, (size_t)p->nt * p->ncol * 4);
+    RMR_HIP(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+void rmr_pileup_destroy(rmr_pileup *p) {
+    if (!p) return;
+    (void)hipSetDevice(p->eng->device);
+    (void)hipStreamSynchronize(p->eng->stream);  // nothing may still read the buffer or the table when they are freed
+    if (p->work) (void)hipFree(p->work);
+    if (p->t_mem) (void)hipFree(p->t_mem);
+    delete p;
 }
 
 int rmr_duplex_align(rmr_engine *e, int64_t n, const uint8_t *bases, const int64_t *q_off, const int64_t *q_len, const int64_t *r_off,

@@ -4,54 +4,12 @@
 // Python loop over pysam's get_aligned_pairs(with_seq=True) with a dictionary lookup per aligned pair, on top of htslib's
 // walk along the bases inside AlignedSegment.modified_bases.
 //
-// One workgroup of four waves per record, the same kernel twice (count, then fill into the caller's prefix-summed offsets):
-//   count pass only
-//     1. the entries' ranges are checked against the flat arrays (nothing below indexes outside them), and whether any
-//        entry counts (strand '+', a code of the alphabet);
-//     2. CIGAR: exclusive prefix sums of the query and the reference lengths of the ops -> cig_q / cig_r (block scan, 256
-//        ops a round);
-//     3. per entry: inclusive prefix sum of (delta + 1) -> ords[k] = d_0 + .. + d_k + k, the occurrence ordinal of call k
-//        (block scan, 256 deltas a round; clamped to int32: an ordinal beyond a read's length is beyond its last occurrence);
-//   both passes
-//     4. the walk: 256 bases of the ORIGINAL sequence a round (a reverse record's from its stored end, complemented).  Four
-//        ballots give every base its occurrence number among the A / C / G / T of the read so far (running totals in
-//        registers, nothing sized by the read: 1 base or megabases alike); for every entry of its base (or N) the thread
-//        searches its occurrence number in the entry's ordinals - found = call k - and takes (ML + 0.5) / 256 for the codes
-//        that count, later entries overwriting earlier ones.  A called base finds its CIGAR op by binary search in cig_q, its
-//        reference position from cig_r, its label by binary search in the truth slice of (ref_id, strand).  Kept calls are
-//        compacted by a block prefix count: ascending stored position, i.e. back to front for a reverse record.
-//   The count pass ends with the check that no entry's last ordinal lies beyond the occurrences of its base.
-// Every probability is a multiple of 1/512 below 8: float arithmetic is exact in any order.
-#include "rmr_internal.h"
+// The walk itself is rmr_modbam_walk.h's (shared with the pileup, k_pileup.hip); this file is its truth-join instantiation.
+#include "rmr_modbam_walk.h"
 
 using namespace rmr;
 
 namespace {
-
-constexpr int MB_THREADS = 256, MB_WAVES = MB_THREADS / 64;
-
-// inclusive scan of two int64 over the block; ta / tb = the block's totals.  s: int64[MB_WAVES][2] of LDS.
-__device__ inline void block_scan2(int64_t &a, int64_t &b, int64_t &ta, int64_t &tb, int64_t (*s)[2], int lane, int wave) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long oa = __shfl_up((long long)a, d), ob = __shfl_up((long long)b, d);
-        if (lane >= d) a += oa, b += ob;
-    }
-    if (lane == 63) s[wave][0] = a, s[wave][1] = b;
-    __syncthreads();
-    int64_t pa = 0, pb = 0;
-    ta = tb = 0;
-#pragma unroll
-    for (int w = 0; w < MB_WAVES; ++w) {
-        if (w < wave) pa += s[w][0], pb += s[w][1];
-        ta += s[w][0], tb += s[w][1];
-    }
-    a += pa, b += pb;
-    __syncthreads();  // s is free again
-}
-
-__device__ inline int base_index(int c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; }
-__device__ inline int complement(int c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c; }
 
 template <bool FILL>
 __global__ __launch_bounds__(MB_THREADS) void modbam_site_kernel(rmr_modbam_batch b, int32_t *__restrict__ ords, int64_t *__restrict__ cig_q,
@@ -59,216 +17,7 @@ __global__ __launch_bounds__(MB_THREADS) void modbam_site_kernel(rmr_modbam_batc
                                                                   int32_t *__restrict__ status, const int64_t *__restrict__ out_off,
                                                                   float *__restrict__ probs, uint8_t *__restrict__ label,
                                                                   int64_t *__restrict__ qpos, int64_t *__restrict__ rpos) {
-    __shared__ int64_t s_scan[MB_WAVES][2];
-    __shared__ int s_base[MB_WAVES][4];
-    __shared__ int s_emit[MB_WAVES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t r = blockIdx.x;
-    // ---- records skipped whole (every test below is uniform over the block) ----
-    if (FILL) {
-        if (status[r] != 0 || out_off[r + 1] <= out_off[r]) return;
-    } else {
-        int st = b.tok_status[r];
-        if (st == 0 && b.ref_id[r] < 0) st = 3;
-        if (st == 0 && !(b.has[r] & 0x80)) st = 4;
-        if (st != 0) {
-            if (tid == 0) status[r] = st, counts[r] = 0;
-            return;
-        }
-    }
-    const int64_t e0 = b.ent_off[r], e1 = b.ent_off[r + 1];
-    const int64_t s0 = b.seq_off[r], L = b.seq_off[r + 1] - s0;
-    const int64_t c0 = b.cigar_off[r], nc = b.cigar_off[r + 1] - c0;
-    const bool rev = (b.flag[r] & 0x10) != 0;
-    const int n_mods = b.n_mods, n_alpha = n_mods + 1;
-    int malformed = 0;
-
-    if (!FILL) {
-        // ---- 1. entries inside the flat arrays; does any of them count? ----
-        int bad = 0, kept = 0;
-        for (int64_t e = e0 + tid; e < e1; e += MB_THREADS) {
-            const rmr_mod_entry &en = b.entries[e];
-            const int64_t nd = en.n_deltas, ncd = en.n_codes;
-            if (nd < 0 || ncd < 1 || ncd > RMR_MOD_MAX_CODES || en.delta_off < 0 || en.delta_off + nd > b.n_deltas || en.ml_off < 0 ||
-                en.ml_off + nd * ncd > b.n_ml)
-                bad = 1;
-            else if (en.strand == '+' && en.chebi == 0)
-                for (int ci = 0; ci < ncd; ++ci)
-                    for (int j = 0; j < n_mods; ++j) kept |= en.codes[ci] == b.mod_codes[j];
-        }
-        bad = __syncthreads_or(bad || L > 0x7fffffff);
-        kept = __syncthreads_or(kept);
-        if (bad || !kept) {
-            if (tid == 0) status[r] = bad ? 2 : 5, counts[r] = 0;
-            return;
-        }
-        // ---- 2. CIGAR prefix sums ----
-        int64_t run_q = 0, run_r = 0;
-        for (int64_t i0 = 0; i0 < nc; i0 += MB_THREADS) {
-            const int64_t i = i0 + tid;
-            int64_t ql = 0, rl = 0, len = 0;
-            if (i < nc) {
-                const uint32_t w = b.cigar[c0 + i];
-                const int op = (int)(w & 15u);
-                len = (int64_t)(w >> 4);
-                ql = (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) ? len : 0;  // M I S = X
-                rl = (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ? len : 0;  // M D N = X
-            }
-            int64_t a = ql, c = rl, ta, tc;
-            block_scan2(a, c, ta, tc, s_scan, lane, wave);
-            if (i < nc) cig_q[c0 + i] = run_q + a - ql, cig_r[c0 + i] = run_r + c - rl;
-            run_q += ta, run_r += tc;
-        }
-        if (run_q != L) malformed = 1;  // (an empty CIGAR included: no base of such a record is aligned)
-        // ---- 3. occurrence ordinals of the calls ----
-        for (int64_t e = e0; e < e1; ++e) {
-            const int64_t nd = b.entries[e].n_deltas, d0 = b.entries[e].delta_off;
-            int64_t run = 0;
-            for (int64_t k0 = 0; k0 < nd; k0 += MB_THREADS) {
-                const int64_t k = k0 + tid;
-                int64_t a = k < nd ? (int64_t)b.deltas[d0 + k] + 1 : 0, unused = 0, ta, tu;
-                if (a < 1) a = 1;  // (the tokeniser writes no negative delta; an array from elsewhere must not run the ordinals backwards)
-                block_scan2(a, unused, ta, tu, s_scan, lane, wave);
-                if (k < nd) {
-                    const int64_t o = run + a - 1;
-                    ords[d0 + k] = o > 0x7fffffff ? 0x7fffffff : (int32_t)o;
-                }
-                run += ta;
-            }
-        }
-        __syncthreads();  // the ordinals and the CIGAR sums of this record are read by all of its threads from here on
-    }
-
-    // ---- 4. the walk ----
-    int64_t run_base[4] = {0, 0, 0, 0}, emitted = 0;
-    const int64_t o_lo = FILL ? out_off[r] : 0, o_hi = FILL ? out_off[r + 1] : 0;
-    const int64_t n_truth_slices = 2 * b.n_refs, slice = 2 * (int64_t)b.ref_id[r] + (rev ? 1 : 0);
-    const int64_t t0 = slice < n_truth_slices ? b.truth_off[slice] : 0, t1 = slice < n_truth_slices ? b.truth_off[slice + 1] : 0;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    for (int64_t p0 = 0; p0 < L && !(FILL ? false : malformed); p0 += MB_THREADS) {
-        const int64_t p = p0 + tid;
-        const bool valid = p < L;
-        const int64_t sp = rev ? L - 1 - p : p;
-        int c = valid ? (int)b.seq[s0 + sp] : 0;
-        if (rev) c = complement(c);
-        const int bi = base_index(c);
-        int excl = 0;
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-            const unsigned long long m = __ballot(bi == x);
-            if (bi == x) excl = __popcll(m & lt);
-            if (lane == 0) s_base[wave][x] = __popcll(m);
-        }
-        __syncthreads();
-        int64_t occ_own = 0;
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-            int before = 0, tot = 0;
-#pragma unroll
-            for (int w = 0; w < MB_WAVES; ++w) {
-                if (w < wave) before += s_base[w][x];
-                tot += s_base[w][x];
-            }
-            if (bi == x) occ_own = run_base[x] + before + excl;
-            run_base[x] += tot;
-        }
-        // the calls on this base
-        float pr[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        bool called = false;
-        if (valid) {
-            for (int64_t e = e0; e < e1; ++e) {
-                const rmr_mod_entry &en = b.entries[e];
-                const int nd = en.n_deltas;
-                if (nd == 0) continue;
-                const int eb = en.base == 'U' ? 'T' : en.base;
-                int64_t occ;
-                if (eb == 'N') occ = p;
-                else if (bi >= 0 && eb == c) occ = occ_own;
-                else continue;
-                const int32_t *o = ords + en.delta_off;
-                int lo = 0, hi = nd;
-                while (lo < hi) {
-                    const int mid = lo + ((hi - lo) >> 1);
-                    if ((int64_t)o[mid] < occ) lo = mid + 1;
-                    else hi = mid;
-                }
-                if (lo >= nd || (int64_t)o[lo] != occ) continue;
-                if (en.strand != '+' || en.chebi != 0) continue;
-                const int ncd = en.n_codes;
-                const uint8_t *q = b.ml + en.ml_off + (int64_t)lo * ncd;
-                for (int ci = 0; ci < ncd; ++ci) {
-                    const char code = en.codes[ci];
-#pragma unroll
-                    for (int j = 0; j < 7; ++j)
-                        if (j < n_mods && code == b.mod_codes[j]) pr[j] = ((float)q[ci] + 0.5f) * (1.0f / 256.0f), called = true;
-                }
-            }
-        }
-        // stored position -> reference position -> truth label
-        bool keep = false;
-        int64_t rp = 0;
-        int lab = 0;
-        if (called && nc > 0) {
-            int64_t lo = 0, hi = nc;  // the last op that starts at or before sp
-            while (lo < hi) {
-                const int64_t mid = lo + ((hi - lo) >> 1);
-                if (cig_q[c0 + mid] <= sp) lo = mid + 1;
-                else hi = mid;
-            }
-            if (lo > 0) {
-                const int64_t i = lo - 1;
-                const uint32_t w = b.cigar[c0 + i];
-                const int op = (int)(w & 15u);
-                const int64_t within = sp - cig_q[c0 + i];
-                if ((op == 0 || op == 7 || op == 8) && within < (int64_t)(w >> 4)) {
-                    rp = (int64_t)b.pos[r] + cig_r[c0 + i] + within;
-                    int64_t a = t0, z = t1;
-                    while (a < z) {
-                        const int64_t mid = a + ((z - a) >> 1);
-                        if (b.truth_pos[mid] < rp) a = mid + 1;
-                        else z = mid;
-                    }
-                    if (a < t1 && b.truth_pos[a] == rp) keep = true, lab = b.truth_label[a];
-                }
-            }
-        }
-        const unsigned long long km = __ballot(keep);
-        if (lane == 0) s_emit[wave] = __popcll(km);
-        __syncthreads();
-        int before = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < MB_WAVES; ++w) {
-            if (w < wave) before += s_emit[w];
-            tot += s_emit[w];
-        }
-        if (FILL && keep) {
-            const int64_t rank = emitted + before + __popcll(km & lt);
-            const int64_t o = rev ? o_hi - 1 - rank : o_lo + rank;
-            if (o >= o_lo && o < o_hi) {  // (offsets that are not this batch's counts write nothing outside the record's slice)
-                float sum = 0.f;
-                for (int j = 0; j < n_mods; ++j) sum += pr[j];
-                float *row = probs + o * n_alpha;
-                row[0] = 1.0f - sum;
-                for (int j = 0; j < n_mods; ++j) row[1 + j] = pr[j];
-                label[o] = (uint8_t)lab;
-                qpos[o] = sp;
-                rpos[o] = rp;
-            }
-        }
-        emitted += tot;
-    }
-    if (!FILL) {
-        // a call beyond the last occurrence of its base: the whole record is malformed (uniform: every thread walks the entries)
-        for (int64_t e = e0; e < e1 && !malformed; ++e) {
-            const rmr_mod_entry &en = b.entries[e];
-            if (en.n_deltas == 0) continue;
-            const int eb = en.base == 'U' ? 'T' : en.base;
-            const int x = base_index(eb);
-            const int64_t have = eb == 'N' ? L : x >= 0 ? run_base[x] : 0;
-            if ((int64_t)ords[en.delta_off + en.n_deltas - 1] >= have) malformed = 1;
-        }
-        if (tid == 0) status[r] = malformed ? 2 : 0, counts[r] = malformed ? 0 : emitted;
-    }
+    modbam_walk<FILL, false>(b, ords, cig_q, cig_r, counts, status, out_off, probs, label, qpos, rpos, PileupEmit{}, nullptr);
 }
 
 }  // namespace

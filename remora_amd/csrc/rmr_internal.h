@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -83,6 +84,9 @@ enum KernelId {
     // the read-id index of a POD5 dataset (k_read_index.hip)
     K_READ_INDEX_BUILD,   // its kernels, the two radix sorts and the scan between them, bracketed in two pieces
     K_READ_INDEX_LOOKUP,
+    // `analyze pileup_modbams` (k_pileup.hip)
+    K_PILEUP_EMIT,   // the walk that writes site words (or the confidence histogram)
+    K_PILEUP_FLUSH,  // one flush: the radix sort, the run counts and the merge into the table
     K_NUM
 };
 const char *kernel_name(int id);
@@ -195,8 +199,46 @@ struct rmr_read_index {
     int64_t *val = nullptr;
 };
 
+// ---- per-site pileup (k_pileup.hip) --------------------------------------------------------
+// the state of rmr_pileup_create: the call buffer with the work arrays of a flush (one allocation, `work`) and the resident
+// table of nt distinct sites in ascending key order (one allocation, `t_mem`: keys, then ncol u32 counts per site)
+struct rmr_pileup {
+    rmr_engine *eng = nullptr;
+    int ncol = 0, end_bit = 0;       // columns of a row (classes + fail); the bits of a word in use
+    int64_t cap = 0, used = 0;       // words the buffer holds / holds now
+    void *work = nullptr;
+    size_t work_bytes = 0, tmp_bytes = 0;
+    uint64_t *buf[2] = {nullptr, nullptr};  // the call buffer and its sort double
+    uint32_t *head = nullptr, *row = nullptr, *counts = nullptr, *miss = nullptr, *miss_rank = nullptr, *miss_src = nullptr;
+    uint64_t *keys = nullptr, *miss_keys = nullptr;
+    unsigned long long *overflow = nullptr;
+    void *tmp = nullptr;             // rocPRIM's scratch
+    void *t_mem = nullptr;
+    size_t t_bytes = 0;
+    uint64_t *t_keys = nullptr;
+    uint32_t *t_counts = nullptr;
+    int64_t nt = 0, n_calls = 0, n_flushes = 0;
+    size_t peak_bytes = 0;
+};
+
 // ---- kernel launchers (defined in k_*.hip) ------------------------------------------------
 namespace rmr {
+
+// k_pileup.hip: the emit of `analyze pileup_modbams` (count pass: out_off == nullptr) and the pileup's three steps
+constexpr int PILEUP_BINS = RMR_PILEUP_BINS;  // 512 x the winning probability of a call: 0 .. 512
+// what the pileup's end of the walk (rmr_modbam_walk.h) needs beside the batch; unused by the truth join
+struct PileupEmit {
+    int32_t region_ref;             // < 0: every contig, every position
+    int64_t region_lo, region_hi;   // [lo, hi) on contig region_ref
+    int32_t k_t;                    // fill pass: a call whose 512 x winning probability is below it gets the code `fail`
+    unsigned long long *hist;       // count pass: u64[PILEUP_BINS], or nullptr
+    uint64_t *words;                // fill pass: one word per kept call
+};
+int launch_modbam_calls(rmr_engine *e, const rmr_modbam_batch &b, const PileupEmit &pe, int32_t *ords, int64_t *cig_q, int64_t *cig_r,
+                        int64_t *counts, int32_t *status, const int64_t *out_off);
+int pileup_alloc(rmr_pileup *p);
+int pileup_append(rmr_pileup *p, const uint64_t *words, int64_t n);
+int pileup_flush(rmr_pileup *p);
 
 // k_read_index.hip: keys u8[n][16], values i64[n] on the host (n >= 1) -> the table of `ix`;  names / name_off / out on the
 // device, the text of name i at names[name_off[i] - base ...]

@@ -1,0 +1,368 @@
+"""`analyze pileup_modbams`: the modified-base calls of mapped BAM files (MM / ML tags, as `infer from_pod5_and_bam` writes
+them) counted per reference site - the bedMethyl table that genome browsers and differential-methylation tools read.  The
+reference's command line stops at the per-read BAM; its users go through a CPU pileup over a sorted, indexed file next.
+
+Here the BAM is streamed in any order (no index, no MD tag): a batch of records is tokenised on native threads
+(rmr_mod_tags_sizes / _fill, shared with `validate from_modbams`), its calls are laid along the reads and carried through the
+CIGARs on the GPU (rmr_modbam_call_counts / _fill: the walk of the site join without the truth table), classified there in
+integers and written as one 64-bit word per call; the words are sorted, counted per site and merged into a resident table on
+the device (rmr_pileup_*, csrc/k_pileup.hip).  One row per site crosses PCIe.
+
+Which calls count, and how they are classified, is DESIGN.md section 4's "Pileup"; in short: mapped primary records, '+'-strand
+entries with single-letter codes of the alphabet, the positions an entry lists, p = (ML + 0.5) / 256, the later entry wins,
+bases inside M / = / X; class = argmax (ties to the lower column), confidence kmax = 512 x the winning probability, the call
+passes when kmax >= k_T."""
+import ctypes
+import logging
+import re
+from collections import namedtuple
+from fractions import Fraction
+
+import numpy as np
+
+from . import RemoraError
+
+LOGGER = logging.getLogger("Remora")
+
+N_BINS = 513                 # kmax = 0 .. 512
+MAX_CONTIGS = 1 << 24        # the fields of a site word: ref_id 24 bits, position 31 bits
+MAX_POS = 1 << 31
+DEFAULT_PCT_FILT = 10.0
+DEFAULT_DEVICE_GIB = 8.0
+PILEUP_STATUS = {1: "no MM tag", 2: "malformed modified-base tags", 3: "unmapped", 5: "no modified base of the alphabet",
+                 6: "secondary or supplementary"}
+MOD_NOT_IN_ALPHABET = "Modified base found in BAM ({}) not among --mod-bases: its calls are not counted."
+
+PileupTable = namedtuple("PileupTable", ("ref_names", "ref_id", "pos", "strand", "counts", "alphabet", "threshold_k", "n_calls", "n_flushes",
+                                         "peak_device_bytes", "hist"))
+PileupTable.__doc__ = """One row per site with a kept call, ordered by (ref_id, pos, strand): ref_id i32[n], pos i64[n], strand u8[n]
+(0 '+', 1 '-'), counts i64[n, len(alphabet) + 1] (canonical, the modified bases in alphabet order, fail).  threshold_k: k_T;
+n_calls: kept calls; n_flushes: flushes of the device call buffer; peak_device_bytes: the pileup's device memory at its
+peak; hist: i64[513], the calls per kmax, when the threshold came from a percentile, else None."""
+
+
+def threshold_k(filter_threshold):
+    """k_T = ceil(512 T) for a probability threshold 0 <= T <= 1, exactly."""
+    t = Fraction(filter_threshold) if not isinstance(filter_threshold, float) else Fraction(repr(filter_threshold))
+    if not 0 <= t <= 1:
+        raise RemoraError(f"--filter-threshold is a probability, 0 to 1, got {filter_threshold}")
+    k = 512 * t
+    return int(-((-k.numerator) // k.denominator))
+
+
+def percentile_k(hist, pct_filt):
+    """k_T that filters `pct_filt` percent of the calls or fewer (ties): the largest k in 0 .. 513 with
+    sum_{j<k} hist[j] <= floor(N pct / 100), N = sum(hist).  (k = 513, above every kmax, only at 100 percent.)"""
+    p = Fraction(repr(float(pct_filt)))
+    if not 0 <= p <= 100:
+        raise RemoraError(f"--pct-filt is a percentage, 0 to 100, got {pct_filt}")
+    hist = [int(h) for h in hist]
+    if len(hist) != N_BINS:
+        raise RemoraError(f"a confidence histogram has {N_BINS} bins, got {len(hist)}")
+    n = sum(hist)
+    allowed = (n * p.numerator) // (100 * p.denominator)
+    below, k_t = 0, 0
+    for k in range(1, N_BINS + 1):
+        below += hist[k - 1]
+        if below <= allowed:
+            k_t = k
+        else:
+            break
+    return k_t
+
+
+def parse_region(region, ref_names, ref_lens):
+    """`ctg` or `ctg:start-end` (0-based, half-open, the coordinates of the output's second and third column) ->
+    (ref_id, start, end); None -> (-1, 0, 0)."""
+    if region is None:
+        return -1, 0, 0
+    if isinstance(region, (tuple, list)):
+        name, lo, hi = region
+    elif region in ref_names:
+        name, lo, hi = region, 0, None
+    else:
+        name, sep, span = str(region).rpartition(":")
+        if not sep:
+            raise RemoraError(f"--region names the contig {region!r}, which the BAM header does not have")
+        m = re.fullmatch(r"([0-9,]+)-([0-9,]+)", span)
+        if m is None:
+            raise RemoraError(f"--region is ctg or ctg:start-end, got {region!r}")
+        lo, hi = (int(x.replace(",", "")) for x in m.groups())
+    if name not in ref_names:
+        raise RemoraError(f"--region names the contig {name!r}, which the BAM header does not have")
+    rid = ref_names.index(name)
+    hi = int(ref_lens[rid]) if hi is None else int(hi)
+    if lo < 0 or hi < lo:
+        raise RemoraError(f"--region {region!r}: start-end must be 0 <= start <= end")
+    return rid, int(lo), hi
+
+
+def bam_reference_dict(bam_path):
+    """[(name, length)] of a BAM header in ref_id order."""
+    import struct
+
+    from .io import read_bam_header_bytes
+
+    hdr = read_bam_header_bytes(bam_path)
+    at = 8 + struct.unpack_from("<i", hdr, 4)[0]
+    n_ref = struct.unpack_from("<i", hdr, at)[0]
+    at += 4
+    out = []
+    for _ in range(n_ref):
+        ln = struct.unpack_from("<i", hdr, at)[0]
+        out.append((hdr[at + 4 : at + 4 + ln - 1].decode(), struct.unpack_from("<I", hdr, at + 4 + ln)[0]))
+        at += 8 + ln
+    return out
+
+
+def check_reference_dicts(bams, dicts):
+    """The reference dictionaries of several BAMs must be equal; the refusal names the first difference."""
+    for path, d in zip(bams[1:], dicts[1:]):
+        for i, (a, b) in enumerate(zip(dicts[0], d)):
+            if a != b:
+                raise RemoraError(f"the reference dictionaries of {bams[0]} and {path} differ at contig #{i}: {a[0]} ({a[1]} bases) "
+                                  f"against {b[0]} ({b[1]} bases); one pileup takes BAMs mapped to one reference")
+        if len(d) != len(dicts[0]):
+            raise RemoraError(f"the reference dictionaries of {bams[0]} and {path} differ: {len(dicts[0])} against {len(d)} contigs "
+                              f"(the first {min(len(d), len(dicts[0]))} are equal)")
+
+
+def check_site_fields(n_contigs, max_len):
+    """What a 64-bit site word cannot hold is refused, before any launch."""
+    if n_contigs < 1:
+        raise RemoraError("the BAM header has no contig: nothing to pile up on")
+    if n_contigs > MAX_CONTIGS:
+        raise RemoraError(f"the BAM header has {n_contigs} contigs; a pileup holds up to {MAX_CONTIGS} (24 bits of a site word)")
+    if max_len > MAX_POS:
+        raise RemoraError(f"the longest contig has {max_len} bases; a pileup holds positions below {MAX_POS} (31 bits of a site word)")
+
+
+def check_alphabet(alphabet):
+    alphabet = list(alphabet)
+    mods = alphabet[1:]
+    if not 1 <= len(mods) <= 7 or any(len(m) != 1 for m in alphabet) or len(set(alphabet)) != len(alphabet):
+        raise RemoraError(f"pileup_modbams takes 1 to 7 distinct single-letter modified bases beside the canonical base, got {alphabet}")
+    return alphabet
+
+
+def bytes_per_buffered_call(n_alpha):
+    """Device bytes the pileup's work block takes per word of its call buffer (include/remora_hip.h, rmr_pileup_create)."""
+    return 52 + 4 * (n_alpha + 1)
+
+
+class DevicePileup:
+    """rmr_pileup_*: the call buffer and the resident per-site table on the device."""
+
+    def __init__(self, eng, n_contigs, max_contig_len, n_alpha, buffer_calls):
+        from . import _lib as L
+
+        self._L, self._lib, self.eng, self.n_alpha = L, L.lib(), eng, int(n_alpha)
+        self.h = ctypes.c_void_p()
+        L.check(self._lib.rmr_pileup_create(eng.handle, int(n_contigs), int(max_contig_len), int(n_alpha), int(buffer_calls), ctypes.byref(self.h)))
+
+    def add(self, words, n):
+        """n site words of a device tensor (kept alive by the caller until the engine's stream has passed them)."""
+        self._L.check(self._lib.rmr_pileup_add(self.h, words.data_ptr(), int(n)))
+
+    def finish(self):
+        """(n_sites, n_calls, n_flushes, peak_device_bytes) after flushing what the buffer holds."""
+        out = [ctypes.c_int64(0) for _ in range(4)]
+        self._L.check(self._lib.rmr_pileup_finish(self.h, *[ctypes.byref(o) for o in out]))
+        return tuple(int(o.value) for o in out)
+
+    def read(self, n_sites):
+        """keys u64[n_sites] (ref_id << 32 | pos << 1 | strand, ascending), counts u32[n_sites, n_alpha + 1]."""
+        keys, counts = np.zeros(max(n_sites, 1), np.uint64), np.zeros((max(n_sites, 1), self.n_alpha + 1), np.uint32)
+        self._L.check(self._lib.rmr_pileup_read(self.h, keys.ctypes.data_as(ctypes.c_void_p), counts.ctypes.data_as(ctypes.c_void_p)))
+        return keys[:n_sites], counts[:n_sites]
+
+    def close(self):
+        if self.h:
+            self._lib.rmr_pileup_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _emit_batch(eng, b, region, k_t, hist, n_cig, n_deltas):
+    """One batch through the emit: the count pass (with the histogram when `hist` is a device tensor), and - k_t not None -
+    the fill pass.  -> (words device tensor or None, calls per record, status per record)."""
+    from . import _lib as L
+    from .engine import _torch
+
+    torch, lib, dev = _torch(), L.lib(), eng.torch_device
+    n = int(b.n_records)
+    ords = torch.empty(max(n_deltas, 1), dtype=torch.int32, device=dev)
+    cig_qr = torch.empty((2, max(n_cig, 1)), dtype=torch.int64, device=dev)
+    counts = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    d_status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    L.check(lib.rmr_modbam_call_counts(eng.handle, ctypes.byref(b), region[0], region[1], region[2], ords.data_ptr(), cig_qr[0].data_ptr(),
+                                       cig_qr[1].data_ptr(), counts.data_ptr(), d_status.data_ptr(),
+                                       hist.data_ptr() if hist is not None else None))
+    eng.synchronize()
+    h_counts, h_status = counts[:n].cpu().numpy(), d_status[:n].cpu().numpy()
+    words = None
+    total = int(h_counts.sum())
+    if k_t is not None and total:
+        out_off = np.zeros(n + 1, np.int64)
+        np.cumsum(h_counts, out=out_off[1:])
+        d_off = torch.from_numpy(out_off).to(dev)
+        words = torch.empty(total, dtype=torch.int64, device=dev)
+        L.check(lib.rmr_modbam_call_fill(eng.handle, ctypes.byref(b), region[0], region[1], region[2], int(k_t), ords.data_ptr(),
+                                         cig_qr[0].data_ptr(), cig_qr[1].data_ptr(), d_status.data_ptr(), d_off.data_ptr(), words.data_ptr()))
+        eng.synchronize()  # the inputs and the workspaces may go once the kernel is through
+    return words, h_counts, h_status
+
+
+def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_FILT, region=None, device=None, batch=512, buffer_calls=None,
+                   device_gib=DEFAULT_DEVICE_GIB):
+    """The per-site counts of the modified-base calls of `bams` (one path or several, piled into one table) -> PileupTable.
+    `alphabet`: the canonical base followed by 1 to 7 single-letter modified-base codes.  The threshold: either
+    `filter_threshold` T (k_T = ceil(512 T); give pct_filt=None with it) or `pct_filt` P - then a first pass over the input
+    builds the histogram of the calls' confidence and k_T filters P percent of the calls, or fewer given ties.  `region`:
+    "ctg" or "ctg:start-end", 0-based half-open.  `buffer_calls`: the capacity of the device call buffer in calls; by default
+    what `device_gib` GiB (capped at half the free device memory) hold.  Everything that is refused is refused before
+    anything is launched; RemoraError when no call is kept."""
+    from .engine import _torch, get_engine
+    from .io import _readahead, iter_bam_raw_batches
+    from .validate import modbam_device_batch, tokenise_mod_tags, warn_ignored_entries
+
+    bams = [bams] if isinstance(bams, (str, bytes)) or hasattr(bams, "__fspath__") else list(bams)
+    if not bams:
+        raise RemoraError("pileup_modbams needs at least one BAM")
+    if filter_threshold is not None and pct_filt is not None:
+        raise RemoraError("give either --filter-threshold or --pct-filt, not both")
+    if filter_threshold is None and pct_filt is None:
+        pct_filt = DEFAULT_PCT_FILT
+    alphabet = check_alphabet(alphabet)
+    mods, n_alpha = alphabet[1:], len(alphabet)
+    k_t = threshold_k(filter_threshold) if filter_threshold is not None else None
+    if k_t is None:
+        percentile_k([0] * N_BINS, pct_filt)  # the range check
+    dicts = [bam_reference_dict(p) for p in bams]
+    check_reference_dicts(bams, dicts)
+    ref_names, ref_lens = [d[0] for d in dicts[0]], [d[1] for d in dicts[0]]
+    check_site_fields(len(ref_names), max(ref_lens, default=0))
+    reg = parse_region(region, ref_names, ref_lens)
+    if buffer_calls is not None and not 1 <= int(buffer_calls) < 2**31:
+        raise RemoraError(f"buffer_calls is 1 to 2^31 - 1, got {buffer_calls}")
+    if buffer_calls is None and not device_gib > 0:
+        raise RemoraError("--pileup-device-gib must be positive")
+
+    torch = _torch()
+    eng = get_engine(device)
+    dev = eng.torch_device
+    if buffer_calls is None:
+        free = torch.cuda.mem_get_info(dev)[0]
+        gib = min(float(device_gib), free / 2 / 2**30)
+        buffer_calls = int(max(1, min(2**31 - 1, (gib * 2**30 - (1 << 20)) // bytes_per_buffered_call(n_alpha))))
+        LOGGER.info(f"pileup call buffer: {buffer_calls} calls in {gib:.3g} GiB of device memory (--pileup-device-gib {device_gib:g}, "
+                    f"{free / 2**30:.1f} GiB free)")
+    warn = {"strand": True, "mod": True}
+
+    def one_pass(k_fill, hist, pile, log_skipped):
+        """All BAMs once: the count pass of every batch, and with k_fill the fill pass and the append.  -> kept calls."""
+        n_kept = 0
+        for path in bams:
+            skipped, n_records = {}, 0
+
+            def tokenised(path=path):  # the reader and the tokeniser of batch k + 1 run beside the GPU work of batch k
+                for rb, _ in iter_bam_raw_batches(path, want_ref=False, batch=int(batch)):
+                    yield rb, tokenise_mod_tags(rb.raw, rb.raw_off, rb.tags_off)
+
+            for rb, tok in _readahead(tokenised(), depth=2):
+                warn_ignored_entries(tok[4], alphabet, warn, MOD_NOT_IN_ALPHABET)
+                buf, b = modbam_device_batch(dev, mods, rb.seq, rb.seq_off, rb.cigar, rb.cigar_off, rb.flag, rb.ref_id, rb.pos, rb.has, tok)
+                b.n_refs = len(ref_names)
+                words, h_counts, h_status = _emit_batch(eng, b, reg, k_fill, hist, int(np.asarray(rb.cigar).size), int(tok[5].size))
+                del buf
+                if words is not None:
+                    pile.add(words, words.numel())
+                    eng.synchronize()  # the words are in the call buffer (or the table) now
+                n_kept += int(h_counts.sum())
+                n_records += rb.n
+                for st, k in zip(*np.unique(h_status, return_counts=True)):
+                    if st:
+                        skipped[int(st)] = skipped.get(int(st), 0) + int(k)
+            if log_skipped:
+                for st, k in sorted(skipped.items()):
+                    LOGGER.info(f"{k} of {n_records} records skipped: {PILEUP_STATUS.get(st, st)} ({path})")
+        return n_kept
+
+    no_calls = (f"No modified-base call of {alphabet[1:]} on an aligned base" + (f" inside {region}" if region is not None else "") +
+                f" in {', '.join(map(str, bams))}.")
+    h_hist = None
+    if k_t is None:  # the percentile needs every call's confidence first: one pass that emits no rows
+        hist = torch.zeros(N_BINS, dtype=torch.int64, device=dev)
+        n_kept = one_pass(None, hist, None, True)
+        eng.synchronize()
+        h_hist = hist.cpu().numpy()
+        if n_kept < 1 or int(h_hist.sum()) != n_kept:
+            if n_kept < 1:
+                raise RemoraError(no_calls)
+            raise RemoraError(f"pileup: the histogram holds {int(h_hist.sum())} calls, the records {n_kept}")
+        k_t = percentile_k(h_hist, pct_filt)
+        LOGGER.info(f"--pct-filt {pct_filt:g}: {int(h_hist[:k_t].sum())} of {n_kept} calls fail at k_T = {k_t} (probability {k_t / 512:.6g})")
+    with DevicePileup(eng, len(ref_names), max(ref_lens), n_alpha, buffer_calls) as pile:
+        n_kept = one_pass(k_t, None, pile, h_hist is None)
+        n_sites, n_calls, n_flushes, peak = _finish(pile, ref_names)
+        if n_calls < 1:
+            raise RemoraError(no_calls)
+        if n_calls != n_kept:
+            raise RemoraError(f"pileup: {n_calls} calls reached the table, the records hold {n_kept}")
+        keys, counts = pile.read(n_sites)
+    LOGGER.info(f"{n_calls} calls on {n_sites} sites; {n_flushes} flushes, {peak / 2**20:.1f} MiB of device memory at the peak")
+    return PileupTable(ref_names=ref_names, ref_id=(keys >> np.uint64(32)).astype(np.int32),
+                       pos=((keys >> np.uint64(1)) & np.uint64(0x7FFFFFFF)).astype(np.int64), strand=(keys & np.uint64(1)).astype(np.uint8),
+                       counts=counts.astype(np.int64), alphabet=alphabet, threshold_k=int(k_t), n_calls=n_calls, n_flushes=n_flushes,
+                       peak_device_bytes=peak, hist=None if h_hist is None else h_hist.astype(np.int64))
+
+
+def _finish(pile, ref_names):
+    try:
+        return pile.finish()
+    except RemoraError as e:  # the refusal of a count beyond 32 bits names the site by its contig index: add the name
+        m = re.search(r"contig #(\d+)", str(e))
+        if m and int(m.group(1)) < len(ref_names):
+            raise RemoraError(f"{e} ({ref_names[int(m.group(1))]})")
+        raise
+
+
+def write_bedmethyl(table, path, min_coverage=1):
+    """The eleven ENCODE bedMethyl columns, header-less, tab-separated: one row per (site, modified base) whose N_valid - the
+    passing calls of any class - is at least max(min_coverage, 1):
+    chrom pos pos+1 code min(N_valid, 1000) strand pos pos+1 255,0,0 N_valid pct, pct = 100 N_mod / N_valid to two decimals.
+    Rows: contigs in header order, then position, then + before -, then the codes in alphabet order.  Returns the rows written."""
+    mods = list(table.alphabet[1:])
+    valid = table.counts[:, :-1].sum(axis=1)
+    keep = np.nonzero(valid >= max(int(min_coverage), 1))[0]
+    n_rows = 0
+    with open(path, "w") as fh:
+        for lo in range(0, keep.size, 65536):
+            lines = []
+            idx = keep[lo : lo + 65536]
+            for rid, pos, st, nv, row in zip(table.ref_id[idx].tolist(), table.pos[idx].tolist(), table.strand[idx].tolist(), valid[idx].tolist(),
+                                             table.counts[idx].tolist()):
+                name, sc = table.ref_names[rid], "-" if st else "+"
+                for j, code in enumerate(mods):
+                    lines.append(f"{name}\t{pos}\t{pos + 1}\t{code}\t{min(nv, 1000)}\t{sc}\t{pos}\t{pos + 1}\t255,0,0\t{nv}\t"
+                                 f"{100 * row[1 + j] / nv:.2f}\n")
+            fh.write("".join(lines))
+            n_rows += len(lines)
+    return n_rows
+
+
+def write_counts(table, path):
+    """TSV with the header chrom start strand N_<canonical> N_<code>... N_fail: one row per site that has a kept call."""
+    with open(path, "w") as fh:
+        fh.write("\t".join(["chrom", "start", "strand"] + [f"N_{a}" for a in table.alphabet] + ["N_fail"]) + "\n")
+        for lo in range(0, table.pos.size, 65536):
+            sl = slice(lo, lo + 65536)
+            fh.write("".join(f"{table.ref_names[rid]}\t{pos}\t{'-' if st else '+'}\t" + "\t".join(map(str, row)) + "\n"
+                             for rid, pos, st, row in zip(table.ref_id[sl].tolist(), table.pos[sl].tolist(), table.strand[sl].tolist(),
+                                                          table.counts[sl].tolist())))
+    return int(table.pos.size)

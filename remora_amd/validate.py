@@ -418,16 +418,14 @@ def tokenise_mod_tags(raw, raw_off, tags_off, threads=None):
     return status, offs[0], offs[1], offs[2], entries[: int(offs[0, n])], deltas[: int(offs[1, n])], ml[: int(offs[2, n])]
 
 
-def modbam_batch_sites(eng, truth, mod_codes, seq, seq_off, cigar, cigar_off, flag, ref_id, pos, has, tok):
-    """The site join of one batch (rmr_modbam_site_counts, prefix sum, rmr_modbam_site_fill): device tensors probs f32[n, 1 +
-    len(mod_codes)], label u8[n], qpos, rpos i64[n], and on the host the calls per record (i64) and the records' status."""
-    import ctypes
-
+def modbam_device_batch(dev, mod_codes, seq, seq_off, cigar, cigar_off, flag, ref_id, pos, has, tok):
+    """The records of a batch and their tokenised tags on the device as an rmr_modbam_batch without its truth fields:
+    (the buffer that owns the arrays, the struct)."""
     from . import _lib as L
 
-    torch, lib, dev = _torch(), L.lib(), eng.torch_device
+    torch = _torch()
     status, ent_off, _, _, entries, deltas, ml = tok
-    n, n_alpha = int(np.asarray(flag).size), len(mod_codes) + 1
+    n = int(np.asarray(flag).size)
     i32 = lambda a: np.ascontiguousarray(a, np.int32)  # noqa: E731
     i64 = lambda a: np.ascontiguousarray(a, np.int64)  # noqa: E731
     seq_arr = np.frombuffer(seq, np.uint8) if not isinstance(seq, np.ndarray) else seq
@@ -441,6 +439,20 @@ def modbam_batch_sites(eng, truth, mod_codes, seq, seq_off, cigar, cigar_off, fl
                           "deltas", "ml"), ptrs):
         setattr(b, name, ptr)
     b.n_deltas, b.n_ml, b.n_mods, b.mod_codes = int(deltas.size), int(ml.size), len(mod_codes), "".join(mod_codes).encode()
+    return buf, b
+
+
+def modbam_batch_sites(eng, truth, mod_codes, seq, seq_off, cigar, cigar_off, flag, ref_id, pos, has, tok):
+    """The site join of one batch (rmr_modbam_site_counts, prefix sum, rmr_modbam_site_fill): device tensors probs f32[n, 1 +
+    len(mod_codes)], label u8[n], qpos, rpos i64[n], and on the host the calls per record (i64) and the records' status."""
+    import ctypes
+
+    from . import _lib as L
+
+    torch, lib, dev = _torch(), L.lib(), eng.torch_device
+    deltas = tok[5]
+    n, n_alpha = int(np.asarray(flag).size), len(mod_codes) + 1
+    buf, b = modbam_device_batch(dev, mod_codes, seq, seq_off, cigar, cigar_off, flag, ref_id, pos, has, tok)
     b.n_refs, b.truth_off, b.truth_pos, b.truth_label = truth.n_refs, truth.off.data_ptr(), truth.pos.data_ptr(), truth.lab.data_ptr()
     n_cig = int(np.asarray(cigar).size)
     ords = torch.empty(max(int(deltas.size), 1), dtype=torch.int32, device=dev)
@@ -466,6 +478,26 @@ def modbam_batch_sites(eng, truth, mod_codes, seq, seq_off, cigar, cigar_off, fl
     return probs[:total], label[:total], qr[0, :total], qr[1, :total], h_counts, h_status
 
 
+MOD_NOT_IN_TRUTH = ("Modified base found in BAM ({}) not found in ground truth. If this should be included in validation, add with "
+                    "--extra-bases.")
+
+
+def warn_ignored_entries(entries, alphabet, warn, mod_message=MOD_NOT_IN_TRUTH):
+    """The one warning each for the entries of a batch that do not count: '-'-strand (duplex) entries, and a code outside the
+    alphabet.  `warn`: {"strand": bool, "mod": bool}, what has not been said yet."""
+    if warn["strand"] and entries.size and (entries["strand"] == b"-").any():
+        LOGGER.warning("Reverse strand (duplex) mods not supported ")
+        warn["strand"] = False
+    if warn["mod"] and entries.size:
+        fwd = entries[entries["strand"] == b"+"]
+        seen = set(np.unique(np.frombuffer(fwd["codes"].tobytes(), np.uint8)).tobytes().decode("latin-1")) - {"\x00"}
+        seen |= {str(c) for c in np.unique(fwd["chebi"]).tolist() if c}
+        for mod_name in sorted(seen - set(alphabet)):
+            LOGGER.warning(mod_message.format(mod_name))
+            warn["mod"] = False
+            break
+
+
 def parse_mod_bam(bam_path, gt_sites, gt_ranges, alphabet, full_fh, context_bases=5, max_sites=None, device=None, batch=512,
                   return_sites=False):
     """Probabilities and ground-truth labels of every modified-base call of `bam_path` that falls on a ground-truth site
@@ -487,25 +519,14 @@ def parse_mod_bam(bam_path, gt_sites, gt_ranges, alphabet, full_fh, context_base
     eng = get_engine(device)
     truth = ModBamTruth(bam_reference_names(bam_path), gt_sites, list(alphabet), eng.torch_device)
     parts, counts, skipped, n_records = [], [], {}, 0
-    warn_mod = warn_strand = True
+    warn = {"strand": True, "mod": True}
+
     def tokenised():  # the reader and the tokeniser of batch k + 1 run on a thread of their own beside the join of batch k
         for rb, _ in iter_bam_raw_batches(bam_path, want_ref=False, batch=int(batch)):
             yield rb, tokenise_mod_tags(rb.raw, rb.raw_off, rb.tags_off)
 
     for rb, tok in _readahead(tokenised(), depth=2):
-        entries = tok[4]
-        if warn_strand and entries.size and (entries["strand"] == b"-").any():
-            LOGGER.warning("Reverse strand (duplex) mods not supported ")
-            warn_strand = False
-        if warn_mod and entries.size:
-            fwd = entries[entries["strand"] == b"+"]
-            seen = set(np.unique(np.frombuffer(fwd["codes"].tobytes(), np.uint8)).tobytes().decode("latin-1")) - {"\x00"}
-            seen |= {str(c) for c in np.unique(fwd["chebi"]).tolist() if c}
-            for mod_name in sorted(seen - set(alphabet)):
-                LOGGER.warning(f"Modified base found in BAM ({mod_name}) not found in ground truth. If this should be included in "
-                               "validation, add with --extra-bases.")
-                warn_mod = False
-                break
+        warn_ignored_entries(tok[4], alphabet, warn)
         out = modbam_batch_sites(eng, truth, mods, rb.seq, rb.seq_off, rb.cigar, rb.cigar_off, rb.flag, rb.ref_id, rb.pos, rb.has, tok)
         parts.append(out[:4])
         counts.append(out[4])
