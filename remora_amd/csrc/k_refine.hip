@@ -1399,6 +1399,8 @@ int rmr_refine_signal_maps(rmr_refiner *rf, int64_t n_reads, const int16_t *dacs
         // largest bands first: the persistent waves finish together and a wave's traceback region,
         // sized for its first read, fits all its later ones
         const int force_w = tune_int("RMR_REFINE_W", 0);
+        // at most this many persistent waves per launch (0 or below: unset); the traceback regions below follow `grid`
+        const int grid_cap = tune_int("RMR_REFINE_GRID", 0);
         for (int64_t r = 0; r < n_reads; ++r) {
             if (hstat[r] != 0) continue;
             if (band_len[r] >= ((int64_t)1 << 31)) continue;  // 32-bit row offsets of the column kernel: row-wise instead
@@ -1414,6 +1416,7 @@ int rmr_refine_signal_maps(rmr_refiner *rf, int64_t n_reads, const int16_t *dacs
             if (lst.empty()) continue;
             const int G = pass == 0 ? 4 : 1;
             int grid = std::min((int)((lst.size() + G - 1) / G), rf->max_grid);
+            if (grid_cap > 0) grid = std::min(grid, grid_cap);
             int64_t cells = 0;
             for (;;) {  // one traceback region per lane group in flight, within the arena budget
                 slot_base.assign((size_t)grid * G, 0);

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import golden
+from refine_cases import random_read as _random_read  # the suite's read generator lives with the case lists
 
 pytestmark = pytest.mark.gpu
 
@@ -94,38 +95,13 @@ def test_refine_reads_batched_equals_per_read(torch_cuda, G):
         np.testing.assert_allclose([r.shift, r.scale], G[f"s0_{n}_shift_scale"], rtol=1e-12)
 
 
-def _random_read(rng, table, k, center, nbases, zero_frac=0.0, stall=False, trim=False, noise=0.3):
-    int_seq = rng.integers(0, 4, nbases).astype(np.int8)
-    dwell = rng.integers(1, 14, nbases)
-    if zero_frac:
-        dwell[rng.random(nbases) < zero_frac] = 0
-        dwell[-1] = max(dwell[-1], 1)
-    if stall:
-        dwell[rng.integers(5, nbases - 5, 2)] = rng.integers(200, 700, 2)
-    lead, tail = (int(rng.integers(0, 50)), int(rng.integers(0, 50))) if trim else (0, 0)
-    smap = lead + np.concatenate([[0], np.cumsum(dwell)]).astype(np.int64)
-    idx = np.zeros(nbases - k + 1, np.int64)
-    for j in range(k):
-        idx = idx * 4 + int_seq[j : nbases - k + 1 + j]
-    lv = np.zeros(nbases, np.float32)
-    lv[center : center + nbases - k + 1] = table[idx]
-    norm = np.concatenate([np.zeros(lead), np.repeat(lv, dwell), np.zeros(tail)])
-    norm = norm + noise * rng.standard_normal(norm.size)
-    dacs = np.round(400 + 60 * norm).astype(np.int16)
-    # perturb the mapping so that the DP has something to move
-    jit = smap.copy()
-    jit[1:-1] += rng.integers(-4, 5, nbases - 1)
-    jit = np.maximum.accumulate(np.clip(jit, smap[0], smap[-1]))
-    jit[0], jit[-1] = smap[0], smap[-1]
-    return dacs, jit, int_seq
-
-
 @pytest.mark.parametrize("algo,sd_len", [("Viterbi", 3), ("dwell_penalty", 1), ("dwell_penalty", 3),
                                           ("dwell_penalty", 6), ("dwell_penalty", 8)])
 def test_refine_random_batches_vs_oracle(torch_cuda, O, algo, sd_len):
     """Seeded random reads (ragged lengths, zero-dwell bases, stalls, maps that neither start at 0
     nor end at the signal end) in one batch: paths and validate_band errors equal the oracle's.
     sd_len 8 exceeds the register path and exercises the row-wise kernel."""
+    from remora_amd.engine import get_engine
     from remora_amd.refine_signal_map import SigMapRefiner
 
     rng = np.random.default_rng(100 + sd_len + (algo == "Viterbi"))
@@ -142,8 +118,15 @@ def test_refine_random_batches_vs_oracle(torch_cuda, O, algo, sd_len):
                                       stall=(i % 4 == 1 and nb > 20), trim=(i % 2 == 0)))
         shifts = rng.uniform(380, 420, len(reads))
         scales = rng.uniform(50, 70, len(reads))
+        eng = get_engine(0)
+        eng.profile_reset()
+        eng.profile_enable(True)
         outs, status, dev = ref._refine_batch([r[0] for r in reads], shifts, scales, [r[1] for r in reads],
                                               [r[2] for r in reads])
+        eng.profile_enable(False)
+        if sd_len == 8:  # past the six penalties of the register path: one row-wise launch, the column kernel not at all
+            launches = {k: v[1] for k, v in eng.profile().items()}
+            assert (launches.get("refine_dp", 0), launches.get("refine_dp_rowwise", 0)) == (0, 1), launches
         n_err = 0
         for i, (d, m, s) in enumerate(reads):
             want, err = O.refine_one(d, shifts[i], scales[i], m, s, table, center, hbw, algo, sd)
