@@ -403,6 +403,60 @@ int rmr_modbam_call_counts(rmr_engine *e, const rmr_modbam_batch *b, int32_t reg
 int rmr_modbam_call_fill(rmr_engine *e, const rmr_modbam_batch *b, int32_t region_ref, int64_t region_lo, int64_t region_hi, int32_t k_t,
                          const int32_t *ords, const int64_t *cig_q, const int64_t *cig_r, const int32_t *status, const int64_t *out_off,
                          uint64_t *words);
+/* The reference genome on the device (GPU), for the motif test and the strand fold of the emit below.
+ * Form: one nibble per base, two bases per byte, low nibble first; every contig starts on a byte boundary; sum of
+ * ceil(len / 2) bytes (1.55 GB for a human genome) plus 16 bytes per contig.  A code is the IUPAC set of the letter as a mask:
+ * A 1, C 2, G 4, T / U 8, an ambiguity letter the union of its bases, N 15; lower case as upper case; 0 is no letter.  The
+ * complement of a code is its four bits reversed.
+ * rmr_ref_genome_create: allocates the table for n_contigs contigs of lens[c] bases (HOST array; 0: a contig that is not
+ * loaded, on which nothing matches) and zeroes it; *device_bytes (nullable) gets the bytes it holds.
+ * rmr_ref_genome_load: fills contig `contig` from `text` (HOST pointer), the text_bytes bytes of its sequence lines as they
+ * stand in a FASTA file, from the first base to the last, line terminators inside included: lines of line_bases bases, each
+ * followed by line_width - line_bases terminator bytes ("\n": 1, "\r\n": 2), the last line possibly shorter - the layout
+ * `samtools faidx` requires.  The bases the text holds by that layout must be lens[contig].  The text goes to the device in
+ * pieces of at most piece_bytes bytes (>= 16; 0: 64 MiB), each an even number of bases from an even base index, one kernel
+ * launch per piece: the thread of a packed byte reads its two bases, and the same threads verify every byte of the text - a
+ * base byte must be an IUPAC letter, a byte behind a line's last base the terminator.  *bad_offset (nullable) gets -1, or
+ * the offset in `text` of the first violation, and the call then fails with RMR_ERR_INVALID naming the 1-based sequence
+ * line; the contig's table is not to be used after that.  Synchronous.
+ * rmr_ref_genome_read: codes [lo, hi) of a contig, one per byte, to a HOST array.  Synchronous; for tests.
+ * rmr_ref_genome_destroy: waits for the engine's stream, then frees the table. */
+typedef struct rmr_ref_genome rmr_ref_genome;
+int rmr_ref_genome_create(rmr_engine *e, int64_t n_contigs, const int64_t *lens, rmr_ref_genome **out, int64_t *device_bytes);
+int rmr_ref_genome_load(rmr_ref_genome *g, int64_t contig, const uint8_t *text, int64_t text_bytes, int64_t line_bases, int64_t line_width,
+                        int64_t piece_bytes, int64_t *bad_offset);
+int rmr_ref_genome_read(rmr_ref_genome *g, int64_t contig, int64_t lo, int64_t hi, uint8_t *codes);
+void rmr_ref_genome_destroy(rmr_ref_genome *g);
+/* The emit with a reference: a call is kept only where the reference shows a motif around it.
+ * A motif: len bases (1 .. RMR_PILEUP_MAX_MOTIF_LEN), the called base at index focus; mask = len nibbles of IUPAC codes, base
+ * i in bits 4 i .. 4 i + 3; rc_mask = its reverse complement, nibble i = the 4 bits of nibble len - 1 - i of mask reversed.
+ * A reference code r matches a nibble m iff r != 0 and (r & ~m) == 0 - everything the reference allows, the motif allows; a
+ * reference N matches only a motif N.  A call at position rp of a '+' record matches when ref[rp - focus + i] matches nibble
+ * i of mask for every i, of a '-' record when ref[rp - (len - 1 - focus) + i] matches nibble i of rc_mask; a window that
+ * leaves the contig does not match.  The call is kept iff a motif matches; the first that does, in array order, is its motif.
+ * combine != 0 (every motif must then be its own reverse complement, mask == rc_mask): a kept '-' call is written on '+' at
+ * rp - (len - 1 - 2 focus) of its motif - the focus of the same window read on '+' - and the table has one row per motif site.
+ * The region is asked of the position that is written.  The histogram and the counts see kept calls only.
+ * rmr_modbam_call_counts_ref / rmr_modbam_call_fill_ref: rmr_modbam_call_counts / _fill with that test; ref == NULL: exactly
+ * those.  The genome must hold the batch's n_refs contigs and belong to the same engine; refused before any launch
+ * otherwise, and for a motif outside the bounds above or an rc_mask that is not mask's reverse complement. */
+#define RMR_PILEUP_MAX_MOTIFS 4
+#define RMR_PILEUP_MAX_MOTIF_LEN 16
+typedef struct rmr_pileup_motif {
+    int32_t len, focus;
+    uint64_t mask, rc_mask;
+} rmr_pileup_motif;
+typedef struct rmr_pileup_ref {
+    const rmr_ref_genome *genome;
+    int32_t n_motifs, combine;
+    rmr_pileup_motif motifs[RMR_PILEUP_MAX_MOTIFS];
+} rmr_pileup_ref;
+int rmr_modbam_call_counts_ref(rmr_engine *e, const rmr_modbam_batch *b, const rmr_pileup_ref *ref, int32_t region_ref, int64_t region_lo,
+                               int64_t region_hi, int32_t *ords, int64_t *cig_q, int64_t *cig_r, int64_t *counts, int32_t *status,
+                               uint64_t *hist);
+int rmr_modbam_call_fill_ref(rmr_engine *e, const rmr_modbam_batch *b, const rmr_pileup_ref *ref, int32_t region_ref, int64_t region_lo,
+                             int64_t region_hi, int32_t k_t, const int32_t *ords, const int64_t *cig_q, const int64_t *cig_r,
+                             const int32_t *status, const int64_t *out_off, uint64_t *words);
 /* The per-site table (GPU).  rmr_pileup_create: a table for n_contigs contigs, the longest of max_contig_len bases, with
  * n_alpha classes (the canonical base and 1 .. 7 modified ones; a row has n_alpha + 1 u32 counts, the last is `fail`) and a
  * call buffer of buffer_calls words (below 2^31).  Refused before anything is allocated or launched: n_contigs outside 1 ..

@@ -398,7 +398,7 @@ def _pileup_modbams(args):
     """`analyze pileup_modbams` (no counterpart in the reference's command line): per-site modified-base counts, bedMethyl."""
     import logging
 
-    from .pileup import pileup_modbams, write_bedmethyl, write_counts
+    from .pileup import check_ref_arguments, pileup_modbams, write_bedmethyl, write_counts
 
     log = logging.getLogger("Remora")
     log.setLevel(logging.INFO)
@@ -408,9 +408,10 @@ def _pileup_modbams(args):
         log.addHandler(logging.FileHandler(args.log_filename, mode="w"))
     if args.min_coverage < 1:
         raise RemoraError("--min-coverage is at least 1")
+    motifs = check_ref_arguments(args.ref, args.motif, args.cpg, args.combine_strands, args.canonical_base)
     table = pileup_modbams(args.bam, [args.canonical_base] + list(args.mod_bases), filter_threshold=args.filter_threshold,
                            pct_filt=args.pct_filt, region=args.region, device=args.device, batch=args.reads_per_batch,
-                           device_gib=args.pileup_device_gib)
+                           device_gib=args.pileup_device_gib, ref=args.ref, motifs=motifs, combine_strands=args.combine_strands)
     # the files are written only now: a run that keeps no call leaves none behind
     n_rows = write_bedmethyl(table, args.out_bed, min_coverage=args.min_coverage)
     if args.counts_filename is not None:
@@ -800,6 +801,17 @@ def build_parser():
     pm.add_argument("--min-coverage", type=int, default=1, help="write a site when at least this many of its calls pass")
     pm.add_argument("--counts-filename", help="TSV of the per-site counts of every class and of the failing calls")
     pm.add_argument("--region", help="ctg or ctg:start-end (0-based, half-open): only calls on these reference positions")
+    pm.add_argument("--ref", metavar="FASTA",
+                    help="the reference the reads were mapped to, plain FASTA with lines of one width per contig (no .fai needed): with "
+                         "--motif or --cpg only calls on a motif of the reference are counted; it is packed into half a byte per base "
+                         "of GPU memory")
+    pm.add_argument("--motif", nargs=2, action="append", metavar=("MOTIF", "FOCUS_POSITION"),
+                    help="count only calls whose reference position shows this IUPAC motif, the called base at FOCUS_POSITION (0-based); "
+                         "up to 4 motifs of up to 16 bases; needs --ref")
+    pm.add_argument("--cpg", action="store_true", help="--motif CG 0 (needs --canonical-base C)")
+    pm.add_argument("--combine-strands", action="store_true",
+                    help="one row per motif site with the calls of both strands, at the '+' position of the motif, strand column '.'; "
+                         "every motif must be its own reverse complement (CG, GC, GATC)")
     pm.add_argument("--pileup-device-gib", type=float, default=8.0,
                     help="GiB of GPU memory for the call buffer and its sort (capped at half of what is free); the per-site table "
                          "comes on top, 8 + 4 (classes + 1) bytes per distinct site")

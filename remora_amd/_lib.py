@@ -51,6 +51,18 @@ class ModbamBatch(ctypes.Structure):
         ("truth_off", c_vp), ("truth_pos", c_vp), ("truth_label", c_vp)]
 
 
+class PileupMotif(ctypes.Structure):
+    """rmr_pileup_motif of include/remora_hip.h."""
+
+    _fields_ = [("len", ctypes.c_int32), ("focus", ctypes.c_int32), ("mask", ctypes.c_uint64), ("rc_mask", ctypes.c_uint64)]
+
+
+class PileupRef(ctypes.Structure):
+    """rmr_pileup_ref of include/remora_hip.h."""
+
+    _fields_ = [("genome", c_vp), ("n_motifs", ctypes.c_int32), ("combine", ctypes.c_int32), ("motifs", PileupMotif * 4)]
+
+
 MOD_MAX_CODES = 16
 # rmr_mod_entry of include/remora_hip.h as a numpy record (48 bytes)
 MOD_ENTRY_FIELDS = [("delta_off", "<i8"), ("ml_off", "<i8"), ("n_deltas", "<i4"), ("n_codes", "<i4"), ("chebi", "<i4"), ("base", "S1"),
@@ -124,6 +136,14 @@ SIGNATURES = {
     "rmr_modbam_call_counts": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), ctypes.c_int32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rmr_modbam_call_fill": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), ctypes.c_int32, c_i64, c_i64, ctypes.c_int32, c_vp, c_vp, c_vp, c_vp, c_vp,
                                      c_vp]),
+    "rmr_ref_genome_create": (c_int, [c_vp, c_i64, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_i64)]),
+    "rmr_ref_genome_load": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, ctypes.POINTER(c_i64)]),
+    "rmr_ref_genome_read": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp]),
+    "rmr_ref_genome_destroy": (None, [c_vp]),
+    "rmr_modbam_call_counts_ref": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), ctypes.POINTER(PileupRef), ctypes.c_int32, c_i64, c_i64, c_vp, c_vp,
+                                           c_vp, c_vp, c_vp, c_vp]),
+    "rmr_modbam_call_fill_ref": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), ctypes.POINTER(PileupRef), ctypes.c_int32, c_i64, c_i64, ctypes.c_int32,
+                                         c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rmr_pileup_create": (c_int, [c_vp, c_i64, c_i64, c_int, c_i64, ctypes.POINTER(c_vp)]),
     "rmr_pileup_add": (c_int, [c_vp, c_vp, c_i64]),
     "rmr_pileup_finish": (c_int, [c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),

@@ -572,31 +572,80 @@ static int check_call_batch(const rmr_modbam_batch *b, int32_t region_ref, int64
     return 0;
 }
 
-int rmr_modbam_call_counts(rmr_engine *e, const rmr_modbam_batch *b, int32_t region_ref, int64_t region_lo, int64_t region_hi,
-                           int32_t *ords, int64_t *cig_q, int64_t *cig_r, int64_t *counts, int32_t *status, uint64_t *hist) {
+static int reverse4(int c) { return ((c & 1) << 3) | ((c & 2) << 1) | ((c & 4) >> 1) | ((c & 8) >> 3); }
+
+// the reference part of an emit from the caller's struct, everything checked
+static int fill_ref_part(rmr_engine *e, const rmr_modbam_batch *b, const rmr_pileup_ref *ref, PileupRef *pr) {
+    const rmr_ref_genome *g = ref->genome;
+    if (!g || !g->data) RMR_FAIL(RMR_ERR_INVALID, "rmr_pileup_ref without a genome");
+    if (g->eng != e) RMR_FAIL(RMR_ERR_INVALID, "the reference genome belongs to another engine");
+    if (g->n_contigs < b->n_refs)
+        RMR_FAIL(RMR_ERR_INVALID, "the reference genome holds %lld contigs, the batch names %lld", (long long)g->n_contigs, (long long)b->n_refs);
+    if (ref->n_motifs < 1 || ref->n_motifs > RMR_PILEUP_MAX_MOTIFS)
+        RMR_FAIL(RMR_ERR_INVALID, "1 to %d motifs, got %d", RMR_PILEUP_MAX_MOTIFS, ref->n_motifs);
+    for (int j = 0; j < ref->n_motifs; ++j) {
+        const rmr_pileup_motif &m = ref->motifs[j];
+        if (m.len < 1 || m.len > RMR_PILEUP_MAX_MOTIF_LEN || m.focus < 0 || m.focus >= m.len)
+            RMR_FAIL(RMR_ERR_INVALID, "motif #%d: a length of 1 to %d and a focus inside it, got %d and %d", j, RMR_PILEUP_MAX_MOTIF_LEN, m.len, m.focus);
+        for (int i = 0; i < RMR_PILEUP_MAX_MOTIF_LEN; ++i) {
+            const int c = (int)(m.mask >> (4 * i)) & 15, rc = (int)(m.rc_mask >> (4 * i)) & 15;
+            if (i >= m.len ? (c != 0 || rc != 0) : (c == 0 || rc != reverse4((int)(m.mask >> (4 * (m.len - 1 - i))) & 15)))
+                RMR_FAIL(RMR_ERR_INVALID, "motif #%d: nibble %d of mask / rc_mask is not a motif of %d bases and its reverse complement", j, i, m.len);
+        }
+        if (ref->combine && m.mask != m.rc_mask)
+            RMR_FAIL(RMR_ERR_INVALID, "motif #%d is not its own reverse complement: its strands cannot be combined", j);
+        pr->motifs[j] = m;
+    }
+    pr->data = g->data, pr->off = g->d_off, pr->len = g->d_len;
+    pr->n_motifs = ref->n_motifs, pr->combine = ref->combine ? 1 : 0;
+    return 0;
+}
+
+int rmr_modbam_call_counts_ref(rmr_engine *e, const rmr_modbam_batch *b, const rmr_pileup_ref *ref, int32_t region_ref, int64_t region_lo,
+                               int64_t region_hi, int32_t *ords, int64_t *cig_q, int64_t *cig_r, int64_t *counts, int32_t *status,
+                               uint64_t *hist) {
     if (!e || !b || !counts || !status) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
     RMR_TRY(check_call_batch(b, region_ref, region_lo, region_hi));
     if ((b->n_deltas > 0 && !ords) || !cig_q || !cig_r) RMR_FAIL(RMR_ERR_INVALID, "NULL workspace");
+    const PileupEmit pe{region_ref, region_lo, region_hi, 0, reinterpret_cast<unsigned long long *>(hist), nullptr};
+    PileupRef pr{};
+    if (ref) RMR_TRY(fill_ref_part(e, b, ref, &pr));
     if (b->n_records == 0) return 0;
     std::lock_guard<std::mutex> lk(e->mu);
     RMR_HIP(hipSetDevice(e->device));
-    const PileupEmit pe{region_ref, region_lo, region_hi, 0, reinterpret_cast<unsigned long long *>(hist), nullptr};
+    if (ref) return launch_modbam_calls_ref(e, *b, pe, pr, ords, cig_q, cig_r, counts, status, nullptr);
     return launch_modbam_calls(e, *b, pe, ords, cig_q, cig_r, counts, status, nullptr);
+}
+
+int rmr_modbam_call_fill_ref(rmr_engine *e, const rmr_modbam_batch *b, const rmr_pileup_ref *ref, int32_t region_ref, int64_t region_lo,
+                             int64_t region_hi, int32_t k_t, const int32_t *ords, const int64_t *cig_q, const int64_t *cig_r,
+                             const int32_t *status, const int64_t *out_off, uint64_t *words) {
+    if (!e || !b || !status || !out_off || !words) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    RMR_TRY(check_call_batch(b, region_ref, region_lo, region_hi));
+    if ((b->n_deltas > 0 && !ords) || !cig_q || !cig_r) RMR_FAIL(RMR_ERR_INVALID, "NULL workspace");
+    if (k_t < 0 || k_t > RMR_PILEUP_BINS) RMR_FAIL(RMR_ERR_INVALID, "the threshold is 0 .. %d in units of 1/512, got %d", RMR_PILEUP_BINS, k_t);
+    const PileupEmit pe{region_ref, region_lo, region_hi, k_t, nullptr, words};
+    PileupRef pr{};
+    if (ref) RMR_TRY(fill_ref_part(e, b, ref, &pr));
+    if (b->n_records == 0) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    if (ref)
+        return launch_modbam_calls_ref(e, *b, pe, pr, const_cast<int32_t *>(ords), const_cast<int64_t *>(cig_q), const_cast<int64_t *>(cig_r), nullptr,
+                                       const_cast<int32_t *>(status), out_off);
+    return launch_modbam_calls(e, *b, pe, const_cast<int32_t *>(ords), const_cast<int64_t *>(cig_q), const_cast<int64_t *>(cig_r), nullptr,
+                               const_cast<int32_t *>(status), out_off);
+}
+
+int rmr_modbam_call_counts(rmr_engine *e, const rmr_modbam_batch *b, int32_t region_ref, int64_t region_lo, int64_t region_hi,
+                           int32_t *ords, int64_t *cig_q, int64_t *cig_r, int64_t *counts, int32_t *status, uint64_t *hist) {
+    return rmr_modbam_call_counts_ref(e, b, nullptr, region_ref, region_lo, region_hi, ords, cig_q, cig_r, counts, status, hist);
 }
 
 int rmr_modbam_call_fill(rmr_engine *e, const rmr_modbam_batch *b, int32_t region_ref, int64_t region_lo, int64_t region_hi, int32_t k_t,
                          const int32_t *ords, const int64_t *cig_q, const int64_t *cig_r, const int32_t *status, const int64_t *out_off,
                          uint64_t *words) {
-    if (!e || !b || !status || !out_off || !words) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
-    RMR_TRY(check_call_batch(b, region_ref, region_lo, region_hi));
-    if ((b->n_deltas > 0 && !ords) || !cig_q || !cig_r) RMR_FAIL(RMR_ERR_INVALID, "NULL workspace");
-    if (k_t < 0 || k_t > RMR_PILEUP_BINS) RMR_FAIL(RMR_ERR_INVALID, "the threshold is 0 .. %d in units of 1/512, got %d", RMR_PILEUP_BINS, k_t);
-    if (b->n_records == 0) return 0;
-    std::lock_guard<std::mutex> lk(e->mu);
-    RMR_HIP(hipSetDevice(e->device));
-    const PileupEmit pe{region_ref, region_lo, region_hi, k_t, nullptr, words};
-    return launch_modbam_calls(e, *b, pe, const_cast<int32_t *>(ords), const_cast<int64_t *>(cig_q), const_cast<int64_t *>(cig_r), nullptr,
-                               const_cast<int32_t *>(status), out_off);
+    return rmr_modbam_call_fill_ref(e, b, nullptr, region_ref, region_lo, region_hi, k_t, ords, cig_q, cig_r, status, out_off, words);
 }
 
 int rmr_pileup_create(rmr_engine *e, int64_t n_contigs, int64_t max_contig_len, int n_alpha, int64_t buffer_calls, rmr_pileup **out) {

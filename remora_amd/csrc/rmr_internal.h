@@ -87,6 +87,7 @@ enum KernelId {
     // `analyze pileup_modbams` (k_pileup.hip)
     K_PILEUP_EMIT,   // the walk that writes site words (or the confidence histogram)
     K_PILEUP_FLUSH,  // one flush: the radix sort, the run counts and the merge into the table
+    K_REF_GENOME_PACK,  // one piece of a contig's FASTA text into nibbles, verified (k_ref_genome.hip)
     K_NUM
 };
 const char *kernel_name(int id);
@@ -221,8 +222,28 @@ struct rmr_pileup {
     size_t peak_bytes = 0;
 };
 
+// ---- reference genome (k_ref_genome.hip) ---------------------------------------------------
+// the state of rmr_ref_genome_create: the contigs' nibbles in one device allocation (`data`: contig c at byte d_off[c], h_len[c]
+// bases in ceil(h_len[c] / 2) bytes), the offsets and lengths on both sides, and the word of the pack kernel's first violation
+struct rmr_ref_genome {
+    rmr_engine *eng = nullptr;
+    int64_t n_contigs = 0;
+    void *mem = nullptr;
+    size_t bytes = 0;               // of `mem`
+    uint8_t *data = nullptr;
+    int64_t *d_off = nullptr, *d_len = nullptr;
+    unsigned long long *first_bad = nullptr;
+    std::vector<int64_t> h_off, h_len;
+};
+
 // ---- kernel launchers (defined in k_*.hip) ------------------------------------------------
 namespace rmr {
+
+// k_ref_genome.hip: one piece of a contig's text (device copy `text` of bytes [text_lo, text_lo + text_bytes) of its span) ->
+// the packed bytes of bases [base_lo, base_hi) at `out`;  codes [lo, hi) of a contig, one per byte
+int launch_ref_pack(rmr_engine *e, const uint8_t *text, int64_t text_lo, int64_t text_bytes, int64_t span_bytes, int64_t base_lo, int64_t base_hi,
+                    int64_t line_bases, int64_t line_width, uint8_t *out, unsigned long long *first_bad);
+int launch_ref_unpack(rmr_engine *e, const rmr_ref_genome *g, int64_t contig, int64_t lo, int64_t hi, uint8_t *codes);
 
 // k_pileup.hip: the emit of `analyze pileup_modbams` (count pass: out_off == nullptr) and the pileup's three steps
 constexpr int PILEUP_BINS = RMR_PILEUP_BINS;  // 512 x the winning probability of a call: 0 .. 512
@@ -234,8 +255,21 @@ struct PileupEmit {
     unsigned long long *hist;       // count pass: u64[PILEUP_BINS], or nullptr
     uint64_t *words;                // fill pass: one word per kept call
 };
+// The reference part of an emit (rmr_modbam_call_counts_ref / _fill_ref): the motif test and the fold of rmr_modbam_walk.h.
+// It is a kernel argument of its own, by value, and only of the kernels with a reference (k_ref_genome.hip): PileupEmit and
+// with it the argument block of the kernels without one stay byte for byte what they were, and so does their code (one
+// pointer more in PileupEmit moved the scalar loads and the register allocation of those kernels, profiles/NOTES_r18.md).
+struct PileupRef {
+    const uint8_t *data;            // the genome's nibbles
+    const int64_t *off, *len;       // per contig: its first byte in `data`, its bases (0: not loaded - nothing matches)
+    int32_t n_motifs, combine;      // 1 .. RMR_PILEUP_MAX_MOTIFS; combine: a kept '-' call is written on '+' at pos - (L - 1 - 2 focus)
+    rmr_pileup_motif motifs[RMR_PILEUP_MAX_MOTIFS];
+};
 int launch_modbam_calls(rmr_engine *e, const rmr_modbam_batch &b, const PileupEmit &pe, int32_t *ords, int64_t *cig_q, int64_t *cig_r,
                         int64_t *counts, int32_t *status, const int64_t *out_off);
+// k_ref_genome.hip: the same emit with the reference part
+int launch_modbam_calls_ref(rmr_engine *e, const rmr_modbam_batch &b, const PileupEmit &pe, const PileupRef &pr, int32_t *ords, int64_t *cig_q,
+                            int64_t *cig_r, int64_t *counts, int32_t *status, const int64_t *out_off);
 int pileup_alloc(rmr_pileup *p);
 int pileup_append(rmr_pileup *p, const uint64_t *words, int64_t n);
 int pileup_flush(rmr_pileup *p);

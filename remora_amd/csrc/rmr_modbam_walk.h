@@ -4,6 +4,9 @@
 //                                   and goes to the host as a row of probabilities with its label;
 //   k_pileup.hip  (PILEUP = true)   every aligned call is kept (inside the region, if one is given), classified in integers
 //                                   and written as one 64-bit site word - or only counted into the histogram of its confidence.
+//                                   With a reference genome (PileupRef) a call is kept only where the reference shows
+//                                   one of up to four motifs around it, and a '-' call can be folded onto the '+' position of
+//                                   its motif (motif_keep below): everything after the keep test sees the filtered, folded calls.
 //
 // One workgroup of four waves per record, the same walk twice (count, then fill into the caller's prefix-summed offsets):
 //   count pass only
@@ -54,14 +57,51 @@ __device__ inline void block_scan2(int64_t &a, int64_t &b, int64_t &ta, int64_t 
 __device__ inline int base_index(int c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; }
 __device__ inline int complement(int c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c; }
 
+// ---- the reference part of the pileup's keep test (k_ref_genome.hip: the form and the codes) ----
+// the code of base i of a contig whose nibbles start at data[off]; 0 outside [0, len)
+__device__ inline int ref_code(const uint8_t *__restrict__ data, int64_t off, int64_t len, int64_t i) {
+    if (i < 0 || i >= len) return 0;
+    const int byte = data[off + (i >> 1)];
+    return (i & 1) ? byte >> 4 : byte & 15;
+}
+
+// do the L bases from s on match the L nibble masks of `masks`?  A reference code r matches a mask m iff r != 0 and
+// (r & ~m) == 0; a window that leaves the contig does not match.
+__device__ inline bool motif_window(const uint8_t *__restrict__ data, int64_t off, int64_t len, int64_t s, int L, uint64_t masks) {
+    if (s < 0 || s + L > len) return false;
+    for (int i = 0; i < L; ++i) {
+        const int r = ref_code(data, off, len, s + i), m = (int)(masks >> (4 * i)) & 15;
+        if (r == 0 || (r & ~m) != 0) return false;
+    }
+    return true;
+}
+
+// A call at reference position rp of contig `rid`, on '-' when rev: is it on a motif, and where is it written?  The first
+// motif that matches decides; *wp = rp, or with pr.combine for a '-' call rp - (L - 1 - 2 focus): the focus of the same
+// window read on '+' (inside the contig, as the window is).
+__device__ inline bool motif_keep(const PileupRef &pr, int64_t rid, bool rev, int64_t rp, int64_t *wp) {
+    const int64_t off = pr.off[rid], len = pr.len[rid];
+    for (int j = 0; j < pr.n_motifs; ++j) {
+        const rmr_pileup_motif &mo = pr.motifs[j];
+        const int64_t s = rp - (rev ? mo.len - 1 - mo.focus : mo.focus);
+        if (motif_window(pr.data, off, len, s, mo.len, rev ? mo.rc_mask : mo.mask)) {
+            *wp = (rev && pr.combine) ? s + mo.focus : rp;
+            return true;
+        }
+    }
+    return false;
+}
+
 // The body of both kernels; called by every thread of a block of MB_THREADS.  PILEUP: probs / label / qpos / rpos are not
 // touched and the truth fields of `b` are not read; s_hist is PILEUP_BINS words of LDS (count pass with pe.hist) or unused.
-template <bool FILL, bool PILEUP>
+// REF (PILEUP only): the motif test and the fold by `rf`; without it `rf` is not read and the pileup compiles the code it had
+// before there was a reference.
+template <bool FILL, bool PILEUP, bool REF = false>
 __device__ __forceinline__ void modbam_walk(const rmr_modbam_batch &b, int32_t *__restrict__ ords, int64_t *__restrict__ cig_q,
                                             int64_t *__restrict__ cig_r, int64_t *__restrict__ counts, int32_t *__restrict__ status,
                                             const int64_t *__restrict__ out_off, float *__restrict__ probs, uint8_t *__restrict__ label,
                                             int64_t *__restrict__ qpos, int64_t *__restrict__ rpos, const PileupEmit &pe,
-                                            unsigned *__restrict__ s_hist) {
+                                            unsigned *__restrict__ s_hist, const PileupRef &rf = PileupRef{}) {
     __shared__ int64_t s_scan[MB_WAVES][2];
     __shared__ int s_base[MB_WAVES][4];
     __shared__ int s_emit[MB_WAVES];
@@ -240,7 +280,10 @@ __device__ __forceinline__ void modbam_walk(const rmr_modbam_batch &b, int32_t *
                     rp = (int64_t)b.pos[r] + cig_r[c0 + i] + within;
                     if (PILEUP) {
                         // (a position outside the word's 31 bits cannot come from a BAM whose header passed the host's check)
-                        keep = rp >= 0 && rp < ((int64_t)1 << 31) &&
+                        // with a reference: only calls on a motif, and a '-' call folded onto '+'; the region is asked of the
+                        // position that is written (rp from here on)
+                        if (REF) keep = rp >= 0 && rp < ((int64_t)1 << 31) && motif_keep(rf, b.ref_id[r], rev, rp, &rp);
+                        keep = (REF ? keep : rp >= 0 && rp < ((int64_t)1 << 31)) &&
                                (pe.region_ref < 0 || (b.ref_id[r] == pe.region_ref && rp >= pe.region_lo && rp < pe.region_hi));
                     } else {
                         int64_t a = t0, z = t1;
@@ -279,7 +322,8 @@ __device__ __forceinline__ void modbam_walk(const rmr_modbam_batch &b, int32_t *
                     const int64_t o = o_lo + emitted + before + __popcll(km & lt);
                     if (o >= o_lo && o < o_hi) {  // (offsets that are not this batch's counts write nothing outside the record's slice)
                         const uint64_t code = kmax >= pe.k_t ? (uint64_t)best : (uint64_t)(n_mods + 1);
-                        pe.words[o] = ((uint64_t)b.ref_id[r] << 36) | ((uint64_t)rp << 5) | ((uint64_t)(rev ? 1 : 0) << 4) | code;
+                        const bool minus = rev && !(REF && rf.combine);  // (a folded call stands on '+')
+                        pe.words[o] = ((uint64_t)b.ref_id[r] << 36) | ((uint64_t)rp << 5) | ((uint64_t)(minus ? 1 : 0) << 4) | code;
                     }
                 } else {
                     atomicAdd(&s_hist[kmax], 1u);

@@ -11,9 +11,16 @@ the device (rmr_pileup_*, csrc/k_pileup.hip).  One row per site crosses PCIe.
 Which calls count, and how they are classified, is DESIGN.md section 4's "Pileup"; in short: mapped primary records, '+'-strand
 entries with single-letter codes of the alphabet, the positions an entry lists, p = (ML + 0.5) / 256, the later entry wins,
 bases inside M / = / X; class = argmax (ties to the lower column), confidence kmax = 512 x the winning probability, the call
-passes when kmax >= k_T."""
+passes when kmax >= k_T.
+
+With a reference FASTA (`ref`, `motifs`) the genome is packed into nibbles on the device once (RefGenome, rmr_ref_genome_*,
+csrc/k_ref_genome.hip) and the emit keeps a call only where the reference shows one of the motifs around it; with
+`combine_strands` a '-' call is written at the '+' position of its motif, so that a CpG is one row (DESIGN.md section 4,
+"Pileup: the reference")."""
 import ctypes
 import logging
+import mmap
+import os
 import re
 from collections import namedtuple
 from fractions import Fraction
@@ -33,12 +40,20 @@ PILEUP_STATUS = {1: "no MM tag", 2: "malformed modified-base tags", 3: "unmapped
                  6: "secondary or supplementary"}
 MOD_NOT_IN_ALPHABET = "Modified base found in BAM ({}) not among --mod-bases: its calls are not counted."
 
+MAX_MOTIFS = 4               # RMR_PILEUP_MAX_MOTIFS, RMR_PILEUP_MAX_MOTIF_LEN of include/remora_hip.h
+MAX_MOTIF_LEN = 16
+DEFAULT_PIECE_BYTES = 64 << 20
+# a base's code: the IUPAC set as a mask, A 1, C 2, G 4, T 8 (the complement of a code is its four bits reversed)
+IUPAC_MASK = {"A": 1, "C": 2, "G": 4, "T": 8, "U": 8, "R": 5, "Y": 10, "S": 6, "W": 9, "K": 12, "M": 3, "B": 14, "D": 13, "H": 11, "V": 7, "N": 15}
+
 PileupTable = namedtuple("PileupTable", ("ref_names", "ref_id", "pos", "strand", "counts", "alphabet", "threshold_k", "n_calls", "n_flushes",
-                                         "peak_device_bytes", "hist"))
+                                         "peak_device_bytes", "hist", "combined"), defaults=(False,))
 PileupTable.__doc__ = """One row per site with a kept call, ordered by (ref_id, pos, strand): ref_id i32[n], pos i64[n], strand u8[n]
 (0 '+', 1 '-'), counts i64[n, len(alphabet) + 1] (canonical, the modified bases in alphabet order, fail).  threshold_k: k_T;
 n_calls: kept calls; n_flushes: flushes of the device call buffer; peak_device_bytes: the pileup's device memory at its
-peak; hist: i64[513], the calls per kmax, when the threshold came from a percentile, else None."""
+peak (the reference genome included); hist: i64[513], the calls per kmax, when the threshold came from a percentile, else
+None; combined: the strands were combined - every row stands on '+' in `strand` and belongs to both strands (the writers print
+'.')."""
 
 
 def threshold_k(filter_threshold):
@@ -150,6 +165,243 @@ def bytes_per_buffered_call(n_alpha):
     return 52 + 4 * (n_alpha + 1)
 
 
+# ---- motifs --------------------------------------------------------------------------------------------------------------
+MotifDescriptor = namedtuple("MotifDescriptor", ("motif", "length", "focus", "mask", "rc_mask", "shift"))
+MotifDescriptor.__doc__ = """A motif as the emit kernel takes it: `length` nibbles of IUPAC masks, base i in bits 4 i .. 4 i + 3 of
+`mask`; rc_mask[i] = complement(mask[length - 1 - i]); shift = length - 1 - 2 focus, what a '-' call moves down by when the
+strands are combined."""
+
+
+def _reverse4(code):
+    return ((code & 1) << 3) | ((code & 2) << 1) | ((code & 4) >> 1) | ((code & 8) >> 3)
+
+
+def motif_descriptor(motif, focus):
+    """(motif, focus) -> MotifDescriptor.  util.Motif validates the letters and the focus; the motif is taken as written - a
+    leading or trailing N, which util.Motif clips, stays: next to a contig's end, or where the reference itself has an N, it
+    is not neutral."""
+    from .util import Motif
+
+    raw = str(motif).upper().replace("U", "T")
+    Motif(raw, focus)  # RemoraError for a letter outside IUPAC, a focus that is no integer or lies past the end
+    focus = int(focus)
+    if not 1 <= len(raw) <= MAX_MOTIF_LEN:
+        raise RemoraError(f"--motif {motif}: a motif has 1 to {MAX_MOTIF_LEN} bases, this one {len(raw)}")
+    if not 0 <= focus < len(raw):
+        raise RemoraError(f"--motif {motif} {focus}: the focus position lies outside the motif")
+    codes = [IUPAC_MASK[c] for c in raw]
+    mask = sum(c << (4 * i) for i, c in enumerate(codes))
+    rc_mask = sum(_reverse4(c) << (4 * i) for i, c in enumerate(reversed(codes)))
+    return MotifDescriptor(raw, len(raw), focus, mask, rc_mask, len(raw) - 1 - 2 * focus)
+
+
+def check_pileup_motifs(motifs, canonical_base, combine_strands):
+    """[(motif, focus)] -> [MotifDescriptor], or RemoraError naming the argument: more than 4 motifs, a motif longer than 16
+    bases, a focus base that is not the canonical base, and with `combine_strands` a motif that is not its own reverse
+    complement."""
+    motifs = [tuple(m) for m in motifs]
+    if not 1 <= len(motifs) <= MAX_MOTIFS:
+        raise RemoraError(f"--motif: 1 to {MAX_MOTIFS} motifs, got {len(motifs)}")
+    can = "T" if canonical_base == "U" else canonical_base
+    out = []
+    for motif, focus in motifs:
+        d = motif_descriptor(motif, focus)
+        if d.motif[d.focus] != can:
+            raise RemoraError(f"--motif {motif} {focus}: the focus base is {d.motif[d.focus]}, the canonical base of the pileup is "
+                              f"{canonical_base} (--canonical-base)")
+        if combine_strands and d.mask != d.rc_mask:
+            raise RemoraError(f"--combine-strands: the motif {d.motif} is not its own reverse complement (CG, GC, GATC, ... are); its "
+                              "two strands do not share a site")
+        out.append(d)
+    return out
+
+
+def check_ref_arguments(ref, motifs, cpg, combine_strands, canonical_base):
+    """The command line's --ref / --motif / --cpg / --combine-strands -> the `motifs` of pileup_modbams (None without a
+    reference), or RemoraError naming the argument."""
+    motifs = list(motifs or [])
+    if cpg and motifs:
+        raise RemoraError("--cpg is --motif CG 0: give one of --cpg and --motif, not both")
+    if cpg:
+        if canonical_base != "C":
+            raise RemoraError(f"--cpg needs --canonical-base C, got {canonical_base}")
+        motifs = [("CG", 0)]
+    if ref is None:
+        for given, name in ((cpg, "--cpg"), (motifs, "--motif"), (combine_strands, "--combine-strands")):
+            if given:
+                raise RemoraError(f"{name} needs --ref: the motif is looked up in the reference FASTA")
+        return None
+    if not motifs:
+        raise RemoraError("--ref needs a motif: give --motif MOTIF FOCUS or --cpg")
+    check_pileup_motifs(motifs, canonical_base, combine_strands)
+    return motifs
+
+
+# ---- the reference FASTA -------------------------------------------------------------------------------------------------
+FastaSpan = namedtuple("FastaSpan", ("name", "start", "end", "line_bases", "line_width", "n_bases"))
+FastaSpan.__doc__ = """One contig of a FASTA file: its sequence lines are the bytes [start, end) (trailing white space stripped), in
+lines of line_bases bases and line_width bytes (by the first line and its terminator); n_bases as `samtools faidx` computes it."""
+REWRAP = "the lines of a contig must have one width: re-wrap the file, as `samtools faidx` requires"
+
+
+def fasta_spans(buf, path="FASTA"):
+    """[FastaSpan] of a FASTA file held in `buf` (bytes or an mmap), in file order, found with `find` only: no line of the
+    sequence is looked at here - the device verifies them when a contig is loaded."""
+    size = len(buf)
+    if buf[:2] == b"\x1f\x8b":
+        raise RemoraError(f"{path} is gzip- or BGZF-compressed: decompress it first, the reference is read as plain text")
+    if size == 0 or buf[:1] != b">":
+        raise RemoraError(f"{path} is not a FASTA file: it does not begin with '>'")
+    spans, seen, h = [], set(), 0
+    while h >= 0:
+        eol = buf.find(b"\n", h)
+        words = bytes(buf[h + 1 : eol if eol >= 0 else size]).split()
+        if not words:
+            raise RemoraError(f"{path}: a header without a name at byte {h}")
+        name = words[0].decode("latin-1")
+        if name in seen:
+            raise RemoraError(f"{path}: the contig name {name} occurs twice")
+        seen.add(name)
+        start = eol + 1 if eol >= 0 else size
+        nxt = buf.find(b"\n>", eol) if eol >= 0 else -1  # (from the header's own line end: a contig without a sequence)
+        end = max(start, nxt + 1 if nxt >= 0 else size)
+        while end > start and buf[end - 1] in b" \t\r\n":
+            end -= 1
+        nl = buf.find(b"\n", start, end)
+        term = 2 if nl > start and buf[nl - 1] == 13 else 1
+        line_bases = (nl if nl >= 0 else end) - start - (term - 1 if nl >= 0 else 0)
+        width, n_text = line_bases + term, end - start
+        if n_text and line_bases < 1:
+            raise RemoraError(f"{path}: contig {name}: a blank line after the header; {REWRAP}")
+        n_bases = (n_text // width) * line_bases + min(n_text % width, line_bases) if n_text else 0
+        spans.append(FastaSpan(name, start, end, line_bases, width, n_bases))
+        h = nxt + 1 if nxt >= 0 else -1
+    return spans
+
+
+def check_fasta_contigs(spans, ref_names, ref_lens, contigs, path="FASTA", bam="the BAM header"):
+    """The contigs to load (indices into ref_names) must be in the FASTA with the header's length -> {index: FastaSpan}."""
+    by_name = {s.name: s for s in spans}
+    out = {}
+    for c in contigs:
+        name, want = ref_names[c], int(ref_lens[c])
+        sp = by_name.get(name)
+        if sp is None:
+            raise RemoraError(f"{path} has no contig {name}, which {bam} names ({len(spans)} contigs in the FASTA)")
+        if sp.n_bases != want:
+            raise RemoraError(f"{path}: contig {name} has {sp.n_bases} bases (lines of {sp.line_bases}), {bam} says {want}: "
+                              "this is not the reference the reads were mapped to")
+        out[c] = sp
+    return out
+
+
+class RefGenome:
+    """rmr_ref_genome_*: the contigs of a reference FASTA as nibbles on the device, loaded once and reused over several
+    pileup_modbams calls.  ref_names / ref_lens: the BAM header's contigs, in its order; contig i of the table is contig i of
+    the header."""
+
+    n_open = 0  # tables alive in this process
+
+    def __init__(self):
+        raise TypeError("use RefGenome.from_fasta")
+
+    @classmethod
+    def from_fasta(cls, path, ref_names, ref_lens, device=None, contigs=None, piece_bytes=None):
+        """Loads `contigs` (names or indices of ref_names; None: all) from the FASTA at `path`.  Refused before anything is
+        allocated: a compressed file, a contig name twice in the file, a contig to load that the file lacks or has at
+        another length.  Refused by the device's check while a contig is loaded, naming contig and line: a byte that is no
+        IUPAC letter, lines of differing width.  FASTA contigs that are not asked for are skipped unread."""
+        from . import _lib as L
+        from .engine import get_engine
+
+        path = os.fspath(path)
+        ref_names, ref_lens = list(ref_names), [int(n) for n in ref_lens]
+        want = list(range(len(ref_names))) if contigs is None else [c if isinstance(c, int) else ref_names.index(c) for c in contigs]
+        piece = DEFAULT_PIECE_BYTES if piece_bytes is None else int(piece_bytes)
+        if piece < 16:
+            raise RemoraError(f"piece_bytes is at least 16, got {piece_bytes}")
+        with open(path, "rb") as fh:
+            if os.fstat(fh.fileno()).st_size == 0:
+                raise RemoraError(f"{path} is not a FASTA file: it is empty")
+            mm = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
+        self = object.__new__(cls)
+        self.h, self._lib, self._L = ctypes.c_void_p(), L.lib(), L
+        text = None
+        try:
+            spans = check_fasta_contigs(fasta_spans(mm, path), ref_names, ref_lens, want, path)
+            self.path, self.ref_names, self.ref_lens, self.loaded = path, ref_names, ref_lens, sorted(spans)
+            self.eng = get_engine(device)
+            lens = np.zeros(max(len(ref_names), 1), np.int64)
+            for c, sp in spans.items():
+                lens[c] = sp.n_bases
+            n_bytes = ctypes.c_int64(0)
+            L.check(self._lib.rmr_ref_genome_create(self.eng.handle, len(ref_names), lens.ctypes.data_as(ctypes.c_void_p), ctypes.byref(self.h),
+                                                    ctypes.byref(n_bytes)))
+            RefGenome.n_open += 1
+            self.device_bytes = int(n_bytes.value)
+            text = np.frombuffer(mm, np.uint8)
+            for c, sp in sorted(spans.items()):
+                if sp.n_bases == 0:
+                    continue
+                bad = ctypes.c_int64(-1)
+                rc = self._lib.rmr_ref_genome_load(self.h, c, text.ctypes.data + sp.start, sp.end - sp.start, sp.line_bases, sp.line_width, piece,
+                                                   ctypes.byref(bad))
+                if rc != 0 and bad.value >= 0:
+                    at = sp.start + int(bad.value)
+                    line = 1 + sum(int(np.count_nonzero(text[lo : min(lo + (1 << 26), at)] == 10)) for lo in range(0, at, 1 << 26))
+                    col = int(bad.value) % sp.line_width
+                    byte = int(text[at])
+                    if col >= sp.line_bases:
+                        what = f"the line does not end after {sp.line_bases} bases like the contig's first; {REWRAP}"
+                    elif byte in (10, 13):
+                        what = f"the line has {col} bases, the contig's first line has {sp.line_bases}; {REWRAP}"
+                    else:
+                        what = f"byte {byte} ({chr(byte)!r}) at column {col + 1} is not an IUPAC letter"
+                    raise RemoraError(f"{path}: contig {sp.name}, line {line} (line {int(bad.value) // sp.line_width + 1} of its sequence): {what}")
+                L.check(rc)
+            LOGGER.info(f"reference: {len(spans)} contigs, {sum(s.n_bases for s in spans.values())} bases of {path} in "
+                        f"{self.device_bytes / 2**20:.1f} MiB of device memory")
+        except BaseException:
+            self.close()
+            raise
+        finally:
+            del text
+            mm.close()
+        return self
+
+    def read(self, contig, lo=0, hi=None):
+        """The codes of bases [lo, hi) of a loaded contig (name or index) -> u8 array, one code per base."""
+        c = contig if isinstance(contig, int) else self.ref_names.index(contig)
+        if c not in self.loaded:
+            raise RemoraError(f"contig {self.ref_names[c]} was not loaded")
+        hi = self.ref_lens[c] if hi is None else int(hi)
+        out = np.zeros(max(hi - int(lo), 1), np.uint8)
+        self._L.check(self._lib.rmr_ref_genome_read(self.h, c, int(lo), hi, out.ctypes.data_as(ctypes.c_void_p)))
+        return out[: max(hi - int(lo), 0)]
+
+    def close(self):
+        if self.h:
+            self._lib.rmr_ref_genome_destroy(self.h)
+            self.h = ctypes.c_void_p()
+            RefGenome.n_open -= 1
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _pileup_ref_struct(genome, descriptors, combine_strands):
+    from . import _lib as L
+
+    pr = L.PileupRef()
+    pr.genome, pr.n_motifs, pr.combine = genome.h, len(descriptors), 1 if combine_strands else 0
+    for j, d in enumerate(descriptors):
+        pr.motifs[j].len, pr.motifs[j].focus, pr.motifs[j].mask, pr.motifs[j].rc_mask = d.length, d.focus, d.mask, d.rc_mask
+    return pr
+
+
 class DevicePileup:
     """rmr_pileup_*: the call buffer and the resident per-site table on the device."""
 
@@ -188,9 +440,10 @@ class DevicePileup:
         self.close()
 
 
-def _emit_batch(eng, b, region, k_t, hist, n_cig, n_deltas):
+def _emit_batch(eng, b, region, k_t, hist, n_cig, n_deltas, pref=None):
     """One batch through the emit: the count pass (with the histogram when `hist` is a device tensor), and - k_t not None -
-    the fill pass.  -> (words device tensor or None, calls per record, status per record)."""
+    the fill pass.  `pref`: the rmr_pileup_ref of a run with a reference, or None.  -> (words device tensor or None, calls per
+    record, status per record)."""
     from . import _lib as L
     from .engine import _torch
 
@@ -200,9 +453,11 @@ def _emit_batch(eng, b, region, k_t, hist, n_cig, n_deltas):
     cig_qr = torch.empty((2, max(n_cig, 1)), dtype=torch.int64, device=dev)
     counts = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
     d_status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    L.check(lib.rmr_modbam_call_counts(eng.handle, ctypes.byref(b), region[0], region[1], region[2], ords.data_ptr(), cig_qr[0].data_ptr(),
-                                       cig_qr[1].data_ptr(), counts.data_ptr(), d_status.data_ptr(),
-                                       hist.data_ptr() if hist is not None else None))
+    with_ref = () if pref is None else (ctypes.byref(pref),)
+    call_counts, call_fill = ((lib.rmr_modbam_call_counts, lib.rmr_modbam_call_fill) if pref is None else
+                              (lib.rmr_modbam_call_counts_ref, lib.rmr_modbam_call_fill_ref))
+    L.check(call_counts(eng.handle, ctypes.byref(b), *with_ref, region[0], region[1], region[2], ords.data_ptr(), cig_qr[0].data_ptr(),
+                        cig_qr[1].data_ptr(), counts.data_ptr(), d_status.data_ptr(), hist.data_ptr() if hist is not None else None))
     eng.synchronize()
     h_counts, h_status = counts[:n].cpu().numpy(), d_status[:n].cpu().numpy()
     words = None
@@ -212,25 +467,26 @@ def _emit_batch(eng, b, region, k_t, hist, n_cig, n_deltas):
         np.cumsum(h_counts, out=out_off[1:])
         d_off = torch.from_numpy(out_off).to(dev)
         words = torch.empty(total, dtype=torch.int64, device=dev)
-        L.check(lib.rmr_modbam_call_fill(eng.handle, ctypes.byref(b), region[0], region[1], region[2], int(k_t), ords.data_ptr(),
-                                         cig_qr[0].data_ptr(), cig_qr[1].data_ptr(), d_status.data_ptr(), d_off.data_ptr(), words.data_ptr()))
+        L.check(call_fill(eng.handle, ctypes.byref(b), *with_ref, region[0], region[1], region[2], int(k_t), ords.data_ptr(),
+                          cig_qr[0].data_ptr(), cig_qr[1].data_ptr(), d_status.data_ptr(), d_off.data_ptr(), words.data_ptr()))
         eng.synchronize()  # the inputs and the workspaces may go once the kernel is through
     return words, h_counts, h_status
 
 
 def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_FILT, region=None, device=None, batch=512, buffer_calls=None,
-                   device_gib=DEFAULT_DEVICE_GIB):
+                   device_gib=DEFAULT_DEVICE_GIB, ref=None, motifs=None, combine_strands=False):
     """The per-site counts of the modified-base calls of `bams` (one path or several, piled into one table) -> PileupTable.
     `alphabet`: the canonical base followed by 1 to 7 single-letter modified-base codes.  The threshold: either
     `filter_threshold` T (k_T = ceil(512 T); give pct_filt=None with it) or `pct_filt` P - then a first pass over the input
     builds the histogram of the calls' confidence and k_T filters P percent of the calls, or fewer given ties.  `region`:
     "ctg" or "ctg:start-end", 0-based half-open.  `buffer_calls`: the capacity of the device call buffer in calls; by default
-    what `device_gib` GiB (capped at half the free device memory) hold.  Everything that is refused is refused before
-    anything is launched; RemoraError when no call is kept."""
-    from .engine import _torch, get_engine
-    from .io import _readahead, iter_bam_raw_batches
-    from .validate import modbam_device_batch, tokenise_mod_tags, warn_ignored_entries
-
+    what `device_gib` GiB (capped at half the free device memory) hold.
+    `ref`: a reference FASTA path, or a RefGenome loaded before (reused, left open); with it `motifs`, 1 to 4 (motif, focus)
+    whose focus base is the canonical base: a call is kept only where the reference shows one of them around its position (on
+    '-' its reverse complement), and the percentile is taken over those calls.  Loaded are the header's contigs, with a region
+    only the region's.  `combine_strands` (every motif its own reverse complement): a '-' call is written at the '+' position
+    of its motif, one row per motif site; the region is asked of the position written.
+    Everything that is refused is refused before any pileup launch; RemoraError when no call is kept."""
     bams = [bams] if isinstance(bams, (str, bytes)) or hasattr(bams, "__fspath__") else list(bams)
     if not bams:
         raise RemoraError("pileup_modbams needs at least one BAM")
@@ -239,10 +495,14 @@ def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_F
     if filter_threshold is None and pct_filt is None:
         pct_filt = DEFAULT_PCT_FILT
     alphabet = check_alphabet(alphabet)
-    mods, n_alpha = alphabet[1:], len(alphabet)
     k_t = threshold_k(filter_threshold) if filter_threshold is not None else None
     if k_t is None:
         percentile_k([0] * N_BINS, pct_filt)  # the range check
+    if ref is None and (motifs or combine_strands):
+        raise RemoraError(("--motif" if motifs else "--combine-strands") + " needs --ref: the motif is looked up in the reference FASTA")
+    if ref is not None and not motifs:
+        raise RemoraError("--ref needs a motif: give --motif MOTIF FOCUS or --cpg")
+    descriptors = check_pileup_motifs(motifs, alphabet[0], combine_strands) if ref is not None else None
     dicts = [bam_reference_dict(p) for p in bams]
     check_reference_dicts(bams, dicts)
     ref_names, ref_lens = [d[0] for d in dicts[0]], [d[1] for d in dicts[0]]
@@ -253,6 +513,33 @@ def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_F
     if buffer_calls is None and not device_gib > 0:
         raise RemoraError("--pileup-device-gib must be positive")
 
+    genome = pref = None
+    if isinstance(ref, RefGenome):
+        genome = ref
+        if not genome.h or genome.ref_names != ref_names or genome.ref_lens != [int(n) for n in ref_lens]:
+            raise RemoraError(f"the RefGenome of {genome.path} is closed or was loaded for another reference dictionary than that of {bams[0]}")
+        missing = [ref_names[c] for c in ([reg[0]] if reg[0] >= 0 else range(len(ref_names))) if c not in genome.loaded]
+        if missing:
+            raise RemoraError(f"the RefGenome of {genome.path} was loaded without contig {missing[0]}")
+    elif ref is not None:  # refused here, before any pileup launch: what the FASTA lacks, and what the device finds wrong in it
+        genome = RefGenome.from_fasta(ref, ref_names, ref_lens, device=device, contigs=[reg[0]] if reg[0] >= 0 else None)
+    try:
+        if genome is not None:
+            pref = _pileup_ref_struct(genome, descriptors, combine_strands)
+        return _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens, device, batch, buffer_calls, device_gib, genome, pref,
+                           bool(combine_strands))
+    finally:
+        if genome is not None and genome is not ref:
+            genome.close()
+
+
+def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens, device, batch, buffer_calls, device_gib, genome, pref, combined):
+    """pileup_modbams once its arguments are checked and the reference is on the device."""
+    from .engine import _torch, get_engine
+    from .io import _readahead, iter_bam_raw_batches
+    from .validate import modbam_device_batch, tokenise_mod_tags, warn_ignored_entries
+
+    mods, n_alpha = alphabet[1:], len(alphabet)
     torch = _torch()
     eng = get_engine(device)
     dev = eng.torch_device
@@ -278,7 +565,7 @@ def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_F
                 warn_ignored_entries(tok[4], alphabet, warn, MOD_NOT_IN_ALPHABET)
                 buf, b = modbam_device_batch(dev, mods, rb.seq, rb.seq_off, rb.cigar, rb.cigar_off, rb.flag, rb.ref_id, rb.pos, rb.has, tok)
                 b.n_refs = len(ref_names)
-                words, h_counts, h_status = _emit_batch(eng, b, reg, k_fill, hist, int(np.asarray(rb.cigar).size), int(tok[5].size))
+                words, h_counts, h_status = _emit_batch(eng, b, reg, k_fill, hist, int(np.asarray(rb.cigar).size), int(tok[5].size), pref)
                 del buf
                 if words is not None:
                     pile.add(words, words.numel())
@@ -294,6 +581,7 @@ def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_F
         return n_kept
 
     no_calls = (f"No modified-base call of {alphabet[1:]} on an aligned base" + (f" inside {region}" if region is not None else "") +
+                (" on a motif of the reference" if genome is not None else "") +
                 f" in {', '.join(map(str, bams))}.")
     h_hist = None
     if k_t is None:  # the percentile needs every call's confidence first: one pass that emits no rows
@@ -315,11 +603,13 @@ def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_F
         if n_calls != n_kept:
             raise RemoraError(f"pileup: {n_calls} calls reached the table, the records hold {n_kept}")
         keys, counts = pile.read(n_sites)
+    if genome is not None:
+        peak += genome.device_bytes
     LOGGER.info(f"{n_calls} calls on {n_sites} sites; {n_flushes} flushes, {peak / 2**20:.1f} MiB of device memory at the peak")
     return PileupTable(ref_names=ref_names, ref_id=(keys >> np.uint64(32)).astype(np.int32),
                        pos=((keys >> np.uint64(1)) & np.uint64(0x7FFFFFFF)).astype(np.int64), strand=(keys & np.uint64(1)).astype(np.uint8),
                        counts=counts.astype(np.int64), alphabet=alphabet, threshold_k=int(k_t), n_calls=n_calls, n_flushes=n_flushes,
-                       peak_device_bytes=peak, hist=None if h_hist is None else h_hist.astype(np.int64))
+                       peak_device_bytes=peak, hist=None if h_hist is None else h_hist.astype(np.int64), combined=combined)
 
 
 def _finish(pile, ref_names):
@@ -338,6 +628,7 @@ def write_bedmethyl(table, path, min_coverage=1):
     chrom pos pos+1 code min(N_valid, 1000) strand pos pos+1 255,0,0 N_valid pct, pct = 100 N_mod / N_valid to two decimals.
     Rows: contigs in header order, then position, then + before -, then the codes in alphabet order.  Returns the rows written."""
     mods = list(table.alphabet[1:])
+    combined = bool(getattr(table, "combined", False))
     valid = table.counts[:, :-1].sum(axis=1)
     keep = np.nonzero(valid >= max(int(min_coverage), 1))[0]
     n_rows = 0
@@ -347,7 +638,7 @@ def write_bedmethyl(table, path, min_coverage=1):
             idx = keep[lo : lo + 65536]
             for rid, pos, st, nv, row in zip(table.ref_id[idx].tolist(), table.pos[idx].tolist(), table.strand[idx].tolist(), valid[idx].tolist(),
                                              table.counts[idx].tolist()):
-                name, sc = table.ref_names[rid], "-" if st else "+"
+                name, sc = table.ref_names[rid], "." if combined else "-" if st else "+"
                 for j, code in enumerate(mods):
                     lines.append(f"{name}\t{pos}\t{pos + 1}\t{code}\t{min(nv, 1000)}\t{sc}\t{pos}\t{pos + 1}\t255,0,0\t{nv}\t"
                                  f"{100 * row[1 + j] / nv:.2f}\n")
@@ -358,11 +649,12 @@ def write_bedmethyl(table, path, min_coverage=1):
 
 def write_counts(table, path):
     """TSV with the header chrom start strand N_<canonical> N_<code>... N_fail: one row per site that has a kept call."""
+    combined = bool(getattr(table, "combined", False))
     with open(path, "w") as fh:
         fh.write("\t".join(["chrom", "start", "strand"] + [f"N_{a}" for a in table.alphabet] + ["N_fail"]) + "\n")
         for lo in range(0, table.pos.size, 65536):
             sl = slice(lo, lo + 65536)
-            fh.write("".join(f"{table.ref_names[rid]}\t{pos}\t{'-' if st else '+'}\t" + "\t".join(map(str, row)) + "\n"
+            fh.write("".join(f"{table.ref_names[rid]}\t{pos}\t{'.' if combined else '-' if st else '+'}\t" + "\t".join(map(str, row)) + "\n"
                              for rid, pos, st, row in zip(table.ref_id[sl].tolist(), table.pos[sl].tolist(), table.strand[sl].tolist(),
                                                           table.counts[sl].tolist())))
     return int(table.pos.size)

@@ -4,7 +4,9 @@
 # rmr_ref_to_signal on random and hostile CIGARs, the batch forms of round 5 (rmr_ref_anchor_batch, rmr_orient_bases), the
 # reference-anchor composition for either signal direction (rmr_ref_anchor_batch_dir against a scalar restatement), the
 # set-order restatement of csrc/pyset_order.c and the MM / ML tokeniser of `validate from_modbams` on grammatical, truncated and
-# mutated tag regions.  From the repository root:
+# mutated tag regions, and the FASTA packing arithmetic of `analyze pileup_modbams --ref` (the piece plan of rmr_ref_genome_load and
+# the per-thread code of the pack kernel, csrc/rmr_ref_pack.h) on contigs at random line widths with planted violations.
+# From the repository root:
 #   bash tools/fuzz/run.sh
 set -e
 cd "$(dirname "$0")"
@@ -15,6 +17,7 @@ g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -pthread
 g++ -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=undefined -pthread -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -I../../include -o /tmp/rmr_reverse_anchor_asan reverse_anchor_asan.cpp
 gcc -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -pthread -o /tmp/rmr_setorder_asan setorder_asan.c ../../remora_amd/csrc/pyset_order.c
 g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -pthread -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -I../../include -o /tmp/rmr_mod_tags_asan mod_tags_asan.cpp
+g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -o /tmp/rmr_ref_pack_asan ref_pack_asan.cpp
 /tmp/rmr_inflate_asan
 /tmp/rmr_bgzf_asan
 /tmp/rmr_r2s_asan
@@ -22,3 +25,4 @@ g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -pthread
 /tmp/rmr_reverse_anchor_asan
 /tmp/rmr_setorder_asan
 /tmp/rmr_mod_tags_asan
+/tmp/rmr_ref_pack_asan
