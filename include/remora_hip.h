@@ -338,6 +338,19 @@ int rmr_mod_tags_sizes(int64_t n, const uint8_t *raw, const int64_t *raw_off, co
 int rmr_mod_tags_fill(int64_t n, const uint8_t *raw, const int64_t *raw_off, const int64_t *tags_off, const int32_t *status,
                       const int64_t *ent_off, const int64_t *delta_off, const int64_t *ml_off, rmr_mod_entry *entries, int32_t *deltas,
                       uint8_t *ml, int threads);
+/* One aux field per record (host), for the partition tag of `analyze pileup_modbams`.
+ * rmr_bam_aux_values: for the records as above, the first aux field named tag[0] tag[1] ([A-Za-z][A-Za-z0-9]):
+ * kind[r] = RMR_AUX_ABSENT; RMR_AUX_INT with value[r] the number, for the types c C s S i I; RMR_AUX_CHAR with value[r] the
+ * byte, for type A; RMR_AUX_OTHER_TYPE with value[r] the type letter, for Z H B f; RMR_AUX_UNWALKABLE (value 0) when the
+ * fields of the aux region do not tile it - the regions rmr_mod_tags_sizes gives status 2 for their framing.  Nothing at or
+ * behind raw_off[r + 1] is read. */
+#define RMR_AUX_ABSENT 0
+#define RMR_AUX_INT 1
+#define RMR_AUX_CHAR 2
+#define RMR_AUX_OTHER_TYPE 3
+#define RMR_AUX_UNWALKABLE 4
+int rmr_bam_aux_values(int64_t n, const uint8_t *raw, const int64_t *raw_off, const int64_t *tags_off, const char *tag, int64_t *value,
+                       uint8_t *kind, int threads);
 
 /* The site join (GPU; DEVICE pointers only, asynchronous on the engine's stream).
  * replaces: validate.check_mod_strand + validate.parse_mod_read for a batch of records (src/remora/validate.py:296-446):
@@ -479,6 +492,16 @@ int rmr_pileup_add(rmr_pileup *p, const uint64_t *words, int64_t n);
 int rmr_pileup_finish(rmr_pileup *p, int64_t *n_sites, int64_t *n_calls, int64_t *n_flushes, int64_t *peak_device_bytes);
 int rmr_pileup_read(rmr_pileup *p, uint64_t *keys, uint32_t *counts);
 void rmr_pileup_destroy(rmr_pileup *p);
+/* A partition field above the contig index (GPU; DEVICE pointers, asynchronous on the engine's stream), for per-haplotype
+ * tables.  rmr_pileup_stamp_partition: between rmr_modbam_call_fill and rmr_pileup_add,
+ *     words[i] |= (uint64_t)part[r] << shift     for out_off[r] <= i < out_off[r + 1],   r = 0 .. n_records - 1,
+ * with shift = 36 + the bits the contig index takes; a pileup created for n_contigs << (bits of the field) contigs then sorts
+ * and counts the partitions apart, and the ref_id of a key it returns is part << (shift - 36) | ref_id.  part: i32[n_records],
+ * 0 <= part[r] < 2^(60 - shift) (the caller's to keep); a record with part 0 or without words writes nothing.  out_off as
+ * rmr_modbam_call_fill took it; the n_words of `words` bound every store.  n_records 0 launches nothing.  Refused before
+ * the launch: n_records or n_words negative, a shift outside 36 .. 59, NULL pointers. */
+int rmr_pileup_stamp_partition(rmr_engine *e, int64_t n_records, const int64_t *out_off, const int32_t *part, int shift, uint64_t *words,
+                               int64_t n_words);
 
 /* The simplex-to-duplex alignment of duplex calling (GPU; HOST pointers, synchronous).
  * replaces: duplex_utils.parasail_align + trim_parasail_alignment, src/remora/duplex_utils.py:22-115, i.e.

@@ -394,11 +394,23 @@ def _estimate_kmer_levels(args):
     return 0
 
 
+def _partition_tag(text):
+    """argparse type of --partition-tag: the refusal of a malformed tag name as the parser's error."""
+    import argparse
+
+    from .pileup import check_partition_tag
+
+    try:
+        return check_partition_tag(text)
+    except RemoraError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
 def _pileup_modbams(args):
     """`analyze pileup_modbams` (no counterpart in the reference's command line): per-site modified-base counts, bedMethyl."""
     import logging
 
-    from .pileup import check_ref_arguments, pileup_modbams, write_bedmethyl, write_counts
+    from .pileup import check_ref_arguments, partition_file_name, pileup_modbams, write_bedmethyl, write_counts, write_partitioned
 
     log = logging.getLogger("Remora")
     log.setLevel(logging.INFO)
@@ -411,8 +423,16 @@ def _pileup_modbams(args):
     motifs = check_ref_arguments(args.ref, args.motif, args.cpg, args.combine_strands, args.canonical_base)
     table = pileup_modbams(args.bam, [args.canonical_base] + list(args.mod_bases), filter_threshold=args.filter_threshold,
                            pct_filt=args.pct_filt, region=args.region, device=args.device, batch=args.reads_per_batch,
-                           device_gib=args.pileup_device_gib, ref=args.ref, motifs=motifs, combine_strands=args.combine_strands)
+                           device_gib=args.pileup_device_gib, ref=args.ref, motifs=motifs, combine_strands=args.combine_strands,
+                           partition_tag=args.partition_tag)
     # the files are written only now: a run that keeps no call leaves none behind
+    if args.partition_tag is not None:  # --out-bed and --counts-filename are templates: one file per partition that has a row
+        rows = write_partitioned(table, args.out_bed, args.counts_filename, min_coverage=args.min_coverage)
+        log.info(f"bedMethyl rows per {args.partition_tag}: " + ", ".join(f"{label}: {n}" for label, n in rows.items()) +
+                 f" ({table.pos.size} rows of partition and site) -> " +
+                 ", ".join(partition_file_name(args.out_bed, args.partition_tag, label) for label in rows))
+        log.info("Done")
+        return 0
     n_rows = write_bedmethyl(table, args.out_bed, min_coverage=args.min_coverage)
     if args.counts_filename is not None:
         write_counts(table, args.counts_filename)
@@ -812,6 +832,11 @@ def build_parser():
     pm.add_argument("--combine-strands", action="store_true",
                     help="one row per motif site with the calls of both strands, at the '+' position of the motif, strand column '.'; "
                          "every motif must be its own reverse complement (CG, GC, GATC)")
+    pm.add_argument("--partition-tag", metavar="TAG", type=_partition_tag,
+                    help="one table per value of this aux tag of the records (HP: per haplotype of phased reads), in one run and with "
+                         "the one threshold of the whole input: --out-bed and --counts-filename become templates, s.bed -> s.TAG_1.bed, "
+                         "s.TAG_2.bed, ..., s.ungrouped.bed for the records without the tag; integer (c C s S i I) or character (A) "
+                         "values, up to 255 distinct ones")
     pm.add_argument("--pileup-device-gib", type=float, default=8.0,
                     help="GiB of GPU memory for the call buffer and its sort (capped at half of what is free); the per-site table "
                          "comes on top, 8 + 4 (classes + 1) bytes per distinct site")

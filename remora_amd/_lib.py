@@ -63,6 +63,7 @@ class PileupRef(ctypes.Structure):
     _fields_ = [("genome", c_vp), ("n_motifs", ctypes.c_int32), ("combine", ctypes.c_int32), ("motifs", PileupMotif * 4)]
 
 
+AUX_ABSENT, AUX_INT, AUX_CHAR, AUX_OTHER_TYPE, AUX_UNWALKABLE = range(5)  # RMR_AUX_* of include/remora_hip.h
 MOD_MAX_CODES = 16
 # rmr_mod_entry of include/remora_hip.h as a numpy record (48 bytes)
 MOD_ENTRY_FIELDS = [("delta_off", "<i8"), ("ml_off", "<i8"), ("n_deltas", "<i4"), ("n_codes", "<i4"), ("chebi", "<i4"), ("base", "S1"),
@@ -131,6 +132,7 @@ SIGNATURES = {
     "rmr_records_with_mod_tags_ref": (c_int, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "rmr_mod_tags_sizes": (c_int, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int]),
     "rmr_mod_tags_fill": (c_int, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int]),
+    "rmr_bam_aux_values": (c_int, [c_i64, c_vp, c_vp, c_vp, ctypes.c_char_p, c_vp, c_vp, c_int]),
     "rmr_modbam_site_counts": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rmr_modbam_site_fill": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rmr_modbam_call_counts": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), ctypes.c_int32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
@@ -149,6 +151,7 @@ SIGNATURES = {
     "rmr_pileup_finish": (c_int, [c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "rmr_pileup_read": (c_int, [c_vp, c_vp, c_vp]),
     "rmr_pileup_destroy": (None, [c_vp]),
+    "rmr_pileup_stamp_partition": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_i64]),
     "rmr_duplex_align": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64)]),
     "rmr_duplex_align_mode": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64),
                                       ctypes.POINTER(c_i64)]),

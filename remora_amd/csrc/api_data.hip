@@ -721,6 +721,17 @@ int rmr_pileup_read(rmr_pileup *p, uint64_t *keys, uint32_t *counts) {
     return 0;
 }
 
+int rmr_pileup_stamp_partition(rmr_engine *e, int64_t n_records, const int64_t *out_off, const int32_t *part, int shift, uint64_t *words,
+                               int64_t n_words) {
+    if (!e || !out_off || !part || !words) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if (n_records < 0 || n_records > (int64_t)1 << 30 || n_words < 0) RMR_FAIL(RMR_ERR_INVALID, "bad n_records or n_words");
+    if (shift < 36 || shift > 59) RMR_FAIL(RMR_ERR_INVALID, "the partition field starts at bit 36 to 59 of a site word, got %d", shift);
+    if (n_records == 0) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    return launch_pileup_stamp(e, n_records, out_off, part, shift, words, n_words);
+}
+
 void rmr_pileup_destroy(rmr_pileup *p) {
     if (!p) return;
     (void)hipSetDevice(p->eng->device);

@@ -125,6 +125,18 @@ __global__ __launch_bounds__(PU_THREADS) void merge_new_kernel(const uint64_t *_
     for (int c = 0; c < ncol; ++c) o_counts[d * ncol + c] = counts[j * ncol + c];
 }
 
+// One block per record, its threads striding over the record's words like the emit's: the partition id into the bits above
+// the contig index.  Records of partition 0 and records without words store nothing; no store at or behind words[n_words].
+__global__ __launch_bounds__(PU_THREADS) void stamp_partition_kernel(const int64_t *__restrict__ out_off, const int32_t *__restrict__ part, int shift,
+                                                                      uint64_t *__restrict__ words, int64_t n_words) {
+    const int64_t r = blockIdx.x;
+    const int32_t id = part[r];
+    if (id <= 0) return;
+    const int64_t lo = out_off[r] > 0 ? out_off[r] : 0, hi = out_off[r + 1] < n_words ? out_off[r + 1] : n_words;
+    const uint64_t field = (uint64_t)(uint32_t)id << shift;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += PU_THREADS) words[i] |= field;
+}
+
 // rocPRIM's scratch for the sort and the scan of n entries, whichever is larger
 int scratch_bytes(int64_t n, int end_bit, size_t *bytes) {
     size_t sort_b = 0, scan_b = 0;
@@ -163,6 +175,15 @@ int launch_modbam_calls(rmr_engine *e, const rmr_modbam_batch &b, const PileupEm
     else
         hipLaunchKernelGGL(modbam_call_kernel<false>, dim3((unsigned)b.n_records), dim3(MB_THREADS), 0, e->stream, b, pe, ords, cig_q, cig_r, counts,
                            status, out_off);
+    RMR_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_pileup_stamp(rmr_engine *e, int64_t n_records, const int64_t *out_off, const int32_t *part, int shift, uint64_t *words,
+                        int64_t n_words) {
+    if (n_records <= 0) return 0;
+    ProfScope ps(e, K_PILEUP_STAMP);
+    hipLaunchKernelGGL(stamp_partition_kernel, dim3((unsigned)n_records), dim3(PU_THREADS), 0, e->stream, out_off, part, shift, words, n_words);
     RMR_HIP(hipGetLastError());
     return 0;
 }

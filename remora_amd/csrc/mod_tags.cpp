@@ -13,6 +13,8 @@
 //                             delta array and the ML bytes (what htslib's bam_parse_basemod reads below pysam's
 //                             AlignedSegment.modified_bases, src/remora/validate.py:326, :420); the walk along the bases is
 //                             the GPU's (k_modbam.hip)
+//   rmr_bam_aux_values      : one aux field's integer or character value per stored record, for the partition tag of
+//                             `analyze pileup_modbams`
 #include "../../include/remora_hip.h"
 #include "rmr_internal.h"
 
@@ -435,6 +437,73 @@ int rmr_mod_tags_fill(int64_t n, const uint8_t *raw, const int64_t *raw_off, con
         }
     });
     if (n > 0 && bad[0] >= 0) RMR_FAIL(RMR_ERR_INVALID, "record %lld: offsets do not match what rmr_mod_tags_sizes counted", (long long)bad[0]);
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- one aux field's value per record ----------------------------------------------------------------------------------
+namespace {
+
+// The value of the first aux field named tag[0] tag[1] in [tags, end): the kind (the RMR_AUX_* of include/remora_hip.h) and,
+// for an integer or a character, the value; for a field of another type, its type letter.  The whole region is walked, so
+// that RMR_AUX_UNWALKABLE is said of exactly the regions the MM / ML tokeniser gives status 2 for their framing; no byte at or
+// behind `end` is read.
+int aux_value(const uint8_t *tags, const uint8_t *end, const char *tag, int64_t *value) {
+    int kind = RMR_AUX_ABSENT;
+    *value = 0;
+    const uint8_t *p = tags;
+    while (end - p >= 3) {
+        const char t = (char)p[2];
+        const uint8_t *v = p + 3;
+        const int64_t sz = value_size(t, v, end);
+        if (sz < 0 || sz > end - v) return *value = 0, RMR_AUX_UNWALKABLE;
+        if (kind == RMR_AUX_ABSENT && p[0] == (uint8_t)tag[0] && p[1] == (uint8_t)tag[1]) {
+            int8_t i8; int16_t i16; uint16_t u16; int32_t i32; uint32_t u32;
+            kind = RMR_AUX_INT;
+            switch (t) {
+                case 'c': memcpy(&i8, v, 1); *value = i8; break;
+                case 'C': *value = v[0]; break;
+                case 's': memcpy(&i16, v, 2); *value = i16; break;
+                case 'S': memcpy(&u16, v, 2); *value = u16; break;
+                case 'i': memcpy(&i32, v, 4); *value = i32; break;
+                case 'I': memcpy(&u32, v, 4); *value = u32; break;
+                case 'A': kind = RMR_AUX_CHAR; *value = v[0]; break;
+                default: kind = RMR_AUX_OTHER_TYPE; *value = (uint8_t)t; break;
+            }
+        }
+        p = v + sz;
+    }
+    if (p != end) return *value = 0, RMR_AUX_UNWALKABLE;
+    return kind;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rmr_bam_aux_values(int64_t n, const uint8_t *raw, const int64_t *raw_off, const int64_t *tags_off, const char *tag, int64_t *value,
+                       uint8_t *kind, int threads) {
+    if (n < 0 || !tag || (n > 0 && (!raw_off || !tags_off || !value || !kind))) RMR_FAIL(RMR_ERR_INVALID, "bad argument");
+    const bool letter = (tag[0] >= 'A' && tag[0] <= 'Z') || (tag[0] >= 'a' && tag[0] <= 'z');
+    if (!letter || !((tag[1] >= 'A' && tag[1] <= 'Z') || (tag[1] >= 'a' && tag[1] <= 'z') || (tag[1] >= '0' && tag[1] <= '9')))
+        RMR_FAIL(RMR_ERR_INVALID, "an aux tag is two characters, [A-Za-z][A-Za-z0-9]");
+    for (int64_t r = 0; r < n; ++r)
+        if (raw_off[r + 1] < raw_off[r] || raw_off[r] < 0 || (raw_off[r + 1] > raw_off[r] && !raw))
+            RMR_FAIL(RMR_ERR_INVALID, "record %lld: bad offsets", (long long)r);
+    const char t0 = tag[0], t1 = tag[1];
+    over_records(n, threads, [=](int64_t r0, int64_t r1) {
+        const char tg[2] = {t0, t1};
+        for (int64_t r = r0; r < r1; ++r) {
+            const int64_t len = raw_off[r + 1] - raw_off[r], to = tags_off[r];
+            if (to < 0 || to > len) {
+                value[r] = 0, kind[r] = RMR_AUX_UNWALKABLE;
+                continue;
+            }
+            const uint8_t *rec = len ? raw + raw_off[r] : nullptr;
+            kind[r] = (uint8_t)aux_value(rec + to, rec + len, tg, value + r);
+        }
+    });
     return 0;
 }
 

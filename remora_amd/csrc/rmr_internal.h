@@ -88,6 +88,7 @@ enum KernelId {
     K_PILEUP_EMIT,   // the walk that writes site words (or the confidence histogram)
     K_PILEUP_FLUSH,  // one flush: the radix sort, the run counts and the merge into the table
     K_REF_GENOME_PACK,  // one piece of a contig's FASTA text into nibbles, verified (k_ref_genome.hip)
+    K_PILEUP_STAMP,  // the partition id into the words of a batch (k_pileup.hip)
     K_NUM
 };
 const char *kernel_name(int id);
@@ -273,6 +274,7 @@ int launch_modbam_calls_ref(rmr_engine *e, const rmr_modbam_batch &b, const Pile
 int pileup_alloc(rmr_pileup *p);
 int pileup_append(rmr_pileup *p, const uint64_t *words, int64_t n);
 int pileup_flush(rmr_pileup *p);
+int launch_pileup_stamp(rmr_engine *e, int64_t n_records, const int64_t *out_off, const int32_t *part, int shift, uint64_t *words, int64_t n_words);
 
 // k_read_index.hip: keys u8[n][16], values i64[n] on the host (n >= 1) -> the table of `ix`;  names / name_off / out on the
 // device, the text of name i at names[name_off[i] - base ...]

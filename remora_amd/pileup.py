@@ -16,7 +16,12 @@ passes when kmax >= k_T.
 With a reference FASTA (`ref`, `motifs`) the genome is packed into nibbles on the device once (RefGenome, rmr_ref_genome_*,
 csrc/k_ref_genome.hip) and the emit keeps a call only where the reference shows one of the motifs around it; with
 `combine_strands` a '-' call is written at the '+' position of its motif, so that a CpG is one row (DESIGN.md section 4,
-"Pileup: the reference")."""
+"Pileup: the reference").
+
+With `partition_tag` (HP of phased reads) the records are piled per value of that aux tag in the same run: the value is read
+on the host (rmr_bam_aux_values), given an id, and the id is stamped into the free bits above the contig index of the
+record's words (rmr_pileup_stamp_partition) - the sort and the table then keep the partitions apart, under the one threshold
+of the whole input ("Pileup: the partition field")."""
 import ctypes
 import logging
 import mmap
@@ -46,14 +51,141 @@ DEFAULT_PIECE_BYTES = 64 << 20
 # a base's code: the IUPAC set as a mask, A 1, C 2, G 4, T 8 (the complement of a code is its four bits reversed)
 IUPAC_MASK = {"A": 1, "C": 2, "G": 4, "T": 8, "U": 8, "R": 5, "Y": 10, "S": 6, "W": 9, "K": 12, "M": 3, "B": 14, "D": 13, "H": 11, "V": 7, "N": 15}
 
-PileupTable = namedtuple("PileupTable", ("ref_names", "ref_id", "pos", "strand", "counts", "alphabet", "threshold_k", "n_calls", "n_flushes",
-                                         "peak_device_bytes", "hist", "combined"), defaults=(False,))
-PileupTable.__doc__ = """One row per site with a kept call, ordered by (ref_id, pos, strand): ref_id i32[n], pos i64[n], strand u8[n]
-(0 '+', 1 '-'), counts i64[n, len(alphabet) + 1] (canonical, the modified bases in alphabet order, fail).  threshold_k: k_T;
-n_calls: kept calls; n_flushes: flushes of the device call buffer; peak_device_bytes: the pileup's device memory at its
-peak (the reference genome included); hist: i64[513], the calls per kmax, when the threshold came from a percentile, else
-None; combined: the strands were combined - every row stands on '+' in `strand` and belongs to both strands (the writers print
-'.')."""
+_PileupFields = namedtuple("PileupTable", ("ref_names", "ref_id", "pos", "strand", "counts", "alphabet", "threshold_k", "n_calls", "n_flushes",
+                                           "peak_device_bytes", "hist", "combined"), defaults=(False,))
+
+
+class PileupTable(_PileupFields):
+    """One row per site with a kept call, ordered by (ref_id, pos, strand): ref_id i32[n], pos i64[n], strand u8[n]
+    (0 '+', 1 '-'), counts i64[n, len(alphabet) + 1] (canonical, the modified bases in alphabet order, fail).  threshold_k: k_T;
+    n_calls: kept calls; n_flushes: flushes of the device call buffer; peak_device_bytes: the pileup's device memory at its
+    peak (the reference genome included); hist: i64[513], the calls per kmax, when the threshold came from a percentile, else
+    None; combined: the strands were combined - every row stands on '+' in `strand` and belongs to both strands (the writers
+    print '.').
+    A run with `partition_tag` has three more, keyword arguments and attributes beside the tuple's twelve fields (None
+    otherwise, and in what _replace returns): one row per (partition, site), partition i32[n] an index into partition_labels -
+    the labels that have a row, integers ascending, then characters by code, then "ungrouped" - and the rows ordered by
+    (partition, ref_id, pos, strand); partition_tag names the tag.  partition_tables splits it into plain tables."""
+
+    partition = partition_labels = partition_tag = None
+
+    def __new__(cls, *args, partition=None, partition_labels=None, partition_tag=None, **fields):
+        self = super().__new__(cls, *args, **fields)
+        self.partition, self.partition_labels, self.partition_tag = partition, partition_labels, partition_tag
+        return self
+
+
+# ---- the partition tag -----------------------------------------------------------------------------------------------------
+CONTIG_SHIFT = 36            # the contig index starts at this bit of a site word (include/remora_hip.h)
+MAX_PART_BITS = 8
+UNGROUPED = "ungrouped"
+_UNGROUPED_KEY = (3, 0)      # sorts behind (_lib.AUX_INT, value) and (_lib.AUX_CHAR, code)
+PartitionPlan = namedtuple("PartitionPlan", ("contig_bits", "part_bits", "max_values", "shift", "n_contigs"))
+PartitionPlan.__doc__ = """Where the partition id stands in a site word: above the contig_bits of the contig index, part_bits wide (ids 1 ..
+max_values = 2^part_bits - 1; 0 is `ungrouped`), from bit `shift`; n_contigs: what the device pileup is created for."""
+
+
+def check_partition_tag(tag):
+    if not isinstance(tag, str) or re.fullmatch(r"[A-Za-z][A-Za-z0-9]", tag) is None:
+        raise RemoraError(f"--partition-tag is the two characters of an aux tag, [A-Za-z][A-Za-z0-9] (HP for example), got {tag!r}")
+    return tag
+
+
+def partition_bit_plan(n_contigs, tag="the partition tag"):
+    """The 24 bits of a site word's contig field shared between the contig index and the partition id -> PartitionPlan.
+    contig_bits by the rule of rmr_pileup_create (the smallest c with 2^c >= n_contigs), the partition gets the rest, 8 bits
+    at the most; refused when nothing is left."""
+    n_contigs = int(n_contigs)
+    if n_contigs < 1:
+        raise RemoraError("the BAM header has no contig: nothing to pile up on")
+    contig_bits = (n_contigs - 1).bit_length()
+    part_bits = min(MAX_PART_BITS, 24 - contig_bits)
+    if part_bits < 1:
+        raise RemoraError(f"--partition-tag {tag}: the BAM header has {n_contigs} contigs, whose index takes {contig_bits} of the 24 bits of a "
+                          f"site word's contig field: none is left for a partition (up to {1 << 23} contigs leave one)")
+    return PartitionPlan(contig_bits, part_bits, (1 << part_bits) - 1, CONTIG_SHIFT + contig_bits, 1 << (contig_bits + part_bits))
+
+
+def partition_label(key):
+    """(kind, value) -> the label: the decimal of an integer, the character of an `A` value, "ungrouped"."""
+    from . import _lib as L
+
+    kind, value = key
+    return str(int(value)) if kind == L.AUX_INT else chr(int(value)) if kind == L.AUX_CHAR else UNGROUPED
+
+
+def partition_order(keys):
+    """(kind, value) keys in label order: integers ascending numerically, characters by code, `ungrouped` (None) last."""
+    return sorted(_UNGROUPED_KEY if k is None else (int(k[0]), int(k[1])) for k in keys)
+
+
+def read_aux_values(raw, raw_off, tags_off, tag, threads=1):
+    """rmr_bam_aux_values for the records of a batch -> (value i64[n], kind u8[n]).  One thread by default: the aux regions of
+    512 records are walked in 35 us, less than it takes to start more threads."""
+    from . import _lib as L
+
+    lib = L.lib()
+    threads = int(threads)
+    raw_off, tags_off = np.ascontiguousarray(raw_off, np.int64), np.ascontiguousarray(tags_off, np.int64)
+    n = int(tags_off.size)
+    raw_arr = np.frombuffer(raw, np.uint8) if len(raw) else np.zeros(1, np.uint8)
+    value, kind = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.uint8)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    L.check(lib.rmr_bam_aux_values(n, p(raw_arr), p(raw_off), p(tags_off), str(tag).encode("latin-1"), p(value), p(kind), threads))
+    return value[:n], kind[:n]
+
+
+class Partitioner:
+    """The partition ids of a run: 0 is `ungrouped`, a value gets the next id when it is first seen, in either pass - ids are
+    internal, the table is put into label order once it is read.  No Python object per record: np.unique per batch."""
+
+    def __init__(self, tag, plan):
+        self.tag, self.plan, self.ids, self.kind = tag, plan, {}, None
+
+    def _read_name(self, rb, r):
+        return bytes(rb.names[int(rb.name_off[r]) : int(rb.name_off[r + 1])]).rstrip(b"\x00").decode("latin-1")
+
+    def ids_of(self, rb, value, kind, path):
+        """part i32[n] of a batch's records, or the refusal: a tag of a type that is neither an integer nor a character, a tag
+        that is an integer here and a character there, more values than the field holds."""
+        from . import _lib as L
+
+        tag = self.tag
+        other = np.nonzero(kind == L.AUX_OTHER_TYPE)[0]
+        if other.size:
+            r = int(other[0])
+            raise RemoraError(f"--partition-tag {tag}: read {self._read_name(rb, r)} of {path} has {tag} of type {chr(int(value[r]))}; a partition "
+                              "is named by an integer (c C s S i I) or a character (A)")
+        tagged = np.nonzero((kind == L.AUX_INT) | (kind == L.AUX_CHAR))[0]
+        part = np.zeros(kind.size, np.int32)
+        if not tagged.size:
+            return part
+        if self.kind is None:
+            self.kind = int(kind[tagged[0]])
+        odd = tagged[kind[tagged] != self.kind]
+        if odd.size:
+            r = int(odd[0])
+            names = {L.AUX_INT: "an integer", L.AUX_CHAR: "a character"}
+            raise RemoraError(f"--partition-tag {tag}: {tag} is {names[int(kind[r])]} in read {self._read_name(rb, r)} of {path} and "
+                              f"{names[self.kind]} in the records before it; one run takes one kind")
+        uniq, first, inverse = np.unique(value[tagged], return_index=True, return_inverse=True)
+        for j in np.argsort(first, kind="stable").tolist():
+            v = int(uniq[j])
+            if v not in self.ids:
+                if len(self.ids) >= self.plan.max_values:
+                    r = int(tagged[first[j]])
+                    raise RemoraError(f"--partition-tag {tag}: more than {self.plan.max_values} distinct values - {tag} = "
+                                      f"{partition_label((self.kind, v))!r} of read {self._read_name(rb, r)} ({path}) did not fit: beside the "
+                                      f"{self.plan.contig_bits} bits of the contig index a site word has {self.plan.part_bits} bits for the partition")
+                self.ids[v] = len(self.ids) + 1
+        part[tagged] = np.array([self.ids[int(v)] for v in uniq.tolist()], np.int32)[inverse.reshape(-1)]
+        return part
+
+    def key_of_id(self):
+        """{id: (kind, value)}, None for `ungrouped`."""
+        out = {0: None}
+        out.update({i: (self.kind, v) for v, i in self.ids.items()})
+        return out
 
 
 def threshold_k(filter_threshold):
@@ -440,10 +572,11 @@ class DevicePileup:
         self.close()
 
 
-def _emit_batch(eng, b, region, k_t, hist, n_cig, n_deltas, pref=None):
+def _emit_batch(eng, b, region, k_t, hist, n_cig, n_deltas, pref=None, part=None, shift=0):
     """One batch through the emit: the count pass (with the histogram when `hist` is a device tensor), and - k_t not None -
-    the fill pass.  `pref`: the rmr_pileup_ref of a run with a reference, or None.  -> (words device tensor or None, calls per
-    record, status per record)."""
+    the fill pass.  `pref`: the rmr_pileup_ref of a run with a reference, or None.  `part` (i32 per record, a partitioned run):
+    after the fill pass the records' partition ids are stamped into their words from bit `shift`.  -> (words device tensor
+    or None, calls per record, status per record)."""
     from . import _lib as L
     from .engine import _torch
 
@@ -469,12 +602,15 @@ def _emit_batch(eng, b, region, k_t, hist, n_cig, n_deltas, pref=None):
         words = torch.empty(total, dtype=torch.int64, device=dev)
         L.check(call_fill(eng.handle, ctypes.byref(b), *with_ref, region[0], region[1], region[2], int(k_t), ords.data_ptr(),
                           cig_qr[0].data_ptr(), cig_qr[1].data_ptr(), d_status.data_ptr(), d_off.data_ptr(), words.data_ptr()))
+        if part is not None:
+            d_part = torch.from_numpy(np.ascontiguousarray(part, np.int32)).to(dev)
+            L.check(lib.rmr_pileup_stamp_partition(eng.handle, n, d_off.data_ptr(), d_part.data_ptr(), int(shift), words.data_ptr(), total))
         eng.synchronize()  # the inputs and the workspaces may go once the kernel is through
     return words, h_counts, h_status
 
 
 def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_FILT, region=None, device=None, batch=512, buffer_calls=None,
-                   device_gib=DEFAULT_DEVICE_GIB, ref=None, motifs=None, combine_strands=False):
+                   device_gib=DEFAULT_DEVICE_GIB, ref=None, motifs=None, combine_strands=False, partition_tag=None):
     """The per-site counts of the modified-base calls of `bams` (one path or several, piled into one table) -> PileupTable.
     `alphabet`: the canonical base followed by 1 to 7 single-letter modified-base codes.  The threshold: either
     `filter_threshold` T (k_T = ceil(512 T); give pct_filt=None with it) or `pct_filt` P - then a first pass over the input
@@ -486,7 +622,14 @@ def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_F
     '-' its reverse complement), and the percentile is taken over those calls.  Loaded are the header's contigs, with a region
     only the region's.  `combine_strands` (every motif its own reverse complement): a '-' call is written at the '+' position
     of its motif, one row per motif site; the region is asked of the position written.
-    Everything that is refused is refused before any pileup launch; RemoraError when no call is kept."""
+    `partition_tag` (two characters, "HP" for phased reads): one table per value of that aux field in one run - a record
+    belongs to the partition its tag names (an integer of type c C s S i I, or a character of type A), without the tag to
+    `ungrouped`; which calls count, their classes and the threshold (one histogram, one k_T for the whole input) are those of
+    the run without it, and the PileupTable has its three partition fields set (partition_tables, write_partitioned).  The
+    id stands in the bits of a site word the contig index leaves free: 2^part_bits - 1 values, partition_bit_plan.
+    Everything that is refused is refused before any pileup launch; RemoraError when no call is kept.  (What a partition tag
+    is refused for - another type, both kinds in one run, too many values - is known when the batch with that record is read:
+    before any launch for that batch, and before any file is written.)"""
     bams = [bams] if isinstance(bams, (str, bytes)) or hasattr(bams, "__fspath__") else list(bams)
     if not bams:
         raise RemoraError("pileup_modbams needs at least one BAM")
@@ -507,6 +650,7 @@ def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_F
     check_reference_dicts(bams, dicts)
     ref_names, ref_lens = [d[0] for d in dicts[0]], [d[1] for d in dicts[0]]
     check_site_fields(len(ref_names), max(ref_lens, default=0))
+    parts = None if partition_tag is None else Partitioner(check_partition_tag(partition_tag), partition_bit_plan(len(ref_names), partition_tag))
     reg = parse_region(region, ref_names, ref_lens)
     if buffer_calls is not None and not 1 <= int(buffer_calls) < 2**31:
         raise RemoraError(f"buffer_calls is 1 to 2^31 - 1, got {buffer_calls}")
@@ -527,14 +671,16 @@ def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_F
         if genome is not None:
             pref = _pileup_ref_struct(genome, descriptors, combine_strands)
         return _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens, device, batch, buffer_calls, device_gib, genome, pref,
-                           bool(combine_strands))
+                           bool(combine_strands), parts)
     finally:
         if genome is not None and genome is not ref:
             genome.close()
 
 
-def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens, device, batch, buffer_calls, device_gib, genome, pref, combined):
-    """pileup_modbams once its arguments are checked and the reference is on the device."""
+def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens, device, batch, buffer_calls, device_gib, genome, pref, combined,
+                parts=None):
+    """pileup_modbams once its arguments are checked and the reference is on the device.  `parts`: the Partitioner of a run with
+    a partition tag."""
     from .engine import _torch, get_engine
     from .io import _readahead, iter_bam_raw_batches
     from .validate import modbam_device_batch, tokenise_mod_tags, warn_ignored_entries
@@ -559,13 +705,16 @@ def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens,
 
             def tokenised(path=path):  # the reader and the tokeniser of batch k + 1 run beside the GPU work of batch k
                 for rb, _ in iter_bam_raw_batches(path, want_ref=False, batch=int(batch)):
-                    yield rb, tokenise_mod_tags(rb.raw, rb.raw_off, rb.tags_off)
+                    yield rb, tokenise_mod_tags(rb.raw, rb.raw_off, rb.tags_off), (None if parts is None else
+                                                                                   read_aux_values(rb.raw, rb.raw_off, rb.tags_off, parts.tag))
 
-            for rb, tok in _readahead(tokenised(), depth=2):
+            for rb, tok, aux in _readahead(tokenised(), depth=2):
+                part = None if aux is None else parts.ids_of(rb, aux[0], aux[1], path)  # (in both passes: a refusal comes early)
                 warn_ignored_entries(tok[4], alphabet, warn, MOD_NOT_IN_ALPHABET)
                 buf, b = modbam_device_batch(dev, mods, rb.seq, rb.seq_off, rb.cigar, rb.cigar_off, rb.flag, rb.ref_id, rb.pos, rb.has, tok)
                 b.n_refs = len(ref_names)
-                words, h_counts, h_status = _emit_batch(eng, b, reg, k_fill, hist, int(np.asarray(rb.cigar).size), int(tok[5].size), pref)
+                words, h_counts, h_status = _emit_batch(eng, b, reg, k_fill, hist, int(np.asarray(rb.cigar).size), int(tok[5].size), pref, part,
+                                                          0 if parts is None else parts.plan.shift)
                 del buf
                 if words is not None:
                     pile.add(words, words.numel())
@@ -595,9 +744,10 @@ def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens,
             raise RemoraError(f"pileup: the histogram holds {int(h_hist.sum())} calls, the records {n_kept}")
         k_t = percentile_k(h_hist, pct_filt)
         LOGGER.info(f"--pct-filt {pct_filt:g}: {int(h_hist[:k_t].sum())} of {n_kept} calls fail at k_T = {k_t} (probability {k_t / 512:.6g})")
-    with DevicePileup(eng, len(ref_names), max(ref_lens), n_alpha, buffer_calls) as pile:
+    # a partitioned run: the id stands above the contig index, and the sort covers its bits too
+    with DevicePileup(eng, len(ref_names) if parts is None else parts.plan.n_contigs, max(ref_lens), n_alpha, buffer_calls) as pile:
         n_kept = one_pass(k_t, None, pile, h_hist is None)
-        n_sites, n_calls, n_flushes, peak = _finish(pile, ref_names)
+        n_sites, n_calls, n_flushes, peak = _finish(pile, ref_names, parts)
         if n_calls < 1:
             raise RemoraError(no_calls)
         if n_calls != n_kept:
@@ -606,18 +756,44 @@ def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens,
     if genome is not None:
         peak += genome.device_bytes
     LOGGER.info(f"{n_calls} calls on {n_sites} sites; {n_flushes} flushes, {peak / 2**20:.1f} MiB of device memory at the peak")
-    return PileupTable(ref_names=ref_names, ref_id=(keys >> np.uint64(32)).astype(np.int32),
-                       pos=((keys >> np.uint64(1)) & np.uint64(0x7FFFFFFF)).astype(np.int64), strand=(keys & np.uint64(1)).astype(np.uint8),
-                       counts=counts.astype(np.int64), alphabet=alphabet, threshold_k=int(k_t), n_calls=n_calls, n_flushes=n_flushes,
-                       peak_device_bytes=peak, hist=None if h_hist is None else h_hist.astype(np.int64), combined=combined)
+    table = PileupTable(ref_names=ref_names, ref_id=(keys >> np.uint64(32)).astype(np.int32),
+                        pos=((keys >> np.uint64(1)) & np.uint64(0x7FFFFFFF)).astype(np.int64), strand=(keys & np.uint64(1)).astype(np.uint8),
+                        counts=counts.astype(np.int64), alphabet=alphabet, threshold_k=int(k_t), n_calls=n_calls, n_flushes=n_flushes,
+                        peak_device_bytes=peak, hist=None if h_hist is None else h_hist.astype(np.int64), combined=combined)
+    return table if parts is None else _partitioned(table, parts)
 
 
-def _finish(pile, ref_names):
+def _partitioned(table, parts):
+    """The table as it was read, its ref_id holding id << contig_bits | ref_id and its rows ordered by (id, site) -> the
+    partitioned table: the ids mapped to the labels that have rows, the blocks stably re-ordered into label order."""
+    cb = parts.plan.contig_bits
+    ids = (table.ref_id >> cb).astype(np.int64)
+    key_of_id = parts.key_of_id()
+    present = np.unique(ids).tolist()
+    by_key = {_UNGROUPED_KEY if key_of_id[i] is None else key_of_id[i]: i for i in present}
+    ordered = partition_order(by_key)
+    rank = np.zeros(max(present) + 1, np.int32)
+    for k, key in enumerate(ordered):
+        rank[by_key[key]] = k
+    partition = rank[ids]
+    order = np.argsort(partition, kind="stable")
+    rows = table._replace(ref_id=(table.ref_id & np.int32((1 << cb) - 1))[order], pos=table.pos[order], strand=table.strand[order],
+                          counts=table.counts[order])
+    return PileupTable(*rows, partition=partition[order], partition_labels=[partition_label(k) for k in ordered], partition_tag=parts.tag)
+
+
+def _finish(pile, ref_names, parts=None):
     try:
         return pile.finish()
     except RemoraError as e:  # the refusal of a count beyond 32 bits names the site by its contig index: add the name
         m = re.search(r"contig #(\d+)", str(e))
-        if m and int(m.group(1)) < len(ref_names):
+        if m and parts is not None:  # the index read there holds the partition id above the contig's
+            rid, pid = int(m.group(1)) & ((1 << parts.plan.contig_bits) - 1), int(m.group(1)) >> parts.plan.contig_bits
+            key = parts.key_of_id().get(pid, None)
+            if rid < len(ref_names):
+                text = str(e).replace(m.group(0), f"contig #{rid}")
+                raise RemoraError(f"{text} ({ref_names[rid]}, {parts.tag} {partition_label(_UNGROUPED_KEY if key is None else key)})")
+        elif m and int(m.group(1)) < len(ref_names):
             raise RemoraError(f"{e} ({ref_names[int(m.group(1))]})")
         raise
 
@@ -658,3 +834,48 @@ def write_counts(table, path):
                              for rid, pos, st, row in zip(table.ref_id[sl].tolist(), table.pos[sl].tolist(), table.strand[sl].tolist(),
                                                           table.counts[sl].tolist())))
     return int(table.pos.size)
+
+
+# ---- a partitioned table: splitting and writing ------------------------------------------------------------------------
+def partition_tables(table):
+    """A partitioned table -> {label: PileupTable} in label order, each a plain table of that partition's rows: n_calls the
+    sum of its counts (the fail column included); threshold_k and hist the whole run's - the threshold is the sample's."""
+    if table.partition is None or table.partition_labels is None:
+        raise RemoraError("partition_tables takes the table of a run with a partition tag")
+    out = {}
+    for k, label in enumerate(table.partition_labels):
+        rows = np.nonzero(table.partition == k)[0]
+        out[label] = table._replace(ref_id=table.ref_id[rows], pos=table.pos[rows], strand=table.strand[rows], counts=table.counts[rows],
+                                    n_calls=int(table.counts[rows].sum()))  # (a plain table: _replace leaves the partition attributes behind)
+    return out
+
+
+def partition_file_name(path, tag, label):
+    """The file of one partition: `.<tag>_<label>` - `.ungrouped` for that partition - before the last extension of `path`, or
+    at its end when it has none: s.bed -> s.HP_1.bed, s.ungrouped.bed.  A character label outside [0-9A-Za-z] is written xHH,
+    its code in hexadecimal."""
+    label = str(label)
+    if label == UNGROUPED:
+        insert = "." + UNGROUPED
+    else:
+        if len(label) == 1 and re.fullmatch(r"[0-9A-Za-z]", label) is None:  # (an integer label of one character is a digit)
+            label = f"x{ord(label):02X}"
+        insert = f".{tag}_{label}"
+    root, ext = os.path.splitext(os.fspath(path))
+    return root + insert + ext
+
+
+def write_partitioned(table, out_bed, counts_path=None, min_coverage=1):
+    """write_bedmethyl - and with `counts_path` write_counts - once per label that has a row, into the files
+    partition_file_name makes of the two paths.  -> {label: bedMethyl rows written}."""
+    tag = table.partition_tag
+    if tag is None:
+        raise RemoraError("write_partitioned takes the table of a run with a partition tag")
+    rows = {}
+    for label, sub in partition_tables(table).items():
+        if sub.pos.size == 0:
+            continue
+        rows[label] = write_bedmethyl(sub, partition_file_name(out_bed, tag, label), min_coverage=min_coverage)
+        if counts_path is not None:
+            write_counts(sub, partition_file_name(counts_path, tag, label))
+    return rows

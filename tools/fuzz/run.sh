@@ -5,7 +5,9 @@
 # reference-anchor composition for either signal direction (rmr_ref_anchor_batch_dir against a scalar restatement), the
 # set-order restatement of csrc/pyset_order.c and the MM / ML tokeniser of `validate from_modbams` on grammatical, truncated and
 # mutated tag regions, and the FASTA packing arithmetic of `analyze pileup_modbams --ref` (the piece plan of rmr_ref_genome_load and
-# the per-thread code of the pack kernel, csrc/rmr_ref_pack.h) on contigs at random line widths with planted violations.
+# the per-thread code of the pack kernel, csrc/rmr_ref_pack.h) on contigs at random line widths with planted violations, and the
+# aux tag reader of `analyze pileup_modbams --partition-tag` (rmr_bam_aux_values) on aux regions of every field type, every
+# truncation of them and random mutations, against a byte-by-byte restatement.
 # From the repository root:
 #   bash tools/fuzz/run.sh
 set -e
@@ -18,6 +20,8 @@ g++ -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=
 gcc -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -pthread -o /tmp/rmr_setorder_asan setorder_asan.c ../../remora_amd/csrc/pyset_order.c
 g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -pthread -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -I../../include -o /tmp/rmr_mod_tags_asan mod_tags_asan.cpp
 g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -o /tmp/rmr_ref_pack_asan ref_pack_asan.cpp
+# (the sanitizer runtimes linked in: the program starts whatever libraries the environment loads in front of it)
+g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -static-libasan -static-libubsan -pthread -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -I../../include -o /tmp/rmr_aux_tag_asan aux_tag_asan.cpp
 /tmp/rmr_inflate_asan
 /tmp/rmr_bgzf_asan
 /tmp/rmr_r2s_asan
@@ -26,3 +30,4 @@ g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefin
 /tmp/rmr_setorder_asan
 /tmp/rmr_mod_tags_asan
 /tmp/rmr_ref_pack_asan
+/tmp/rmr_aux_tag_asan
