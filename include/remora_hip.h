@@ -647,7 +647,16 @@ int rmr_zstd_rows(const uint8_t *const *src, const int64_t *src_len, int64_t n_r
  * data bytes) -> zigzag -> running sum in int16.  `svb` holds the zstd-DEcompressed bytes of the rows back to
  * back (row r = svb[row_off[r] : row_off[r+1]]), row_samples[r] its sample count; `out` receives the rows'
  * samples back to back (sum(row_samples) int16).  The delta coding restarts in every row.
- * Errors: RMR_ERR_INVALID "corrupt VBZ signal block" when a row's byte count disagrees with its keys. */
+ * Reads with RMR_MEM_DEVICE: the kernel fetches each step's data bytes as whole aligned dwords, so it reads up to 3 bytes
+ * behind the last row and up to 3 bytes in front of a step's first data byte (for a first row of fewer than 3 key bytes and an `svb` off a dword
+ * boundary these lie before `svb`); both reads stay inside the aligned dwords that hold valid
+ * bytes, and what they return beyond the row is never used.  `svb` may have any alignment; remora_amd/io.py leaves 16 bytes
+ * of slack behind the last row.  With RMR_MEM_HOST the library stages `svb` itself and the caller's buffer is read as given.
+ * `out` may have any int16 alignment (16-byte aligned spans are stored as vectors); nothing outside a row's own span of
+ * `out` is written.  After an error the contents of `out` are unspecified within the rows' spans: rows other than the
+ * refused one may be decoded, and a row refused for bytes left over, or at a later step, is stored up to that point.
+ * Errors: RMR_ERR_INVALID "corrupt VBZ signal block (row r)", r the first such row, when a row's byte count disagrees with
+ * its keys (a row without samples has no bytes), row_samples[r] < 0 or row_off decreases. */
 int rmr_vbz_decode(rmr_engine *e, const uint8_t *svb, const int64_t *row_off, const int32_t *row_samples,
                    int64_t n_rows, int16_t *out, int mem);
 

@@ -505,7 +505,8 @@ int rmr_vbz_decode(rmr_engine *e, const uint8_t *svb, const int64_t *row_off, co
     }
     oo[0] = 0;
     for (int64_t r = 0; r < n_rows; ++r) {
-        if (rn[r] < 0 || ro[r + 1] < ro[r] || ro[r + 1] - ro[r] < ((int64_t)rn[r] + 7) / 8 + rn[r])
+        // (a row without samples has no bytes: the kernel's waves leave such rows before they look at them)
+        if (rn[r] < 0 || ro[r + 1] < ro[r] || ro[r + 1] - ro[r] < ((int64_t)rn[r] + 7) / 8 + rn[r] || (rn[r] == 0 && ro[r + 1] != ro[r]))
             RMR_FAIL(RMR_ERR_INVALID, "corrupt VBZ signal block (row %lld)", (long long)r);
         oo[r + 1] = oo[r] + rn[r];
     }

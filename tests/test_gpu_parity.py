@@ -1235,18 +1235,7 @@ def test_motif_scan_kernel_vs_host(torch_cuda):
             assert np.array_equal(got, np.array(sorted(want), dtype=np.int64)), (spec, i)
 
 
-def _svb16_encode(sig):
-    """Test-side encoder of the VBZ layer below zstd: int16 samples -> deltas -> zigzag -> streamvbyte16."""
-    sig = np.asarray(sig, np.int16)
-    d = np.diff(np.concatenate([[0], sig.astype(np.int64)])).astype(np.int16)  # wraps like the decoder's sum
-    zz = ((d.astype(np.int32) << 1) ^ (d.astype(np.int32) >> 15)).astype(np.uint32) & 0xFFFF
-    two = zz > 0xFF
-    keys = np.packbits(two, bitorder="little")
-    data = np.empty(sig.size + int(two.sum()), np.uint8)
-    offs = np.cumsum(two + 1) - (two + 1)
-    data[offs] = zz & 0xFF
-    data[offs[two] + 1] = zz[two] >> 8
-    return keys.tobytes() + data.tobytes()
+from vbz_cases import encode as _svb16_encode  # noqa: E402  (the encoder this test has always used; it lives with the VBZ cases now)
 
 
 def test_vbz_decode_kernel(torch_cuda):
