@@ -502,6 +502,43 @@ void rmr_pileup_destroy(rmr_pileup *p);
  * the launch: n_records or n_words negative, a shift outside 36 .. 59, NULL pointers. */
 int rmr_pileup_stamp_partition(rmr_engine *e, int64_t n_records, const int64_t *out_off, const int32_t *part, int shift, uint64_t *words,
                                int64_t n_words);
+/* Duplex records (GPU; DEVICE pointers, asynchronous on the engine's stream): `infer duplex_from_pod5_and_bam` writes a `C+m?`
+ * part from the template read and a `G-m?` part from the complement read into one record.
+ * rmr_modbam_call_counts_duplex / rmr_modbam_call_fill_duplex: rmr_modbam_call_counts_ref / _fill_ref (ref nullable: then
+ * rmr_modbam_call_counts / _fill) in which an entry counts when its strand is '+' or '-', it has no ChEBI code and a code of
+ * it is among mod_codes (status 5 is asked of the entries of both strands).  The call of a '-' entry lies on the reference
+ * strand opposite to its record's: the effective strand, rev XOR (entry strand == '-'), goes into the site word, picks mask or
+ * rc_mask and the window start of the motif test, and is what combine folds.  A position that entries of both strands list: the
+ * strand of the last entry in tag order that lists it with a code of mod_codes decides, and what entries of the other strand
+ * gave the position is dropped; within one strand the later entry wins, as before.  Kernels of their own: the emits above are
+ * untouched.
+ * hemi != 0 (the fill; the count pass checks it and counts the same calls): a '-' call is written at the '+' position of its
+ * window, as combine does, but KEEPS its strand bit - the '+' call at rp and the '-' call at rp + (len - 1 - 2 focus) of one
+ * record then differ in bit 4 and the code alone, which is what the pair passes look for.  Refused before any launch with hemi:
+ * a NULL ref, combine == 0, n_motifs != 1 (and, by combine, a motif that is not its own reverse complement).
+ * rmr_pileup_pair_counts / rmr_pileup_pair_fill: the two strands' calls of one record at one site -> one pair word.  words /
+ * out_off as the hemi fill wrote and took them: a record's words stand in walk order, their positions are monotone, so the
+ * partner of a '+' word (bit 4 clear) is the first word, in index order, among the RMR_PILEUP_MAX_MOTIF_LEN - 1 words before
+ * and behind it IN ITS RECORD'S SLICE [out_off[r], out_off[r + 1]) with an equal word >> 5 and bit 4 set.  pairs[r] (i64
+ * [n_records]) gets the pairs of record r; with pair_off their exclusive prefix sum (n_records + 1 entries, the caller's), the
+ * fill writes pair_words[pair_off[r] .. pair_off[r + 1]) in the order of the '+' words:
+ *     pair word = the '+' word with code a * n_codes + b,   a / b = the code of the '+' / '-' word (at most n_codes - 1),
+ * n_codes = n_mods + 2, so that a table created with rmr_pileup_create_cols(n_codes^2) counts the patterns per site.  Words of
+ * different records are never paired; a word without a partner is in no pair word.  n_words and the record's slice bound
+ * every load and store.  n_records 0 launches nothing.  Refused before the launch: negative sizes, NULL pointers, n_codes
+ * outside 3 .. 4.
+ * rmr_pileup_create_cols: rmr_pileup_create for rows of ncol u32 counts, 3 .. 16 (a word's code must lie below ncol; the
+ * device memory is that of n_alpha = ncol - 1). */
+int rmr_modbam_call_counts_duplex(rmr_engine *e, const rmr_modbam_batch *b, const rmr_pileup_ref *ref, int32_t region_ref, int64_t region_lo,
+                                  int64_t region_hi, int32_t *ords, int64_t *cig_q, int64_t *cig_r, int64_t *counts, int32_t *status,
+                                  uint64_t *hist, int32_t hemi);
+int rmr_modbam_call_fill_duplex(rmr_engine *e, const rmr_modbam_batch *b, const rmr_pileup_ref *ref, int32_t region_ref, int64_t region_lo,
+                                int64_t region_hi, int32_t k_t, const int32_t *ords, const int64_t *cig_q, const int64_t *cig_r,
+                                const int32_t *status, const int64_t *out_off, uint64_t *words, int32_t hemi);
+int rmr_pileup_pair_counts(rmr_engine *e, int64_t n_records, const int64_t *out_off, const uint64_t *words, int64_t n_words, int64_t *pairs);
+int rmr_pileup_pair_fill(rmr_engine *e, int64_t n_records, const int64_t *out_off, const uint64_t *words, int64_t n_words, int n_codes,
+                         const int64_t *pair_off, uint64_t *pair_words);
+int rmr_pileup_create_cols(rmr_engine *e, int64_t n_contigs, int64_t max_contig_len, int ncol, int64_t buffer_calls, rmr_pileup **out);
 
 /* The simplex-to-duplex alignment of duplex calling (GPU; HOST pointers, synchronous).
  * replaces: duplex_utils.parasail_align + trim_parasail_alignment, src/remora/duplex_utils.py:22-115, i.e.

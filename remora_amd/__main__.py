@@ -410,7 +410,8 @@ def _pileup_modbams(args):
     """`analyze pileup_modbams` (no counterpart in the reference's command line): per-site modified-base counts, bedMethyl."""
     import logging
 
-    from .pileup import check_ref_arguments, partition_file_name, pileup_modbams, write_bedmethyl, write_counts, write_partitioned
+    from .pileup import (check_hemi_arguments, check_ref_arguments, partition_file_name, pileup_modbams, write_bedmethyl, write_counts,
+                         write_partitioned)
 
     log = logging.getLogger("Remora")
     log.setLevel(logging.INFO)
@@ -421,10 +422,12 @@ def _pileup_modbams(args):
     if args.min_coverage < 1:
         raise RemoraError("--min-coverage is at least 1")
     motifs = check_ref_arguments(args.ref, args.motif, args.cpg, args.combine_strands, args.canonical_base)
+    if args.hemi:
+        check_hemi_arguments(args.ref, motifs, args.combine_strands, args.partition_tag, [args.canonical_base] + list(args.mod_bases))
     table = pileup_modbams(args.bam, [args.canonical_base] + list(args.mod_bases), filter_threshold=args.filter_threshold,
                            pct_filt=args.pct_filt, region=args.region, device=args.device, batch=args.reads_per_batch,
                            device_gib=args.pileup_device_gib, ref=args.ref, motifs=motifs, combine_strands=args.combine_strands,
-                           partition_tag=args.partition_tag)
+                           partition_tag=args.partition_tag, duplex=args.duplex, hemi=args.hemi)
     # the files are written only now: a run that keeps no call leaves none behind
     if args.partition_tag is not None:  # --out-bed and --counts-filename are templates: one file per partition that has a row
         rows = write_partitioned(table, args.out_bed, args.counts_filename, min_coverage=args.min_coverage)
@@ -837,6 +840,15 @@ def build_parser():
                          "the one threshold of the whole input: --out-bed and --counts-filename become templates, s.bed -> s.TAG_1.bed, "
                          "s.TAG_2.bed, ..., s.ungrouped.bed for the records without the tag; integer (c C s S i I) or character (A) "
                          "values, up to 255 distinct ones")
+    pm.add_argument("--duplex", action="store_true",
+                    help="count the '-'-strand MM entries too (the G-m? part `infer duplex_from_pod5_and_bam` writes from the complement "
+                         "read): such a call lies on the reference strand opposite to its record's")
+    pm.add_argument("--hemi", action="store_true",
+                    help="one row per motif site with the counts of the strand pairs of duplex records - both strands modified, either "
+                         "one, neither: the '+' and the '-' call of one record at one site are a pair, named <+ class>,<- class>,<canonical "
+                         "base> in the bedMethyl (m,m,C  m,-,C  -,m,C  -,-,C), columns N_<a>_<b> in --counts-filename; implies --duplex "
+                         "and the fold of --combine-strands; needs --ref, one motif that is its own reverse complement (--cpg) and at "
+                         "most two --mod-bases")
     pm.add_argument("--pileup-device-gib", type=float, default=8.0,
                     help="GiB of GPU memory for the call buffer and its sort (capped at half of what is free); the per-site table "
                          "comes on top, 8 + 4 (classes + 1) bytes per distinct site")

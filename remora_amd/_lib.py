@@ -152,6 +152,13 @@ SIGNATURES = {
     "rmr_pileup_read": (c_int, [c_vp, c_vp, c_vp]),
     "rmr_pileup_destroy": (None, [c_vp]),
     "rmr_pileup_stamp_partition": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_i64]),
+    "rmr_modbam_call_counts_duplex": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), ctypes.POINTER(PileupRef), ctypes.c_int32, c_i64, c_i64, c_vp, c_vp,
+                                              c_vp, c_vp, c_vp, c_vp, ctypes.c_int32]),
+    "rmr_modbam_call_fill_duplex": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), ctypes.POINTER(PileupRef), ctypes.c_int32, c_i64, c_i64,
+                                            ctypes.c_int32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_int32]),
+    "rmr_pileup_pair_counts": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "rmr_pileup_pair_fill": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
+    "rmr_pileup_create_cols": (c_int, [c_vp, c_i64, c_i64, c_int, c_i64, ctypes.POINTER(c_vp)]),
     "rmr_duplex_align": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64)]),
     "rmr_duplex_align_mode": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64),
                                       ctypes.POINTER(c_i64)]),

@@ -649,7 +649,85 @@ int rmr_modbam_call_fill(rmr_engine *e, const rmr_modbam_batch *b, int32_t regio
     return rmr_modbam_call_fill_ref(e, b, nullptr, region_ref, region_lo, region_hi, k_t, ords, cig_q, cig_r, status, out_off, words);
 }
 
+// the reference part of a duplex emit: none (ref == NULL, not with hemi), or fill_ref_part's; hemi travels as combine == 2
+static int fill_duplex_ref_part(rmr_engine *e, const rmr_modbam_batch *b, const rmr_pileup_ref *ref, int32_t hemi, PileupRef *pr) {
+    if (hemi != 0) {
+        if (!ref) RMR_FAIL(RMR_ERR_INVALID, "the hemi mode of the emit needs a reference: ref is NULL");
+        if (ref->combine == 0) RMR_FAIL(RMR_ERR_INVALID, "the hemi mode of the emit folds the strands: combine must be set");
+        if (ref->n_motifs != 1) RMR_FAIL(RMR_ERR_INVALID, "the hemi mode of the emit takes exactly one motif, got %d", ref->n_motifs);
+    }
+    if (ref) RMR_TRY(fill_ref_part(e, b, ref, pr));
+    if (hemi != 0) pr->combine = 2;
+    return 0;
+}
+
+int rmr_modbam_call_counts_duplex(rmr_engine *e, const rmr_modbam_batch *b, const rmr_pileup_ref *ref, int32_t region_ref, int64_t region_lo,
+                                  int64_t region_hi, int32_t *ords, int64_t *cig_q, int64_t *cig_r, int64_t *counts, int32_t *status,
+                                  uint64_t *hist, int32_t hemi) {
+    if (!e || !b || !counts || !status) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    RMR_TRY(check_call_batch(b, region_ref, region_lo, region_hi));
+    if ((b->n_deltas > 0 && !ords) || !cig_q || !cig_r) RMR_FAIL(RMR_ERR_INVALID, "NULL workspace");
+    const PileupEmit pe{region_ref, region_lo, region_hi, 0, reinterpret_cast<unsigned long long *>(hist), nullptr};
+    PileupRef pr{};
+    RMR_TRY(fill_duplex_ref_part(e, b, ref, hemi, &pr));
+    if (b->n_records == 0) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    return launch_modbam_calls_duplex(e, *b, pe, pr, ref != nullptr, ords, cig_q, cig_r, counts, status, nullptr);
+}
+
+int rmr_modbam_call_fill_duplex(rmr_engine *e, const rmr_modbam_batch *b, const rmr_pileup_ref *ref, int32_t region_ref, int64_t region_lo,
+                                int64_t region_hi, int32_t k_t, const int32_t *ords, const int64_t *cig_q, const int64_t *cig_r,
+                                const int32_t *status, const int64_t *out_off, uint64_t *words, int32_t hemi) {
+    if (!e || !b || !status || !out_off || !words) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    RMR_TRY(check_call_batch(b, region_ref, region_lo, region_hi));
+    if ((b->n_deltas > 0 && !ords) || !cig_q || !cig_r) RMR_FAIL(RMR_ERR_INVALID, "NULL workspace");
+    if (k_t < 0 || k_t > RMR_PILEUP_BINS) RMR_FAIL(RMR_ERR_INVALID, "the threshold is 0 .. %d in units of 1/512, got %d", RMR_PILEUP_BINS, k_t);
+    const PileupEmit pe{region_ref, region_lo, region_hi, k_t, nullptr, words};
+    PileupRef pr{};
+    RMR_TRY(fill_duplex_ref_part(e, b, ref, hemi, &pr));
+    if (b->n_records == 0) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    return launch_modbam_calls_duplex(e, *b, pe, pr, ref != nullptr, const_cast<int32_t *>(ords), const_cast<int64_t *>(cig_q),
+                                      const_cast<int64_t *>(cig_r), nullptr, const_cast<int32_t *>(status), out_off);
+}
+
+int rmr_pileup_pair_counts(rmr_engine *e, int64_t n_records, const int64_t *out_off, const uint64_t *words, int64_t n_words, int64_t *pairs) {
+    if (!e || !out_off || !words || !pairs) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if (n_records < 0 || n_records > (int64_t)1 << 30 || n_words < 0) RMR_FAIL(RMR_ERR_INVALID, "bad n_records or n_words");
+    if (n_records == 0) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    return launch_pileup_pairs(e, n_records, out_off, words, n_words, 0, pairs, nullptr, nullptr);
+}
+
+int rmr_pileup_pair_fill(rmr_engine *e, int64_t n_records, const int64_t *out_off, const uint64_t *words, int64_t n_words, int n_codes,
+                         const int64_t *pair_off, uint64_t *pair_words) {
+    if (!e || !out_off || !words || !pair_off || !pair_words) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if (n_records < 0 || n_records > (int64_t)1 << 30 || n_words < 0) RMR_FAIL(RMR_ERR_INVALID, "bad n_records or n_words");
+    if (n_codes < 3 || n_codes > 4)
+        RMR_FAIL(RMR_ERR_INVALID, "a pair word holds n_codes^2 <= 16 pattern codes: n_codes (the modified bases + 2) is 3 or 4, got %d", n_codes);
+    if (n_records == 0) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    return launch_pileup_pairs(e, n_records, out_off, words, n_words, n_codes, nullptr, pair_off, pair_words);
+}
+
+// n_alpha: rmr_pileup_create's argument (ncol = n_alpha + 1 then; its own bound and message), NULL from rmr_pileup_create_cols
+static int pileup_create(rmr_engine *e, int64_t n_contigs, int64_t max_contig_len, int ncol, const int *n_alpha, int64_t buffer_calls,
+                         rmr_pileup **out);
+
 int rmr_pileup_create(rmr_engine *e, int64_t n_contigs, int64_t max_contig_len, int n_alpha, int64_t buffer_calls, rmr_pileup **out) {
+    return pileup_create(e, n_contigs, max_contig_len, n_alpha >= 2 && n_alpha <= 8 ? n_alpha + 1 : 0, &n_alpha, buffer_calls, out);
+}
+
+int rmr_pileup_create_cols(rmr_engine *e, int64_t n_contigs, int64_t max_contig_len, int ncol, int64_t buffer_calls, rmr_pileup **out) {
+    return pileup_create(e, n_contigs, max_contig_len, ncol, nullptr, buffer_calls, out);
+}
+
+static int pileup_create(rmr_engine *e, int64_t n_contigs, int64_t max_contig_len, int ncol, const int *n_alpha, int64_t buffer_calls,
+                         rmr_pileup **out) {
     if (out) *out = nullptr;
     if (!e || !out) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
     if (n_contigs < 1 || n_contigs > RMR_PILEUP_MAX_CONTIGS)
@@ -658,11 +736,12 @@ int rmr_pileup_create(rmr_engine *e, int64_t n_contigs, int64_t max_contig_len, 
     if (max_contig_len < 0 || max_contig_len > RMR_PILEUP_MAX_POS)
         RMR_FAIL(RMR_ERR_INVALID, "a pileup holds positions below %lld (31 bits of a site word), the longest contig has %lld bases",
                  (long long)RMR_PILEUP_MAX_POS, (long long)max_contig_len);
-    if (n_alpha < 2 || n_alpha > 8) RMR_FAIL(RMR_ERR_INVALID, "a pileup counts the canonical base and 1 to 7 modified bases, got %d classes", n_alpha);
+    if (n_alpha && ncol == 0) RMR_FAIL(RMR_ERR_INVALID, "a pileup counts the canonical base and 1 to 7 modified bases, got %d classes", *n_alpha);
+    if (ncol < 3 || ncol > 16) RMR_FAIL(RMR_ERR_INVALID, "a row of the pileup has 3 to 16 columns (the 4 bits of a word's code), got %d", ncol);
     if (buffer_calls < 1 || buffer_calls > (int64_t)INT32_MAX) RMR_FAIL(RMR_ERR_INVALID, "the call buffer holds 1 to 2^31 - 1 words, got %lld", (long long)buffer_calls);
     rmr_pileup *p = new (std::nothrow) rmr_pileup();
     if (!p) RMR_FAIL(RMR_ERR_NOMEM, "out of host memory");
-    p->eng = e, p->ncol = n_alpha + 1, p->cap = buffer_calls;
+    p->eng = e, p->ncol = ncol, p->cap = buffer_calls;
     p->end_bit = 36;
     while (p->end_bit < 60 && ((int64_t)1 << (p->end_bit - 36)) < n_contigs) p->end_bit += 1;
     std::lock_guard<std::mutex> lk(e->mu);

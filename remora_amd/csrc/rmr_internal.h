@@ -89,6 +89,7 @@ enum KernelId {
     K_PILEUP_FLUSH,  // one flush: the radix sort, the run counts and the merge into the table
     K_REF_GENOME_PACK,  // one piece of a contig's FASTA text into nibbles, verified (k_ref_genome.hip)
     K_PILEUP_STAMP,  // the partition id into the words of a batch (k_pileup.hip)
+    K_PILEUP_PAIR,   // the two strands' calls of a record paired into pattern words (k_pileup_duplex.hip)
     K_NUM
 };
 const char *kernel_name(int id);
@@ -275,6 +276,12 @@ int pileup_alloc(rmr_pileup *p);
 int pileup_append(rmr_pileup *p, const uint64_t *words, int64_t n);
 int pileup_flush(rmr_pileup *p);
 int launch_pileup_stamp(rmr_engine *e, int64_t n_records, const int64_t *out_off, const int32_t *part, int shift, uint64_t *words, int64_t n_words);
+// k_pileup_duplex.hip: the emit that counts '-'-strand entries too (has_ref: with the reference part `pr`; pr.combine == 2 is
+// the hemi mode of the fill: folded positions, strand bits kept), and the two passes that pair a record's '+' and '-' words
+int launch_modbam_calls_duplex(rmr_engine *e, const rmr_modbam_batch &b, const PileupEmit &pe, const PileupRef &pr, bool has_ref, int32_t *ords,
+                               int64_t *cig_q, int64_t *cig_r, int64_t *counts, int32_t *status, const int64_t *out_off);
+int launch_pileup_pairs(rmr_engine *e, int64_t n_records, const int64_t *out_off, const uint64_t *words, int64_t n_words, int n_codes,
+                        int64_t *pairs, const int64_t *pair_off, uint64_t *pair_words);
 
 // k_read_index.hip: keys u8[n][16], values i64[n] on the host (n >= 1) -> the table of `ix`;  names / name_off / out on the
 // device, the text of name i at names[name_off[i] - base ...]

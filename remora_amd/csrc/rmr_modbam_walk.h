@@ -7,11 +7,14 @@
 //                                   With a reference genome (PileupRef) a call is kept only where the reference shows
 //                                   one of up to four motifs around it, and a '-' call can be folded onto the '+' position of
 //                                   its motif (motif_keep below): everything after the keep test sees the filtered, folded calls.
+//                                   DUPLEX (k_pileup_duplex.hip): '-'-strand entries count too - their calls lie on the reference
+//                                   strand opposite to the record's, and that effective strand is what the word, the motif
+//                                   test and the fold see.
 //
 // One workgroup of four waves per record, the same walk twice (count, then fill into the caller's prefix-summed offsets):
 //   count pass only
 //     1. the entries' ranges are checked against the flat arrays (nothing below indexes outside them), and whether any
-//        entry counts (strand '+', a code of the alphabet);
+//        entry counts (strand '+' - DUPLEX: or '-' -, a code of the alphabet);
 //     2. CIGAR: exclusive prefix sums of the query and the reference lengths of the ops -> cig_q / cig_r (block scan, 256
 //        ops a round);
 //     3. per entry: inclusive prefix sum of (delta + 1) -> ords[k] = d_0 + .. + d_k + k, the occurrence ordinal of call k
@@ -96,7 +99,11 @@ __device__ inline bool motif_keep(const PileupRef &pr, int64_t rid, bool rev, in
 // touched and the truth fields of `b` are not read; s_hist is PILEUP_BINS words of LDS (count pass with pe.hist) or unused.
 // REF (PILEUP only): the motif test and the fold by `rf`; without it `rf` is not read and the pileup compiles the code it had
 // before there was a reference.
-template <bool FILL, bool PILEUP, bool REF = false>
+// DUPLEX (PILEUP only): entries of strand '-' count like those of '+'.  A position keeps the strand of the last entry, in tag
+// order, that lists it with a code of the alphabet; what entries of the other strand gave it before is dropped.  The call's
+// effective strand is rev XOR (that entry's strand == '-').  rf.combine == 2 (the hemi mode of the fill): the fold writes the
+// '+' position of the window and the word keeps the strand bit.  Without DUPLEX none of this is compiled.
+template <bool FILL, bool PILEUP, bool REF = false, bool DUPLEX = false>
 __device__ __forceinline__ void modbam_walk(const rmr_modbam_batch &b, int32_t *__restrict__ ords, int64_t *__restrict__ cig_q,
                                             int64_t *__restrict__ cig_r, int64_t *__restrict__ counts, int32_t *__restrict__ status,
                                             const int64_t *__restrict__ out_off, float *__restrict__ probs, uint8_t *__restrict__ label,
@@ -143,7 +150,7 @@ __device__ __forceinline__ void modbam_walk(const rmr_modbam_batch &b, int32_t *
             if (nd < 0 || ncd < 1 || ncd > RMR_MOD_MAX_CODES || en.delta_off < 0 || en.delta_off + nd > b.n_deltas || en.ml_off < 0 ||
                 en.ml_off + nd * ncd > b.n_ml)
                 bad = 1;
-            else if (en.strand == '+' && en.chebi == 0)
+            else if ((en.strand == '+' || (DUPLEX && en.strand == '-')) && en.chebi == 0)
                 for (int ci = 0; ci < ncd; ++ci)
                     for (int j = 0; j < n_mods; ++j) kept |= en.codes[ci] == b.mod_codes[j];
         }
@@ -231,6 +238,7 @@ __device__ __forceinline__ void modbam_walk(const rmr_modbam_batch &b, int32_t *
         // the calls on this base
         float pr[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         bool called = false;
+        bool on_minus = false;  // DUPLEX: the strand of the entries the probabilities are from
         if (valid) {
             for (int64_t e = e0; e < e1; ++e) {
                 const rmr_mod_entry &en = b.entries[e];
@@ -249,9 +257,21 @@ __device__ __forceinline__ void modbam_walk(const rmr_modbam_batch &b, int32_t *
                     else hi = mid;
                 }
                 if (lo >= nd || (int64_t)o[lo] != occ) continue;
-                if (en.strand != '+' || en.chebi != 0) continue;
+                if ((en.strand != '+' && !(DUPLEX && en.strand == '-')) || en.chebi != 0) continue;
                 const int ncd = en.n_codes;
                 const uint8_t *q = b.ml + en.ml_off + (int64_t)lo * ncd;
+                if (DUPLEX) {
+                    bool listed = false;  // an entry without a code of the alphabet decides nothing
+                    for (int ci = 0; ci < ncd; ++ci)
+                        for (int j = 0; j < n_mods; ++j) listed |= en.codes[ci] == b.mod_codes[j];
+                    if (!listed) continue;
+                    const bool em = en.strand == '-';
+                    if (called && em != on_minus) {
+#pragma unroll
+                        for (int j = 0; j < 7; ++j) pr[j] = 0.f;
+                    }
+                    on_minus = em;
+                }
                 for (int ci = 0; ci < ncd; ++ci) {
                     const char code = en.codes[ci];
 #pragma unroll
@@ -282,7 +302,10 @@ __device__ __forceinline__ void modbam_walk(const rmr_modbam_batch &b, int32_t *
                         // (a position outside the word's 31 bits cannot come from a BAM whose header passed the host's check)
                         // with a reference: only calls on a motif, and a '-' call folded onto '+'; the region is asked of the
                         // position that is written (rp from here on)
-                        if (REF) keep = rp >= 0 && rp < ((int64_t)1 << 31) && motif_keep(rf, b.ref_id[r], rev, rp, &rp);
+                        // (DUPLEX: the call lies on the effective strand, rev XOR the strand of its entries; written out at
+                        // its two uses - a variable for it moved an instruction of the kernels without the flag)
+                        if (REF) keep = rp >= 0 && rp < ((int64_t)1 << 31) && motif_keep(rf, b.ref_id[r], DUPLEX ? rev != on_minus : rev, rp,
+                                                                                                &rp);
                         keep = (REF ? keep : rp >= 0 && rp < ((int64_t)1 << 31)) &&
                                (pe.region_ref < 0 || (b.ref_id[r] == pe.region_ref && rp >= pe.region_lo && rp < pe.region_hi));
                     } else {
@@ -322,7 +345,8 @@ __device__ __forceinline__ void modbam_walk(const rmr_modbam_batch &b, int32_t *
                     const int64_t o = o_lo + emitted + before + __popcll(km & lt);
                     if (o >= o_lo && o < o_hi) {  // (offsets that are not this batch's counts write nothing outside the record's slice)
                         const uint64_t code = kmax >= pe.k_t ? (uint64_t)best : (uint64_t)(n_mods + 1);
-                        const bool minus = rev && !(REF && rf.combine);  // (a folded call stands on '+')
+                        // (a folded call stands on '+' - in the hemi mode, combine == 2, it keeps its strand bit)
+                        const bool minus = (DUPLEX ? rev != on_minus : rev) && !(REF && (DUPLEX ? rf.combine == 1 : rf.combine != 0));
                         pe.words[o] = ((uint64_t)b.ref_id[r] << 36) | ((uint64_t)rp << 5) | ((uint64_t)(minus ? 1 : 0) << 4) | code;
                     }
                 } else {

@@ -21,7 +21,12 @@ csrc/k_ref_genome.hip) and the emit keeps a call only where the reference shows 
 With `partition_tag` (HP of phased reads) the records are piled per value of that aux tag in the same run: the value is read
 on the host (rmr_bam_aux_values), given an id, and the id is stamped into the free bits above the contig index of the
 record's words (rmr_pileup_stamp_partition) - the sort and the table then keep the partitions apart, under the one threshold
-of the whole input ("Pileup: the partition field")."""
+of the whole input ("Pileup: the partition field").
+
+With `duplex` the '-'-strand entries of duplex records count too, on the reference strand opposite to the record's
+(rmr_modbam_call_counts_duplex / _fill_duplex); with `hemi` the '+' and the '-' call of one record at one motif site are paired
+on the device (rmr_pileup_pair_counts / _fill, csrc/k_pileup_duplex.hip) and the table counts the strand patterns per site
+("Pileup: duplex entries and strand pairs")."""
 import ctypes
 import logging
 import mmap
@@ -65,13 +70,19 @@ class PileupTable(_PileupFields):
     A run with `partition_tag` has three more, keyword arguments and attributes beside the tuple's twelve fields (None
     otherwise, and in what _replace returns): one row per (partition, site), partition i32[n] an index into partition_labels -
     the labels that have a row, integers ascending, then characters by code, then "ungrouped" - and the rows ordered by
-    (partition, ref_id, pos, strand); partition_tag names the tag.  partition_tables splits it into plain tables."""
+    (partition, ref_id, pos, strand); partition_tag names the tag.  partition_tables splits it into plain tables.
+    A run with `hemi` has two more of that kind, hemi=True and n_unpaired: one row per motif site (its '+' position; combined is
+    set) and counts i64[n, (n_mods + 2)^2] indexed by the pattern code a (n_mods + 2) + b - a / b the class of the '+' / '-' call
+    of a pair, 0 canonical, 1 .. n_mods the modified bases, n_mods + 1 fail; n_calls counts the pairs, n_unpaired the kept
+    calls without a partner in their record, and hist / threshold_k are those of all kept single calls."""
 
-    partition = partition_labels = partition_tag = None
+    partition = partition_labels = partition_tag = n_unpaired = None
+    hemi = False
 
-    def __new__(cls, *args, partition=None, partition_labels=None, partition_tag=None, **fields):
+    def __new__(cls, *args, partition=None, partition_labels=None, partition_tag=None, hemi=False, n_unpaired=None, **fields):
         self = super().__new__(cls, *args, **fields)
         self.partition, self.partition_labels, self.partition_tag = partition, partition_labels, partition_tag
+        self.hemi, self.n_unpaired = bool(hemi), n_unpaired
         return self
 
 
@@ -369,6 +380,36 @@ def check_ref_arguments(ref, motifs, cpg, combine_strands, canonical_base):
     return motifs
 
 
+def check_hemi_arguments(ref, motifs, combine_strands, partition_tag, alphabet):
+    """What `hemi` needs beside it, or RemoraError naming the argument: a reference, exactly one motif that is its own reverse
+    complement, at most two modified bases ((n_mods + 2)^2 pattern codes fit the 4 bits of a site word's code), no
+    --combine-strands (the fold is implied) and no --partition-tag.  `motifs`: [(motif, focus)] as check_ref_arguments returns
+    them.  -> the motif's MotifDescriptor.  No device is touched."""
+    alphabet = check_alphabet(alphabet)
+    if ref is None:
+        raise RemoraError("--hemi needs --ref: the two strands of a site are found through the motif in the reference FASTA")
+    motifs = [tuple(m) for m in (motifs or [])]
+    if len(motifs) != 1:
+        raise RemoraError(f"--hemi takes exactly one motif (--cpg, or one --motif MOTIF FOCUS), got {len(motifs)}")
+    if combine_strands:
+        raise RemoraError("--hemi implies the fold of --combine-strands: give --hemi alone")
+    if partition_tag is not None:
+        raise RemoraError("--hemi with --partition-tag is not built: give one of them")
+    if len(alphabet) - 1 > 2:
+        raise RemoraError(f"--hemi counts (n + 2)^2 strand patterns of n modified bases in the 16 codes of a site word: at most two "
+                          f"--mod-bases, got {len(alphabet) - 1} ({' '.join(alphabet[1:])})")
+    d = check_pileup_motifs(motifs, alphabet[0], False)[0]
+    if d.mask != d.rc_mask:
+        raise RemoraError(f"--hemi: the motif {d.motif} is not its own reverse complement (CG, GC, GATC, ... are); its two strands do "
+                          "not share a site")
+    return d
+
+
+def hemi_class_names(alphabet):
+    """The classes of one strand's call in a hemi table: the canonical base, the modified bases, `fail`."""
+    return list(alphabet) + ["fail"]
+
+
 # ---- the reference FASTA -------------------------------------------------------------------------------------------------
 FastaSpan = namedtuple("FastaSpan", ("name", "start", "end", "line_bases", "line_width", "n_bases"))
 FastaSpan.__doc__ = """One contig of a FASTA file: its sequence lines are the bytes [start, end) (trailing white space stripped), in
@@ -537,12 +578,17 @@ def _pileup_ref_struct(genome, descriptors, combine_strands):
 class DevicePileup:
     """rmr_pileup_*: the call buffer and the resident per-site table on the device."""
 
-    def __init__(self, eng, n_contigs, max_contig_len, n_alpha, buffer_calls):
+    def __init__(self, eng, n_contigs, max_contig_len, n_alpha, buffer_calls, ncol=None):
+        """`ncol` (3 to 16, rmr_pileup_create_cols): the columns of a row when they are not the n_alpha + 1 of a plain table."""
         from . import _lib as L
 
-        self._L, self._lib, self.eng, self.n_alpha = L, L.lib(), eng, int(n_alpha)
+        self._L, self._lib, self.eng, self.n_alpha = L, L.lib(), eng, int(n_alpha) if ncol is None else int(ncol) - 1
         self.h = ctypes.c_void_p()
-        L.check(self._lib.rmr_pileup_create(eng.handle, int(n_contigs), int(max_contig_len), int(n_alpha), int(buffer_calls), ctypes.byref(self.h)))
+        if ncol is None:
+            L.check(self._lib.rmr_pileup_create(eng.handle, int(n_contigs), int(max_contig_len), int(n_alpha), int(buffer_calls), ctypes.byref(self.h)))
+        else:
+            L.check(self._lib.rmr_pileup_create_cols(eng.handle, int(n_contigs), int(max_contig_len), int(ncol), int(buffer_calls),
+                                                     ctypes.byref(self.h)))
 
     def add(self, words, n):
         """n site words of a device tensor (kept alive by the caller until the engine's stream has passed them)."""
@@ -572,11 +618,13 @@ class DevicePileup:
         self.close()
 
 
-def _emit_batch(eng, b, region, k_t, hist, n_cig, n_deltas, pref=None, part=None, shift=0):
+def _emit_batch(eng, b, region, k_t, hist, n_cig, n_deltas, pref=None, part=None, shift=0, duplex=False, n_codes=0):
     """One batch through the emit: the count pass (with the histogram when `hist` is a device tensor), and - k_t not None -
     the fill pass.  `pref`: the rmr_pileup_ref of a run with a reference, or None.  `part` (i32 per record, a partitioned run):
-    after the fill pass the records' partition ids are stamped into their words from bit `shift`.  -> (words device tensor
-    or None, calls per record, status per record)."""
+    after the fill pass the records' partition ids are stamped into their words from bit `shift`.  `duplex`: the emit that
+    counts '-'-strand entries.  `n_codes` (a hemi run: n_mods + 2): the fill keeps the strand bits and its words go through the
+    pair passes - what comes back are the pair words.  -> (words device tensor or None, calls per record, status per record,
+    pairs in the batch or None)."""
     from . import _lib as L
     from .engine import _torch
 
@@ -589,11 +637,15 @@ def _emit_batch(eng, b, region, k_t, hist, n_cig, n_deltas, pref=None, part=None
     with_ref = () if pref is None else (ctypes.byref(pref),)
     call_counts, call_fill = ((lib.rmr_modbam_call_counts, lib.rmr_modbam_call_fill) if pref is None else
                               (lib.rmr_modbam_call_counts_ref, lib.rmr_modbam_call_fill_ref))
+    hemi_arg = ()
+    if duplex:  # the `_ref` arguments with a nullable ref, and hemi at the end
+        with_ref, hemi_arg = (None if pref is None else ctypes.byref(pref),), (1 if n_codes else 0,)
+        call_counts, call_fill = lib.rmr_modbam_call_counts_duplex, lib.rmr_modbam_call_fill_duplex
     L.check(call_counts(eng.handle, ctypes.byref(b), *with_ref, region[0], region[1], region[2], ords.data_ptr(), cig_qr[0].data_ptr(),
-                        cig_qr[1].data_ptr(), counts.data_ptr(), d_status.data_ptr(), hist.data_ptr() if hist is not None else None))
+                        cig_qr[1].data_ptr(), counts.data_ptr(), d_status.data_ptr(), hist.data_ptr() if hist is not None else None, *hemi_arg))
     eng.synchronize()
     h_counts, h_status = counts[:n].cpu().numpy(), d_status[:n].cpu().numpy()
-    words = None
+    words, n_pairs = None, (0 if n_codes else None)
     total = int(h_counts.sum())
     if k_t is not None and total:
         out_off = np.zeros(n + 1, np.int64)
@@ -601,16 +653,31 @@ def _emit_batch(eng, b, region, k_t, hist, n_cig, n_deltas, pref=None, part=None
         d_off = torch.from_numpy(out_off).to(dev)
         words = torch.empty(total, dtype=torch.int64, device=dev)
         L.check(call_fill(eng.handle, ctypes.byref(b), *with_ref, region[0], region[1], region[2], int(k_t), ords.data_ptr(),
-                          cig_qr[0].data_ptr(), cig_qr[1].data_ptr(), d_status.data_ptr(), d_off.data_ptr(), words.data_ptr()))
+                          cig_qr[0].data_ptr(), cig_qr[1].data_ptr(), d_status.data_ptr(), d_off.data_ptr(), words.data_ptr(), *hemi_arg))
         if part is not None:
             d_part = torch.from_numpy(np.ascontiguousarray(part, np.int32)).to(dev)
             L.check(lib.rmr_pileup_stamp_partition(eng.handle, n, d_off.data_ptr(), d_part.data_ptr(), int(shift), words.data_ptr(), total))
+        if n_codes:  # the two strands' calls of a record at one site -> one pair word
+            d_pairs = torch.empty(n, dtype=torch.int64, device=dev)
+            L.check(lib.rmr_pileup_pair_counts(eng.handle, n, d_off.data_ptr(), words.data_ptr(), total, d_pairs.data_ptr()))
+            eng.synchronize()
+            pair_off = np.zeros(n + 1, np.int64)
+            np.cumsum(d_pairs.cpu().numpy(), out=pair_off[1:])
+            n_pairs = int(pair_off[-1])
+            if not 0 <= 2 * n_pairs <= total:
+                raise RemoraError(f"pileup: {n_pairs} pairs out of {total} calls")
+            singles, words = words, None
+            if n_pairs:
+                d_pair_off = torch.from_numpy(pair_off).to(dev)
+                words = torch.empty(n_pairs, dtype=torch.int64, device=dev)
+                L.check(lib.rmr_pileup_pair_fill(eng.handle, n, d_off.data_ptr(), singles.data_ptr(), total, int(n_codes), d_pair_off.data_ptr(),
+                                                 words.data_ptr()))
         eng.synchronize()  # the inputs and the workspaces may go once the kernel is through
-    return words, h_counts, h_status
+    return words, h_counts, h_status, n_pairs
 
 
 def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_FILT, region=None, device=None, batch=512, buffer_calls=None,
-                   device_gib=DEFAULT_DEVICE_GIB, ref=None, motifs=None, combine_strands=False, partition_tag=None):
+                   device_gib=DEFAULT_DEVICE_GIB, ref=None, motifs=None, combine_strands=False, partition_tag=None, duplex=False, hemi=False):
     """The per-site counts of the modified-base calls of `bams` (one path or several, piled into one table) -> PileupTable.
     `alphabet`: the canonical base followed by 1 to 7 single-letter modified-base codes.  The threshold: either
     `filter_threshold` T (k_T = ceil(512 T); give pct_filt=None with it) or `pct_filt` P - then a first pass over the input
@@ -627,6 +694,13 @@ def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_F
     `ungrouped`; which calls count, their classes and the threshold (one histogram, one k_T for the whole input) are those of
     the run without it, and the PileupTable has its three partition fields set (partition_tables, write_partitioned).  The
     id stands in the bits of a site word the contig index leaves free: 2^part_bits - 1 values, partition_bit_plan.
+    `duplex`: the '-'-strand MM entries of duplex records (`G-m?` beside `C+m?`) count too; their calls lie on the reference
+    strand opposite to the record's, and that strand is what the rows, the motif test and the fold see.  A position that
+    entries of both strands list takes the strand of the last entry, in tag order, that lists it with a code of the alphabet.
+    `hemi` (implies duplex; needs `ref`, one motif that is its own reverse complement, at most two modified bases, neither
+    combine_strands nor partition_tag): one row per motif site with the counts of the strand pairs - the '+' call at rp and
+    the '-' call at rp + (len - 1 - 2 focus) of ONE record are a pair of pattern (class on '+', class on '-'); a kept call
+    without a partner in its record is counted in n_unpaired only.  The threshold is that of all kept single calls.
     Everything that is refused is refused before any pileup launch; RemoraError when no call is kept.  (What a partition tag
     is refused for - another type, both kinds in one run, too many values - is known when the batch with that record is read:
     before any launch for that batch, and before any file is written.)"""
@@ -638,6 +712,9 @@ def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_F
     if filter_threshold is None and pct_filt is None:
         pct_filt = DEFAULT_PCT_FILT
     alphabet = check_alphabet(alphabet)
+    if hemi:
+        check_hemi_arguments(ref, motifs, combine_strands, partition_tag, alphabet)
+    duplex = bool(duplex or hemi)
     k_t = threshold_k(filter_threshold) if filter_threshold is not None else None
     if k_t is None:
         percentile_k([0] * N_BINS, pct_filt)  # the range check
@@ -645,7 +722,7 @@ def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_F
         raise RemoraError(("--motif" if motifs else "--combine-strands") + " needs --ref: the motif is looked up in the reference FASTA")
     if ref is not None and not motifs:
         raise RemoraError("--ref needs a motif: give --motif MOTIF FOCUS or --cpg")
-    descriptors = check_pileup_motifs(motifs, alphabet[0], combine_strands) if ref is not None else None
+    descriptors = check_pileup_motifs(motifs, alphabet[0], combine_strands or hemi) if ref is not None else None
     dicts = [bam_reference_dict(p) for p in bams]
     check_reference_dicts(bams, dicts)
     ref_names, ref_lens = [d[0] for d in dicts[0]], [d[1] for d in dicts[0]]
@@ -669,16 +746,16 @@ def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_F
         genome = RefGenome.from_fasta(ref, ref_names, ref_lens, device=device, contigs=[reg[0]] if reg[0] >= 0 else None)
     try:
         if genome is not None:
-            pref = _pileup_ref_struct(genome, descriptors, combine_strands)
+            pref = _pileup_ref_struct(genome, descriptors, combine_strands or hemi)
         return _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens, device, batch, buffer_calls, device_gib, genome, pref,
-                           bool(combine_strands), parts)
+                           bool(combine_strands or hemi), parts, duplex, bool(hemi))
     finally:
         if genome is not None and genome is not ref:
             genome.close()
 
 
 def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens, device, batch, buffer_calls, device_gib, genome, pref, combined,
-                parts=None):
+                parts=None, duplex=False, hemi=False):
     """pileup_modbams once its arguments are checked and the reference is on the device.  `parts`: the Partitioner of a run with
     a partition tag."""
     from .engine import _torch, get_engine
@@ -686,20 +763,22 @@ def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens,
     from .validate import modbam_device_batch, tokenise_mod_tags, warn_ignored_entries
 
     mods, n_alpha = alphabet[1:], len(alphabet)
+    n_codes = n_alpha + 1 if hemi else 0          # the classes of one strand's call in a pair: the alphabet and fail
+    ncol = n_codes * n_codes if hemi else n_alpha + 1
     torch = _torch()
     eng = get_engine(device)
     dev = eng.torch_device
     if buffer_calls is None:
         free = torch.cuda.mem_get_info(dev)[0]
         gib = min(float(device_gib), free / 2 / 2**30)
-        buffer_calls = int(max(1, min(2**31 - 1, (gib * 2**30 - (1 << 20)) // bytes_per_buffered_call(n_alpha))))
+        buffer_calls = int(max(1, min(2**31 - 1, (gib * 2**30 - (1 << 20)) // bytes_per_buffered_call(ncol - 1))))
         LOGGER.info(f"pileup call buffer: {buffer_calls} calls in {gib:.3g} GiB of device memory (--pileup-device-gib {device_gib:g}, "
                     f"{free / 2**30:.1f} GiB free)")
-    warn = {"strand": True, "mod": True}
+    warn = {"strand": not duplex, "mod": True}  # (in a duplex run the '-' entries count: nothing to warn of)
 
     def one_pass(k_fill, hist, pile, log_skipped):
-        """All BAMs once: the count pass of every batch, and with k_fill the fill pass and the append.  -> kept calls."""
-        n_kept = 0
+        """All BAMs once: the count pass of every batch, and with k_fill the fill pass and the append.  -> (kept calls, pairs)."""
+        n_kept = n_paired = 0
         for path in bams:
             skipped, n_records = {}, 0
 
@@ -713,8 +792,9 @@ def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens,
                 warn_ignored_entries(tok[4], alphabet, warn, MOD_NOT_IN_ALPHABET)
                 buf, b = modbam_device_batch(dev, mods, rb.seq, rb.seq_off, rb.cigar, rb.cigar_off, rb.flag, rb.ref_id, rb.pos, rb.has, tok)
                 b.n_refs = len(ref_names)
-                words, h_counts, h_status = _emit_batch(eng, b, reg, k_fill, hist, int(np.asarray(rb.cigar).size), int(tok[5].size), pref, part,
-                                                          0 if parts is None else parts.plan.shift)
+                words, h_counts, h_status, n_pairs = _emit_batch(eng, b, reg, k_fill, hist, int(np.asarray(rb.cigar).size), int(tok[5].size), pref,
+                                                                   part, 0 if parts is None else parts.plan.shift, duplex, n_codes)
+                n_paired += n_pairs or 0
                 del buf
                 if words is not None:
                     pile.add(words, words.numel())
@@ -727,7 +807,7 @@ def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens,
             if log_skipped:
                 for st, k in sorted(skipped.items()):
                     LOGGER.info(f"{k} of {n_records} records skipped: {PILEUP_STATUS.get(st, st)} ({path})")
-        return n_kept
+        return n_kept, n_paired
 
     no_calls = (f"No modified-base call of {alphabet[1:]} on an aligned base" + (f" inside {region}" if region is not None else "") +
                 (" on a motif of the reference" if genome is not None else "") +
@@ -735,7 +815,7 @@ def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens,
     h_hist = None
     if k_t is None:  # the percentile needs every call's confidence first: one pass that emits no rows
         hist = torch.zeros(N_BINS, dtype=torch.int64, device=dev)
-        n_kept = one_pass(None, hist, None, True)
+        n_kept, _ = one_pass(None, hist, None, True)
         eng.synchronize()
         h_hist = hist.cpu().numpy()
         if n_kept < 1 or int(h_hist.sum()) != n_kept:
@@ -745,21 +825,30 @@ def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens,
         k_t = percentile_k(h_hist, pct_filt)
         LOGGER.info(f"--pct-filt {pct_filt:g}: {int(h_hist[:k_t].sum())} of {n_kept} calls fail at k_T = {k_t} (probability {k_t / 512:.6g})")
     # a partitioned run: the id stands above the contig index, and the sort covers its bits too
-    with DevicePileup(eng, len(ref_names) if parts is None else parts.plan.n_contigs, max(ref_lens), n_alpha, buffer_calls) as pile:
-        n_kept = one_pass(k_t, None, pile, h_hist is None)
+    with DevicePileup(eng, len(ref_names) if parts is None else parts.plan.n_contigs, max(ref_lens), n_alpha, buffer_calls,
+                      ncol if hemi else None) as pile:
+        n_kept, n_paired = one_pass(k_t, None, pile, h_hist is None)
         n_sites, n_calls, n_flushes, peak = _finish(pile, ref_names, parts)
+        if hemi and n_kept >= 1 and n_paired < 1:
+            raise RemoraError(f"{n_kept} modified-base calls are kept, none of them has a partner on the other strand in its record: "
+                              "--hemi counts the strand pairs of duplex records (C+m? with G-m?)")
         if n_calls < 1:
             raise RemoraError(no_calls)
-        if n_calls != n_kept:
-            raise RemoraError(f"pileup: {n_calls} calls reached the table, the records hold {n_kept}")
+        if n_calls != (n_paired if hemi else n_kept):
+            raise RemoraError(f"pileup: {n_calls} calls reached the table, the records hold {n_paired if hemi else n_kept}")
         keys, counts = pile.read(n_sites)
     if genome is not None:
         peak += genome.device_bytes
-    LOGGER.info(f"{n_calls} calls on {n_sites} sites; {n_flushes} flushes, {peak / 2**20:.1f} MiB of device memory at the peak")
+    if hemi:
+        LOGGER.info(f"{n_calls} strand pairs on {n_sites} sites, {n_kept - 2 * n_calls} of {n_kept} calls unpaired; {n_flushes} flushes, "
+                    f"{peak / 2**20:.1f} MiB of device memory at the peak")
+    else:
+        LOGGER.info(f"{n_calls} calls on {n_sites} sites; {n_flushes} flushes, {peak / 2**20:.1f} MiB of device memory at the peak")
     table = PileupTable(ref_names=ref_names, ref_id=(keys >> np.uint64(32)).astype(np.int32),
                         pos=((keys >> np.uint64(1)) & np.uint64(0x7FFFFFFF)).astype(np.int64), strand=(keys & np.uint64(1)).astype(np.uint8),
                         counts=counts.astype(np.int64), alphabet=alphabet, threshold_k=int(k_t), n_calls=n_calls, n_flushes=n_flushes,
-                        peak_device_bytes=peak, hist=None if h_hist is None else h_hist.astype(np.int64), combined=combined)
+                        peak_device_bytes=peak, hist=None if h_hist is None else h_hist.astype(np.int64), combined=combined,
+                        hemi=hemi, n_unpaired=n_kept - 2 * n_calls if hemi else None)
     return table if parts is None else _partitioned(table, parts)
 
 
@@ -802,7 +891,13 @@ def write_bedmethyl(table, path, min_coverage=1):
     """The eleven ENCODE bedMethyl columns, header-less, tab-separated: one row per (site, modified base) whose N_valid - the
     passing calls of any class - is at least max(min_coverage, 1):
     chrom pos pos+1 code min(N_valid, 1000) strand pos pos+1 255,0,0 N_valid pct, pct = 100 N_mod / N_valid to two decimals.
-    Rows: contigs in header order, then position, then + before -, then the codes in alphabet order.  Returns the rows written."""
+    Rows: contigs in header order, then position, then + before -, then the codes in alphabet order.  Returns the rows written.
+    A hemi table: per site whose N_valid - the pairs whose two classes both pass - reaches the coverage, one row per pattern of
+    passing classes, (n_mods + 1)^2 rows ordered by the '+' class, then the '-' class; the name column is `<a>,<b>,<canonical>`
+    (a modified base's code, `-` for the canonical class: m,m,C  m,-,C  -,m,C  -,-,C), the strand column `.`, pct = 100
+    N_pattern / N_valid."""
+    if getattr(table, "hemi", False):
+        return _write_bedmethyl_hemi(table, path, min_coverage)
     mods = list(table.alphabet[1:])
     combined = bool(getattr(table, "combined", False))
     valid = table.counts[:, :-1].sum(axis=1)
@@ -823,8 +918,40 @@ def write_bedmethyl(table, path, min_coverage=1):
     return n_rows
 
 
+def _write_bedmethyl_hemi(table, path, min_coverage):
+    n_alpha = len(table.alphabet)
+    nc = n_alpha + 1
+    names = ["-"] + list(table.alphabet[1:])
+    cols = [(a * nc + b, f"{names[a]},{names[b]},{table.alphabet[0]}") for a in range(n_alpha) for b in range(n_alpha)]
+    valid = table.counts[:, [c for c, _ in cols]].sum(axis=1)
+    keep = np.nonzero(valid >= max(int(min_coverage), 1))[0]
+    n_rows = 0
+    with open(path, "w") as fh:
+        for lo in range(0, keep.size, 65536):
+            lines = []
+            idx = keep[lo : lo + 65536]
+            for rid, pos, nv, row in zip(table.ref_id[idx].tolist(), table.pos[idx].tolist(), valid[idx].tolist(), table.counts[idx].tolist()):
+                name = table.ref_names[rid]
+                for c, label in cols:
+                    lines.append(f"{name}\t{pos}\t{pos + 1}\t{label}\t{min(nv, 1000)}\t.\t{pos}\t{pos + 1}\t255,0,0\t{nv}\t{100 * row[c] / nv:.2f}\n")
+            fh.write("".join(lines))
+            n_rows += len(lines)
+    return n_rows
+
+
 def write_counts(table, path):
-    """TSV with the header chrom start strand N_<canonical> N_<code>... N_fail: one row per site that has a kept call."""
+    """TSV with the header chrom start strand N_<canonical> N_<code>... N_fail: one row per site that has a kept call.  A hemi
+    table: N_<a>_<b> for all (n_mods + 2)^2 pattern codes in code order, the classes named by the canonical base's letter, the
+    modified bases' codes and `fail`; one row per site that has a pair."""
+    if getattr(table, "hemi", False):
+        cls = hemi_class_names(table.alphabet)
+        with open(path, "w") as fh:
+            fh.write("\t".join(["chrom", "start", "strand"] + [f"N_{a}_{b}" for a in cls for b in cls]) + "\n")
+            for lo in range(0, table.pos.size, 65536):
+                sl = slice(lo, lo + 65536)
+                fh.write("".join(f"{table.ref_names[rid]}\t{pos}\t.\t" + "\t".join(map(str, row)) + "\n"
+                                 for rid, pos, row in zip(table.ref_id[sl].tolist(), table.pos[sl].tolist(), table.counts[sl].tolist())))
+        return int(table.pos.size)
     combined = bool(getattr(table, "combined", False))
     with open(path, "w") as fh:
         fh.write("\t".join(["chrom", "start", "strand"] + [f"N_{a}" for a in table.alphabet] + ["N_fail"]) + "\n")
