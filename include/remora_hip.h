@@ -539,6 +539,40 @@ int rmr_pileup_pair_counts(rmr_engine *e, int64_t n_records, const int64_t *out_
 int rmr_pileup_pair_fill(rmr_engine *e, int64_t n_records, const int64_t *out_off, const uint64_t *words, int64_t n_words, int n_codes,
                          const int64_t *pair_off, uint64_t *pair_words);
 int rmr_pileup_create_cols(rmr_engine *e, int64_t n_contigs, int64_t max_contig_len, int ncol, int64_t buffer_calls, rmr_pileup **out);
+/* The coverage join (GPU): per site of the finished table, how many records cover it WITHOUT a call - the N_delete, N_diff and
+ * N_nocall columns of the eighteen-column bedMethyl.  replaces: nothing in the reference; these are this project's own
+ * definitions (the column order of the files is modkit's).
+ * A record takes part iff its status is 0.  It is asked about every site of the table on its contig, on its strand (bit 0 of
+ * the key = flag & 0x10), in its partition (part[r] above the contig index, as rmr_pileup_stamp_partition puts it; part NULL:
+ * none) whose position rp lies in its reference span [pos, pos + the reference length of its CIGAR).  The first rule that fits:
+ *   1. one of the record's own words, words[out_off[r] .. out_off[r + 1]) - passing or `fail` - has the site's key: nothing;
+ *   2. rp lies inside a D operation: delete += 1;
+ *   3. rp lies inside M / = / X: the base of the original read there (the stored base, complemented for flag & 0x10; U as T)
+ *      equals the canonical base: nocall += 1; anything else, N included: diff += 1;
+ *   4. otherwise (an N skip): nothing.
+ * ref with ref->combine != 0 (the table of a combined emit: one row per motif site, strand bit 0): a '+' record is asked at rp =
+ * S of a site S, a '-' record at rp = S + (len - 1 - 2 focus) of the first motif, in array order, whose window matches the
+ * reference on '+' with its focus at S; a site no motif matches at, or an rp outside the span, adds nothing.  ref NULL or
+ * combine == 0: ref is not read.
+ * rmr_pileup_set_canonical: the canonical base of the table, 'A' 'C' 'G' 'T' or 'U' (= 'T'); the join is refused without it.
+ * rmr_pileup_cover: DEVICE pointers, asynchronous on the engine's stream.  b, status, cig_q, cig_r, out_off and words are those
+ * of the rmr_modbam_call_counts / _fill (_ref) of the same batch, the words stamped already when part is given (shift as
+ * there; ignored without part); words may be NULL when n_words is 0.  One workgroup of 256 threads per record: two binary
+ * searches in the table's keys bracket its sites, each lane finds the CIGAR operation of its rp - the LAST index with
+ * cig_r <= rp - pos, since operations that consume no reference share their cig_r with the next one -, takes the stored
+ * position from cig_q, searches the record's slice of words (monotone in position) for the key and does one integer atomicAdd.
+ * Every load is bounded by the record's slices, n_words and n_sites; the result does not depend on the order or the batches.
+ * Each record adds at most 1 per site and column: the caller refuses 2^32 records.  The counts live in a u32[n_sites][3] array
+ * beside the table (12 bytes per site, in the peak rmr_pileup_finish reports from then on), allocated and zeroed by the first
+ * call after rmr_pileup_finish and dropped when rmr_pileup_add is called again.  Refused before any launch: before
+ * rmr_pileup_finish, without a canonical base, NULL pointers, bad sizes, a ref the emit would refuse.  n_records 0 or a table
+ * without a site: nothing is launched or stored.
+ * rmr_pileup_read_cover: cover u32[n_sites][3] (HOST; delete, diff, nocall per site in the order of rmr_pileup_read's keys);
+ * all zero when no record was joined since the table last changed.  Synchronous. */
+int rmr_pileup_set_canonical(rmr_pileup *p, int base);
+int rmr_pileup_cover(rmr_pileup *p, const rmr_modbam_batch *b, const rmr_pileup_ref *ref, const int32_t *status, const int64_t *cig_q,
+                     const int64_t *cig_r, const int64_t *out_off, const uint64_t *words, int64_t n_words, const int32_t *part, int shift);
+int rmr_pileup_read_cover(rmr_pileup *p, uint32_t *cover);
 
 /* The simplex-to-duplex alignment of duplex calling (GPU; HOST pointers, synchronous).
  * replaces: duplex_utils.parasail_align + trim_parasail_alignment, src/remora/duplex_utils.py:22-115, i.e.

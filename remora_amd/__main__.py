@@ -413,6 +413,9 @@ def _pileup_modbams(args):
     from .pileup import (check_hemi_arguments, check_ref_arguments, partition_file_name, pileup_modbams, write_bedmethyl, write_counts,
                          write_partitioned)
 
+    if args.coverage_columns and (args.duplex or args.hemi):  # before any file is opened or written, the log included
+        raise RemoraError(f"--coverage-columns with {'--hemi' if args.hemi else '--duplex'} is not built: there a record stands for two "
+                          "strands; give one of them")
     log = logging.getLogger("Remora")
     log.setLevel(logging.INFO)
     if not log.handlers:
@@ -427,7 +430,7 @@ def _pileup_modbams(args):
     table = pileup_modbams(args.bam, [args.canonical_base] + list(args.mod_bases), filter_threshold=args.filter_threshold,
                            pct_filt=args.pct_filt, region=args.region, device=args.device, batch=args.reads_per_batch,
                            device_gib=args.pileup_device_gib, ref=args.ref, motifs=motifs, combine_strands=args.combine_strands,
-                           partition_tag=args.partition_tag, duplex=args.duplex, hemi=args.hemi)
+                           partition_tag=args.partition_tag, duplex=args.duplex, hemi=args.hemi, coverage=args.coverage_columns)
     # the files are written only now: a run that keeps no call leaves none behind
     if args.partition_tag is not None:  # --out-bed and --counts-filename are templates: one file per partition that has a row
         rows = write_partitioned(table, args.out_bed, args.counts_filename, min_coverage=args.min_coverage)
@@ -849,6 +852,12 @@ def build_parser():
                          "base> in the bedMethyl (m,m,C  m,-,C  -,m,C  -,-,C), columns N_<a>_<b> in --counts-filename; implies --duplex "
                          "and the fold of --combine-strands; needs --ref, one motif that is its own reverse complement (--cpg) and at "
                          "most two --mod-bases")
+    pm.add_argument("--coverage-columns", action="store_true",
+                    help="the eighteen-column bedMethyl: N_mod N_canonical N_other_mod N_delete N_fail N_diff N_nocall behind the eleven "
+                         "columns, and N_delete N_diff N_nocall behind N_fail in --counts-filename.  Costs one more pass over the BAMs "
+                         "once the table is finished - every record is joined on the GPU against the sites it spans: a deletion "
+                         "there, another base than the canonical one, or the canonical base without a call - and 12 bytes of GPU "
+                         "memory per site; not with --duplex or --hemi")
     pm.add_argument("--pileup-device-gib", type=float, default=8.0,
                     help="GiB of GPU memory for the call buffer and its sort (capped at half of what is free); the per-site table "
                          "comes on top, 8 + 4 (classes + 1) bytes per distinct site")

@@ -159,6 +159,9 @@ SIGNATURES = {
     "rmr_pileup_pair_counts": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "rmr_pileup_pair_fill": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
     "rmr_pileup_create_cols": (c_int, [c_vp, c_i64, c_i64, c_int, c_i64, ctypes.POINTER(c_vp)]),
+    "rmr_pileup_set_canonical": (c_int, [c_vp, c_int]),
+    "rmr_pileup_cover": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), ctypes.POINTER(PileupRef), c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int]),
+    "rmr_pileup_read_cover": (c_int, [c_vp, c_vp]),
     "rmr_duplex_align": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64)]),
     "rmr_duplex_align_mode": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64),
                                       ctypes.POINTER(c_i64)]),

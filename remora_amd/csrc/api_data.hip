@@ -780,6 +780,7 @@ int rmr_pileup_finish(rmr_pileup *p, int64_t *n_sites, int64_t *n_calls, int64_t
         RMR_FAIL(RMR_ERR_INVALID, "the count of a site would pass 2^32 - 1: contig #%lld, position %lld, strand %c", (long long)(key >> 32),
                  (long long)((key >> 1) & 0x7fffffffull), (key & 1) ? '-' : '+');
     }
+    p->finished = true;
     if (n_sites) *n_sites = p->nt;
     if (n_calls) *n_calls = p->n_calls;
     if (n_flushes) *n_flushes = p->n_flushes;
@@ -812,10 +813,76 @@ int rmr_pileup_stamp_partition(rmr_engine *e, int64_t n_records, const int64_t *
     return launch_pileup_stamp(e, n_records, out_off, part, shift, words, n_words);
 }
 
+int rmr_pileup_set_canonical(rmr_pileup *p, int base) {
+    if (!p || !p->eng) RMR_FAIL(RMR_ERR_INVALID, "bad argument");
+    if (base == 'U') base = 'T';
+    if (base != 'A' && base != 'C' && base != 'G' && base != 'T')
+        RMR_FAIL(RMR_ERR_INVALID, "the canonical base of a pileup is A, C, G, T or U, got character %d", base);
+    p->canonical = base;
+    return 0;
+}
+
+int rmr_pileup_cover(rmr_pileup *p, const rmr_modbam_batch *b, const rmr_pileup_ref *ref, const int32_t *status, const int64_t *cig_q,
+                     const int64_t *cig_r, const int64_t *out_off, const uint64_t *words, int64_t n_words, const int32_t *part, int shift) {
+    if (!p || !p->eng || !b) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    rmr_engine *e = p->eng;
+    if (!p->finished || p->used != 0) RMR_FAIL(RMR_ERR_INVALID, "rmr_pileup_cover before rmr_pileup_finish: the table is not complete");
+    if (!p->canonical) RMR_FAIL(RMR_ERR_INVALID, "rmr_pileup_cover before rmr_pileup_set_canonical: the canonical base is not known");
+    RMR_TRY(check_call_batch(b, -1, 0, 0));
+    if (n_words < 0 || (n_words > 0 && !words)) RMR_FAIL(RMR_ERR_INVALID, "bad n_words or NULL words");
+    if (b->n_records > 0 && (!status || !cig_q || !cig_r || !out_off || !b->seq || !b->cigar)) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    if (part && (shift < 36 || shift > 59)) RMR_FAIL(RMR_ERR_INVALID, "the partition field starts at bit 36 to 59 of a site word, got %d", shift);
+    PileupRef pr{};
+    const bool combine = ref && ref->combine != 0;
+    int fold_window = 0;
+    if (combine) {
+        RMR_TRY(fill_ref_part(e, b, ref, &pr));
+        for (int j = 0; j < pr.n_motifs; ++j) {  // a folded '-' word stands within max |len - 1 - 2 focus| of its own position
+            const int sh = pr.motifs[j].len - 1 - 2 * pr.motifs[j].focus;
+            fold_window = std::max(fold_window, 2 * (sh < 0 ? -sh : sh));
+        }
+        if (pr.n_motifs == 1) fold_window = 0;  // one motif: one shift, the folded words are strictly monotone
+    }
+    if (b->n_records == 0 || p->nt == 0) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    if (!p->cover) {
+        const size_t bytes = (size_t)p->nt * 3 * sizeof(uint32_t);
+        void *mem = nullptr;
+        if (hipMalloc(&mem, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            RMR_FAIL(RMR_ERR_NOMEM, "the coverage counts of %lld sites need %zu bytes of device memory and they could not be allocated", (long long)p->nt,
+                     bytes);
+        }
+        p->cover = static_cast<uint32_t *>(mem), p->cover_bytes = bytes;
+        RMR_HIP(hipMemsetAsync(p->cover, 0, bytes, e->stream));
+        if (p->work_bytes + p->t_bytes + bytes > p->peak_bytes) p->peak_bytes = p->work_bytes + p->t_bytes + bytes;
+    }
+    return launch_pileup_cover(p, *b, pr, combine, fold_window, status, cig_q, cig_r, out_off, words, n_words, part, shift);
+}
+
+int rmr_pileup_read_cover(rmr_pileup *p, uint32_t *cover) {
+    if (!p || !p->eng) RMR_FAIL(RMR_ERR_INVALID, "bad argument");
+    if (!p->finished || p->used != 0) RMR_FAIL(RMR_ERR_INVALID, "rmr_pileup_read_cover before rmr_pileup_finish: the table is not complete");
+    if (p->nt == 0) return 0;
+    if (!cover) RMR_FAIL(RMR_ERR_INVALID, "NULL argument");
+    rmr_engine *e = p->eng;
+    std::lock_guard<std::mutex> lk(e->mu);
+    RMR_HIP(hipSetDevice(e->device));
+    if (!p->cover) {  // no record was joined against this table
+        std::memset(cover, 0, (size_t)p->nt * 3 * sizeof(uint32_t));
+        return 0;
+    }
+    D2H(cover, p->cover, p->cover_bytes);
+    RMR_HIP(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
 void rmr_pileup_destroy(rmr_pileup *p) {
     if (!p) return;
     (void)hipSetDevice(p->eng->device);
     (void)hipStreamSynchronize(p->eng->stream);  // nothing may still read the buffer or the table when they are freed
+    if (p->cover) (void)hipFree(p->cover);
     if (p->work) (void)hipFree(p->work);
     if (p->t_mem) (void)hipFree(p->t_mem);
     delete p;

@@ -28,7 +28,7 @@ static const char *k_names[K_NUM] = {
     "base_metrics", "region_metrics", "region_signals", "site_kmer_levels", "modbam_sites", "rescale_points", "theil_sen_fit",
     "duplex_dp", "duplex_traceback", "duplex_lines", "duplex_backtrack", "train_gemm", "train_wgrad", "train_reduce", "train_bn", "train_lstm",
     "train_loss", "train_adamw", "train_aux", "read_index_build", "read_index_lookup", "pileup_emit", "pileup_flush", "ref_genome_pack", "pileup_stamp",
-    "pileup_pair"};
+    "pileup_pair", "pileup_cover"};
 const char *kernel_name(int id) { return (id >= 0 && id < K_NUM) ? k_names[id] : "?"; }
 
 }  // namespace rmr

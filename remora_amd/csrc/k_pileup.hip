@@ -16,6 +16,9 @@
 //   merge   into the resident table (ascending unique keys): every new row searches the table; a hit is added in place (keys
 //           are unique on both sides: no two threads touch one row), the misses are compacted and merged by rank - a row's
 //           place is its own index plus its lower bound in the other list - into a table allocated at its new size.
+//   cover   after the table is finished (--coverage-columns): every record against the sites of the table inside its reference
+//           span - a deletion there, another base than the canonical one, or the canonical base without a call - one block per
+//           record, two binary searches in the table's keys, one integer atomic per (record, site) into u32[n_sites][3].
 // Device memory: the work block (sized by the capacity of the call buffer) plus 8 + 4 ncol bytes per distinct site, twice
 // that while a merge copies the table.  All arithmetic is integer; the table does not depend on how the calls were cut
 // into batches or flushes.
@@ -137,6 +140,111 @@ __global__ __launch_bounds__(PU_THREADS) void stamp_partition_kernel(const int64
     for (int64_t i = lo + threadIdx.x; i < hi; i += PU_THREADS) words[i] |= field;
 }
 
+// ---- the coverage join ----
+// what the join needs beside the batch and the reference part
+struct CoverArgs {
+    const int32_t *status;          // the emit's, per record
+    const int64_t *cig_q, *cig_r;   // the count pass's prefix sums, indexed like b.cigar
+    const int64_t *out_off;         // the record's slice of `words`
+    const uint64_t *words;
+    int64_t n_words;
+    const int32_t *part;            // nullable
+    int shift;                      // the partition field's first bit in a word
+    int canonical;                  // 'A' 'C' 'G' 'T'
+    int fold_window;
+    const uint64_t *t_keys;
+    int64_t nt;
+    uint32_t *cover;                // u32[nt][3]: delete, diff, nocall
+};
+
+// does one of words[lo, hi) have the site key `key`?  The slice is monotone in its keys - ascending when !desc - up to `window`
+// places (the folded '-' words of several motifs): a binary search for the place where the keys pass `key`, then the words
+// within `window` of it.
+__device__ inline bool slice_has_key(const uint64_t *__restrict__ words, int64_t lo, int64_t hi, uint64_t key, bool desc, int window) {
+    int64_t a = lo, z = hi;
+    while (a < z) {
+        const int64_t mid = a + ((z - a) >> 1);
+        const uint64_t k = words[mid] >> 4;
+        if (desc ? k > key : k < key) a = mid + 1;
+        else z = mid;
+    }
+    const int64_t from = a - window > lo ? a - window : lo, to = a + window + 1 < hi ? a + window + 1 : hi;
+    for (int64_t i = from; i < to; ++i)
+        if ((words[i] >> 4) == key) return true;
+    return false;
+}
+
+// One block per record, its lanes striding over the sites of the resident table inside the record's span.  COMBINE: the table
+// is that of a combined emit (`rf` is read).
+template <bool COMBINE>
+__global__ __launch_bounds__(PU_THREADS) void cover_kernel(rmr_modbam_batch b, CoverArgs ca, PileupRef rf) {
+    const int64_t r = blockIdx.x;
+    if (ca.status[r] != 0) return;
+    const int64_t c0 = b.cigar_off[r], nc = b.cigar_off[r + 1] - c0;
+    const int64_t s0 = b.seq_off[r], L = b.seq_off[r + 1] - s0;
+    const int64_t rid = b.ref_id[r], pos = b.pos[r];
+    if (nc <= 0 || rid < 0 || rid >= b.n_refs || pos < 0) return;
+    const bool rev = (b.flag[r] & 0x10) != 0;
+    const uint32_t last = b.cigar[c0 + nc - 1];
+    const int last_op = (int)(last & 15u);
+    const int64_t span = ca.cig_r[c0 + nc - 1] + ((last_op == 0 || last_op == 2 || last_op == 3 || last_op == 7 || last_op == 8) ? (int64_t)(last >> 4) : 0);
+    if (span <= 0) return;
+    // the sites that can be asked: positions [p_lo, p_hi) of the record's contig (and partition)
+    const int64_t reach = COMBINE && rev ? RMR_PILEUP_MAX_MOTIF_LEN - 1 : 0;
+    int64_t p_lo = pos - reach, p_hi = pos + span + reach;
+    if (p_lo < 0) p_lo = 0;
+    if (p_hi > ((int64_t)1 << 31)) p_hi = (int64_t)1 << 31;
+    const uint64_t id = ca.part ? (uint64_t)(uint32_t)ca.part[r] : 0ull;
+    const uint64_t prefix = (ca.part ? id << (ca.shift - 4) : 0ull) | ((uint64_t)rid << 32);
+    const int64_t i_lo = lower_bound_u64(ca.t_keys, 0, ca.nt, prefix | ((uint64_t)p_lo << 1));
+    const int64_t i_hi = lower_bound_u64(ca.t_keys, i_lo, ca.nt, prefix + ((uint64_t)p_hi << 1));  // (p_hi = 2^31 carries into the contig)
+    const uint64_t want_strand = COMBINE ? 0ull : (rev ? 1ull : 0ull);
+    int64_t w_lo = ca.out_off[r], w_hi = ca.out_off[r + 1];
+    if (w_lo < 0) w_lo = 0;
+    if (w_hi > ca.n_words) w_hi = ca.n_words;
+    const int64_t off = COMBINE ? rf.off[rid] : 0, len = COMBINE ? rf.len[rid] : 0;
+    for (int64_t i = i_lo + threadIdx.x; i < i_hi; i += PU_THREADS) {
+        const uint64_t key = ca.t_keys[i];
+        if ((key & 1ull) != want_strand) continue;
+        const int64_t site = (int64_t)((key >> 1) & 0x7fffffffull);
+        int64_t rp = site;
+        if (COMBINE && rev) {  // the '-' focus of the first motif at the site
+            bool found = false;
+            for (int j = 0; j < rf.n_motifs && !found; ++j) {
+                const rmr_pileup_motif &mo = rf.motifs[j];
+                if (motif_window(rf.data, off, len, site - mo.focus, mo.len, mo.mask)) rp = site + (mo.len - 1 - 2 * mo.focus), found = true;
+            }
+            if (!found) continue;
+        }
+        const int64_t x = rp - pos;
+        if (x < 0 || x >= span) continue;
+        int64_t a = 0, z = nc;  // the last operation with cig_r <= x: the one that holds x
+        while (a < z) {
+            const int64_t mid = a + ((z - a) >> 1);
+            if (ca.cig_r[c0 + mid] <= x) a = mid + 1;
+            else z = mid;
+        }
+        if (a < 1) continue;
+        const int64_t ci = a - 1;
+        const uint32_t w = b.cigar[c0 + ci];
+        const int op = (int)(w & 15u);
+        const int64_t within = x - ca.cig_r[c0 + ci];
+        if (within >= (int64_t)(w >> 4)) continue;  // (never for a CIGAR whose sums these are)
+        int col;
+        if (op == 2) col = 0;
+        else if (op == 0 || op == 7 || op == 8) {
+            const int64_t sp = ca.cig_q[c0 + ci] + within;
+            if (sp < 0 || sp >= L) continue;
+            int c = (int)b.seq[s0 + sp];
+            if (c == 'U') c = 'T';
+            if (rev) c = complement(c);
+            col = c == ca.canonical ? 2 : 1;
+        } else continue;  // an N skip
+        if (slice_has_key(ca.words, w_lo, w_hi, key, rev, COMBINE && rev ? ca.fold_window : 0)) continue;  // a kept call: it is in the row
+        atomicAdd(&ca.cover[i * 3 + col], 1u);
+    }
+}
+
 // rocPRIM's scratch for the sort and the scan of n entries, whichever is larger
 int scratch_bytes(int64_t n, int end_bit, size_t *bytes) {
     size_t sort_b = 0, scan_b = 0;
@@ -184,6 +292,19 @@ int launch_pileup_stamp(rmr_engine *e, int64_t n_records, const int64_t *out_off
     if (n_records <= 0) return 0;
     ProfScope ps(e, K_PILEUP_STAMP);
     hipLaunchKernelGGL(stamp_partition_kernel, dim3((unsigned)n_records), dim3(PU_THREADS), 0, e->stream, out_off, part, shift, words, n_words);
+    RMR_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_pileup_cover(rmr_pileup *p, const rmr_modbam_batch &b, const PileupRef &pr, bool combine, int fold_window, const int32_t *status,
+                        const int64_t *cig_q, const int64_t *cig_r, const int64_t *out_off, const uint64_t *words, int64_t n_words,
+                        const int32_t *part, int shift) {
+    rmr_engine *e = p->eng;
+    if (b.n_records <= 0 || p->nt <= 0 || !p->cover) return 0;
+    ProfScope ps(e, K_PILEUP_COVER);
+    const CoverArgs ca{status, cig_q, cig_r, out_off, words, n_words, part, shift, p->canonical, fold_window, p->t_keys, p->nt, p->cover};
+    if (combine) hipLaunchKernelGGL(cover_kernel<true>, dim3((unsigned)b.n_records), dim3(PU_THREADS), 0, e->stream, b, ca, pr);
+    else hipLaunchKernelGGL(cover_kernel<false>, dim3((unsigned)b.n_records), dim3(PU_THREADS), 0, e->stream, b, ca, pr);
     RMR_HIP(hipGetLastError());
     return 0;
 }
@@ -272,6 +393,14 @@ int pileup_flush(rmr_pileup *p) {
 // n words (device) into the call buffer, flushing whenever it is full
 int pileup_append(rmr_pileup *p, const uint64_t *words, int64_t n) {
     rmr_engine *e = p->eng;
+    if (n > 0) {
+        p->finished = false;
+        if (p->cover) {  // counted against a table that is about to change: dropped once nothing writes it any more
+            RMR_HIP(hipStreamSynchronize(e->stream));
+            (void)hipFree(p->cover);
+            p->cover = nullptr, p->cover_bytes = 0;
+        }
+    }
     for (int64_t at = 0; at < n;) {
         const int64_t take = std::min(n - at, p->cap - p->used);
         RMR_HIP(hipMemcpyAsync(p->buf[0] + p->used, words + at, (size_t)take * 8, hipMemcpyDeviceToDevice, e->stream));

@@ -90,6 +90,7 @@ enum KernelId {
     K_REF_GENOME_PACK,  // one piece of a contig's FASTA text into nibbles, verified (k_ref_genome.hip)
     K_PILEUP_STAMP,  // the partition id into the words of a batch (k_pileup.hip)
     K_PILEUP_PAIR,   // the two strands' calls of a record paired into pattern words (k_pileup_duplex.hip)
+    K_PILEUP_COVER,  // the coverage join: every record against the sites of the resident table it spans (k_pileup.hip)
     K_NUM
 };
 const char *kernel_name(int id);
@@ -222,6 +223,12 @@ struct rmr_pileup {
     uint32_t *t_counts = nullptr;
     int64_t nt = 0, n_calls = 0, n_flushes = 0;
     size_t peak_bytes = 0;
+    // the coverage join (rmr_pileup_cover): u32[nt][3] - delete, diff, nocall - beside the table, allocated and zeroed by the
+    // first join after a finish and dropped when words are added again
+    bool finished = false;           // rmr_pileup_finish has run and no word was added since
+    int canonical = 0;               // rmr_pileup_set_canonical: 'A' 'C' 'G' 'T', 0 while unset
+    uint32_t *cover = nullptr;
+    size_t cover_bytes = 0;
 };
 
 // ---- reference genome (k_ref_genome.hip) ---------------------------------------------------
@@ -276,6 +283,12 @@ int pileup_alloc(rmr_pileup *p);
 int pileup_append(rmr_pileup *p, const uint64_t *words, int64_t n);
 int pileup_flush(rmr_pileup *p);
 int launch_pileup_stamp(rmr_engine *e, int64_t n_records, const int64_t *out_off, const int32_t *part, int shift, uint64_t *words, int64_t n_words);
+// the coverage join of one batch against the table of `p` (finished, nt > 0, p->cover allocated).  combine: `pr` is read and a
+// '-' record is asked at the '-' focus of the first motif at a site; fold_window: how many words before and behind the place a
+// binary search ends at are compared with a site's key (0 where a record's words are strictly monotone)
+int launch_pileup_cover(rmr_pileup *p, const rmr_modbam_batch &b, const PileupRef &pr, bool combine, int fold_window, const int32_t *status,
+                        const int64_t *cig_q, const int64_t *cig_r, const int64_t *out_off, const uint64_t *words, int64_t n_words,
+                        const int32_t *part, int shift);
 // k_pileup_duplex.hip: the emit that counts '-'-strand entries too (has_ref: with the reference part `pr`; pr.combine == 2 is
 // the hemi mode of the fill: folded positions, strand bits kept), and the two passes that pair a record's '+' and '-' words
 int launch_modbam_calls_duplex(rmr_engine *e, const rmr_modbam_batch &b, const PileupEmit &pe, const PileupRef &pr, bool has_ref, int32_t *ords,

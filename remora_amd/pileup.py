@@ -26,7 +26,11 @@ of the whole input ("Pileup: the partition field").
 With `duplex` the '-'-strand entries of duplex records count too, on the reference strand opposite to the record's
 (rmr_modbam_call_counts_duplex / _fill_duplex); with `hemi` the '+' and the '-' call of one record at one motif site are paired
 on the device (rmr_pileup_pair_counts / _fill, csrc/k_pileup_duplex.hip) and the table counts the strand patterns per site
-("Pileup: duplex entries and strand pairs")."""
+("Pileup: duplex entries and strand pairs").
+
+With `coverage` the BAMs are streamed once more after the table is finished and every record is joined on the device against
+the sites it spans (rmr_pileup_cover): N_delete, N_diff and N_nocall per site, the columns that make the bedMethyl the
+eighteen-column form ("Pileup: the coverage join")."""
 import ctypes
 import logging
 import mmap
@@ -74,15 +78,17 @@ class PileupTable(_PileupFields):
     A run with `hemi` has two more of that kind, hemi=True and n_unpaired: one row per motif site (its '+' position; combined is
     set) and counts i64[n, (n_mods + 2)^2] indexed by the pattern code a (n_mods + 2) + b - a / b the class of the '+' / '-' call
     of a pair, 0 canonical, 1 .. n_mods the modified bases, n_mods + 1 fail; n_calls counts the pairs, n_unpaired the kept
-    calls without a partner in their record, and hist / threshold_k are those of all kept single calls."""
+    calls without a partner in their record, and hist / threshold_k are those of all kept single calls.
+    A run with `coverage` has one more of that kind: coverage i64[n, 3], per row the records that cover the site without a call
+    there - N_delete, N_diff, N_nocall (pileup_modbams) - and None otherwise."""
 
-    partition = partition_labels = partition_tag = n_unpaired = None
+    partition = partition_labels = partition_tag = n_unpaired = coverage = None
     hemi = False
 
-    def __new__(cls, *args, partition=None, partition_labels=None, partition_tag=None, hemi=False, n_unpaired=None, **fields):
+    def __new__(cls, *args, partition=None, partition_labels=None, partition_tag=None, hemi=False, n_unpaired=None, coverage=None, **fields):
         self = super().__new__(cls, *args, **fields)
         self.partition, self.partition_labels, self.partition_tag = partition, partition_labels, partition_tag
-        self.hemi, self.n_unpaired = bool(hemi), n_unpaired
+        self.hemi, self.n_unpaired, self.coverage = bool(hemi), n_unpaired, coverage
         return self
 
 
@@ -606,6 +612,23 @@ class DevicePileup:
         self._L.check(self._lib.rmr_pileup_read(self.h, keys.ctypes.data_as(ctypes.c_void_p), counts.ctypes.data_as(ctypes.c_void_p)))
         return keys[:n_sites], counts[:n_sites]
 
+    def set_canonical(self, base):
+        """The canonical base of the table (rmr_pileup_set_canonical): what the coverage join tells N_nocall from N_diff by."""
+        self._L.check(self._lib.rmr_pileup_set_canonical(self.h, ord(str(base))))
+
+    def cover(self, b, pref, status, cig_q, cig_r, out_off, words, n_words, part=None, shift=0):
+        """rmr_pileup_cover for one batch: device tensors of the emit of that batch (words may be None when n_words is 0), kept
+        alive by the caller until the engine's stream has passed them."""
+        self._L.check(self._lib.rmr_pileup_cover(self.h, ctypes.byref(b), None if pref is None else ctypes.byref(pref), status.data_ptr(),
+                                                 cig_q.data_ptr(), cig_r.data_ptr(), out_off.data_ptr(), None if words is None else words.data_ptr(),
+                                                 int(n_words), None if part is None else part.data_ptr(), int(shift)))
+
+    def read_cover(self, n_sites):
+        """u32[n_sites, 3]: N_delete, N_diff, N_nocall per site, in the order of read()'s keys."""
+        cover = np.zeros((max(n_sites, 1), 3), np.uint32)
+        self._L.check(self._lib.rmr_pileup_read_cover(self.h, cover.ctypes.data_as(ctypes.c_void_p)))
+        return cover[:n_sites]
+
     def close(self):
         if self.h:
             self._lib.rmr_pileup_destroy(self.h)
@@ -618,13 +641,14 @@ class DevicePileup:
         self.close()
 
 
-def _emit_batch(eng, b, region, k_t, hist, n_cig, n_deltas, pref=None, part=None, shift=0, duplex=False, n_codes=0):
+def _emit_batch(eng, b, region, k_t, hist, n_cig, n_deltas, pref=None, part=None, shift=0, duplex=False, n_codes=0, cover=None):
     """One batch through the emit: the count pass (with the histogram when `hist` is a device tensor), and - k_t not None -
     the fill pass.  `pref`: the rmr_pileup_ref of a run with a reference, or None.  `part` (i32 per record, a partitioned run):
     after the fill pass the records' partition ids are stamped into their words from bit `shift`.  `duplex`: the emit that
     counts '-'-strand entries.  `n_codes` (a hemi run: n_mods + 2): the fill keeps the strand bits and its words go through the
-    pair passes - what comes back are the pair words.  -> (words device tensor or None, calls per record, status per record,
-    pairs in the batch or None)."""
+    pair passes - what comes back are the pair words.  `cover` (the DevicePileup of a finished table; the pass of `coverage`):
+    the batch is joined against the table's sites, rmr_pileup_cover, while its workspaces are alive - also when it has no word.
+    -> (words device tensor or None, calls per record, status per record, pairs in the batch or None)."""
     from . import _lib as L
     from .engine import _torch
 
@@ -672,12 +696,20 @@ def _emit_batch(eng, b, region, k_t, hist, n_cig, n_deltas, pref=None, part=None
                 words = torch.empty(n_pairs, dtype=torch.int64, device=dev)
                 L.check(lib.rmr_pileup_pair_fill(eng.handle, n, d_off.data_ptr(), singles.data_ptr(), total, int(n_codes), d_pair_off.data_ptr(),
                                                  words.data_ptr()))
+        if cover is not None:
+            cover.cover(b, pref, d_status, cig_qr[0], cig_qr[1], d_off, words, total, d_part if part is not None else None, shift)
         eng.synchronize()  # the inputs and the workspaces may go once the kernel is through
+    elif cover is not None and n:  # no word in the batch: its status-0 records still cover sites
+        d_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        d_part = None if part is None else torch.from_numpy(np.ascontiguousarray(part, np.int32)).to(dev)
+        cover.cover(b, pref, d_status, cig_qr[0], cig_qr[1], d_off, None, 0, d_part, shift)
+        eng.synchronize()
     return words, h_counts, h_status, n_pairs
 
 
 def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_FILT, region=None, device=None, batch=512, buffer_calls=None,
-                   device_gib=DEFAULT_DEVICE_GIB, ref=None, motifs=None, combine_strands=False, partition_tag=None, duplex=False, hemi=False):
+                   device_gib=DEFAULT_DEVICE_GIB, ref=None, motifs=None, combine_strands=False, partition_tag=None, duplex=False, hemi=False,
+                   coverage=False):
     """The per-site counts of the modified-base calls of `bams` (one path or several, piled into one table) -> PileupTable.
     `alphabet`: the canonical base followed by 1 to 7 single-letter modified-base codes.  The threshold: either
     `filter_threshold` T (k_T = ceil(512 T); give pct_filt=None with it) or `pct_filt` P - then a first pass over the input
@@ -701,12 +733,25 @@ def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_F
     combine_strands nor partition_tag): one row per motif site with the counts of the strand pairs - the '+' call at rp and
     the '-' call at rp + (len - 1 - 2 focus) of ONE record are a pair of pattern (class on '+', class on '-'); a kept call
     without a partner in its record is counted in n_unpaired only.  The threshold is that of all kept single calls.
+    `coverage` (not with duplex or hemi): once the table is finished the BAMs are streamed once more and every record that
+    ended the emit with status 0 - also one none of whose calls was kept - is asked about every site of the table on its
+    contig, on its strand, in its partition, whose position rp lies in its reference span.  The first rule that fits: the
+    record has a kept call at the site (passing or fail): nothing, it is in the row; rp lies inside a D: N_delete + 1; rp lies
+    inside M / = / X: the base of the original read there (U as T) is the canonical base: N_nocall + 1, anything else, N
+    included: N_diff + 1; an N skip: nothing.  Only the positions an MM entry lists are calls, for `.` and `?` alike, and a
+    position listed only with codes outside the alphabet is no call either: both are N_nocall.  With combine_strands a '+'
+    record is asked at rp = S of a site S, a '-' record at S + (len - 1 - 2 focus) of the first motif, in the order given, that
+    matches the reference at S.  The table, the threshold and the histogram are those of the run without it; the PileupTable
+    has `coverage` set, and the writers print the eighteen-column bedMethyl.  12 bytes of device memory per site more.
     Everything that is refused is refused before any pileup launch; RemoraError when no call is kept.  (What a partition tag
     is refused for - another type, both kinds in one run, too many values - is known when the batch with that record is read:
     before any launch for that batch, and before any file is written.)"""
     bams = [bams] if isinstance(bams, (str, bytes)) or hasattr(bams, "__fspath__") else list(bams)
     if not bams:
         raise RemoraError("pileup_modbams needs at least one BAM")
+    if coverage and (duplex or hemi):
+        raise RemoraError(f"--coverage-columns with {'--hemi' if hemi else '--duplex'} is not built: there a record stands for two strands; "
+                          "give one of them")
     if filter_threshold is not None and pct_filt is not None:
         raise RemoraError("give either --filter-threshold or --pct-filt, not both")
     if filter_threshold is None and pct_filt is None:
@@ -748,16 +793,16 @@ def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_F
         if genome is not None:
             pref = _pileup_ref_struct(genome, descriptors, combine_strands or hemi)
         return _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens, device, batch, buffer_calls, device_gib, genome, pref,
-                           bool(combine_strands or hemi), parts, duplex, bool(hemi))
+                           bool(combine_strands or hemi), parts, duplex, bool(hemi), bool(coverage))
     finally:
         if genome is not None and genome is not ref:
             genome.close()
 
 
 def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens, device, batch, buffer_calls, device_gib, genome, pref, combined,
-                parts=None, duplex=False, hemi=False):
+                parts=None, duplex=False, hemi=False, coverage=False):
     """pileup_modbams once its arguments are checked and the reference is on the device.  `parts`: the Partitioner of a run with
-    a partition tag."""
+    a partition tag.  `coverage`: the third pass, the coverage join against the finished table."""
     from .engine import _torch, get_engine
     from .io import _readahead, iter_bam_raw_batches
     from .validate import modbam_device_batch, tokenise_mod_tags, warn_ignored_entries
@@ -776,9 +821,10 @@ def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens,
                     f"{free / 2**30:.1f} GiB free)")
     warn = {"strand": not duplex, "mod": True}  # (in a duplex run the '-' entries count: nothing to warn of)
 
-    def one_pass(k_fill, hist, pile, log_skipped):
-        """All BAMs once: the count pass of every batch, and with k_fill the fill pass and the append.  -> (kept calls, pairs)."""
-        n_kept = n_paired = 0
+    def one_pass(k_fill, hist, pile, log_skipped, cover=False):
+        """All BAMs once: the count pass of every batch, and with k_fill the fill pass and the append - or, `cover`, the coverage
+        join against the finished table of `pile` in place of the append.  -> (kept calls, pairs)."""
+        n_kept = n_paired = n_asked = 0
         for path in bams:
             skipped, n_records = {}, 0
 
@@ -793,10 +839,16 @@ def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens,
                 buf, b = modbam_device_batch(dev, mods, rb.seq, rb.seq_off, rb.cigar, rb.cigar_off, rb.flag, rb.ref_id, rb.pos, rb.has, tok)
                 b.n_refs = len(ref_names)
                 words, h_counts, h_status, n_pairs = _emit_batch(eng, b, reg, k_fill, hist, int(np.asarray(rb.cigar).size), int(tok[5].size), pref,
-                                                                   part, 0 if parts is None else parts.plan.shift, duplex, n_codes)
+                                                                   part, 0 if parts is None else parts.plan.shift, duplex, n_codes,
+                                                                   pile if cover else None)
                 n_paired += n_pairs or 0
                 del buf
-                if words is not None:
+                if cover:  # a record adds at most 1 per site and column: 2^32 of them could pass a u32 count
+                    n_asked += int(np.count_nonzero(h_status == 0))
+                    if n_asked >= 2**32:
+                        raise RemoraError(f"--coverage-columns: {n_asked} records take part, N_delete / N_diff / N_nocall are counted in 32 bits "
+                                          "(fewer than 2^32 records)")
+                elif words is not None:
                     pile.add(words, words.numel())
                     eng.synchronize()  # the words are in the call buffer (or the table) now
                 n_kept += int(h_counts.sum())
@@ -837,6 +889,16 @@ def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens,
         if n_calls != (n_paired if hemi else n_kept):
             raise RemoraError(f"pileup: {n_calls} calls reached the table, the records hold {n_paired if hemi else n_kept}")
         keys, counts = pile.read(n_sites)
+        cover = None
+        if coverage:  # the third pass: the same emit with the final k_T and no histogram, joined against the finished table
+            pile.set_canonical(alphabet[0])
+            n_again, _ = one_pass(k_t, None, pile, False, cover=True)
+            if n_again != n_kept:
+                raise RemoraError(f"pileup: the coverage pass kept {n_again} calls, the pass before it {n_kept}: the input changed between them")
+            peak = pile.finish()[3]  # (nothing to flush: the peak with the coverage counts in it)
+            cover = pile.read_cover(n_sites).astype(np.int64)
+            LOGGER.info(f"--coverage-columns: N_delete {int(cover[:, 0].sum())}, N_diff {int(cover[:, 1].sum())}, N_nocall "
+                        f"{int(cover[:, 2].sum())} on {n_sites} sites")
     if genome is not None:
         peak += genome.device_bytes
     if hemi:
@@ -848,7 +910,7 @@ def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens,
                         pos=((keys >> np.uint64(1)) & np.uint64(0x7FFFFFFF)).astype(np.int64), strand=(keys & np.uint64(1)).astype(np.uint8),
                         counts=counts.astype(np.int64), alphabet=alphabet, threshold_k=int(k_t), n_calls=n_calls, n_flushes=n_flushes,
                         peak_device_bytes=peak, hist=None if h_hist is None else h_hist.astype(np.int64), combined=combined,
-                        hemi=hemi, n_unpaired=n_kept - 2 * n_calls if hemi else None)
+                        hemi=hemi, n_unpaired=n_kept - 2 * n_calls if hemi else None, coverage=cover)
     return table if parts is None else _partitioned(table, parts)
 
 
@@ -868,7 +930,8 @@ def _partitioned(table, parts):
     order = np.argsort(partition, kind="stable")
     rows = table._replace(ref_id=(table.ref_id & np.int32((1 << cb) - 1))[order], pos=table.pos[order], strand=table.strand[order],
                           counts=table.counts[order])
-    return PileupTable(*rows, partition=partition[order], partition_labels=[partition_label(k) for k in ordered], partition_tag=parts.tag)
+    return PileupTable(*rows, partition=partition[order], partition_labels=[partition_label(k) for k in ordered], partition_tag=parts.tag,
+                       coverage=None if table.coverage is None else table.coverage[order])
 
 
 def _finish(pile, ref_names, parts=None):
@@ -895,11 +958,14 @@ def write_bedmethyl(table, path, min_coverage=1):
     A hemi table: per site whose N_valid - the pairs whose two classes both pass - reaches the coverage, one row per pattern of
     passing classes, (n_mods + 1)^2 rows ordered by the '+' class, then the '-' class; the name column is `<a>,<b>,<canonical>`
     (a modified base's code, `-` for the canonical class: m,m,C  m,-,C  -,m,C  -,-,C), the strand column `.`, pct = 100
-    N_pattern / N_valid."""
+    N_pattern / N_valid.
+    A table with `coverage`: eighteen columns, all tab-separated - the eleven, then N_mod N_canonical N_other_mod N_delete
+    N_fail N_diff N_nocall, N_other_mod = N_valid - N_mod - N_canonical of that row's code; the same rows."""
     if getattr(table, "hemi", False):
         return _write_bedmethyl_hemi(table, path, min_coverage)
     mods = list(table.alphabet[1:])
     combined = bool(getattr(table, "combined", False))
+    coverage = getattr(table, "coverage", None)
     valid = table.counts[:, :-1].sum(axis=1)
     keep = np.nonzero(valid >= max(int(min_coverage), 1))[0]
     n_rows = 0
@@ -907,12 +973,14 @@ def write_bedmethyl(table, path, min_coverage=1):
         for lo in range(0, keep.size, 65536):
             lines = []
             idx = keep[lo : lo + 65536]
-            for rid, pos, st, nv, row in zip(table.ref_id[idx].tolist(), table.pos[idx].tolist(), table.strand[idx].tolist(), valid[idx].tolist(),
-                                             table.counts[idx].tolist()):
+            cover = [None] * idx.size if coverage is None else coverage[idx].tolist()
+            for rid, pos, st, nv, row, cov in zip(table.ref_id[idx].tolist(), table.pos[idx].tolist(), table.strand[idx].tolist(),
+                                                  valid[idx].tolist(), table.counts[idx].tolist(), cover):
                 name, sc = table.ref_names[rid], "." if combined else "-" if st else "+"
                 for j, code in enumerate(mods):
+                    more = "" if cov is None else f"\t{row[1 + j]}\t{row[0]}\t{nv - row[1 + j] - row[0]}\t{cov[0]}\t{row[-1]}\t{cov[1]}\t{cov[2]}"
                     lines.append(f"{name}\t{pos}\t{pos + 1}\t{code}\t{min(nv, 1000)}\t{sc}\t{pos}\t{pos + 1}\t255,0,0\t{nv}\t"
-                                 f"{100 * row[1 + j] / nv:.2f}\n")
+                                 f"{100 * row[1 + j] / nv:.2f}{more}\n")
             fh.write("".join(lines))
             n_rows += len(lines)
     return n_rows
@@ -942,7 +1010,8 @@ def _write_bedmethyl_hemi(table, path, min_coverage):
 def write_counts(table, path):
     """TSV with the header chrom start strand N_<canonical> N_<code>... N_fail: one row per site that has a kept call.  A hemi
     table: N_<a>_<b> for all (n_mods + 2)^2 pattern codes in code order, the classes named by the canonical base's letter, the
-    modified bases' codes and `fail`; one row per site that has a pair."""
+    modified bases' codes and `fail`; one row per site that has a pair.  A table with `coverage`: N_delete N_diff N_nocall behind
+    N_fail."""
     if getattr(table, "hemi", False):
         cls = hemi_class_names(table.alphabet)
         with open(path, "w") as fh:
@@ -953,13 +1022,15 @@ def write_counts(table, path):
                                  for rid, pos, row in zip(table.ref_id[sl].tolist(), table.pos[sl].tolist(), table.counts[sl].tolist())))
         return int(table.pos.size)
     combined = bool(getattr(table, "combined", False))
+    coverage = getattr(table, "coverage", None)
     with open(path, "w") as fh:
-        fh.write("\t".join(["chrom", "start", "strand"] + [f"N_{a}" for a in table.alphabet] + ["N_fail"]) + "\n")
+        fh.write("\t".join(["chrom", "start", "strand"] + [f"N_{a}" for a in table.alphabet] + ["N_fail"] +
+                           ([] if coverage is None else ["N_delete", "N_diff", "N_nocall"])) + "\n")
         for lo in range(0, table.pos.size, 65536):
             sl = slice(lo, lo + 65536)
+            rows = table.counts[sl].tolist() if coverage is None else np.concatenate([table.counts[sl], coverage[sl]], axis=1).tolist()
             fh.write("".join(f"{table.ref_names[rid]}\t{pos}\t{'.' if combined else '-' if st else '+'}\t" + "\t".join(map(str, row)) + "\n"
-                             for rid, pos, st, row in zip(table.ref_id[sl].tolist(), table.pos[sl].tolist(), table.strand[sl].tolist(),
-                                                          table.counts[sl].tolist())))
+                             for rid, pos, st, row in zip(table.ref_id[sl].tolist(), table.pos[sl].tolist(), table.strand[sl].tolist(), rows)))
     return int(table.pos.size)
 
 
@@ -974,6 +1045,7 @@ def partition_tables(table):
         rows = np.nonzero(table.partition == k)[0]
         out[label] = table._replace(ref_id=table.ref_id[rows], pos=table.pos[rows], strand=table.strand[rows], counts=table.counts[rows],
                                     n_calls=int(table.counts[rows].sum()))  # (a plain table: _replace leaves the partition attributes behind)
+        out[label].coverage = None if table.coverage is None else table.coverage[rows]
     return out
 
 
