@@ -399,23 +399,6 @@ int rmr_modbam_site_fill(rmr_engine *e, const rmr_modbam_batch *b, const int32_t
 #define RMR_PILEUP_BINS 513                          /* 512 x the winning probability of a call: 0 .. 512 */
 #define RMR_PILEUP_MAX_CONTIGS ((int64_t)1 << 24)
 #define RMR_PILEUP_MAX_POS ((int64_t)1 << 31)       /* positions lie below it */
-/* The emit (GPU; DEVICE pointers only, asynchronous on the engine's stream): the walk of rmr_modbam_site_counts / _fill
- * with another end.  The batch is the same struct; n_refs is the header's contig count and truth_off / truth_pos /
- * truth_label are not read.  Differences to the site join:
- *   - a record is skipped whole with status 3 when ref_id < 0 or flag & 0x4, 6 when flag & 0x900 (secondary, supplementary),
- *     2 when ref_id >= n_refs; an MD tag is not asked for (no status 4); statuses 1, 2 and 5 as there;
- *   - every called base inside M / = / X is kept - when region_ref >= 0, only on that contig at region_lo <= pos < region_hi;
- *   - the call is classified in integers: k_j = 2 ML + 1 for a listed code (the later entry wins), 0 for the other modified
- *     bases, column 0 = 512 - sum; class = the first largest column, kmax = its value.
- * rmr_modbam_call_counts: counts / status / workspaces as rmr_modbam_site_counts; hist (nullable, u64[RMR_PILEUP_BINS],
- * zeroed by the caller once) gets +1 at kmax for every kept call of every record that ends with status 0.
- * rmr_modbam_call_fill: one site word per kept call into words[out_off[r] .. out_off[r+1]) (a record's calls in the order
- * of the walk along the original sequence), its code `fail` where kmax < k_t. */
-int rmr_modbam_call_counts(rmr_engine *e, const rmr_modbam_batch *b, int32_t region_ref, int64_t region_lo, int64_t region_hi,
-                           int32_t *ords, int64_t *cig_q, int64_t *cig_r, int64_t *counts, int32_t *status, uint64_t *hist);
-int rmr_modbam_call_fill(rmr_engine *e, const rmr_modbam_batch *b, int32_t region_ref, int64_t region_lo, int64_t region_hi, int32_t k_t,
-                         const int32_t *ords, const int64_t *cig_q, const int64_t *cig_r, const int32_t *status, const int64_t *out_off,
-                         uint64_t *words);
 /* The reference genome on the device (GPU), for the motif test and the strand fold of the emit below.
  * Form: one nibble per base, two bases per byte, low nibble first; every contig starts on a byte boundary; sum of
  * ceil(len / 2) bytes (1.55 GB for a human genome) plus 16 bytes per contig.  A code is the IUPAC set of the letter as a mask:
@@ -440,7 +423,20 @@ int rmr_ref_genome_load(rmr_ref_genome *g, int64_t contig, const uint8_t *text, 
                         int64_t piece_bytes, int64_t *bad_offset);
 int rmr_ref_genome_read(rmr_ref_genome *g, int64_t contig, int64_t lo, int64_t hi, uint8_t *codes);
 void rmr_ref_genome_destroy(rmr_ref_genome *g);
-/* The emit with a reference: a call is kept only where the reference shows a motif around it.
+/* The emit (GPU; DEVICE pointers only, asynchronous on the engine's stream): the walk of rmr_modbam_site_counts / _fill
+ * with another end.  The batch is the same struct; n_refs is the header's contig count and truth_off / truth_pos /
+ * truth_label are not read.  Differences to the site join:
+ *   - a record is skipped whole with status 3 when ref_id < 0 or flag & 0x4, 6 when flag & 0x900 (secondary, supplementary),
+ *     2 when ref_id >= n_refs; an MD tag is not asked for (no status 4); statuses 1, 2 and 5 as there;
+ *   - every called base inside M / = / X is kept - when region_ref >= 0, only on that contig at region_lo <= pos < region_hi;
+ *   - the call is classified in integers: k_j = 2 ML + 1 for a listed code (the later entry wins), 0 for the other modified
+ *     bases, column 0 = 512 - sum; class = the first largest column, kmax = its value.
+ * rmr_pileup_emit_counts: counts / status / workspaces as rmr_modbam_site_counts; hist (nullable, u64[RMR_PILEUP_BINS],
+ * zeroed by the caller once) gets +1 at kmax for every kept call of every record that ends with status 0.
+ * rmr_pileup_emit_fill: one site word per kept call into words[out_off[r] .. out_off[r+1]) (a record's calls in the order
+ * of the walk along the original sequence), its code `fail` where kmax < k_t (0 .. RMR_PILEUP_BINS).
+ * Both take the same rmr_pileup_emit_opts (HOST struct, read before the call returns): the region, and three modes.
+ * ref != NULL: a call is kept only where the reference shows a motif around it.
  * A motif: len bases (1 .. RMR_PILEUP_MAX_MOTIF_LEN), the called base at index focus; mask = len nibbles of IUPAC codes, base
  * i in bits 4 i .. 4 i + 3; rc_mask = its reverse complement, nibble i = the 4 bits of nibble len - 1 - i of mask reversed.
  * A reference code r matches a nibble m iff r != 0 and (r & ~m) == 0 - everything the reference allows, the motif allows; a
@@ -449,10 +445,21 @@ void rmr_ref_genome_destroy(rmr_ref_genome *g);
  * leaves the contig does not match.  The call is kept iff a motif matches; the first that does, in array order, is its motif.
  * combine != 0 (every motif must then be its own reverse complement, mask == rc_mask): a kept '-' call is written on '+' at
  * rp - (len - 1 - 2 focus) of its motif - the focus of the same window read on '+' - and the table has one row per motif site.
- * The region is asked of the position that is written.  The histogram and the counts see kept calls only.
- * rmr_modbam_call_counts_ref / rmr_modbam_call_fill_ref: rmr_modbam_call_counts / _fill with that test; ref == NULL: exactly
- * those.  The genome must hold the batch's n_refs contigs and belong to the same engine; refused before any launch
- * otherwise, and for a motif outside the bounds above or an rc_mask that is not mask's reverse complement. */
+ * The region is asked of the position that is written.  The histogram and the counts see kept calls only.  The genome must
+ * hold the batch's n_refs contigs and belong to the same engine; refused before any launch otherwise, and for a motif outside
+ * the bounds above or an rc_mask that is not mask's reverse complement.
+ * duplex != 0 (`infer duplex_from_pod5_and_bam` writes a `C+m?` part from the template read and a `G-m?` part from the
+ * complement read into one record): an entry counts when its strand is '+' or '-', it has no ChEBI code and a code of it is
+ * among mod_codes (status 5 is asked of the entries of both strands).  The call of a '-' entry lies on the reference strand
+ * opposite to its record's: the effective strand, rev XOR (entry strand == '-'), goes into the site word, picks mask or rc_mask
+ * and the window start of the motif test, and is what combine folds.  A position that entries of both strands list: the strand
+ * of the last entry in tag order that lists it with a code of mod_codes decides, and what entries of the other strand gave the
+ * position is dropped; within one strand the later entry wins.
+ * hemi != 0 (the fill; the count pass checks it and counts the same calls): a '-' call is written at the '+' position of its
+ * window, as combine does, but KEEPS its strand bit - the '+' call at rp and the '-' call at rp + (len - 1 - 2 focus) of one
+ * record then differ in bit 4 and the code alone, which is what the pair passes below look for.  Refused before any launch
+ * with hemi: duplex == 0, a NULL ref, combine == 0, n_motifs != 1 (and, by combine, a motif that is not its own reverse
+ * complement).  n_records 0 launches nothing. */
 #define RMR_PILEUP_MAX_MOTIFS 4
 #define RMR_PILEUP_MAX_MOTIF_LEN 16
 typedef struct rmr_pileup_motif {
@@ -464,12 +471,17 @@ typedef struct rmr_pileup_ref {
     int32_t n_motifs, combine;
     rmr_pileup_motif motifs[RMR_PILEUP_MAX_MOTIFS];
 } rmr_pileup_ref;
-int rmr_modbam_call_counts_ref(rmr_engine *e, const rmr_modbam_batch *b, const rmr_pileup_ref *ref, int32_t region_ref, int64_t region_lo,
-                               int64_t region_hi, int32_t *ords, int64_t *cig_q, int64_t *cig_r, int64_t *counts, int32_t *status,
-                               uint64_t *hist);
-int rmr_modbam_call_fill_ref(rmr_engine *e, const rmr_modbam_batch *b, const rmr_pileup_ref *ref, int32_t region_ref, int64_t region_lo,
-                             int64_t region_hi, int32_t k_t, const int32_t *ords, const int64_t *cig_q, const int64_t *cig_r,
-                             const int32_t *status, const int64_t *out_off, uint64_t *words);
+typedef struct rmr_pileup_emit_opts {
+    int32_t region_ref;                 /* < 0: everywhere */
+    int64_t region_lo, region_hi;
+    const rmr_pileup_ref *ref;          /* NULL: no motif test, no fold */
+    int32_t duplex;                     /* '-'-strand entries count too */
+    int32_t hemi;                       /* needs duplex, ref, combine, exactly one motif */
+} rmr_pileup_emit_opts;
+int rmr_pileup_emit_counts(rmr_engine *e, const rmr_modbam_batch *b, const rmr_pileup_emit_opts *opt, int32_t *ords, int64_t *cig_q,
+                           int64_t *cig_r, int64_t *counts, int32_t *status, uint64_t *hist);
+int rmr_pileup_emit_fill(rmr_engine *e, const rmr_modbam_batch *b, const rmr_pileup_emit_opts *opt, int32_t k_t, const int32_t *ords,
+                         const int64_t *cig_q, const int64_t *cig_r, const int32_t *status, const int64_t *out_off, uint64_t *words);
 /* The per-site table (GPU).  rmr_pileup_create: a table for n_contigs contigs, the longest of max_contig_len bases, with
  * n_alpha classes (the canonical base and 1 .. 7 modified ones; a row has n_alpha + 1 u32 counts, the last is `fail`) and a
  * call buffer of buffer_calls words (below 2^31).  Refused before anything is allocated or launched: n_contigs outside 1 ..
@@ -493,29 +505,16 @@ int rmr_pileup_finish(rmr_pileup *p, int64_t *n_sites, int64_t *n_calls, int64_t
 int rmr_pileup_read(rmr_pileup *p, uint64_t *keys, uint32_t *counts);
 void rmr_pileup_destroy(rmr_pileup *p);
 /* A partition field above the contig index (GPU; DEVICE pointers, asynchronous on the engine's stream), for per-haplotype
- * tables.  rmr_pileup_stamp_partition: between rmr_modbam_call_fill and rmr_pileup_add,
+ * tables.  rmr_pileup_stamp_partition: between rmr_pileup_emit_fill and rmr_pileup_add,
  *     words[i] |= (uint64_t)part[r] << shift     for out_off[r] <= i < out_off[r + 1],   r = 0 .. n_records - 1,
  * with shift = 36 + the bits the contig index takes; a pileup created for n_contigs << (bits of the field) contigs then sorts
  * and counts the partitions apart, and the ref_id of a key it returns is part << (shift - 36) | ref_id.  part: i32[n_records],
  * 0 <= part[r] < 2^(60 - shift) (the caller's to keep); a record with part 0 or without words writes nothing.  out_off as
- * rmr_modbam_call_fill took it; the n_words of `words` bound every store.  n_records 0 launches nothing.  Refused before
+ * rmr_pileup_emit_fill took it; the n_words of `words` bound every store.  n_records 0 launches nothing.  Refused before
  * the launch: n_records or n_words negative, a shift outside 36 .. 59, NULL pointers. */
 int rmr_pileup_stamp_partition(rmr_engine *e, int64_t n_records, const int64_t *out_off, const int32_t *part, int shift, uint64_t *words,
                                int64_t n_words);
-/* Duplex records (GPU; DEVICE pointers, asynchronous on the engine's stream): `infer duplex_from_pod5_and_bam` writes a `C+m?`
- * part from the template read and a `G-m?` part from the complement read into one record.
- * rmr_modbam_call_counts_duplex / rmr_modbam_call_fill_duplex: rmr_modbam_call_counts_ref / _fill_ref (ref nullable: then
- * rmr_modbam_call_counts / _fill) in which an entry counts when its strand is '+' or '-', it has no ChEBI code and a code of
- * it is among mod_codes (status 5 is asked of the entries of both strands).  The call of a '-' entry lies on the reference
- * strand opposite to its record's: the effective strand, rev XOR (entry strand == '-'), goes into the site word, picks mask or
- * rc_mask and the window start of the motif test, and is what combine folds.  A position that entries of both strands list: the
- * strand of the last entry in tag order that lists it with a code of mod_codes decides, and what entries of the other strand
- * gave the position is dropped; within one strand the later entry wins, as before.  Kernels of their own: the emits above are
- * untouched.
- * hemi != 0 (the fill; the count pass checks it and counts the same calls): a '-' call is written at the '+' position of its
- * window, as combine does, but KEEPS its strand bit - the '+' call at rp and the '-' call at rp + (len - 1 - 2 focus) of one
- * record then differ in bit 4 and the code alone, which is what the pair passes look for.  Refused before any launch with hemi:
- * a NULL ref, combine == 0, n_motifs != 1 (and, by combine, a motif that is not its own reverse complement).
+/* The strand pairs of a hemi emit (GPU; DEVICE pointers, asynchronous on the engine's stream).
  * rmr_pileup_pair_counts / rmr_pileup_pair_fill: the two strands' calls of one record at one site -> one pair word.  words /
  * out_off as the hemi fill wrote and took them: a record's words stand in walk order, their positions are monotone, so the
  * partner of a '+' word (bit 4 clear) is the first word, in index order, among the RMR_PILEUP_MAX_MOTIF_LEN - 1 words before
@@ -529,12 +528,6 @@ int rmr_pileup_stamp_partition(rmr_engine *e, int64_t n_records, const int64_t *
  * outside 3 .. 4.
  * rmr_pileup_create_cols: rmr_pileup_create for rows of ncol u32 counts, 3 .. 16 (a word's code must lie below ncol; the
  * device memory is that of n_alpha = ncol - 1). */
-int rmr_modbam_call_counts_duplex(rmr_engine *e, const rmr_modbam_batch *b, const rmr_pileup_ref *ref, int32_t region_ref, int64_t region_lo,
-                                  int64_t region_hi, int32_t *ords, int64_t *cig_q, int64_t *cig_r, int64_t *counts, int32_t *status,
-                                  uint64_t *hist, int32_t hemi);
-int rmr_modbam_call_fill_duplex(rmr_engine *e, const rmr_modbam_batch *b, const rmr_pileup_ref *ref, int32_t region_ref, int64_t region_lo,
-                                int64_t region_hi, int32_t k_t, const int32_t *ords, const int64_t *cig_q, const int64_t *cig_r,
-                                const int32_t *status, const int64_t *out_off, uint64_t *words, int32_t hemi);
 int rmr_pileup_pair_counts(rmr_engine *e, int64_t n_records, const int64_t *out_off, const uint64_t *words, int64_t n_words, int64_t *pairs);
 int rmr_pileup_pair_fill(rmr_engine *e, int64_t n_records, const int64_t *out_off, const uint64_t *words, int64_t n_words, int n_codes,
                          const int64_t *pair_off, uint64_t *pair_words);
@@ -556,7 +549,7 @@ int rmr_pileup_create_cols(rmr_engine *e, int64_t n_contigs, int64_t max_contig_
  * combine == 0: ref is not read.
  * rmr_pileup_set_canonical: the canonical base of the table, 'A' 'C' 'G' 'T' or 'U' (= 'T'); the join is refused without it.
  * rmr_pileup_cover: DEVICE pointers, asynchronous on the engine's stream.  b, status, cig_q, cig_r, out_off and words are those
- * of the rmr_modbam_call_counts / _fill (_ref) of the same batch, the words stamped already when part is given (shift as
+ * of the rmr_pileup_emit_counts / _fill of the same batch, the words stamped already when part is given (shift as
  * there; ignored without part); words may be NULL when n_words is 0.  One workgroup of 256 threads per record: two binary
  * searches in the table's keys bracket its sites, each lane finds the CIGAR operation of its rp - the LAST index with
  * cig_r <= rp - pos, since operations that consume no reference share their cig_r with the next one -, takes the stored

@@ -63,6 +63,13 @@ class PileupRef(ctypes.Structure):
     _fields_ = [("genome", c_vp), ("n_motifs", ctypes.c_int32), ("combine", ctypes.c_int32), ("motifs", PileupMotif * 4)]
 
 
+class PileupEmitOpts(ctypes.Structure):
+    """rmr_pileup_emit_opts of include/remora_hip.h."""
+
+    _fields_ = [("region_ref", ctypes.c_int32), ("region_lo", c_i64), ("region_hi", c_i64), ("ref", ctypes.POINTER(PileupRef)),
+                ("duplex", ctypes.c_int32), ("hemi", ctypes.c_int32)]
+
+
 AUX_ABSENT, AUX_INT, AUX_CHAR, AUX_OTHER_TYPE, AUX_UNWALKABLE = range(5)  # RMR_AUX_* of include/remora_hip.h
 MOD_MAX_CODES = 16
 # rmr_mod_entry of include/remora_hip.h as a numpy record (48 bytes)
@@ -135,27 +142,19 @@ SIGNATURES = {
     "rmr_bam_aux_values": (c_int, [c_i64, c_vp, c_vp, c_vp, ctypes.c_char_p, c_vp, c_vp, c_int]),
     "rmr_modbam_site_counts": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rmr_modbam_site_fill": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "rmr_modbam_call_counts": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), ctypes.c_int32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "rmr_modbam_call_fill": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), ctypes.c_int32, c_i64, c_i64, ctypes.c_int32, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                     c_vp]),
     "rmr_ref_genome_create": (c_int, [c_vp, c_i64, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_i64)]),
     "rmr_ref_genome_load": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, ctypes.POINTER(c_i64)]),
     "rmr_ref_genome_read": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp]),
     "rmr_ref_genome_destroy": (None, [c_vp]),
-    "rmr_modbam_call_counts_ref": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), ctypes.POINTER(PileupRef), ctypes.c_int32, c_i64, c_i64, c_vp, c_vp,
-                                           c_vp, c_vp, c_vp, c_vp]),
-    "rmr_modbam_call_fill_ref": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), ctypes.POINTER(PileupRef), ctypes.c_int32, c_i64, c_i64, ctypes.c_int32,
-                                         c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rmr_pileup_emit_counts": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), ctypes.POINTER(PileupEmitOpts), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rmr_pileup_emit_fill": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), ctypes.POINTER(PileupEmitOpts), ctypes.c_int32, c_vp, c_vp, c_vp, c_vp,
+                                     c_vp, c_vp]),
     "rmr_pileup_create": (c_int, [c_vp, c_i64, c_i64, c_int, c_i64, ctypes.POINTER(c_vp)]),
     "rmr_pileup_add": (c_int, [c_vp, c_vp, c_i64]),
     "rmr_pileup_finish": (c_int, [c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "rmr_pileup_read": (c_int, [c_vp, c_vp, c_vp]),
     "rmr_pileup_destroy": (None, [c_vp]),
     "rmr_pileup_stamp_partition": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_i64]),
-    "rmr_modbam_call_counts_duplex": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), ctypes.POINTER(PileupRef), ctypes.c_int32, c_i64, c_i64, c_vp, c_vp,
-                                              c_vp, c_vp, c_vp, c_vp, ctypes.c_int32]),
-    "rmr_modbam_call_fill_duplex": (c_int, [c_vp, ctypes.POINTER(ModbamBatch), ctypes.POINTER(PileupRef), ctypes.c_int32, c_i64, c_i64,
-                                            ctypes.c_int32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_int32]),
     "rmr_pileup_pair_counts": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "rmr_pileup_pair_fill": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
     "rmr_pileup_create_cols": (c_int, [c_vp, c_i64, c_i64, c_int, c_i64, ctypes.POINTER(c_vp)]),

@@ -1,5 +1,5 @@
 // api_ref.hip — the reference genome entry points of the C ABI (rmr_ref_genome_*: the table, its load from FASTA text piece
-// by piece through k_ref_genome.hip, the read-back).  The emit that reads it is api_data.hip's rmr_modbam_call_counts_ref / _fill_ref.
+// by piece through k_ref_genome.hip, the read-back).  The emit that reads it is api_pileup.hip's rmr_pileup_emit_counts / _fill.
 #include <algorithm>
 #include <new>
 

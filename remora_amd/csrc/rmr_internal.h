@@ -264,7 +264,7 @@ struct PileupEmit {
     unsigned long long *hist;       // count pass: u64[PILEUP_BINS], or nullptr
     uint64_t *words;                // fill pass: one word per kept call
 };
-// The reference part of an emit (rmr_modbam_call_counts_ref / _fill_ref): the motif test and the fold of rmr_modbam_walk.h.
+// The reference part of an emit (rmr_pileup_emit_counts / _fill with opt->ref): the motif test and the fold of rmr_modbam_walk.h.
 // It is a kernel argument of its own, by value, and only of the kernels with a reference (k_ref_genome.hip): PileupEmit and
 // with it the argument block of the kernels without one stay byte for byte what they were, and so does their code (one
 // pointer more in PileupEmit moved the scalar loads and the register allocation of those kernels, profiles/NOTES_r18.md).

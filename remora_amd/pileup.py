@@ -4,9 +4,10 @@ reference's command line stops at the per-read BAM; its users go through a CPU p
 
 Here the BAM is streamed in any order (no index, no MD tag): a batch of records is tokenised on native threads
 (rmr_mod_tags_sizes / _fill, shared with `validate from_modbams`), its calls are laid along the reads and carried through the
-CIGARs on the GPU (rmr_modbam_call_counts / _fill: the walk of the site join without the truth table), classified there in
+CIGARs on the GPU (rmr_pileup_emit_counts / _fill: the walk of the site join without the truth table), classified there in
 integers and written as one 64-bit word per call; the words are sorted, counted per site and merged into a resident table on
-the device (rmr_pileup_*, csrc/k_pileup.hip).  One row per site crosses PCIe.
+the device (rmr_pileup_*, csrc/k_pileup.hip).  One row per site crosses PCIe.  What a run asks of the emit - the region, the
+reference, `duplex`, `hemi` - travels in one rmr_pileup_emit_opts, filled once per run.
 
 Which calls count, and how they are classified, is DESIGN.md section 4's "Pileup"; in short: mapped primary records, '+'-strand
 entries with single-letter codes of the alphabet, the positions an entry lists, p = (ML + 0.5) / 256, the later entry wins,
@@ -23,10 +24,10 @@ on the host (rmr_bam_aux_values), given an id, and the id is stamped into the fr
 record's words (rmr_pileup_stamp_partition) - the sort and the table then keep the partitions apart, under the one threshold
 of the whole input ("Pileup: the partition field").
 
-With `duplex` the '-'-strand entries of duplex records count too, on the reference strand opposite to the record's
-(rmr_modbam_call_counts_duplex / _fill_duplex); with `hemi` the '+' and the '-' call of one record at one motif site are paired
-on the device (rmr_pileup_pair_counts / _fill, csrc/k_pileup_duplex.hip) and the table counts the strand patterns per site
-("Pileup: duplex entries and strand pairs").
+With `duplex` the '-'-strand entries of duplex records count too, on the reference strand opposite to the record's; with
+`hemi` the '+' and the '-' call of one record at one motif site are paired on the device (rmr_pileup_pair_counts / _fill,
+csrc/k_pileup_duplex.hip) and the table counts the strand patterns per site ("Pileup: duplex entries
+and strand pairs").
 
 With `coverage` the BAMs are streamed once more after the table is finished and every record is joined on the device against
 the sites it spans (rmr_pileup_cover): N_delete, N_diff and N_nocall per site, the columns that make the bedMethyl the
@@ -38,6 +39,7 @@ import os
 import re
 from collections import namedtuple
 from fractions import Fraction
+from functools import partial
 
 import numpy as np
 
@@ -641,32 +643,26 @@ class DevicePileup:
         self.close()
 
 
-def _emit_batch(eng, b, region, k_t, hist, n_cig, n_deltas, pref=None, part=None, shift=0, duplex=False, n_codes=0, cover=None):
+def _emit_batch(eng, b, opts, k_t, hist, n_cig, n_deltas, part=None, shift=0, cover=None):
     """One batch through the emit: the count pass (with the histogram when `hist` is a device tensor), and - k_t not None -
-    the fill pass.  `pref`: the rmr_pileup_ref of a run with a reference, or None.  `part` (i32 per record, a partitioned run):
-    after the fill pass the records' partition ids are stamped into their words from bit `shift`.  `duplex`: the emit that
-    counts '-'-strand entries.  `n_codes` (a hemi run: n_mods + 2): the fill keeps the strand bits and its words go through the
-    pair passes - what comes back are the pair words.  `cover` (the DevicePileup of a finished table; the pass of `coverage`):
-    the batch is joined against the table's sites, rmr_pileup_cover, while its workspaces are alive - also when it has no word.
+    the fill pass.  `opts`: the run's rmr_pileup_emit_opts (_lib.PileupEmitOpts).  `part` (i32 per record, a partitioned run): after the
+    fill pass the records' partition ids are stamped into their words from bit `shift`.  With opts.hemi the fill keeps the
+    strand bits and its words go through the pair passes (n_codes = n_mods + 2) - what comes back are the pair words.  `cover`
+    (the DevicePileup of a finished table; the pass of `coverage`): the batch is joined against the table's sites,
+    rmr_pileup_cover, while its workspaces are alive - also when it has no word.
     -> (words device tensor or None, calls per record, status per record, pairs in the batch or None)."""
     from . import _lib as L
     from .engine import _torch
 
     torch, lib, dev = _torch(), L.lib(), eng.torch_device
     n = int(b.n_records)
+    n_codes, pref = int(b.n_mods) + 2 if opts.hemi else 0, opts.ref.contents if opts.ref else None
     ords = torch.empty(max(n_deltas, 1), dtype=torch.int32, device=dev)
     cig_qr = torch.empty((2, max(n_cig, 1)), dtype=torch.int64, device=dev)
     counts = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
     d_status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    with_ref = () if pref is None else (ctypes.byref(pref),)
-    call_counts, call_fill = ((lib.rmr_modbam_call_counts, lib.rmr_modbam_call_fill) if pref is None else
-                              (lib.rmr_modbam_call_counts_ref, lib.rmr_modbam_call_fill_ref))
-    hemi_arg = ()
-    if duplex:  # the `_ref` arguments with a nullable ref, and hemi at the end
-        with_ref, hemi_arg = (None if pref is None else ctypes.byref(pref),), (1 if n_codes else 0,)
-        call_counts, call_fill = lib.rmr_modbam_call_counts_duplex, lib.rmr_modbam_call_fill_duplex
-    L.check(call_counts(eng.handle, ctypes.byref(b), *with_ref, region[0], region[1], region[2], ords.data_ptr(), cig_qr[0].data_ptr(),
-                        cig_qr[1].data_ptr(), counts.data_ptr(), d_status.data_ptr(), hist.data_ptr() if hist is not None else None, *hemi_arg))
+    L.check(lib.rmr_pileup_emit_counts(eng.handle, ctypes.byref(b), ctypes.byref(opts), ords.data_ptr(), cig_qr[0].data_ptr(), cig_qr[1].data_ptr(),
+                                       counts.data_ptr(), d_status.data_ptr(), hist.data_ptr() if hist is not None else None))
     eng.synchronize()
     h_counts, h_status = counts[:n].cpu().numpy(), d_status[:n].cpu().numpy()
     words, n_pairs = None, (0 if n_codes else None)
@@ -676,8 +672,8 @@ def _emit_batch(eng, b, region, k_t, hist, n_cig, n_deltas, pref=None, part=None
         np.cumsum(h_counts, out=out_off[1:])
         d_off = torch.from_numpy(out_off).to(dev)
         words = torch.empty(total, dtype=torch.int64, device=dev)
-        L.check(call_fill(eng.handle, ctypes.byref(b), *with_ref, region[0], region[1], region[2], int(k_t), ords.data_ptr(),
-                          cig_qr[0].data_ptr(), cig_qr[1].data_ptr(), d_status.data_ptr(), d_off.data_ptr(), words.data_ptr(), *hemi_arg))
+        L.check(lib.rmr_pileup_emit_fill(eng.handle, ctypes.byref(b), ctypes.byref(opts), int(k_t), ords.data_ptr(), cig_qr[0].data_ptr(),
+                                         cig_qr[1].data_ptr(), d_status.data_ptr(), d_off.data_ptr(), words.data_ptr()))
         if part is not None:
             d_part = torch.from_numpy(np.ascontiguousarray(part, np.int32)).to(dev)
             L.check(lib.rmr_pileup_stamp_partition(eng.handle, n, d_off.data_ptr(), d_part.data_ptr(), int(shift), words.data_ptr(), total))
@@ -779,7 +775,9 @@ def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_F
     if buffer_calls is None and not device_gib > 0:
         raise RemoraError("--pileup-device-gib must be positive")
 
-    genome = pref = None
+    from . import _lib as L
+
+    genome = None
     if isinstance(ref, RefGenome):
         genome = ref
         if not genome.h or genome.ref_names != ref_names or genome.ref_lens != [int(n) for n in ref_lens]:
@@ -790,83 +788,85 @@ def pileup_modbams(bams, alphabet, filter_threshold=None, pct_filt=DEFAULT_PCT_F
     elif ref is not None:  # refused here, before any pileup launch: what the FASTA lacks, and what the device finds wrong in it
         genome = RefGenome.from_fasta(ref, ref_names, ref_lens, device=device, contigs=[reg[0]] if reg[0] >= 0 else None)
     try:
-        if genome is not None:
-            pref = _pileup_ref_struct(genome, descriptors, combine_strands or hemi)
-        return _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens, device, batch, buffer_calls, device_gib, genome, pref,
-                           bool(combine_strands or hemi), parts, duplex, bool(hemi), bool(coverage))
+        pref = None if genome is None else ctypes.pointer(_pileup_ref_struct(genome, descriptors, combine_strands or hemi))
+        opts = L.PileupEmitOpts(region_ref=reg[0], region_lo=reg[1], region_hi=reg[2], ref=pref, duplex=int(duplex), hemi=int(bool(hemi)))
+        return _pileup_run(PileupRun(bams, alphabet, k_t, pct_filt, region, ref_names, ref_lens, device, batch, buffer_calls, device_gib, genome,
+                                     opts, bool(combine_strands or hemi), parts, bool(coverage)))
     finally:
         if genome is not None and genome is not ref:
             genome.close()
 
 
-def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens, device, batch, buffer_calls, device_gib, genome, pref, combined,
-                parts=None, duplex=False, hemi=False, coverage=False):
-    """pileup_modbams once its arguments are checked and the reference is on the device.  `parts`: the Partitioner of a run with
-    a partition tag.  `coverage`: the third pass, the coverage join against the finished table."""
-    from .engine import _torch, get_engine
+PileupRun = namedtuple("PileupRun", ("bams", "alphabet", "k_t", "pct_filt", "region", "ref_names", "ref_lens", "device", "batch", "buffer_calls",
+                                     "device_gib", "genome", "opts", "combined", "parts", "coverage"))
+PileupRun.__doc__ = """The checked arguments of one pileup_modbams run.  k_t: None when the threshold comes from pct_filt; region: the text, for
+messages; opts: the rmr_pileup_emit_opts of every emit (the parsed region, the reference, duplex, hemi); parts: the Partitioner or None."""
+
+
+def _one_pass(run, eng, warn, k_fill, hist, pile, log_skipped, cover=False):
+    """All BAMs of `run` once: the count pass of every batch, and with k_fill the fill pass and the append - or, `cover`, the
+    coverage join against the finished table of `pile` in place of the append.  -> (kept calls, pairs)."""
     from .io import _readahead, iter_bam_raw_batches
     from .validate import modbam_device_batch, tokenise_mod_tags, warn_ignored_entries
 
-    mods, n_alpha = alphabet[1:], len(alphabet)
-    n_codes = n_alpha + 1 if hemi else 0          # the classes of one strand's call in a pair: the alphabet and fail
-    ncol = n_codes * n_codes if hemi else n_alpha + 1
-    torch = _torch()
-    eng = get_engine(device)
-    dev = eng.torch_device
+    parts, dev, mods = run.parts, eng.torch_device, run.alphabet[1:]
+    n_kept = n_paired = n_asked = 0
+    for path in run.bams:
+        skipped, n_records = {}, 0
+
+        def tokenised(path=path):  # the reader and the tokeniser of batch k + 1 run beside the GPU work of batch k
+            for rb, _ in iter_bam_raw_batches(path, want_ref=False, batch=int(run.batch)):
+                yield rb, tokenise_mod_tags(rb.raw, rb.raw_off, rb.tags_off), (None if parts is None else
+                                                                               read_aux_values(rb.raw, rb.raw_off, rb.tags_off, parts.tag))
+
+        for rb, tok, aux in _readahead(tokenised(), depth=2):
+            part = None if aux is None else parts.ids_of(rb, aux[0], aux[1], path)  # (in both passes: a refusal comes early)
+            warn_ignored_entries(tok[4], run.alphabet, warn, MOD_NOT_IN_ALPHABET)
+            buf, b = modbam_device_batch(dev, mods, rb.seq, rb.seq_off, rb.cigar, rb.cigar_off, rb.flag, rb.ref_id, rb.pos, rb.has, tok)
+            b.n_refs = len(run.ref_names)
+            words, h_counts, h_status, n_pairs = _emit_batch(eng, b, run.opts, k_fill, hist, int(np.asarray(rb.cigar).size), int(tok[5].size), part,
+                                                               0 if parts is None else parts.plan.shift, pile if cover else None)
+            n_paired += n_pairs or 0
+            del buf
+            if cover:  # a record adds at most 1 per site and column: 2^32 of them could pass a u32 count
+                n_asked += int(np.count_nonzero(h_status == 0))
+                if n_asked >= 2**32:
+                    raise RemoraError(f"--coverage-columns: {n_asked} records take part, N_delete / N_diff / N_nocall are counted in 32 bits "
+                                      "(fewer than 2^32 records)")
+            elif words is not None:
+                pile.add(words, words.numel())
+                eng.synchronize()  # the words are in the call buffer (or the table) now
+            n_kept += int(h_counts.sum())
+            n_records += rb.n
+            for st, k in zip(*np.unique(h_status, return_counts=True)):
+                if st:
+                    skipped[int(st)] = skipped.get(int(st), 0) + int(k)
+        if log_skipped:
+            for st, k in sorted(skipped.items()):
+                LOGGER.info(f"{k} of {n_records} records skipped: {PILEUP_STATUS.get(st, st)} ({path})")
+    return n_kept, n_paired
+
+
+def _pileup_run(run):
+    """pileup_modbams once its arguments are checked (`run`, a PileupRun) and the reference is on the device."""
+    from .engine import _torch, get_engine
+
+    alphabet, n_alpha, ref_names, parts, hemi = run.alphabet, len(run.alphabet), run.ref_names, run.parts, bool(run.opts.hemi)
+    ncol = (n_alpha + 1) ** 2 if hemi else n_alpha + 1  # (hemi: a pair of classes of one strand's call - the alphabet and fail)
+    torch, eng, buffer_calls = _torch(), get_engine(run.device), run.buffer_calls
     if buffer_calls is None:
-        free = torch.cuda.mem_get_info(dev)[0]
-        gib = min(float(device_gib), free / 2 / 2**30)
+        free = torch.cuda.mem_get_info(eng.torch_device)[0]
+        gib = min(float(run.device_gib), free / 2 / 2**30)
         buffer_calls = int(max(1, min(2**31 - 1, (gib * 2**30 - (1 << 20)) // bytes_per_buffered_call(ncol - 1))))
-        LOGGER.info(f"pileup call buffer: {buffer_calls} calls in {gib:.3g} GiB of device memory (--pileup-device-gib {device_gib:g}, "
+        LOGGER.info(f"pileup call buffer: {buffer_calls} calls in {gib:.3g} GiB of device memory (--pileup-device-gib {run.device_gib:g}, "
                     f"{free / 2**30:.1f} GiB free)")
-    warn = {"strand": not duplex, "mod": True}  # (in a duplex run the '-' entries count: nothing to warn of)
-
-    def one_pass(k_fill, hist, pile, log_skipped, cover=False):
-        """All BAMs once: the count pass of every batch, and with k_fill the fill pass and the append - or, `cover`, the coverage
-        join against the finished table of `pile` in place of the append.  -> (kept calls, pairs)."""
-        n_kept = n_paired = n_asked = 0
-        for path in bams:
-            skipped, n_records = {}, 0
-
-            def tokenised(path=path):  # the reader and the tokeniser of batch k + 1 run beside the GPU work of batch k
-                for rb, _ in iter_bam_raw_batches(path, want_ref=False, batch=int(batch)):
-                    yield rb, tokenise_mod_tags(rb.raw, rb.raw_off, rb.tags_off), (None if parts is None else
-                                                                                   read_aux_values(rb.raw, rb.raw_off, rb.tags_off, parts.tag))
-
-            for rb, tok, aux in _readahead(tokenised(), depth=2):
-                part = None if aux is None else parts.ids_of(rb, aux[0], aux[1], path)  # (in both passes: a refusal comes early)
-                warn_ignored_entries(tok[4], alphabet, warn, MOD_NOT_IN_ALPHABET)
-                buf, b = modbam_device_batch(dev, mods, rb.seq, rb.seq_off, rb.cigar, rb.cigar_off, rb.flag, rb.ref_id, rb.pos, rb.has, tok)
-                b.n_refs = len(ref_names)
-                words, h_counts, h_status, n_pairs = _emit_batch(eng, b, reg, k_fill, hist, int(np.asarray(rb.cigar).size), int(tok[5].size), pref,
-                                                                   part, 0 if parts is None else parts.plan.shift, duplex, n_codes,
-                                                                   pile if cover else None)
-                n_paired += n_pairs or 0
-                del buf
-                if cover:  # a record adds at most 1 per site and column: 2^32 of them could pass a u32 count
-                    n_asked += int(np.count_nonzero(h_status == 0))
-                    if n_asked >= 2**32:
-                        raise RemoraError(f"--coverage-columns: {n_asked} records take part, N_delete / N_diff / N_nocall are counted in 32 bits "
-                                          "(fewer than 2^32 records)")
-                elif words is not None:
-                    pile.add(words, words.numel())
-                    eng.synchronize()  # the words are in the call buffer (or the table) now
-                n_kept += int(h_counts.sum())
-                n_records += rb.n
-                for st, k in zip(*np.unique(h_status, return_counts=True)):
-                    if st:
-                        skipped[int(st)] = skipped.get(int(st), 0) + int(k)
-            if log_skipped:
-                for st, k in sorted(skipped.items()):
-                    LOGGER.info(f"{k} of {n_records} records skipped: {PILEUP_STATUS.get(st, st)} ({path})")
-        return n_kept, n_paired
-
-    no_calls = (f"No modified-base call of {alphabet[1:]} on an aligned base" + (f" inside {region}" if region is not None else "") +
-                (" on a motif of the reference" if genome is not None else "") +
-                f" in {', '.join(map(str, bams))}.")
-    h_hist = None
+    one_pass = partial(_one_pass, run, eng, {"strand": not run.opts.duplex, "mod": True})  # (a duplex run counts the '-' entries: no warning)
+    no_calls = (f"No modified-base call of {alphabet[1:]} on an aligned base" + (f" inside {run.region}" if run.region is not None else "") +
+                (" on a motif of the reference" if run.genome is not None else "") +
+                f" in {', '.join(map(str, run.bams))}.")
+    h_hist, k_t = None, run.k_t
     if k_t is None:  # the percentile needs every call's confidence first: one pass that emits no rows
-        hist = torch.zeros(N_BINS, dtype=torch.int64, device=dev)
+        hist = torch.zeros(N_BINS, dtype=torch.int64, device=eng.torch_device)
         n_kept, _ = one_pass(None, hist, None, True)
         eng.synchronize()
         h_hist = hist.cpu().numpy()
@@ -874,10 +874,10 @@ def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens,
             if n_kept < 1:
                 raise RemoraError(no_calls)
             raise RemoraError(f"pileup: the histogram holds {int(h_hist.sum())} calls, the records {n_kept}")
-        k_t = percentile_k(h_hist, pct_filt)
-        LOGGER.info(f"--pct-filt {pct_filt:g}: {int(h_hist[:k_t].sum())} of {n_kept} calls fail at k_T = {k_t} (probability {k_t / 512:.6g})")
+        k_t = percentile_k(h_hist, run.pct_filt)
+        LOGGER.info(f"--pct-filt {run.pct_filt:g}: {int(h_hist[:k_t].sum())} of {n_kept} calls fail at k_T = {k_t} (probability {k_t / 512:.6g})")
     # a partitioned run: the id stands above the contig index, and the sort covers its bits too
-    with DevicePileup(eng, len(ref_names) if parts is None else parts.plan.n_contigs, max(ref_lens), n_alpha, buffer_calls,
+    with DevicePileup(eng, len(ref_names) if parts is None else parts.plan.n_contigs, max(run.ref_lens), n_alpha, buffer_calls,
                       ncol if hemi else None) as pile:
         n_kept, n_paired = one_pass(k_t, None, pile, h_hist is None)
         n_sites, n_calls, n_flushes, peak = _finish(pile, ref_names, parts)
@@ -890,7 +890,7 @@ def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens,
             raise RemoraError(f"pileup: {n_calls} calls reached the table, the records hold {n_paired if hemi else n_kept}")
         keys, counts = pile.read(n_sites)
         cover = None
-        if coverage:  # the third pass: the same emit with the final k_T and no histogram, joined against the finished table
+        if run.coverage:  # the third pass: the same emit with the final k_T and no histogram, joined against the finished table
             pile.set_canonical(alphabet[0])
             n_again, _ = one_pass(k_t, None, pile, False, cover=True)
             if n_again != n_kept:
@@ -899,8 +899,8 @@ def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens,
             cover = pile.read_cover(n_sites).astype(np.int64)
             LOGGER.info(f"--coverage-columns: N_delete {int(cover[:, 0].sum())}, N_diff {int(cover[:, 1].sum())}, N_nocall "
                         f"{int(cover[:, 2].sum())} on {n_sites} sites")
-    if genome is not None:
-        peak += genome.device_bytes
+    if run.genome is not None:
+        peak += run.genome.device_bytes
     if hemi:
         LOGGER.info(f"{n_calls} strand pairs on {n_sites} sites, {n_kept - 2 * n_calls} of {n_kept} calls unpaired; {n_flushes} flushes, "
                     f"{peak / 2**20:.1f} MiB of device memory at the peak")
@@ -909,7 +909,7 @@ def _pileup_run(bams, alphabet, k_t, pct_filt, region, reg, ref_names, ref_lens,
     table = PileupTable(ref_names=ref_names, ref_id=(keys >> np.uint64(32)).astype(np.int32),
                         pos=((keys >> np.uint64(1)) & np.uint64(0x7FFFFFFF)).astype(np.int64), strand=(keys & np.uint64(1)).astype(np.uint8),
                         counts=counts.astype(np.int64), alphabet=alphabet, threshold_k=int(k_t), n_calls=n_calls, n_flushes=n_flushes,
-                        peak_device_bytes=peak, hist=None if h_hist is None else h_hist.astype(np.int64), combined=combined,
+                        peak_device_bytes=peak, hist=None if h_hist is None else h_hist.astype(np.int64), combined=run.combined,
                         hemi=hemi, n_unpaired=n_kept - 2 * n_calls if hemi else None, coverage=cover)
     return table if parts is None else _partitioned(table, parts)
 

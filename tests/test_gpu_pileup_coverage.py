@@ -335,7 +335,7 @@ def test_cover_kernel_on_a_hand_made_site_table(torch_cuda, tmp_path):
                 b.n_records = n_records
                 assert rc == 0 and "pileup_cover" not in eng.profile() and not pile.read_cover(n_sites).any()
                 peak = pile.finish()[3]
-                _emit_batch(eng, b, (-1, 0, 0), K_08, None, n_cig, n_deltas, cover=pile)
+                _emit_batch(eng, b, L.PileupEmitOpts(region_ref=-1), K_08, None, n_cig, n_deltas, cover=pile)
                 eng.synchronize()
                 assert eng.profile()["pileup_cover"][1] == 1  # one launch, under its own name
                 keys, counts = pile.read(n_sites)

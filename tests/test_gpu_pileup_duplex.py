@@ -320,7 +320,7 @@ def test_pair_refusals_launch_nothing(torch_cuda):
 
 
 def test_hemi_emit_refusals_launch_nothing(torch_cuda, duplex_input, device_genome):
-    """The C entries: hemi without a reference, without the fold, with two motifs."""
+    """The C entries: hemi without a reference, without the fold, with two motifs, without duplex."""
     import torch
 
     from remora_amd import _lib as L
@@ -337,17 +337,19 @@ def test_hemi_emit_refusals_launch_nothing(torch_cuda, duplex_input, device_geno
     eng.synchronize()
     eng.profile_enable(True)
     eng.profile_reset()
+    def opts(pref, duplex, hemi):
+        return ctypes.byref(L.PileupEmitOpts(region_ref=-1, ref=None if pref is None else ctypes.pointer(pref), duplex=duplex, hemi=hemi))
+
+    ok = _pileup_ref_struct(device_genome, one, True)
     try:
-        for pref, message in ((None, b"needs a reference"), (_pileup_ref_struct(device_genome, one, False), b"combine must be set"),
-                              (_pileup_ref_struct(device_genome, two, True), b"exactly one motif")):
-            ref = None if pref is None else ctypes.byref(pref)
-            assert lib.rmr_modbam_call_counts_duplex(eng.handle, ctypes.byref(b), ref, -1, 0, 0, p, p, p, p, p, None, 1) != 0
+        for pref, duplex, message in ((None, 1, b"needs a reference"), (_pileup_ref_struct(device_genome, one, False), 1, b"combine must be set"),
+                                      (_pileup_ref_struct(device_genome, two, True), 1, b"exactly one motif"), (ok, 0, b"duplex must be set")):
+            assert lib.rmr_pileup_emit_counts(eng.handle, ctypes.byref(b), opts(pref, duplex, 1), p, p, p, p, p, None) != 0
             assert message in lib.rmr_last_error()
-            assert lib.rmr_modbam_call_fill_duplex(eng.handle, ctypes.byref(b), ref, -1, 0, 0, 0, p, p, p, p, p, p, 1) != 0
+            assert lib.rmr_pileup_emit_fill(eng.handle, ctypes.byref(b), opts(pref, duplex, 1), 0, p, p, p, p, p, p) != 0
             assert message in lib.rmr_last_error()
-        ok = _pileup_ref_struct(device_genome, one, True)
-        assert lib.rmr_modbam_call_counts_duplex(eng.handle, ctypes.byref(b), ctypes.byref(ok), -1, 0, 0, p, p, p, p, p, None, 1) == 0
-        assert lib.rmr_modbam_call_counts_duplex(eng.handle, ctypes.byref(b), None, -1, 0, 0, p, p, p, p, p, None, 0) == 0
+        assert lib.rmr_pileup_emit_counts(eng.handle, ctypes.byref(b), opts(ok, 1, 1), p, p, p, p, p, None) == 0
+        assert lib.rmr_pileup_emit_counts(eng.handle, ctypes.byref(b), opts(None, 1, 0), p, p, p, p, p, None) == 0
         assert not any(k.startswith("pileup_") for k in eng.profile()), eng.profile()
     finally:
         eng.profile_enable(False)

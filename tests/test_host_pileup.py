@@ -10,7 +10,7 @@ import pytest
 
 from conftest import ROOT
 
-NEW_SYMBOLS = ("rmr_modbam_call_counts", "rmr_modbam_call_fill", "rmr_pileup_create", "rmr_pileup_add", "rmr_pileup_finish", "rmr_pileup_read",
+NEW_SYMBOLS = ("rmr_pileup_emit_counts", "rmr_pileup_emit_fill", "rmr_pileup_create", "rmr_pileup_add", "rmr_pileup_finish", "rmr_pileup_read",
                "rmr_pileup_destroy")
 
 

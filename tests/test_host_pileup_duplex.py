@@ -16,7 +16,7 @@ import test_gpu_pileup_ref as tgr
 from conftest import ROOT
 
 REFS = tp.REFS
-NEW_SYMBOLS = ("rmr_modbam_call_counts_duplex", "rmr_modbam_call_fill_duplex", "rmr_pileup_pair_counts", "rmr_pileup_pair_fill",
+NEW_SYMBOLS = ("rmr_pileup_emit_counts", "rmr_pileup_emit_fill", "rmr_pileup_pair_counts", "rmr_pileup_pair_fill",
                "rmr_pileup_create_cols")
 
 
@@ -421,8 +421,8 @@ def test_new_symbols_are_declared_exported_and_bound():
         assert name in _lib.SIGNATURES, f"{name} is not bound"
         assert any(name in c for c in re.findall(r"/\*.*?\*/", hdr, flags=re.S)), name
     assert "k_pileup_duplex.hip" in open(os.path.join(ROOT, "remora_amd", "csrc", "Makefile")).read()
-    # the `_ref` arguments and hemi; the pair passes; the parent's entries keep theirs
-    assert len(_lib.SIGNATURES["rmr_modbam_call_counts_duplex"][1]) == 13 and len(_lib.SIGNATURES["rmr_modbam_call_fill_duplex"][1]) == 14
-    assert len(_lib.SIGNATURES["rmr_modbam_call_counts_ref"][1]) == 12 and len(_lib.SIGNATURES["rmr_modbam_call_fill_ref"][1]) == 13
+    # the emit pair, duplex and hemi in its options struct; the pair passes
+    assert len(_lib.SIGNATURES["rmr_pileup_emit_counts"][1]) == 9 and len(_lib.SIGNATURES["rmr_pileup_emit_fill"][1]) == 10
+    assert [n for n, _ in _lib.PileupEmitOpts._fields_][-2:] == ["duplex", "hemi"]
     assert len(_lib.SIGNATURES["rmr_pileup_pair_counts"][1]) == 6 and len(_lib.SIGNATURES["rmr_pileup_pair_fill"][1]) == 8
     assert bytes_per_buffered_call(15) == 52 + 4 * 16  # a hemi table of 16 columns

@@ -10,8 +10,10 @@ import pytest
 
 from conftest import ROOT
 
-NEW_SYMBOLS = ("rmr_ref_genome_create", "rmr_ref_genome_load", "rmr_ref_genome_read", "rmr_ref_genome_destroy", "rmr_modbam_call_counts_ref",
-               "rmr_modbam_call_fill_ref")
+NEW_SYMBOLS = ("rmr_ref_genome_create", "rmr_ref_genome_load", "rmr_ref_genome_read", "rmr_ref_genome_destroy", "rmr_pileup_emit_counts",
+               "rmr_pileup_emit_fill")
+REMOVED_SYMBOLS = ("rmr_modbam_call_counts", "rmr_modbam_call_fill", "rmr_modbam_call_counts_ref", "rmr_modbam_call_fill_ref",
+                   "rmr_modbam_call_counts_duplex", "rmr_modbam_call_fill_duplex")
 
 
 # ---- the FASTA span index -------------------------------------------------------------------------------------------------------
@@ -229,6 +231,18 @@ def test_new_symbols_are_declared_exported_and_bound():
     assert "k_ref_genome.hip" in mk and "api_ref.hip" in mk
     assert re.search(r"#define RMR_PILEUP_MAX_MOTIFS 4\b", hdr) and re.search(r"#define RMR_PILEUP_MAX_MOTIF_LEN 16\b", hdr)
     assert ctypes.sizeof(_lib.PileupMotif) == 24 and ctypes.sizeof(_lib.PileupRef) == 16 + 4 * 24  # the layout of the C structs
-    # the existing emit entry points keep their signatures
-    assert len(_lib.SIGNATURES["rmr_modbam_call_counts"][1]) == 11 and len(_lib.SIGNATURES["rmr_modbam_call_fill"][1]) == 12
-    assert len(_lib.SIGNATURES["rmr_modbam_call_counts_ref"][1]) == 12 and len(_lib.SIGNATURES["rmr_modbam_call_fill_ref"][1]) == 13
+    # one emit pair: the engine, the batch, the options, (k_t,) and six arrays
+    assert len(_lib.SIGNATURES["rmr_pileup_emit_counts"][1]) == 9 and len(_lib.SIGNATURES["rmr_pileup_emit_fill"][1]) == 10
+    # the three generations of entries it replaces are gone: not declared, not bound, not exported
+    for name in REMOVED_SYMBOLS:
+        assert not re.search(rf"\b{name}\b", code), f"{name} is still declared"
+        assert name not in _lib.SIGNATURES and not hasattr(L, name), name
+    # the options struct of the header, field for field (names and C types), in the ctypes binding
+    body = re.search(r"typedef struct rmr_pileup_emit_opts \{(.*?)\} rmr_pileup_emit_opts;", code, flags=re.S).group(1)
+    ctype = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "const rmr_pileup_ref *": ctypes.POINTER(_lib.PileupRef)}
+    fields = [(n.strip(), ctype[t]) for t, names in re.findall(r"(int32_t|int64_t|const rmr_pileup_ref \*)\s*([\w\s,]+);", body)
+              for n in names.split(",")]
+    assert fields == list(_lib.PileupEmitOpts._fields_)
+    assert [n for n, _ in fields] == ["region_ref", "region_lo", "region_hi", "ref", "duplex", "hemi"]
+    assert len(re.findall(r";", body)) == 5  # (five declarations, region_lo and region_hi in one: nothing the pattern above passed over)
+    assert ctypes.sizeof(_lib.PileupEmitOpts) == 40 and _lib.PileupEmitOpts.ref.offset == 24
