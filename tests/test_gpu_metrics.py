@@ -122,31 +122,7 @@ def test_a_reads_metrics_do_not_depend_on_the_batch(torch_cuda, fx, gpu_metrics)
 
 
 # ---- site and k-mer levels ------------------------------------------------------------------------------------------------
-def _region_kmer_levels(reads, ctg_len, kb, ka, min_cov):
-    """numpy restatement of io.get_region_kmers (src/remora/io.py:966-982; the metrics matrix of get_ref_reg_sample_metrics
-    :864-886 with ref_orient=False and the sequence of get_ref_int_seq_from_reads :671-695), one region per strand spanning
-    the contig.  reads: (is_reverse, ref_start, read-oriented base codes, read-oriented trimmean).  -> {k-mer index: levels}."""
-    k = kb + ka + 1
-    out = {}
-    for rev in (False, True):
-        mine = [r for r in reads if r[0] == rev]
-        mat = np.full((len(mine), ctg_len), np.nan)
-        seq = np.full(ctg_len + kb + ka, -2, np.int64)  # read-oriented; [kb + o] is the base of read-oriented offset o
-        for row, (_, start, codes, vals) in enumerate(mine):
-            o0 = ctg_len - (start + codes.size) if rev else start  # read-oriented offset of the read's first base
-            mat[row, o0 : o0 + codes.size] = vals
-            seq[kb + o0 : kb + o0 + codes.size] = codes
-        for offset in range(ctg_len):
-            kmer = seq[offset : offset + k]
-            if (kmer < 0).any():
-                continue
-            site = mat[:, offset]
-            site = site[np.isfinite(site)]
-            if site.size < min_cov:
-                continue
-            idx = int(sum(int(b) * 4 ** (k - 1 - j) for j, b in enumerate(kmer)))
-            out.setdefault(idx, []).append(np.median(site))
-    return out
+from metric_cases import region_kmer_levels as _region_kmer_levels  # noqa: E402  (the numpy restatement of io.get_region_kmers)
 
 
 @pytest.fixture(scope="module")
